@@ -8,10 +8,12 @@ the timed region starts. With --gpus N the DB is row-sharded over the ranks (one
 searches its shard, one RCCL all_gather of the per-shard top-k, merge on every rank (strong scaling: total
 work fixed).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel = the fused MFMA
-candidate scan; algorithmic FLOPs = 2*Q*N*D per launch / its hipEvent-measured duration vs the dense MFMA peak of the
-dtype the scan multiplies in: 2.5 PF for the default f16 scan and for --mode 2 = split-bf16)
-and `cpu_baseline` (the numpy oracle of training/coarse.py:119-125 timed on this host).
+Prints ONE JSON line on rank 0 (contract in the task statement). A plain run does set-up, warmup, the timed steps and
+(--dump-outputs DIR) writes the last timed step's results, nothing else. --full adds everything measured or checked
+beside the headline, with the line carrying it: `roofline` (dominant kernel = the fused MFMA candidate scan; algorithmic
+FLOPs = 2*Q*N*D per launch / its hipEvent-measured duration vs the dense MFMA peak of the dtype the scan multiplies in:
+2.5 PF for the default f16 scan and for --mode 2 = split-bf16), `cpu_baseline` (the numpy oracle of
+training/coarse.py:119-125 timed on this host), parity against the float64 C oracle, the side measurements.
 """
 import argparse
 import json
@@ -82,7 +84,8 @@ def measure_traffic_in_run(kernel_prefix="t2l::scanp_kernel"):
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="t2l_pmc_")
         cmd = ["rocprofv3", "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", d, "-o", "p", "--", sys.executable,
-               os.path.abspath(__file__), "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-secondary", "--no-pipelined", "--quick"]
+               os.path.abspath(__file__), "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-secondary", "--no-pipelined",
+               "--quick"]
         try:
             subprocess.run(cmd, env=dict(os.environ, T2L_BENCH_CHILD="1", TMPDIR="/tmp"), cwd="/tmp", timeout=240, capture_output=True, check=True)
             acc = []
@@ -1185,8 +1188,9 @@ def format_headline(d):
                                       "scaling", "vs_baseline", "dtype", "data")}
     line["config"] = {k: cfg.get(k) for k in ("workload", "n_cells", "queries_per_step", "embed_dim", "top_k", "parallelism", "layout")
                       if cfg.get(k) is not None}
-    line["roofline"] = {k: _r(rl.get(k)) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "kernel_ms",
-                                                   "launches_timed", "flops_per_launch")}
+    if rl:  # (a plain run, without --full, measures the headline only: no roofline, no CPU baseline, no parity)
+        line["roofline"] = {k: _r(rl.get(k)) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "kernel_ms",
+                                                       "launches_timed", "flops_per_launch")}
     if rl.get("frac_of_measured_ceiling") is not None:  # `peak` is the nominal rate; dense random-data MFMAs are power-limited below it
         line["roofline"]["measured_random_data_mfma_ceiling"] = _r(rl.get("measured_random_data_mfma_ceiling_tflops"))
         line["roofline"]["frac_of_measured_ceiling"] = _r(rl.get("frac_of_measured_ceiling"))
@@ -1194,11 +1198,13 @@ def format_headline(d):
         line["cpu_baseline"] = {k: _r(cb.get(k)) for k in ("value", "unit", "cores", "kind", "sample")}
         line["cpu_baseline"]["sample"] = str(line["cpu_baseline"]["sample"])[:160]
         line["speedup_vs_cpu_baseline"] = _r(d.get("speedup_vs_cpu_baseline"))
-    line["parity"] = {"ids_equal": par.get("ids_equal_float64_oracle"), "pairs_checked": par.get("pairs_checked"),
-                      "max_abs_score_err": _r(par.get("max_abs_score_err"))}
+    if par:
+        line["parity"] = {"ids_equal": par.get("ids_equal_float64_oracle"), "pairs_checked": par.get("pairs_checked"),
+                          "max_abs_score_err": _r(par.get("max_abs_score_err"))}
     line["ranks_seen"] = d.get("ranks_seen")
     km = d.get("kernels_ms") or {}
-    line["kernels_ms"] = {k: _r(v) for k, v in km.items()}
+    if km:
+        line["kernels_ms"] = {k: _r(v) for k, v in km.items()}
     st = d.get("steady_state")
     if st:
         line["steady_state"] = {k: _r(st.get(k)) for k in ("steps", "untimed_ramp_steps", "ms_per_step", "queries_per_s")}
@@ -1259,6 +1265,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline: roofline, "
+                    "steady state, parity vs the float64 C oracle, pipelined and N > 1 side lines, side measurements, CPU baseline, "
+                    "the full record in --detail-out (the --no-* and --quick options below apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's results as DIR/ids.npy and DIR/scores.npy (float64 [Q, top_k])")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the encoder / loss side measurements")
     ap.add_argument("--cells", type=int, default=N_CELLS, help="dev: database rows (default = the BASELINE workload)")
@@ -1272,6 +1283,8 @@ def main():
     ap.add_argument("--detail-out", default=os.path.join(REPO, "gpurun_out", "bench_detail.json"),
                     help="where the full record (side measurements, distribution lists, notes) goes; the stdout line stays < 4 KB")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher — N ranks of this same script, one per GPU, over RCCL
@@ -1347,7 +1360,7 @@ def main():
     # THE CONTRACT REGION (`value`): W warmup steps, then exactly K timed steps between barrier + synchronize on both sides.
     # Nothing runs on the GPU before it but the set-up above — no clock-ramp steps: at the driver's --warmup 5 --steps 20 the
     # GPU is still climbing from its idle clocks (it needs ~40 ms of load to reach the sustained ones), and that is what the
-    # headline reports. The sustained rate of the same loop is measured right behind it (`steady_state`, a side field).
+    # headline reports. With --full the sustained rate of the same loop is measured right behind it (`steady_state`, a side field).
     for i in range(args.warmup):
         step(i)
     # forget the samples so far and restart the sampling phase — host-only, the stream keeps running
@@ -1368,6 +1381,45 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:  # before anything else runs: later steps of --full reuse the rotated `outs` buffers
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "ids.npy"), idx.cpu().numpy().astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "scores.npy"), sc.cpu().numpy().astype(np.float64))
+
+    ms = 1e3 * elapsed / args.steps
+    if args.mode == 2:
+        kname, peak, dtype, mult = "scanw_kernel<8, 4>", BF16_MFMA_PEAK_TFLOPS, "bf16x3", 3
+    else:
+        kname, peak, dtype, mult = ("scanp_kernel<6, 4, true, 1>" if os.environ.get("T2L_BENCH_TILE_SEL", "1") != "0" else "scanp_kernel<6, 4, true, 0>"), BF16_MFMA_PEAK_TFLOPS, "f16", 1  # (merged records + tile-local selection: the default on benign data)
+    out = {
+        "metric": "coarse-retrieval queries/sec over 11k-cell DB, embed_dim=256; top-1/3/5 recall parity",
+        "value": N_QUERIES * args.steps / elapsed,
+        "unit": "queries/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": dtype, "data": "synthetic",
+        "config": {"workload": "KITTI360Pose-sized val DB: N=11259 cells x D=256 resident in HBM, Q=4096 "
+                               "precomputed text embeddings per step, top-10 (float64-exact ids)",
+                   "n_cells": N_CELLS, "queries_per_step": N_QUERIES, "embed_dim": DIM, "top_k": TOPK,
+                   "arithmetic": {0: "f16 MFMA candidate scan (power-of-two scaled operands, f32 accumulate)",
+                                  2: "split-bf16 (3 MFMAs per product) candidate scan (f32 accumulate)"}[args.mode]
+                                 + " -> float64 re-rank + certificate (ids and scores are the float64 ranking)",
+                   "parallelism": f"db-row-shard x{world}" if world > 1 else "single-gpu",
+                   "layout": (f"db-row-shard x{world}: shard search -> ONE all_gather of the per-shard top-k -> merge on every rank"
+                              if world > 1 else "one resident DB, two launches per step (scan, re-rank)"),
+                   "pipelining": "none (stream-ordered steps)",
+                   "region": "set-up, then W warmup steps, then K timed steps: no clock-ramp steps before the region"},
+        "ranks_seen": ranks_seen,
+    }
+    if not args.full:
+        # the timed region above is the same in both forms (its sampled HIP events included), so `value` means the same;
+        # only what --full measures behind it is skipped
+        if rank == 0:
+            print(format_headline(out), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
+
     scan_region_ms, scan_region_n = eng.kernel_stats("search_scan")
     span_region_ms, span_region_n = eng.kernel_stats("search_scan_span")
     fallbacks = eng.search_fallbacks()
@@ -1577,37 +1629,15 @@ def main():
         _QUICK = bool(args.quick)
         secondary = secondary_measurements(eng)
     if rank == 0:
-        ms = 1e3 * elapsed / args.steps
         n_local = hi - lo
         flops = 2.0 * N_QUERIES * n_local * DIM  # algorithmic FLOPs of one scan launch on this rank's shard
-        if args.mode == 2:
-            kname, peak, dtype, mult = "scanw_kernel<8, 4>", BF16_MFMA_PEAK_TFLOPS, "bf16x3", 3
-        else:
-            kname, peak, dtype, mult = ("scanp_kernel<6, 4, true, 1>" if os.environ.get("T2L_BENCH_TILE_SEL", "1") != "0" else "scanp_kernel<6, 4, true, 0>"), BF16_MFMA_PEAK_TFLOPS, "f16", 1  # (merged records + tile-local selection: the default on benign data)
         if world == 1 and not args.quick:
             measure_mfma_ceiling()  # (outside every timed region)
         if world == 1 and args.mode == 0 and not args.quick and not os.environ.get("T2L_BENCH_CHILD"):
             live = measure_traffic_in_run("t2l::scanp_kernel")  # (outside every timed region; ~40 s; None without rocprofv3)
             if live is not None:
                 _PMC_LIVE["t2l::" + kname] = live
-        out = {
-            "metric": "coarse-retrieval queries/sec over 11k-cell DB, embed_dim=256; top-1/3/5 recall parity",
-            "value": N_QUERIES * args.steps / elapsed,
-            "unit": "queries/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": dtype, "data": "synthetic",
-            "config": {"workload": "KITTI360Pose-sized val DB: N=11259 cells x D=256 resident in HBM, Q=4096 "
-                                   "precomputed text embeddings per step, top-10 (float64-exact ids)",
-                       "n_cells": N_CELLS, "queries_per_step": N_QUERIES, "embed_dim": DIM, "top_k": TOPK,
-                       "arithmetic": {0: "f16 MFMA candidate scan (power-of-two scaled operands, f32 accumulate)",
-                                      2: "split-bf16 (3 MFMAs per product) candidate scan (f32 accumulate)"}[args.mode]
-                                     + " -> float64 re-rank + certificate (ids and scores are the float64 ranking)",
-                       "parallelism": f"db-row-shard x{world}" if world > 1 else "single-gpu",
-                       "layout": (f"db-row-shard x{world}: shard search -> ONE all_gather of the per-shard top-k -> merge on every rank"
-                                  if world > 1 else "one resident DB, two launches per step (scan, re-rank)"),
-                       "pipelining": "none (stream-ordered steps)",
-                       "region": "set-up, then W warmup steps, then K timed steps: no clock-ramp steps before the region"},
+        out.update({
             "roofline": roofline(kname, peak, mult, flops, scan_ms, scan_n, span_ms, span_n, busy_ms, busy_n),
             "kernels_ms": {"search_scan": scan_ms, "search_rerank": rerank_ms},  # the whole step is these two launches
             "scan_kernel_event_samples": {"inside_the_timed_region": {"kernel_ms": scan_region_ms, "launches_timed": scan_region_n},
@@ -1623,8 +1653,8 @@ def main():
                        "max_abs_score_err": max_score_err, "recall_at_1_planted": recall1,
                        "exact_fallback_queries_last_step": fallbacks,
                        "first_certificate_failures_last_step": rescored, "counters_last_step": counters},
-            "ranks_seen": ranks_seen, "query_batches_rotated": N_BATCH,
-        }
+            "query_batches_rotated": N_BATCH,
+        })
         if alt is not None:
             out["alt_query_sharded"] = alt
         if weak is not None:

@@ -81,6 +81,15 @@ def test_headline_is_short_and_round_trips(world, bloat):
         assert o["weak_scaling_point"]["rows_total"] == 90072 and len(o["config5_coarse_plus_fine"]["error"]) <= 120
 
 
+def test_plain_run_record_gives_the_headline_alone():
+    """A run without --full measures no roofline, parity, kernel times or CPU baseline: its line carries the contract's keys and
+    ranks_seen, and no empty placeholder groups for what it did not measure."""
+    d = {k: v for k, v in canned().items() if k in CONTRACT_KEYS or k == "ranks_seen"}
+    o = json.loads(bench.format_headline(d))
+    assert set(o) == set(CONTRACT_KEYS) | {"ranks_seen"}
+    assert o["ms_per_step"] == pytest.approx(d["ms_per_step"], rel=1e-5) and o["dtype"] == "f16"
+
+
 def test_secondary_line_is_short_and_not_a_json_line():
     for bloat in (1, 8):
         s = bench.format_secondary(canned(1, bloat)["secondary"])

@@ -9,10 +9,10 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python $ROOT/bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-secondary --no-pipelined"
+CMD="python $ROOT/bench.py --steps 50 --warmup 5 --full --no-cpu-baseline --no-secondary --no-pipelined"
 # (the headline command keeps its clock-ramp steps — 1.6 k launches survive the PMC passes; the side measurements run --quick:
 # rocprofv3 --pmc slows every launch ~100x and crashed / hung on the tens of thousands of launches of the full side loops)
-SEC="python $ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline --quick"
+SEC="python $ROOT/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --quick"
 timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- $CMD > $OUT/trace.log 2>&1
 timeout 420 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_INSTS_VALU SQ_INSTS_MFMA GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_sq -o p -- $CMD > $OUT/pmc_sq.log 2>&1
 timeout 420 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o p -- $CMD > $OUT/pmc_fetch.log 2>&1

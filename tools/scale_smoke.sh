@@ -13,7 +13,7 @@ mkdir -p "$OUT"
 export T2L_DIST_BACKEND=${T2L_DIST_BACKEND:-gloo} HSA_ENABLE_IPC_MODE_LEGACY=0
 rc=0
 for N in ${SCALE_SMOKE_NS:-2 4 8}; do
-  timeout 900 python bench.py --gpus "$N" --steps 20 --warmup 5 --no-cpu-baseline --detail-out "$OUT/detail_g$N.json" > "$OUT/bench_g$N.json" 2> "$OUT/bench_g$N.err"
+  timeout 900 python bench.py --gpus "$N" --steps 20 --warmup 5 --full --no-cpu-baseline --detail-out "$OUT/detail_g$N.json" > "$OUT/bench_g$N.json" 2> "$OUT/bench_g$N.err"
   st=$?
   if [ $st -ne 0 ]; then echo "scale_smoke: bench.py --gpus $N exited $st"; tail -20 "$OUT/bench_g$N.err"; rc=1; continue; fi
   python - "$OUT/bench_g$N.json" "$N" <<'EOF' || rc=1
