@@ -349,6 +349,43 @@ int t2l_pointnet_backward(t2l_ctx* ctx, const float* grad_features2, void* strea
  * last t2l_zero_grad (a batch fed precomputed features2 leaves the backbone's weights AND moments untouched). */
 int t2l_zero_grad(t2l_ctx* ctx, void* stream);
 
+/* ---- training step of the fine stage (f-1 under model.train()) -------------------------------------- */
+/* Replaces, for everything downstream of the text branch, the body of the reference's fine train_epoch (training/fine.py:38-91):
+ * CrossMatch.forward under model.train() (models/cross_matcher.py:86-135), loss.backward() through it. The text branch
+ * (LanguageEncoder(is_fine=True): T5 + its head) stays on PyTorch autograd; the two meet at the hint encodings. torch.optim.Adam
+ * steps the parameters (the library has no optimizer state for this stage).
+ *
+ * t2l_fine_train_bind: t2l_train_tensor entries (live data / grad pointers, the a9 convention) named as in the fine checkpoint:
+ * object_encoder.* at fine_embed_dim 128 for the configured features — class_embedding.weight (class_embed) or mlp_pointnet.0.*
+ * (features2 supplied by the caller; the PointNet++ backbone is not part of this step), color_embedding.weight or color_encoder.*,
+ * pos_encoder.*, num_encoder.*, mlp_merge.0.* (more than one feature); with class_embed == 0 mlp_pointnet.0.* is needed even without
+ * use_class (the reference runs it anyway: its BatchNorm statistics move, nothing else depends on it) — with the BatchNorm1d buffers ("...1.running_mean",
+ * "...1.running_var", no grad); cross_objects.{i}.* and cross_hints.{i}.* (i < cfg->num_layers), or cross_hints.* alone when
+ * num_layers == 0 (models/cross_matcher.py:75-79); mlp_offsets.{0,2}.*. A missing tensor or a wrong element count is T2L_EINVAL;
+ * a parameter bound with grad = NULL is frozen (gets no gradient). cfg->num_heads must be 4. Pointers must stay valid until the
+ * next bind. Synchronous. */
+int t2l_fine_train_bind(t2l_ctx* ctx, const t2l_train_tensor* tensors, int32_t n, const t2l_model_config* cfg);
+
+/* The training-mode forward of n_pairs (pose, cell) pairs — one per batch entry, as training/fine.py:51-55 batches them.
+ * in: n_pairs padded cells of exactly 16 objects (in->n_cells == n_pairs); pn_feat: dev f32[16*n_pairs,256] features2
+ * (class_embed == 0; NULL = in->pn_feat); hint_desc: dev f32[n_pairs,n_hints,128], 1 <= n_hints <= 8; out_offsets: dev
+ * f32[n_pairs,2]. Every BatchNorm1d of the ObjectEncoder normalises over all 16*n_pairs objects (pads included) and updates its
+ * running buffers in place (momentum 0.1, unbiased variance; the caller bumps num_batches_tracked).
+ * Dropout (nn.TransformerDecoderLayer's dropout, torch default 0.1) uses the a9 mask rule: element i of site j is kept iff
+ * lowbias32(i*0x9E3779B1 + (seed ^ j*0x85EBCA77)) >> 8 >= dropout_p*2^24 (thr == 0: no dropout), kept values scaled by
+ * 1/(1-dropout_p). Sites: 6 per decoder layer, in cascade order c = 2i (cross_objects.i), 2i+1 (cross_hints.i), or c = 0 for the
+ * single cross_hints layer: j = 6c + {0 self-attention probabilities, 1 dropout1, 2 cross-attention probabilities, 3 dropout2,
+ * 4 feed-forward dropout (after ReLU(linear1)), 5 dropout3}. Element index: probabilities [pair, head, query, key] (the layer's
+ * own query / key counts: 16 objects or n_hints hints); activations [pair, token, feature] (128 features, 512 for site 4).
+ * Activations stay in the context until the next forward; `in`, pn_feat and hint_desc must stay valid until the last backward. */
+int t2l_fine_train_forward(t2l_ctx* ctx, const t2l_packed_cells* in, const float* pn_feat, const float* hint_desc, int32_t n_pairs,
+                           int32_t n_hints, float dropout_p, uint32_t seed, float* out_offsets, void* stream);
+
+/* loss.backward() through the last forward: grad_offsets dev f32[n_pairs,2] (the MSE gradient from torch). Parameter gradients
+ * are ADDED to the bound grad buffers (float atomics: the last bits vary between runs); grad_hint_desc dev f32[n_pairs,n_hints,128]
+ * and grad_pn_feat dev f32[16*n_pairs,256] are written when non-NULL. May run more than once per forward (each call adds again). */
+int t2l_fine_train_backward(t2l_ctx* ctx, const float* grad_offsets, float* grad_hint_desc, float* grad_pn_feat, void* stream);
+
 /* ---- the text head in TRAINING mode (f-4 / the text half of a9) ---------------------------------- */
 /* Replaces: LanguageEncoder.forward downstream of T5's last_hidden_state under model.train() + its autograd backward
  * (models/language_encoder.py:127-147 as run by training/coarse.py:44,55-56; the published command trains this head —

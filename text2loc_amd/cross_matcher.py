@@ -10,7 +10,13 @@
 The text branch (``LanguageEncoder(is_fine=True)``: T5 + one Transformer layer over tokens + Linear/BN) stays on
 PyTorch-ROCm; the 3D-submap branch (ObjectEncoder at fine_embed_dim incl. PointNet++ in the published mode), the cascaded
 cross-attention decoder layers and the offset head run in the engine (t2l_fine_*). The nn.Modules below are PARAMETER
-CONTAINERS for the engine-side tensors. Eval only (the fine model's training step is not built).
+CONTAINERS for the engine-side tensors.
+
+Under ``model.train()``, ``forward`` is one training step's forward in the engine (t2l_fine_train_*): BatchNorm over the
+batch's objects, the decoder layers' dropout, and a backward that adds every parameter gradient straight into the live
+``.grad`` tensors and hands d loss / d hint encodings (and d features2) back to autograd, so ``loss.backward()`` continues into
+the text branch and ``torch.optim.Adam(model.parameters())`` steps everything (training/fine.py:38-91). ``encode_cells`` /
+``match`` stay eval-only; the PointNet++ backbone is not trained here (features2 must be supplied as tensors).
 """
 from __future__ import annotations
 
@@ -90,6 +96,11 @@ class CrossMatch(nn.Module):
             self.cross_objects = None
         self._engine: Optional[Engine] = None
         self._weights_version = None
+        self._train_generation = 0  # bumped by every training-mode forward (running statistics move outside torch's _version)
+        self._fine_train_bound = None
+        self._fine_train_grads = {}
+        self._fine_train_token = None
+        self._fine_train_hook = None
 
     @property
     def device(self):
@@ -99,7 +110,7 @@ class CrossMatch(nn.Module):
         return self.device
 
     # ---- engine plumbing ----------------------------------------------------------------------------------
-    def engine(self) -> Engine:
+    def _device_engine(self) -> Engine:
         dev = self.device
         if dev.type != "cuda":
             raise T2LError("the fine stage runs on the MI355X only (model.to('cuda')); there is no CPU fallback")
@@ -107,8 +118,12 @@ class CrossMatch(nn.Module):
         if self._engine is None or self._engine.device != idx:
             self._engine = Engine(idx)
             self._weights_version = None
+        return self._engine
+
+    def engine(self) -> Engine:
+        self._device_engine()
         params = [p for n, p in self.state_dict(keep_vars=True).items() if not n.startswith("language_encoder.")]
-        version = tuple((p.data_ptr(), p._version) for p in params)
+        version = (tuple((p.data_ptr(), p._version) for p in params), self._train_generation)
         if version != self._weights_version:
             a = self.args
             sd = {k: v for k, v in self.state_dict().items() if not k.startswith("language_encoder.")}
@@ -154,11 +169,157 @@ class CrossMatch(nn.Module):
         hi = None if hint_index is None else torch.as_tensor(hint_index, dtype=torch.int32, device=cell_desc.device).contiguous()
         return self.engine().fine_match(cell_desc.contiguous(), hint_desc.detach().float().contiguous(), ci, hi)
 
-    @torch.no_grad()
     def forward(self, objects, hints, object_points=None) -> torch.Tensor:
-        """One (pose, cell) pair per batch entry, as ``run_fine`` calls it (evaluation/pipeline.py:113-116)."""
-        hint_enc = self.language_encoder(hints)  # [B, n_hints, 128]  (cross_matcher.py:95)
-        return self.match(self.encode_cells(objects, object_points), hint_enc)
+        """One (pose, cell) pair per batch entry, as ``run_fine`` calls it (evaluation/pipeline.py:113-116) and as the
+        reference's fine train_epoch batches them (training/fine.py:51-55)."""
+        if self.training:
+            return self._forward_train(objects, hints, object_points)
+        with torch.no_grad():
+            hint_enc = self.language_encoder(hints)  # [B, n_hints, 128]  (cross_matcher.py:95)
+            return self.match(self.encode_cells(objects, object_points), hint_enc)
+
+    # ---- training mode ------------------------------------------------------------------------------------
+    def _fine_train_modules(self):
+        """(prefixes of the modules the engine step runs, prefixes of those whose parameters receive a gradient) — the
+        ObjectEncoder branches of args.use_features (object_encoder.py:102-149), plus mlp_pointnet whenever class_embed is off:
+        the reference runs it then even without "class" (object_encoder.py:86-99), which moves its BatchNorm statistics only."""
+        a = self.args
+        ce, co = bool(getattr(a, "class_embed", False)), bool(getattr(a, "color_embed", False))
+        oe = "object_encoder."
+        grad = ["cross_hints.", "cross_objects.", "mlp_offsets."]
+        if "class" in a.use_features:
+            grad.append(oe + ("class_embedding." if ce else "mlp_pointnet."))
+        if "color" in a.use_features:
+            grad.append(oe + ("color_embedding." if co else "color_encoder."))
+        if "position" in a.use_features:
+            grad.append(oe + "pos_encoder.")
+        if "num" in a.use_features:
+            grad.append(oe + "num_encoder.")
+        if len(a.use_features) > 1:
+            grad.append(oe + "mlp_merge.")
+        run = grad + ([oe + "mlp_pointnet."] if not ce else [])
+        return tuple(run), tuple(grad)
+
+    def _fine_train_tensors(self):
+        """state_dict key -> (live tensor, persistent .grad buffer or None) for everything the engine step reads. Only the
+        parameters the step differentiates get a .grad (the others stay None, as in the reference, and optimizers skip them)."""
+        run, with_grad = self._fine_train_modules()
+        out = {}
+        for n, t in self.named_parameters():
+            if not n.startswith(run):
+                continue
+            if not t.requires_grad or not n.startswith(with_grad):
+                out[n] = (t.data, None)  # frozen: no gradient
+                continue
+            g = self._fine_train_grads.get(n)
+            if g is None or g.shape != t.shape or g.device != t.device:
+                g = self._fine_train_grads[n] = torch.zeros_like(t.data)
+            if t.grad is None:
+                t.grad = g  # hand the persistent buffer back (zero_grad(set_to_none=True) only drops the reference)
+                g.zero_()
+            elif t.grad.data_ptr() != g.data_ptr():
+                g.copy_(t.grad)  # a gradient assigned from outside keeps its VALUE; the storage stays the bound buffer
+                t.grad = g
+            out[n] = (t.data, g)
+        for n, b in self.named_buffers():
+            if n.startswith(run) and n.endswith(("running_mean", "running_var")):
+                out[n] = (b, None)
+        return out
+
+    def _fine_train_dropout(self) -> float:
+        """The one dropout probability the engine applies at all six sites of every decoder layer; layers (or sites) that
+        disagree are refused rather than trained with the wrong p."""
+        layers = list(self.cross_hints) + list(self.cross_objects) if self.cross_objects is not None else [self.cross_hints]
+        ps = set()
+        for l in layers:
+            ps |= {float(l.dropout.p), float(l.dropout1.p), float(l.dropout2.p), float(l.dropout3.p),
+                   float(l.self_attn.dropout), float(l.multihead_attn.dropout)}
+        if len(ps) != 1:
+            raise T2LError(f"the engine applies one dropout probability to every decoder layer; these layers use {sorted(ps)}")
+        return ps.pop()
+
+    def _fine_train_engine(self) -> Engine:
+        """The engine with t2l_fine_train_bind pointing at the CURRENT parameter / gradient / buffer storage (no re-packing:
+        the step reads the live tensors)."""
+        eng = self._device_engine()
+        tensors = self._fine_train_tensors()
+        key = (id(eng),) + tuple((n, d.data_ptr(), None if g is None else g.data_ptr()) for n, (d, g) in tensors.items())
+        if key != self._fine_train_bound:
+            a = self.args
+            eng.fine_train_bind(tensors, class_embed=bool(getattr(a, "class_embed", False)), color_embed=bool(getattr(a, "color_embed", False)),
+                                use_features=tuple(a.use_features), num_layers=a.fine_num_decoder_layers, num_heads=a.fine_num_decoder_heads)
+            self._fine_train_bound = key
+        return eng
+
+    def _forward_train(self, objects, hints, object_points):
+        if any(len(o) != PAD_SIZE for o in objects):
+            raise T2LError(f"every cell must hold exactly pad_size={PAD_SIZE} objects (cross_matcher.pad_objects pads / cuts)")
+        a = self.args
+        want_pn = not bool(getattr(a, "class_embed", False))  # object_encoder.py:86-99: features2 whenever class_embed is off
+        if want_pn:
+            if object_points is None or any(p is None for p in object_points):
+                raise T2LError("class_embed is off: object_points must hold, per cell, features2 [16,256]")
+            if not all(isinstance(p, (torch.Tensor, np.ndarray)) for p in object_points):
+                raise T2LError("training the fine stage on point batches needs the jointly trained PointNet++ backbone, which is not "
+                               "built for the fine stage: pass features2 [16,256] per cell as tensors")
+        p_drop = self._fine_train_dropout()                         # nn.TransformerDecoderLayer default 0.1
+        dev = self.device
+        if dev.type != "cuda":
+            raise T2LError("the fine stage runs on the MI355X only (model.to('cuda')); there is no CPU fallback")
+        pn = None
+        if want_pn:
+            pn = torch.cat([p if isinstance(p, torch.Tensor) else torch.from_numpy(np.asarray(p)) for p in object_points]).to(dev, torch.float32)
+            if tuple(pn.shape) != (len(objects) * PAD_SIZE, 256):
+                raise T2LError(f"features2 must be [16,256] per cell, got {tuple(pn.shape)} in all")
+        eng = self._fine_train_engine()
+        oe = self.object_encoder
+        if any(getattr(o, "_t2l_feat", None) is None for objs in objects for o in objs):
+            packed = packing.pack_cells_gpu(eng, objects, oe.known_classes, oe.known_colors, dev)
+        else:
+            packed = packing.to_device(packing.pack_cells(objects, oe.known_classes, oe.known_colors), dev)
+        hint_enc = self.language_encoder(hints)  # [B, n_hints, 128]  (cross_matcher.py:95), on torch autograd
+        if hint_enc.dim() != 3 or hint_enc.shape[0] != len(objects) or not 1 <= hint_enc.shape[1] <= 8 or hint_enc.shape[2] != FINE_DIM:
+            raise T2LError(f"hint encodings must be [B={len(objects)}, 1..8, 128], got {tuple(hint_enc.shape)}")
+        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())        # torch.manual_seed governs the masks
+        if self._fine_train_hook is None or self._fine_train_hook.device != dev:
+            self._fine_train_hook = torch.zeros(1, device=dev, requires_grad=True)
+        out = _FineTrainFn.apply(self._fine_train_hook, hint_enc, pn, self, packed, p_drop, seed)
+        run, _ = self._fine_train_modules()
+        for name, m in self.object_encoder.named_modules():  # BatchNorm1d.train() side effect the engine does not see (int64)
+            if isinstance(m, nn.BatchNorm1d) and m.num_batches_tracked is not None and f"object_encoder.{name}.".startswith(run):
+                m.num_batches_tracked += 1
+        self._train_generation += 1  # running statistics moved: the eval path must re-load its weights
+        return out
+
+
+class _FineTrainFn(torch.autograd.Function):
+    """Training-mode CrossMatch downstream of the text branch: forward and backward are HIP (t2l_fine_train_forward /
+    _backward). Parameter gradients do not flow through autograd: the engine adds them straight into the bound ``.grad``
+    buffers; the differentiable inputs are the hint encodings and features2 (``hook`` is a dummy leaf that makes autograd call
+    ``backward`` even when neither requires grad)."""
+
+    @staticmethod
+    def forward(ctx, hook, hint_enc, pn, model, packed, p_drop, seed):
+        hint_c = hint_enc.detach().float().contiguous()
+        pn_c = None if pn is None else pn.detach().contiguous()
+        out = model._engine.fine_train_forward(packed, pn_c, hint_c, dropout_p=p_drop, seed=seed)
+        ctx.model = model
+        ctx.token = model._fine_train_token = object()
+        ctx.hint_shape, ctx.hint_dtype = hint_c.shape, hint_enc.dtype
+        ctx.pn_shape = None if pn is None else pn_c.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        model = ctx.model
+        if model._fine_train_token is not ctx.token:
+            raise T2LError("backward of a stale CrossMatch training forward: the engine keeps the activations of the LAST "
+                           "training-mode forward only (the reference's loop does one forward per backward too)")
+        need_hint, need_pn = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        gh = torch.empty(ctx.hint_shape, dtype=torch.float32, device=grad_out.device) if need_hint else None
+        gp = torch.empty(ctx.pn_shape, dtype=torch.float32, device=grad_out.device) if need_pn else None
+        model._engine.fine_train_backward(grad_out.contiguous().float(), gh, gp)
+        return None, (gh.to(ctx.hint_dtype) if gh is not None else None), gp, None, None, None, None
 
 
 @torch.no_grad()

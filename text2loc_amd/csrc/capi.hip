@@ -105,6 +105,7 @@ void t2l_destroy(t2l_ctx* ctx) {
   free_text_train(ctx);
   free_pointnet(ctx);
   free_fine(ctx);
+  free_fine_train(ctx);
   free_text_head(ctx);
   for (void* p : {(void*)ctx->db, (void*)ctx->db_split, (void*)ctx->db_half, (void*)ctx->db_norm_max, (void*)ctx->cand_score, (void*)ctx->seg_idx,
                   (void*)ctx->seg_score, (void*)ctx->flags, (void*)(ctx->fb_count < ctx->fb_prev ? ctx->fb_count : ctx->fb_prev), ctx->fast_ws, (void*)ctx->fast_zero, ctx->reduce_ws, ctx->loss_ws, (void*)ctx->small_ticket, ctx->small_part, (void*)ctx->scan_span})
@@ -414,6 +415,25 @@ int t2l_text_train_bind(t2l_ctx* ctx, const t2l_train_tensor* tensors, int32_t n
   if (!ctx) return T2L_EINVAL;
   T2L_HIP(ctx, hipSetDevice(ctx->device));
   return text_train_bind_impl(ctx, tensors, n, prefix);
+}
+
+int t2l_fine_train_bind(t2l_ctx* ctx, const t2l_train_tensor* tensors, int32_t n, const t2l_model_config* cfg) {
+  if (!ctx) return T2L_EINVAL;
+  T2L_HIP(ctx, hipSetDevice(ctx->device));
+  return fine_train_bind_impl(ctx, tensors, n, cfg);
+}
+
+int t2l_fine_train_forward(t2l_ctx* ctx, const t2l_packed_cells* in, const float* pn_feat, const float* hint_desc, int32_t n_pairs,
+                           int32_t n_hints, float dropout_p, uint32_t seed, float* out_offsets, void* stream) {
+  if (!ctx) return T2L_EINVAL;
+  T2L_HIP(ctx, hipSetDevice(ctx->device));
+  return fine_train_forward_impl(ctx, in, pn_feat, hint_desc, n_pairs, n_hints, dropout_p, seed, out_offsets, (hipStream_t)stream);
+}
+
+int t2l_fine_train_backward(t2l_ctx* ctx, const float* grad_offsets, float* grad_hint_desc, float* grad_pn_feat, void* stream) {
+  if (!ctx) return T2L_EINVAL;
+  T2L_HIP(ctx, hipSetDevice(ctx->device));
+  return fine_train_backward_impl(ctx, grad_offsets, grad_hint_desc, grad_pn_feat, (hipStream_t)stream);
 }
 
 int t2l_text_head_train(t2l_ctx* ctx, const float* hidden, int32_t n_sentences, int32_t n_tokens, int32_t n_descriptions, float dropout_p,

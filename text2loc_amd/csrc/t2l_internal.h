@@ -84,6 +84,7 @@ struct t2l_ctx {
   void* train = nullptr;         // t2l::TrainState (train.hip)
   void* pn = nullptr;            // t2l::PointNetWeights (pointnet.hip), null when no pointnet.* tensors were loaded
   void* fine = nullptr;          // t2l::FineWeights (fine.hip)
+  void* fine_train = nullptr;    // t2l::ft::FineTrain (fine_train.hip): the fine stage's training state
   void* text_head = nullptr;     // t2l::th::Weights (text_head.hip)
   void* text_train = nullptr;    // t2l::TextTrain (train.hip): the text head's training state
   // cross-rank BatchNorm statistics (t2l_train_sync_bn): the accumulator slots live in the caller's buffer and the callback sums a
@@ -243,6 +244,12 @@ int fine_encode_impl(t2l_ctx* ctx, const t2l_packed_cells* in, float* out, hipSt
 int fine_match_impl(t2l_ctx* ctx, const float* cell_desc, const int32_t* cell_index, const float* hint_desc, const int32_t* hint_index,
                     int n_pairs, int n_hints, float* out, hipStream_t s);
 void free_fine(t2l_ctx* ctx);
+// fine_train.hip
+int fine_train_bind_impl(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n, const t2l_model_config* cfg);
+int fine_train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, const float* pn_feat, const float* hint_desc, int n_pairs,
+                            int n_hints, float p, uint32_t seed, float* out, hipStream_t s);
+int fine_train_backward_impl(t2l_ctx* ctx, const float* grad_offsets, float* grad_hint, float* grad_pn, hipStream_t s);
+void free_fine_train(t2l_ctx* ctx);
 // text_head.hip
 int text_head_load_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const char* prefix);
 int text_head_impl(t2l_ctx* ctx, const float* hidden, int n_sentences, int n_tokens, float* out, int32_t* overflow, hipStream_t s);

@@ -85,6 +85,10 @@ EXPORTS = {
     "t2l_train_bind": (C.c_int, [C.c_void_p, C.POINTER(_TrainTensor), C.c_int32, C.POINTER(_ModelConfig)]),
     "t2l_encode_cells_train": (C.c_int, [C.c_void_p, C.POINTER(_PackedCells), C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]),
     "t2l_encode_cells_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "t2l_fine_train_bind": (C.c_int, [C.c_void_p, C.POINTER(_TrainTensor), C.c_int32, C.POINTER(_ModelConfig)]),
+    "t2l_fine_train_forward": (C.c_int, [C.c_void_p, C.POINTER(_PackedCells), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float,
+                                         C.c_uint32, C.c_void_p, C.c_void_p]),
+    "t2l_fine_train_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "t2l_text_train_bind": (C.c_int, [C.c_void_p, C.POINTER(_TrainTensor), C.c_int32, C.c_char_p]),
     "t2l_text_head_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]),
     "t2l_text_head_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -357,6 +361,42 @@ class Engine:
                                             self._ptr(hint_index, torch.int32, "hint_index"), n_pairs, int(hint_desc.shape[1]),
                                             out.data_ptr(), _stream_ptr(self.device)))
         return out
+
+    # ------------------------------------------------------------------ the fine stage in training mode (t2l_fine_train_*)
+    def fine_train_bind(self, tensors: Dict[str, Tuple[torch.Tensor, Optional[torch.Tensor]]], class_embed: bool, color_embed: bool,
+                        use_features=("class", "color", "position", "num"), num_layers: int = 2, num_heads: int = 4):
+        """tensors: state_dict key -> (live fp32 CUDA tensor, its gradient buffer, or None for a frozen parameter / BatchNorm buffer).
+        The engine keeps the POINTERS: keep the tensors alive and re-bind if they are re-allocated."""
+        descs, keep = [], []
+        for name, (data, grad) in tensors.items():
+            keep.append((data, grad))
+            descs.append(_TrainTensor(name.encode(), self._ptr(data, torch.float32, name),
+                                      self._ptr(grad, torch.float32, name + ".grad"), data.numel()))
+        arr = (_TrainTensor * len(descs))(*descs)
+        cfg = _ModelConfig(int(class_embed), int(color_embed), int("class" in use_features), int("color" in use_features),
+                           int("position" in use_features), int("num" in use_features), int(num_layers), int(num_heads))
+        self._check(self.lib.t2l_fine_train_bind(self._h, arr, len(descs), C.byref(cfg)))
+        self._fine_train_keepalive = keep
+
+    def fine_train_forward(self, packed: Dict[str, torch.Tensor], pn_feat: Optional[torch.Tensor], hint_desc: torch.Tensor,
+                           dropout_p: float = 0.1, seed: int = 0) -> torch.Tensor:
+        """packed cells of 16 objects each (one per pair), features2 f32[16*n_pairs,256] or None, hint encodings
+        f32[n_pairs,n_hints,128] -> offsets f32[n_pairs,2]. The inputs stay referenced until the next forward."""
+        pc = self._packed_struct(packed)
+        if hint_desc.dim() != 3 or hint_desc.shape[0] != pc.n_cells or hint_desc.shape[2] != 128:
+            raise T2LError(f"fine_train_forward: hint_desc must be [n_pairs={pc.n_cells},n_hints,128], got {tuple(hint_desc.shape)}")
+        out = torch.empty((pc.n_cells, 2), dtype=torch.float32, device=hint_desc.device)
+        self._check(self.lib.t2l_fine_train_forward(self._h, C.byref(pc), self._ptr(pn_feat, torch.float32, "pn_feat"),
+                                                    self._ptr(hint_desc, torch.float32, "hint_desc"), pc.n_cells, int(hint_desc.shape[1]),
+                                                    float(dropout_p), int(seed) & 0xFFFFFFFF, out.data_ptr(), _stream_ptr(self.device)))
+        self._fine_train_inputs = (packed, pn_feat, hint_desc)
+        return out
+
+    def fine_train_backward(self, grad_offsets: torch.Tensor, grad_hint_desc: Optional[torch.Tensor] = None,
+                            grad_pn_feat: Optional[torch.Tensor] = None):
+        self._check(self.lib.t2l_fine_train_backward(self._h, self._ptr(grad_offsets, torch.float32, "grad_offsets"),
+                                                     self._ptr(grad_hint_desc, torch.float32, "grad_hint_desc"),
+                                                     self._ptr(grad_pn_feat, torch.float32, "grad_pn_feat"), _stream_ptr(self.device)))
 
     # ------------------------------------------------------------------ training step (a9)
     def _packed_struct(self, packed: Dict[str, torch.Tensor]) -> "_PackedCells":

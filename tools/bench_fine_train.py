@@ -1,0 +1,134 @@
+"""ms per full training step of the fine stage downstream of the text branch (forward, offset_lambda * MSE, backward,
+torch.optim.Adam) on the engine (t2l_fine_train_*) and, beside it, the same step on PyTorch-ROCm: the package's CrossMatch
+parameter containers (nn.Linear / nn.BatchNorm1d / nn.TransformerDecoderLayer, float32, dropout 0.1) run as
+models/cross_matcher.py:86-135 runs them. Same weights, inputs and batch. Device events around `--iters` steps after
+`--warmup` steps; the median of `--reps` repetitions. Prints one JSON line.
+
+    python tools/bench_fine_train.py [--batches 32,256] [--iters 20] [--warmup 10] [--reps 5]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os.path as osp
+import sys
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, osp.dirname(osp.dirname(osp.abspath(__file__))))
+from text2loc_amd import synth  # noqa: E402
+from text2loc_amd.cross_matcher import CrossMatch  # noqa: E402
+from text2loc_amd.engine import Engine  # noqa: E402
+
+NUM_MEAN, NUM_STD = 1826.6844940968194, 2516.8905096993817
+LAMBDA = 5.0
+
+
+def make_args(embed):
+    return argparse.Namespace(fine_embed_dim=128, fine_num_decoder_heads=4, fine_num_decoder_layers=2, pad_size=16, num_mentioned=6,
+                              fine_intra_module_num_layers=1, fine_intra_module_num_heads=4, hungging_model=None, fixed_embedding=True,
+                              class_embed=embed, color_embed=embed, pointnet_freeze=True, use_features=["class", "color", "position", "num"])
+
+
+def problem(embed, B, H=6):
+    model = CrossMatch(synth.KNOWN_CLASS, synth.COLOR_NAMES, make_args(embed), language_encoder=torch.nn.Identity())
+    model.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in synth.make_fine_weights(0).items()}, strict=False)
+    model = model.cuda().train()
+    cells = synth.make_cells(B, seed=1, min_obj=16, max_obj=16)
+    packed = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in cells.items() if k != "counts"}
+    rng = np.random.default_rng(2)
+    hints = torch.from_numpy(rng.standard_normal((B, H, 128)).astype(np.float32)).cuda()
+    pn = None if embed else torch.from_numpy(np.abs(rng.standard_normal((B * 16, 256))).astype(np.float32)).cuda()
+    target = torch.from_numpy(rng.random((B, 2)).astype(np.float32)).cuda()
+    return model, packed, hints, pn, target
+
+
+def torch_forward(model, packed, hints, pn):
+    a, oe = model.args, model.object_encoder
+    emb = [F.normalize(oe.class_embedding(packed["class_idx"].long()) if a.class_embed else oe.mlp_pointnet(pn), dim=-1),
+           F.normalize(oe.color_embedding(packed["color_idx"].long()) if a.color_embed else oe.color_encoder(packed["rgb"]), dim=-1),
+           F.normalize(oe.pos_encoder(packed["center"]), dim=-1),
+           F.normalize(oe.num_encoder(((packed["n_pts"] - NUM_MEAN) / NUM_STD)[:, None]), dim=-1)]
+    obj = F.normalize(oe.mlp_merge(torch.cat(emb, -1)), dim=-1).reshape(hints.shape[0], 16, 128).transpose(0, 1)
+    hint = hints.transpose(0, 1)
+    for i in range(a.fine_num_decoder_layers):
+        obj = model.cross_objects[i](obj, hint)
+        hint = model.cross_hints[i](hint, obj)
+    return model.mlp_offsets(hint.max(dim=0).values)
+
+
+def time_steps(step, iters, warmup, reps):
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(iters):
+            step()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b) / iters)
+    return float(np.median(ms))
+
+
+def bench(embed, B, iters, warmup, reps):
+    model, packed, hints, pn, target = problem(embed, B)
+    params = [p for p in model.parameters() if p.requires_grad]
+    # ---- engine: t2l_fine_train_forward / _backward on the live tensors, torch's MSE and Adam around them
+    eng = Engine(torch.cuda.current_device())
+    run, with_grad = model._fine_train_modules()
+    tensors = model._fine_train_tensors()
+    eng.fine_train_bind(tensors, class_embed=embed, color_embed=embed, use_features=tuple(model.args.use_features), num_layers=2)
+    opt_e = torch.optim.Adam([p for n, p in model.named_parameters() if p.grad is not None], lr=1e-4)
+    gh = torch.empty_like(hints)
+    gp = None if pn is None else torch.empty_like(pn)
+    seed = [0]
+
+    def engine_step():
+        opt_e.zero_grad(set_to_none=False)
+        seed[0] += 1
+        out = eng.fine_train_forward(packed, pn, hints, dropout_p=0.1, seed=seed[0]).requires_grad_(True)
+        loss = LAMBDA * F.mse_loss(out, target)
+        loss.backward()
+        eng.fine_train_backward(out.grad, gh, gp)
+        opt_e.step()
+
+    ms_engine = time_steps(engine_step, iters, warmup, reps)
+    eng.close()
+    # ---- PyTorch-ROCm: the same step through torch's own modules (fresh copy of the weights)
+    model2, _, _, _, _ = problem(embed, B)
+    h_leaf = hints.clone().requires_grad_(True)
+    pn_leaf = None if pn is None else pn.clone().requires_grad_(True)
+    opt_t = torch.optim.Adam([p for p in model2.parameters() if p.requires_grad], lr=1e-4)
+
+    def torch_step():
+        opt_t.zero_grad(set_to_none=False)
+        loss = LAMBDA * F.mse_loss(torch_forward(model2, packed, h_leaf, pn_leaf), target)
+        loss.backward()
+        opt_t.step()
+
+    ms_torch = time_steps(torch_step, iters, warmup, reps)
+    del params
+    return {"mode": "embed" if embed else "features2", "B": B, "ms_engine": round(ms_engine, 4), "ms_pytorch": round(ms_torch, 4),
+            "speedup": round(ms_torch / ms_engine, 3)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="32,256")
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--reps", type=int, default=5)
+    a = ap.parse_args()
+    torch.manual_seed(0)
+    rows = [bench(embed, int(B), a.iters, a.warmup, a.reps) for embed in (True, False) for B in a.batches.split(",")]
+    print(json.dumps({"metric": "fine-stage training step (fwd + offset_lambda*MSE + bwd + Adam), L=2, 6 hints, dropout 0.1",
+                      "unit": "ms/step", "rows": rows}))
+
+
+if __name__ == "__main__":
+    main()
