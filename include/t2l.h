@@ -357,13 +357,19 @@ int t2l_zero_grad(t2l_ctx* ctx, void* stream);
  *
  * t2l_fine_train_bind: t2l_train_tensor entries (live data / grad pointers, the a9 convention) named as in the fine checkpoint:
  * object_encoder.* at fine_embed_dim 128 for the configured features — class_embedding.weight (class_embed) or mlp_pointnet.0.*
- * (features2 supplied by the caller; the PointNet++ backbone is not part of this step), color_embedding.weight or color_encoder.*,
+ * (features2 from the caller, or from the PointNet++ backbone below), color_embedding.weight or color_encoder.*,
  * pos_encoder.*, num_encoder.*, mlp_merge.0.* (more than one feature); with class_embed == 0 mlp_pointnet.0.* is needed even without
  * use_class (the reference runs it anyway: its BatchNorm statistics move, nothing else depends on it) — with the BatchNorm1d buffers ("...1.running_mean",
  * "...1.running_var", no grad); cross_objects.{i}.* and cross_hints.{i}.* (i < cfg->num_layers), or cross_hints.* alone when
  * num_layers == 0 (models/cross_matcher.py:75-79); mlp_offsets.{0,2}.*. A missing tensor or a wrong element count is T2L_EINVAL;
  * a parameter bound with grad = NULL is frozen (gets no gradient). cfg->num_heads must be 4. Pointers must stay valid until the
- * next bind. Synchronous. */
+ * next bind. Synchronous.
+ * Optionally (class_embed == 0 only; T2L_EINVAL otherwise) the PointNet++ backbone's object_encoder.pointnet.* group, under the
+ * names and rule of t2l_train_bind: every {sa1,sa2,sa3}.point_conv.local_nn.* / ga.mlp.* / lin1.* / lin2.* tensor, all WITH gradient
+ * buffers (trained jointly: the published fine command passes no --pointnet_freeze) or all WITHOUT (--pointnet_freeze), plus the
+ * BatchNorm running buffers; the classifier heads are ignored. It enables t2l_fine_train_forward_points. The fine stage's backbone
+ * state is its own: binding or running the coarse step (t2l_train_bind, t2l_pointnet_features_train) does not touch it, nor the
+ * reverse. Without the group nothing changes. */
 int t2l_fine_train_bind(t2l_ctx* ctx, const t2l_train_tensor* tensors, int32_t n, const t2l_model_config* cfg);
 
 /* The training-mode forward of n_pairs (pose, cell) pairs — one per batch entry, as training/fine.py:51-55 batches them.
@@ -381,9 +387,24 @@ int t2l_fine_train_bind(t2l_ctx* ctx, const t2l_train_tensor* tensors, int32_t n
 int t2l_fine_train_forward(t2l_ctx* ctx, const t2l_packed_cells* in, const float* pn_feat, const float* hint_desc, int32_t n_pairs,
                            int32_t n_hints, float dropout_p, uint32_t seed, float* out_offsets, void* stream);
 
+/* The same forward with features2 from the PointNet++ backbone (bound by t2l_fine_train_bind) on the pairs' point batches, as the
+ * reference's ObjectEncoder computes it without --class_embed (models/object_encoder.py:86-99). pos, rgb: dev f32[16*n_pairs,256,3],
+ * object-major, the 16 objects of each pair pads included. The backbone runs in training mode with the segmentation of
+ * t2l_pointnet_features_train: one cell = one pair = 16 objects, so every BatchNorm1d of the backbone uses that pair's rows and its
+ * running statistics are updated once per pair, in pair order (the reference calls the backbone once per cell; the caller bumps
+ * num_batches_tracked by n_pairs). This happens whether the backbone is trained or frozen, and also when "class" is not among the
+ * features (the reference still runs it and mlp_pointnet; only their statistics move). features2 stays in a context-owned buffer
+ * and feeds the forward above; train_bf16 applies to the backbone as in the coarse step. The backbone's activations stay in the
+ * context until the next forward; pos and rgb need not outlive this call. PARITY UNPINNED like t2l_pointnet_features. */
+int t2l_fine_train_forward_points(t2l_ctx* ctx, const t2l_packed_cells* in, const float* pos, const float* rgb, const float* hint_desc,
+                                  int32_t n_pairs, int32_t n_hints, float dropout_p, uint32_t seed, float* out_offsets, void* stream);
+
 /* loss.backward() through the last forward: grad_offsets dev f32[n_pairs,2] (the MSE gradient from torch). Parameter gradients
  * are ADDED to the bound grad buffers (float atomics: the last bits vary between runs); grad_hint_desc dev f32[n_pairs,n_hints,128]
- * and grad_pn_feat dev f32[16*n_pairs,256] are written when non-NULL. May run more than once per forward (each call adds again). */
+ * and grad_pn_feat dev f32[16*n_pairs,256] are written when non-NULL. May run more than once per forward (each call adds again).
+ * After t2l_fine_train_forward_points with the backbone bound WITH gradient buffers and "class" among the features, the backward
+ * continues through the backbone and adds its parameter gradients to its bound buffers too; a frozen backbone, a forward fed
+ * features2 by the caller, or features2 feeding mlp_pointnet's statistics only leave the backbone's buffers untouched. */
 int t2l_fine_train_backward(t2l_ctx* ctx, const float* grad_offsets, float* grad_hint_desc, float* grad_pn_feat, void* stream);
 
 /* ---- the text head in TRAINING mode (f-4 / the text half of a9) ---------------------------------- */

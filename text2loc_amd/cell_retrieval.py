@@ -82,6 +82,29 @@ class PointNet2Params(nn.Module):
         self.color_classifier = nn.Linear(256, num_colors)
 
 
+def _point_field(p, name):
+    return p[name] if isinstance(p, dict) else getattr(p, name, None)
+
+
+def is_point_batch(p) -> bool:
+    """A cell's point batch as the reference's dataloader builds it: a PyG ``Batch`` or anything with ``.pos`` / ``.x``
+    [n*256,3], or a dict with those keys (anything else in ``object_points`` is a precomputed features2 array / tensor)."""
+    return not isinstance(p, (torch.Tensor, np.ndarray)) and _point_field(p, "pos") is not None
+
+
+def point_batch_tensors(object_points, use_color: bool, dev):
+    """Per-cell point batches -> (pos f32[n,256,3], rgb f32[n,256,3], objects per cell) on ``dev``. Without ``use_color`` the
+    colours are voided, as the reference's ObjectEncoder does (object_encoder.py:87-90); the caller's arrays are not touched."""
+    if use_color:
+        xs = [torch.as_tensor(_point_field(p, "x")) for p in object_points]
+    else:  # ablation of the reference: void all colours (object_encoder.py:87-90)
+        xs = [torch.zeros_like(torch.as_tensor(_point_field(p, "x"))) for p in object_points]
+    pos = torch.cat([torch.as_tensor(_point_field(p, "pos")).reshape(-1, 256, 3) for p in object_points]).to(dev, torch.float32)
+    rgb = torch.cat([x.reshape(-1, 256, 3) for x in xs]).to(dev, torch.float32)
+    counts = [int(torch.as_tensor(_point_field(p, "pos")).shape[0]) // 256 for p in object_points]
+    return pos.contiguous(), rgb.contiguous(), counts
+
+
 class ObjectEncoderParams(nn.Module):
     """Parameters of models/object_encoder.py:28-64 under the same names (PointNet++ sub-module excluded)."""
 
@@ -606,25 +629,15 @@ class CellRetrievalNetwork(nn.Module):
             raise T2LError("class_embed is off: object_points must hold, per cell, PointNet++ features2 [n_i,256] or the "
                            "cell's point batch (.pos/.x [n_i*256,3])")
         dev = self.device
-
-        def field(p, name):
-            return p[name] if isinstance(p, dict) else getattr(p, name, None)
-
-        if all(field(p, "pos") is not None for p in object_points if not isinstance(p, (torch.Tensor, np.ndarray))) and \
+        if all(_point_field(p, "pos") is not None for p in object_points if not isinstance(p, (torch.Tensor, np.ndarray))) and \
                 not isinstance(object_points[0], (torch.Tensor, np.ndarray)):
-            if "color" not in a.use_features:  # ablation of the reference: void all colours (object_encoder.py:87-90)
-                xs = [torch.zeros_like(torch.as_tensor(field(p, "x"))) for p in object_points]
-            else:
-                xs = [torch.as_tensor(field(p, "x")) for p in object_points]
-            pos = torch.cat([torch.as_tensor(field(p, "pos")).reshape(-1, 256, 3) for p in object_points]).to(dev, torch.float32)
-            rgb = torch.cat([x.reshape(-1, 256, 3) for x in xs]).to(dev, torch.float32)
-            counts = [int(torch.as_tensor(field(p, "pos")).shape[0]) // 256 for p in object_points]
+            pos, rgb, counts = point_batch_tensors(object_points, "color" in a.use_features, dev)
             offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
             if train:
                 self._pn_in_engine = any(p.requires_grad for p in self.object_encoder.pointnet.lin2.parameters())
                 self._pn_train_cells = len(counts)
-                return eng.pointnet_features_train(pos.contiguous(), rgb.contiguous(), offs)
-            return eng.pointnet_features(pos.contiguous(), rgb.contiguous(), offs)
+                return eng.pointnet_features_train(pos, rgb, offs)
+            return eng.pointnet_features(pos, rgb, offs)
         return torch.cat([p if isinstance(p, torch.Tensor) else torch.as_tensor(np.asarray(p)) for p in object_points],
                          dim=0).to(dev, torch.float32).reshape(-1, 256)
 

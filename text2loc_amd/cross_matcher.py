@@ -16,7 +16,16 @@ Under ``model.train()``, ``forward`` is one training step's forward in the engin
 batch's objects, the decoder layers' dropout, and a backward that adds every parameter gradient straight into the live
 ``.grad`` tensors and hands d loss / d hint encodings (and d features2) back to autograd, so ``loss.backward()`` continues into
 the text branch and ``torch.optim.Adam(model.parameters())`` steps everything (training/fine.py:38-91). ``encode_cells`` /
-``match`` stay eval-only; the PointNet++ backbone is not trained here (features2 must be supplied as tensors).
+``match`` stay eval-only.
+
+With class_embed off (the published fine command) ``object_points`` holds per cell EITHER features2 [16,256] as tensors OR the
+cell's point batch (``.pos`` / ``.x`` [16*256,3], or a dict with those keys, as ``CellRetrievalNetwork`` takes them). Point
+batches run the PointNet++ backbone in the engine in training mode, one call per cell as in the reference (per-cell BatchNorm
+statistics; its running statistics move once per cell and ``num_batches_tracked`` by B), and the backward continues into it:
+trained jointly unless ``--pointnet_freeze``, in which case only its forward runs. Backbone parameters get their ``.grad`` only
+from a backward that went through the backbone; a step fed features2 tensors leaves them at None, so optimizers skip them.
+Parity of the backbone with torch_geometric stays unpinned (self-consistent with the build's own restatement only), as for
+the coarse stage's backbone.
 """
 from __future__ import annotations
 
@@ -28,10 +37,12 @@ import torch
 import torch.nn as nn
 
 from . import packing
-from .cell_retrieval import LanguageEncoder, ObjectEncoderParams
+from .cell_retrieval import LanguageEncoder, ObjectEncoderParams, is_point_batch, point_batch_tensors
 from .engine import Engine, T2LError
 
 FINE_DIM, PAD_SIZE = 128, 16
+BACKBONE = "object_encoder.pointnet."
+_HEADS = (BACKBONE + "class_classifier.", BACKBONE + "color_classifier.")  # PointNet2's classifiers: not on the features2 path
 
 
 def get_mlp_offset(dims: List[int]) -> nn.Sequential:
@@ -101,6 +112,7 @@ class CrossMatch(nn.Module):
         self._fine_train_grads = {}
         self._fine_train_token = None
         self._fine_train_hook = None
+        self._fine_train_pn_live = []  # (backbone parameter, its bound gradient buffer) of the last bind that trains the backbone
 
     @property
     def device(self):
@@ -181,14 +193,17 @@ class CrossMatch(nn.Module):
     # ---- training mode ------------------------------------------------------------------------------------
     def _fine_train_modules(self):
         """(prefixes of the modules the engine step runs, prefixes of those whose parameters receive a gradient) — the
-        ObjectEncoder branches of args.use_features (object_encoder.py:102-149), plus mlp_pointnet whenever class_embed is off:
-        the reference runs it then even without "class" (object_encoder.py:86-99), which moves its BatchNorm statistics only."""
+        ObjectEncoder branches of args.use_features (object_encoder.py:102-149), plus mlp_pointnet and the PointNet++ backbone
+        whenever class_embed is off: the reference runs them then even without "class" (object_encoder.py:86-99), which moves
+        their BatchNorm statistics only. (The backbone runs only on point batches; its classifier heads never do.)"""
         a = self.args
         ce, co = bool(getattr(a, "class_embed", False)), bool(getattr(a, "color_embed", False))
         oe = "object_encoder."
         grad = ["cross_hints.", "cross_objects.", "mlp_offsets."]
         if "class" in a.use_features:
             grad.append(oe + ("class_embedding." if ce else "mlp_pointnet."))
+            if not ce:
+                grad.append(BACKBONE)
         if "color" in a.use_features:
             grad.append(oe + ("color_embedding." if co else "color_encoder."))
         if "position" in a.use_features:
@@ -197,16 +212,18 @@ class CrossMatch(nn.Module):
             grad.append(oe + "num_encoder.")
         if len(a.use_features) > 1:
             grad.append(oe + "mlp_merge.")
-        run = grad + ([oe + "mlp_pointnet."] if not ce else [])
+        run = grad + ([oe + "mlp_pointnet.", BACKBONE] if not ce else [])
         return tuple(run), tuple(grad)
 
     def _fine_train_tensors(self):
         """state_dict key -> (live tensor, persistent .grad buffer or None) for everything the engine step reads. Only the
-        parameters the step differentiates get a .grad (the others stay None, as in the reference, and optimizers skip them)."""
+        parameters the step differentiates get a .grad (the others stay None, as in the reference, and optimizers skip them).
+        The backbone's buffers are handed out as .grad by the backward that goes through the backbone (_FineTrainFn), not here."""
         run, with_grad = self._fine_train_modules()
         out = {}
+        self._fine_train_pn_live = []
         for n, t in self.named_parameters():
-            if not n.startswith(run):
+            if not n.startswith(run) or n.startswith(_HEADS):
                 continue
             if not t.requires_grad or not n.startswith(with_grad):
                 out[n] = (t.data, None)  # frozen: no gradient
@@ -214,7 +231,9 @@ class CrossMatch(nn.Module):
             g = self._fine_train_grads.get(n)
             if g is None or g.shape != t.shape or g.device != t.device:
                 g = self._fine_train_grads[n] = torch.zeros_like(t.data)
-            if t.grad is None:
+            if n.startswith(BACKBONE):
+                self._fine_train_pn_live.append((t, g))
+            elif t.grad is None:
                 t.grad = g  # hand the persistent buffer back (zero_grad(set_to_none=True) only drops the reference)
                 g.zero_()
             elif t.grad.data_ptr() != g.data_ptr():
@@ -256,18 +275,32 @@ class CrossMatch(nn.Module):
             raise T2LError(f"every cell must hold exactly pad_size={PAD_SIZE} objects (cross_matcher.pad_objects pads / cuts)")
         a = self.args
         want_pn = not bool(getattr(a, "class_embed", False))  # object_encoder.py:86-99: features2 whenever class_embed is off
+        points = False
         if want_pn:
             if object_points is None or any(p is None for p in object_points):
-                raise T2LError("class_embed is off: object_points must hold, per cell, features2 [16,256]")
-            if not all(isinstance(p, (torch.Tensor, np.ndarray)) for p in object_points):
+                raise T2LError("class_embed is off: object_points must hold, per cell, features2 [16,256] or the cell's point batch "
+                               "(.pos/.x [16*256,3])")
+            kinds = {is_point_batch(p) for p in object_points}
+            if len(kinds) > 1:
+                raise T2LError("object_points mixes point batches and features2 tensors: pass one kind for every cell")
+            points = kinds == {True}
+            if points and self.device.type != "cuda":
                 raise T2LError("training the fine stage on point batches needs the jointly trained PointNet++ backbone, which is not "
-                               "built for the fine stage: pass features2 [16,256] per cell as tensors")
+                               "built for the fine stage on the host: it runs on the MI355X only (model.to('cuda')); there is no CPU fallback")
         p_drop = self._fine_train_dropout()                         # nn.TransformerDecoderLayer default 0.1
         dev = self.device
         if dev.type != "cuda":
             raise T2LError("the fine stage runs on the MI355X only (model.to('cuda')); there is no CPU fallback")
-        pn = None
-        if want_pn:
+        pn = pts = None
+        if points:
+            get = lambda p, n: p[n] if isinstance(p, dict) else getattr(p, n, None)
+            for p in object_points:
+                shapes = [tuple(np.shape(get(p, n))) if get(p, n) is not None else None for n in ("pos", "x")]
+                if any(sh != (PAD_SIZE * 256, 3) for sh in shapes):
+                    raise T2LError(f"a point batch must hold {PAD_SIZE}*256 points per cell (.pos and .x [{PAD_SIZE * 256},3]), got {shapes}")
+            pos, rgb, _ = point_batch_tensors(object_points, "color" in a.use_features, dev)
+            pts = (pos, rgb)
+        elif want_pn:
             pn = torch.cat([p if isinstance(p, torch.Tensor) else torch.from_numpy(np.asarray(p)) for p in object_points]).to(dev, torch.float32)
             if tuple(pn.shape) != (len(objects) * PAD_SIZE, 256):
                 raise T2LError(f"features2 must be [16,256] per cell, got {tuple(pn.shape)} in all")
@@ -283,10 +316,16 @@ class CrossMatch(nn.Module):
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())        # torch.manual_seed governs the masks
         if self._fine_train_hook is None or self._fine_train_hook.device != dev:
             self._fine_train_hook = torch.zeros(1, device=dev, requires_grad=True)
-        out = _FineTrainFn.apply(self._fine_train_hook, hint_enc, pn, self, packed, p_drop, seed)
+        out = _FineTrainFn.apply(self._fine_train_hook, hint_enc, pn, self, packed, p_drop, seed, pts)
         run, _ = self._fine_train_modules()
         for name, m in self.object_encoder.named_modules():  # BatchNorm1d.train() side effect the engine does not see (int64)
-            if isinstance(m, nn.BatchNorm1d) and m.num_batches_tracked is not None and f"object_encoder.{name}.".startswith(run):
+            full = f"object_encoder.{name}."
+            if not (isinstance(m, nn.BatchNorm1d) and m.num_batches_tracked is not None and full.startswith(run)):
+                continue
+            if full.startswith(BACKBONE):
+                if points:
+                    m.num_batches_tracked += len(objects)  # one backbone call per cell in the reference (object_encoder.py:92-95)
+            else:
                 m.num_batches_tracked += 1
         self._train_generation += 1  # running statistics moved: the eval path must re-load its weights
         return out
@@ -296,17 +335,22 @@ class _FineTrainFn(torch.autograd.Function):
     """Training-mode CrossMatch downstream of the text branch: forward and backward are HIP (t2l_fine_train_forward /
     _backward). Parameter gradients do not flow through autograd: the engine adds them straight into the bound ``.grad``
     buffers; the differentiable inputs are the hint encodings and features2 (``hook`` is a dummy leaf that makes autograd call
-    ``backward`` even when neither requires grad)."""
+    ``backward`` even when neither requires grad). ``pts`` = (pos, rgb): features2 comes from the backbone's training-mode
+    forward instead, and the backward continues into it when it trains."""
 
     @staticmethod
-    def forward(ctx, hook, hint_enc, pn, model, packed, p_drop, seed):
+    def forward(ctx, hook, hint_enc, pn, model, packed, p_drop, seed, pts=None):
         hint_c = hint_enc.detach().float().contiguous()
         pn_c = None if pn is None else pn.detach().contiguous()
-        out = model._engine.fine_train_forward(packed, pn_c, hint_c, dropout_p=p_drop, seed=seed)
+        if pts is not None:
+            out = model._engine.fine_train_forward_points(packed, pts[0], pts[1], hint_c, dropout_p=p_drop, seed=seed)
+        else:
+            out = model._engine.fine_train_forward(packed, pn_c, hint_c, dropout_p=p_drop, seed=seed)
         ctx.model = model
         ctx.token = model._fine_train_token = object()
         ctx.hint_shape, ctx.hint_dtype = hint_c.shape, hint_enc.dtype
         ctx.pn_shape = None if pn is None else pn_c.shape
+        ctx.pn_live = list(model._fine_train_pn_live) if pts is not None else []  # the backbone's backward will run
         return out
 
     @staticmethod
@@ -318,8 +362,15 @@ class _FineTrainFn(torch.autograd.Function):
         need_hint, need_pn = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         gh = torch.empty(ctx.hint_shape, dtype=torch.float32, device=grad_out.device) if need_hint else None
         gp = torch.empty(ctx.pn_shape, dtype=torch.float32, device=grad_out.device) if need_pn else None
+        for t, g in ctx.pn_live:  # the engine ADDS into the bound buffers: give them the value .grad has now
+            if t.grad is None:
+                g.zero_()
+            elif t.grad.data_ptr() != g.data_ptr():
+                g.copy_(t.grad)
         model._engine.fine_train_backward(grad_out.contiguous().float(), gh, gp)
-        return None, (gh.to(ctx.hint_dtype) if gh is not None else None), gp, None, None, None, None
+        for t, g in ctx.pn_live:
+            t.grad = g
+        return None, (gh.to(ctx.hint_dtype) if gh is not None else None), gp, None, None, None, None, None
 
 
 @torch.no_grad()

@@ -430,6 +430,13 @@ int t2l_fine_train_forward(t2l_ctx* ctx, const t2l_packed_cells* in, const float
   return fine_train_forward_impl(ctx, in, pn_feat, hint_desc, n_pairs, n_hints, dropout_p, seed, out_offsets, (hipStream_t)stream);
 }
 
+int t2l_fine_train_forward_points(t2l_ctx* ctx, const t2l_packed_cells* in, const float* pos, const float* rgb, const float* hint_desc,
+                                  int32_t n_pairs, int32_t n_hints, float dropout_p, uint32_t seed, float* out_offsets, void* stream) {
+  if (!ctx) return T2L_EINVAL;
+  T2L_HIP(ctx, hipSetDevice(ctx->device));
+  return fine_train_forward_points_impl(ctx, in, pos, rgb, hint_desc, n_pairs, n_hints, dropout_p, seed, out_offsets, (hipStream_t)stream);
+}
+
 int t2l_fine_train_backward(t2l_ctx* ctx, const float* grad_offsets, float* grad_hint_desc, float* grad_pn_feat, void* stream) {
   if (!ctx) return T2L_EINVAL;
   T2L_HIP(ctx, hipSetDevice(ctx->device));

@@ -1,10 +1,15 @@
 // Fine stage under model.train(): one training step of CrossMatch downstream of the text branch
 // (models/cross_matcher.py:86-135, training/fine.py:38-91) —
-//   t2l_fine_train_bind     : live data / grad pointers of object_encoder.* (no backbone), cross_objects.*, cross_hints.*, mlp_offsets.*
+//   t2l_fine_train_bind     : live data / grad pointers of object_encoder.* (optionally with the PointNet++ backbone's
+//                             object_encoder.pointnet.* group, class_embed == 0), cross_objects.*, cross_hints.*, mlp_offsets.*
 //   t2l_fine_train_forward  : ObjectEncoder at d = 128 with batch-statistics BatchNorm (running buffers updated in place) +
 //                             F.normalize, the CCAT cascade with the six dropout sites of every nn.TransformerDecoderLayer, max over
 //                             the hints (arg-max kept), mlp_offsets
-//   t2l_fine_train_backward : d offsets -> parameter gradients ADDED into the bound .grad buffers, d hint encodings, d features2
+//   t2l_fine_train_forward_points : the same, with features2 from the backbone's training-mode forward on the pairs' point
+//                             batches (one cell = one pair = 16 objects: pointnet_train.h, the coarse step's backbone code on a
+//                             state of this context's own)
+//   t2l_fine_train_backward : d offsets -> parameter gradients ADDED into the bound .grad buffers, d hint encodings, d features2,
+//                             and on through the backbone after a points forward when it is bound with gradients
 // Everything is f32 on the vector ALU: a row-major tiled GEMM (64x64 tiles, strided operands so one kernel serves X·Wᵀ, dY·W and
 // the weight gradients dYᵀ·X, the latter split over the rows with float atomics), one workgroup per (pair, head) for attention
 // forward / backward, one wave per 128-wide row for residual + dropout + LayerNorm and F.normalize, one workgroup per column for
@@ -482,8 +487,10 @@ struct FineTrain {
   BnLayer pn_only;        // ... for its BatchNorm running statistics only (its output is unused: no gradient)
   std::vector<DecLayer> dec;  // cascade order: cross_objects.0, cross_hints.0, cross_objects.1, ... (or cross_hints alone)
   Ten o0w, o0b, o2w, o2b;
+  PnTrain* pn = nullptr;  // the PointNet++ backbone's training state (object_encoder.pointnet.* bound), or null
   // the last forward
   bool have_fwd = false;
+  bool pn_fwd = false;    // ... took features2 from the backbone (t2l_fine_train_forward_points)
   int P = 0, H = 0;
   float p = 0.f;
   uint32_t seed = 0;
@@ -493,6 +500,7 @@ struct FineTrain {
   int32_t* arg = nullptr;
   // backward scratch
   float *gA0, *gB0, *gA1, *gB1, *t_dx1, *t_dx2, *t_ds, *t_do, *t_dq, *t_dkv, *t_dh, *dE, *ta, *tb, *dpool, *da1;
+  float* dpn = nullptr;  // d features2 on its way into the backbone's backward (when the caller passes no grad_pn_feat)
   char* arena = nullptr;
   size_t cap = 0;
 };
@@ -500,6 +508,7 @@ struct FineTrain {
 static void free_ft(FineTrain* st) {
   if (!st) return;
   if (st->arena) (void)hipFree(st->arena);
+  pn_train_release(st->pn);
   delete st;
 }
 
@@ -625,6 +634,7 @@ static void plan(FineTrain* st, Bump& a, int P, int H, float p) {
   st->tb = a.take<float>((int64_t)M0 * 256);
   st->dpool = a.take<float>((int64_t)P * kW);
   st->da1 = a.take<float>((int64_t)P * 64);
+  st->dpn = st->pn ? a.take<float>((int64_t)M0 * 256) : nullptr;
 }
 
 static void add_ln(hipStream_t s, const float* X, const float* S, int M, const Ten& g, const Ten& b, Drop dr, float* xh, float* r, float* Y) {
@@ -829,9 +839,39 @@ int fine_train_bind_impl(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n, c
     free_ft(st);
     return fail(ctx, T2L_EINVAL, err);
   }
+  // the backbone: bound completely (trained, or frozen: no gradient buffers) or not at all; the classifier heads are ignored
+  if (int rc = pn_train_bind_group(ctx, tensors, n, "fine_train_bind", &st->pn)) {
+    free_ft(st);
+    return rc;
+  }
+  if (st->pn && cfg->class_embed) {
+    free_ft(st);
+    return fail(ctx, T2L_EINVAL, "fine_train_bind: object_encoder.pointnet.* is bound only with class_embed == 0 (class_embed looks the "
+                                 "classes up instead of running the backbone)");
+  }
   T2L_HIP(ctx, hipDeviceSynchronize());  // the previous state's arena may still be in use
   free_fine_train(ctx);
   ctx->fine_train = st;
+  return T2L_OK;
+}
+
+// the arguments of a forward (have_pn: features2 arrives, from the caller or from the backbone)
+static int check_forward(t2l_ctx* ctx, const FineTrain* st, const t2l_packed_cells* in, bool have_pn, const float* hint_desc, int n_pairs,
+                         int n_hints, float p, const float* out) {
+  if (!in || !hint_desc || !out) return fail(ctx, T2L_EINVAL, "fine_train_forward: null input / hint_desc / out_offsets");
+  if (n_pairs < 1) return fail(ctx, T2L_EINVAL, "fine_train_forward: n_pairs must be >= 1");
+  if (n_hints < 1 || n_hints > kHintMax) return fail(ctx, T2L_EINVAL, "fine_train_forward: n_hints must be 1..8");
+  if (in->n_cells != n_pairs || in->n_objects != n_pairs * kObj)
+    return fail(ctx, T2L_EINVAL, "fine_train_forward: one padded cell of exactly 16 objects per pair");
+  if (!(p >= 0.f && p < 1.f)) return fail(ctx, T2L_EINVAL, "fine_train_forward: dropout_p must be in [0, 1)");
+  const Branch* b = st->br;
+  if (((b[0].used && !b[0].embed) || st->pn_stats) && !have_pn)
+    return fail(ctx, T2L_EINVAL, "fine_train_forward: class_embed is off: pn_feat is required");
+  if (b[0].used && b[0].embed && !in->class_idx) return fail(ctx, T2L_EINVAL, "fine_train_forward: class_idx is required");
+  if (b[1].used && b[1].embed && !in->color_idx) return fail(ctx, T2L_EINVAL, "fine_train_forward: color_idx is required");
+  if (b[1].used && !b[1].embed && !in->rgb) return fail(ctx, T2L_EINVAL, "fine_train_forward: rgb is required");
+  if (b[2].used && !in->center) return fail(ctx, T2L_EINVAL, "fine_train_forward: center is required");
+  if (b[3].used && !in->n_pts) return fail(ctx, T2L_EINVAL, "fine_train_forward: n_pts is required");
   return T2L_OK;
 }
 
@@ -839,22 +879,10 @@ int fine_train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, const floa
                             int n_hints, float p, uint32_t seed, float* out, hipStream_t s) {
   auto* st = (FineTrain*)ctx->fine_train;
   if (!st) return fail(ctx, T2L_ESTATE, "fine_train_forward: call t2l_fine_train_bind first");
-  if (!in || !hint_desc || !out) return fail(ctx, T2L_EINVAL, "fine_train_forward: null input / hint_desc / out_offsets");
-  if (n_pairs < 1) return fail(ctx, T2L_EINVAL, "fine_train_forward: n_pairs must be >= 1");
-  if (n_hints < 1 || n_hints > kHintMax) return fail(ctx, T2L_EINVAL, "fine_train_forward: n_hints must be 1..8");
-  if (in->n_cells != n_pairs || in->n_objects != n_pairs * kObj)
-    return fail(ctx, T2L_EINVAL, "fine_train_forward: one padded cell of exactly 16 objects per pair");
-  if (!(p >= 0.f && p < 1.f)) return fail(ctx, T2L_EINVAL, "fine_train_forward: dropout_p must be in [0, 1)");
-  if (!pn_feat) pn_feat = in->pn_feat;
-  const Branch* b = st->br;
-  if (((b[0].used && !b[0].embed) || st->pn_stats) && !pn_feat)
-    return fail(ctx, T2L_EINVAL, "fine_train_forward: class_embed is off: pn_feat is required");
-  if (b[0].used && b[0].embed && !in->class_idx) return fail(ctx, T2L_EINVAL, "fine_train_forward: class_idx is required");
-  if (b[1].used && b[1].embed && !in->color_idx) return fail(ctx, T2L_EINVAL, "fine_train_forward: color_idx is required");
-  if (b[1].used && !b[1].embed && !in->rgb) return fail(ctx, T2L_EINVAL, "fine_train_forward: rgb is required");
-  if (b[2].used && !in->center) return fail(ctx, T2L_EINVAL, "fine_train_forward: center is required");
-  if (b[3].used && !in->n_pts) return fail(ctx, T2L_EINVAL, "fine_train_forward: n_pts is required");
+  if (!pn_feat && in) pn_feat = in->pn_feat;
+  if (int rc = check_forward(ctx, st, in, pn_feat != nullptr, hint_desc, n_pairs, n_hints, p, out)) return rc;
   st->have_fwd = false;
+  st->pn_fwd = false;
   st->P = n_pairs;
   st->H = n_hints;
   for (auto& L : st->dec) {
@@ -930,6 +958,27 @@ int fine_train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, const floa
   return T2L_OK;
 }
 
+int fine_train_forward_points_impl(t2l_ctx* ctx, const t2l_packed_cells* in, const float* pos, const float* rgb, const float* hint_desc,
+                                   int n_pairs, int n_hints, float p, uint32_t seed, float* out, hipStream_t s) {
+  auto* st = (FineTrain*)ctx->fine_train;
+  if (!st) return fail(ctx, T2L_ESTATE, "fine_train_forward_points: call t2l_fine_train_bind first");
+  if (!st->pn)
+    return fail(ctx, T2L_ESTATE, "fine_train_forward_points: the PointNet++ backbone is not bound (object_encoder.pointnet.* in "
+                                 "t2l_fine_train_bind, class_embed == 0)");
+  if (!pos || !rgb) return fail(ctx, T2L_EINVAL, "fine_train_forward_points: null pos / rgb");
+  if (int rc = check_forward(ctx, st, in, true, hint_desc, n_pairs, n_hints, p, out)) return rc;
+  st->have_fwd = false;
+  st->pn_fwd = false;
+  // one backbone call per cell in the reference (object_encoder.py:92-95): a cell is a pair's 16 objects
+  std::vector<int32_t> offs((size_t)n_pairs + 1);
+  for (int i = 0; i <= n_pairs; ++i) offs[i] = i * kObj;
+  const float* f2 = nullptr;
+  if (int rc = pn_train_forward_on(ctx, st->pn, "fine_train_forward_points", pos, rgb, offs.data(), n_pairs, &f2, s)) return rc;
+  if (int rc = fine_train_forward_impl(ctx, in, f2, hint_desc, n_pairs, n_hints, p, seed, out, s)) return rc;
+  st->pn_fwd = true;
+  return T2L_OK;
+}
+
 int fine_train_backward_impl(t2l_ctx* ctx, const float* grad_offsets, float* grad_hint, float* grad_pn, hipStream_t s) {
   auto* st = (FineTrain*)ctx->fine_train;
   if (!st || !st->have_fwd) return fail(ctx, T2L_ESTATE, "fine_train_backward: no training-mode forward to differentiate");
@@ -937,6 +986,9 @@ int fine_train_backward_impl(t2l_ctx* ctx, const float* grad_offsets, float* gra
   const float p = st->p;
   const uint32_t seed = st->seed;
   const int P = st->P, H = st->H, M0 = P * kObj, M1 = P * H;
+  // on into the backbone: after a points forward, when it trains and features2 reaches the loss ("class" via mlp_pointnet)
+  const bool pn_bwd = st->pn_fwd && pn_train_trainable(st->pn) && st->br[0].used && !st->br[0].embed;
+  float* dpn = grad_pn ? grad_pn : pn_bwd ? st->dpn : nullptr;
   // head
   lin_dw(s, grad_offsets, 2, st->a1, 64, P, 2, 64, st->o2w.g, 64, st->o2b.g);
   lin_dx(s, grad_offsets, 2, P, 2, st->o2w.d, 64, 64, st->da1, 64, 0);
@@ -980,7 +1032,7 @@ int fine_train_backward_impl(t2l_ctx* ctx, const float* grad_offsets, float* gra
       // layers in reverse: dout in gA0 / gB0 alternately, dy in ta, dx of the first layer only for features2
       float *dout = st->gA0, *dnext = st->gB0;
       for (int li = (int)br.mlp.size() - 1; li >= 0; --li) {
-        float* dx = li > 0 ? dnext : (f == 0 ? grad_pn : nullptr);
+        float* dx = li > 0 ? dnext : (f == 0 ? dpn : nullptr);
         bn_layer_bwd(br.mlp[li], dout, M0, st->ta, dx, s);
         std::swap(dout, dnext);
       }
@@ -988,6 +1040,7 @@ int fine_train_backward_impl(t2l_ctx* ctx, const float* grad_offsets, float* gra
     ++col;
   }
   T2L_HIP(ctx, hipGetLastError());
+  if (pn_bwd) return pn_train_backward_on(ctx, st->pn, "fine_train_backward", dpn, s);
   return T2L_OK;
 }
 

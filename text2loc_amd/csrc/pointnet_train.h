@@ -1,6 +1,8 @@
 // PointNet++ object backbone in TRAINING mode (SURVEY.md §8 rows a3 + a9; models/pointcloud/pointnet2.py:18-100 under
 // model.train(), trained jointly in the published configuration, README.md:87-99). Included by train.hip (same translation
-// unit: it works on the TrainState's live tensors and its GEMM launchers). PARITY UNPINNED like the eval kernels
+// unit: it uses its GEMM launchers). A PnTrain holds its own table of the bound object_encoder.pointnet.* tensors, so one
+// state serves the coarse step (TrainState::pn, t2l_train_bind) and another the fine step (ft::FineTrain, t2l_fine_train_bind)
+// without either touching the other; fine_train.hip reaches it through the pn_train_*_on entry points at the end. PARITY UNPINNED like the eval kernels
 // (pointnet.hip): the index structure follows the build's deterministic restatement (oracle/t2l_oracle_pointnet.py), the
 // training arithmetic oracle/t2l_oracle_pointnet_train.py.
 //
@@ -36,6 +38,7 @@ struct PnLevel {
 };
 
 struct PnTrain {
+  std::unordered_map<std::string, TTensor> t;  // the bound object_encoder.pointnet.* tensors (live pointers) + BatchNorm buffers
   bool bound = false, trainable = false, have_forward = false;
   char *ws = nullptr, *iws = nullptr;  // activations + scratch (sized exactly per call) / index tables (worst case, small)
   size_t ws_cap = 0, ws_off = 0, iws_cap = 0, scratch_off = 0, scratch_bytes = 0;
@@ -587,6 +590,7 @@ __global__ void pt_relu_mask_kernel(float* __restrict__ d, const float* __restri
 }  // namespace train
 
 static PnTrain* pn_state(TrainState* st) { return reinterpret_cast<PnTrain*>(st->pn); }
+static const TTensor& PT(const PnTrain* pt, const std::string& n) { return pt->t.at(n); }
 
 static void pn_train_free(void* p) {
   PnTrain* pt = reinterpret_cast<PnTrain*>(p);
@@ -723,7 +727,10 @@ static bool gemm_tn2(const float* dY, const float* X, float* dW, float* db, size
 // object_encoder.pointnet.* tensors of the binding: all of them with gradient buffers -> the backbone trains in the engine
 // (their names join the Adam list); all without -> frozen (models/object_encoder.py:53-55: requires_grad_(False), but still
 // under model.train(): batch statistics + running-statistics updates in the forward); absent -> no backbone on the path
-static int pn_train_bind(t2l_ctx* ctx, TrainState* st, std::vector<std::string>& adam) {
+// (*out stays null). `who` names the bind call in the messages; `adam` (or null) receives the trained names.
+static int pn_bind_core(t2l_ctx* ctx, const std::unordered_map<std::string, TTensor>& src, const std::string& who, PnTrain** out,
+                        std::vector<std::string>* adam) {
+  *out = nullptr;
   const std::string P = "object_encoder.pointnet.";
   const int cin3[4] = {6, 67, 131, 259}, h1[4] = {32, 128, 256, 512}, h2[4] = {64, 128, 256, 1024};
   std::vector<std::pair<std::string, int64_t>> req, bufs;
@@ -746,29 +753,41 @@ static int pn_train_bind(t2l_ctx* ctx, TrainState* st, std::vector<std::string>&
   req.push_back({P + "lin2.bias", 256});
   int with_grad = 0, present = 0;
   for (auto& r : req) {
-    auto it = st->t.find(r.first);
-    if (it == st->t.end()) continue;
+    auto it = src.find(r.first);
+    if (it == src.end()) continue;
     ++present;
     if (it->second.grad) ++with_grad;
   }
   if (present == 0) return T2L_OK;  // no backbone in this binding (precomputed features2 / class embedding)
   const bool trainable = with_grad > 0;
   if (present != (int)req.size() || (trainable && with_grad != (int)req.size()))
-    return fail(ctx, T2L_EINVAL, "t2l_train_bind: object_encoder.pointnet.* must be bound completely — every sa*/ga/lin1/lin2 tensor, "
-                                 "all of them with gradient buffers (trained jointly) or none (--pointnet_freeze: batch statistics in "
-                                 "the forward, no backward)");
-  int rc;
-  for (auto& r : req)
-    if ((rc = need(ctx, st, r.first, r.second, trainable, nullptr))) return rc;
-  for (auto& r : bufs)
-    if ((rc = need(ctx, st, r.first, r.second, false, nullptr))) return rc;
-  if (trainable)
-    for (auto& r : req) adam.push_back(r.first);
+    return fail(ctx, T2L_EINVAL, who + ": object_encoder.pointnet.* must be bound completely — every sa*/ga/lin1/lin2 tensor, "
+                                       "all of them with gradient buffers (trained jointly) or none (--pointnet_freeze: batch statistics in "
+                                       "the forward, no backward)");
+  std::unordered_map<std::string, TTensor> mine;
+  for (auto* group : {&req, &bufs})
+    for (auto& r : *group) {
+      auto it = src.find(r.first);
+      if (it == src.end()) return fail(ctx, T2L_EINVAL, who + ": missing tensor '" + r.first + "'");
+      if (it->second.numel != r.second)
+        return fail(ctx, T2L_EINVAL, who + ": '" + r.first + "' has " + std::to_string(it->second.numel) + " elements, expected " +
+                                         std::to_string(r.second));
+      mine[r.first] = TTensor{it->second.data, group == &req ? it->second.grad : nullptr, it->second.numel};
+    }
+  if (trainable && adam)
+    for (auto& r : req) adam->push_back(r.first);
   PnTrain* pt = new PnTrain();
+  pt->t = std::move(mine);
   pt->bound = true;
   pt->trainable = trainable;
-  st->pn = pt;
+  *out = pt;
   return T2L_OK;
+}
+static int pn_train_bind(t2l_ctx* ctx, TrainState* st, std::vector<std::string>& adam) {
+  PnTrain* pt = nullptr;
+  const int rc = pn_bind_core(ctx, st->t, "t2l_train_bind", &pt, &adam);
+  st->pn = pt;
+  return rc;
 }
 
 template <typename T>
@@ -831,31 +850,31 @@ static size_t pn_layout(PnTrain* pt) {
 // one get_mlp block in training mode over segmented rows: y = X W^T + b; per-cell BatchNorm; ReLU.
 // Second version (default): the GEMM's epilogue forms the BatchNorm partial sums, and a block's first layer leaves only y1 — its
 // BatchNorm + ReLU is applied by whoever loads it (x_fuse: the layer below's tables for THIS layer's left operand).
-static void pn_block_fwd(TrainState* st, PnTrain* pt, const PnLevel& L, int layer, const float* X, const float* W, int K, int C, float* y,
+static void pn_block_fwd(PnTrain* pt, const PnLevel& L, int layer, const float* X, const float* W, int K, int C, float* y,
                          float* a, float* mean, float* rstd, float* rg, bool x_fuse, hipStream_t s) {
   using namespace train;
   const std::string p = L.prefix + "." + std::to_string(layer);
   (void)hipMemsetAsync(pt->acc, 0, sizeof(double) * 2 * 1024 * pt->n_cells, s);
-  gemm_rows2(X, W, T_(st, p + ".0.bias").data, y, L.E, C, K, x_fuse ? L.mean1 : nullptr, x_fuse ? L.rg1 : nullptr,
-             x_fuse ? T_(st, L.prefix + ".0.1.bias").data : nullptr, L.row_cell, pt->acc, s);
+  gemm_rows2(X, W, PT(pt, p + ".0.bias").data, y, L.E, C, K, x_fuse ? L.mean1 : nullptr, x_fuse ? L.rg1 : nullptr,
+             x_fuse ? PT(pt, L.prefix + ".0.1.bias").data : nullptr, L.row_cell, pt->acc, s);
   hipLaunchKernelGGL(pt_bn_finalize_kernel, dim3((C + 31) / 32), dim3(256), 0, s, (const double*)pt->acc, (const int32_t*)L.cnt, pt->n_cells, C,
-                     mean, rstd, T_(st, p + ".1.running_mean").data, T_(st, p + ".1.running_var").data, 0.1f,
-                     (const float*)T_(st, p + ".1.weight").data, rg);
+                     mean, rstd, PT(pt, p + ".1.running_mean").data, PT(pt, p + ".1.running_var").data, 0.1f,
+                     (const float*)PT(pt, p + ".1.weight").data, rg);
   if (a) {
     if (pt->half)
       hipLaunchKernelGGL((pt_bn_apply_fwd_kernel<pn_bf16>), dim3(pn_blocks(L.E * C / 4)), dim3(256), 0, s, reinterpret_cast<const pn_bf16*>(y), L.E, C,
-                         (const int32_t*)L.row_cell, (const float*)mean, (const float*)rstd, (const float*)T_(st, p + ".1.weight").data,
-                         (const float*)T_(st, p + ".1.bias").data, reinterpret_cast<pn_bf16*>(a));
+                         (const int32_t*)L.row_cell, (const float*)mean, (const float*)rstd, (const float*)PT(pt, p + ".1.weight").data,
+                         (const float*)PT(pt, p + ".1.bias").data, reinterpret_cast<pn_bf16*>(a));
     else
       hipLaunchKernelGGL((pt_bn_apply_fwd_kernel<float>), dim3(pn_blocks(L.E * C / 4)), dim3(256), 0, s, (const float*)y, L.E, C,
-                         (const int32_t*)L.row_cell, (const float*)mean, (const float*)rstd, (const float*)T_(st, p + ".1.weight").data,
-                         (const float*)T_(st, p + ".1.bias").data, a);
+                         (const int32_t*)L.row_cell, (const float*)mean, (const float*)rstd, (const float*)PT(pt, p + ".1.weight").data,
+                         (const float*)PT(pt, p + ".1.bias").data, a);
   }
 }
 
 // d: gradient w.r.t. the block's ReLU output [E, C] (overwritten with the gradient w.r.t. the Linear output). dxout != nullptr
 // (second layer): that gradient is implied by the max aggregation (dxout [G, C] at the arg-max rows) and d is only written.
-static void pn_block_bwd(TrainState* st, PnTrain* pt, const PnLevel& L, int layer, float* d, const float* y, const float* a, int C,
+static void pn_block_bwd(PnTrain* pt, const PnLevel& L, int layer, float* d, const float* y, const float* a, int C,
                          const float* mean, const float* rstd, const float* rg, const float* dxout, hipStream_t s) {
   using namespace train;
   const std::string p = L.prefix + "." + std::to_string(layer);
@@ -871,18 +890,18 @@ static void pn_block_bwd(TrainState* st, PnTrain* pt, const PnLevel& L, int laye
     if (pt->half)
       hipLaunchKernelGGL((pt_bn_stats_kernel<1, pn_bf16>), sgrid, dim3(256), 0, s, reinterpret_cast<const pn_bf16*>(y), reinterpret_cast<const pn_bf16*>(d),
                          reinterpret_cast<const pn_bf16*>(a), C, L.E, (const int32_t*)L.row_cell, mean, rstd, pt->acc, rg,
-                         (const float*)T_(st, p + ".1.bias").data);
+                         (const float*)PT(pt, p + ".1.bias").data);
     else
       hipLaunchKernelGGL((pt_bn_stats_kernel<1, float>), sgrid, dim3(256), 0, s, y, (const float*)d, a, C, L.E, (const int32_t*)L.row_cell, mean, rstd,
-                         pt->acc, rg, (const float*)T_(st, p + ".1.bias").data);
+                         pt->acc, rg, (const float*)PT(pt, p + ".1.bias").data);
   }
   hipLaunchKernelGGL(pt_bn_bwd_finalize_kernel, dim3((C + 31) / 32), dim3(256), 0, s, (const double*)pt->acc, (const int32_t*)L.cnt, pt->n_cells, C,
-                     (const float*)T_(st, p + ".1.weight").data, rstd, pt->bk1, pt->bk2, T_(st, p + ".1.weight").grad, T_(st, p + ".1.bias").grad);
+                     (const float*)PT(pt, p + ".1.weight").data, rstd, pt->bk1, pt->bk2, PT(pt, p + ".1.weight").grad, PT(pt, p + ".1.bias").grad);
   if (dxout) {
 #define T2L_PN_BWD_GROUPS(ST_)                                                                                                                          \
   hipLaunchKernelGGL((pt_bn_apply_bwd_groups_kernel<ST_>), dim3(pn_blocks(L.G * C / 4)), dim3(256), 0, s, reinterpret_cast<ST_*>(d),                    \
                      reinterpret_cast<const ST_*>(y), (const int32_t*)L.goff, L.G, C, L.nd, (const int32_t*)pt->cell_of_obj, (const float*)pt->bk1,     \
-                     (const float*)pt->bk2, (const float*)T_(st, p + ".1.weight").data, (const float*)T_(st, p + ".1.bias").data, mean, rstd,         \
+                     (const float*)pt->bk2, (const float*)PT(pt, p + ".1.weight").data, (const float*)PT(pt, p + ".1.bias").data, mean, rstd,         \
                      (const int32_t*)L.arg, dxout)
     if (pt->half) T2L_PN_BWD_GROUPS(pn_bf16);
     else T2L_PN_BWD_GROUPS(float);
@@ -892,25 +911,22 @@ static void pn_block_bwd(TrainState* st, PnTrain* pt, const PnLevel& L, int laye
 #define T2L_PN_BWD_ROWS(ST_)                                                                                                                          \
   hipLaunchKernelGGL((pt_bn_apply_bwd_rows_kernel<ST_>), agrid, dim3(256), 0, s, reinterpret_cast<ST_*>(d), reinterpret_cast<const ST_*>(a),        \
                      reinterpret_cast<const ST_*>(y), C, L.E, (const int32_t*)L.row_cell, (const float*)pt->bk1, (const float*)pt->bk2,              \
-                     (const float*)T_(st, p + ".1.weight").data, mean, rstd, (const float*)T_(st, p + ".1.bias").data, rg)
+                     (const float*)PT(pt, p + ".1.weight").data, mean, rstd, (const float*)PT(pt, p + ".1.bias").data, rg)
     if (pt->half) T2L_PN_BWD_ROWS(pn_bf16);
     else T2L_PN_BWD_ROWS(float);
 #undef T2L_PN_BWD_ROWS
   }
 }
 
-int pn_train_forward_impl(t2l_ctx* ctx, const float* pos, const float* rgb, const int32_t* cell_offsets, int n_cells, float* out_f2,
-                          hipStream_t s) {
+// The training-mode forward of a bound backbone state; features2 stays in pt->f2 (and is copied to out_f2 unless that is null).
+static int pn_forward_core(t2l_ctx* ctx, PnTrain* pt, const std::string& who, const float* pos, const float* rgb, const int32_t* cell_offsets,
+                           int n_cells, float* out_f2, hipStream_t s) {
   using namespace train;
-  TrainState* st = state(ctx);
-  PnTrain* pt = st ? pn_state(st) : nullptr;
-  if (!pt || !pt->bound)
-    return fail(ctx, T2L_ESTATE, "t2l_pointnet_features_train: bind the object_encoder.pointnet.* tensors first (t2l_train_bind)");
-  if (!pos || !rgb || !cell_offsets || n_cells <= 0 || !out_f2) return fail(ctx, T2L_EINVAL, "t2l_pointnet_features_train: bad arguments");
+  if (!pos || !rgb || !cell_offsets || n_cells <= 0) return fail(ctx, T2L_EINVAL, who + ": bad arguments");
   const int n_obj = cell_offsets[n_cells];
-  if (n_obj <= 0) return fail(ctx, T2L_EINVAL, "t2l_pointnet_features_train: no objects");
+  if (n_obj <= 0) return fail(ctx, T2L_EINVAL, who + ": no objects");
   for (int c = 0; c < n_cells; ++c)
-    if (cell_offsets[c + 1] <= cell_offsets[c]) return fail(ctx, T2L_EINVAL, "t2l_pointnet_features_train: every cell needs at least one object");
+    if (cell_offsets[c + 1] <= cell_offsets[c]) return fail(ctx, T2L_EINVAL, who + ": every cell needs at least one object");
   pt->have_forward = false;
   pt->n_obj = n_obj;
   pt->n_cells = n_cells;
@@ -1007,12 +1023,12 @@ int pn_train_forward_impl(t2l_ctx* ctx, const float* pos, const float* rgb, cons
     long long total = 0;
     for (size_t i = 0; i < L.G; ++i) {
       const int c = g[i + 1];
-      if (c < 1 || c > 33) return fail(ctx, T2L_EHIP, "t2l_pointnet_features_train: ball query returned an impossible row count");
+      if (c < 1 || c > 33) return fail(ctx, T2L_EHIP, who + ": ball query returned an impossible row count");
       h_cnt[l][h_tab[i / L.nd]] += c;
       total += c;
       g[i + 1] = (int32_t)total;
     }
-    if (total > 0x3fffffffll) return fail(ctx, T2L_EINVAL, "t2l_pointnet_features_train: batch too large (more than 2^30 edge rows in one level)");
+    if (total > 0x3fffffffll) return fail(ctx, T2L_EINVAL, who + ": batch too large (more than 2^30 edge rows in one level)");
     L.E = (size_t)total;
   }
   pt->lv[3].E = (size_t)n_obj * 32;
@@ -1057,15 +1073,15 @@ int pn_train_forward_impl(t2l_ctx* ctx, const float* pos, const float* rgb, cons
     else
       hipLaunchKernelGGL((pt_gather_kernel<float>), dim3(pn_blocks(L.E * (L.kp / 4))), dim3(256), 0, s, cur_x, cur_pos,
                          L.sa ? (const float*)L.pos_out : nullptr, (const int32_t*)L.src, (const int32_t*)L.row_group, L.E, L.cin, L.kp, L.X);
-    hipLaunchKernelGGL(pt_pad_kernel, dim3(pn_blocks((size_t)L.h1 * L.kp)), dim3(256), 0, s, (const float*)T_(st, L.prefix + ".0.0.weight").data,
+    hipLaunchKernelGGL(pt_pad_kernel, dim3(pn_blocks((size_t)L.h1 * L.kp)), dim3(256), 0, s, (const float*)PT(pt, L.prefix + ".0.0.weight").data,
                        L.h1, L.kin, L.kp, L.w1p);
-    pn_block_fwd(st, pt, L, 0, L.X, L.w1p, L.kp, L.h1, L.y1, L.a1, L.mean1, L.rstd1, L.rg1, false, s);
-    pn_block_fwd(st, pt, L, 1, L.a1 ? L.a1 : L.y1, T_(st, L.prefix + ".1.0.weight").data, L.h1, L.h2, L.y2, nullptr, L.mean2, L.rstd2, nullptr,
+    pn_block_fwd(pt, L, 0, L.X, L.w1p, L.kp, L.h1, L.y1, L.a1, L.mean1, L.rstd1, L.rg1, false, s);
+    pn_block_fwd(pt, L, 1, L.a1 ? L.a1 : L.y1, PT(pt, L.prefix + ".1.0.weight").data, L.h1, L.h2, L.y2, nullptr, L.mean2, L.rstd2, nullptr,
                  L.a1 == nullptr, s);
 #define T2L_PN_SEGMAX(ST_)                                                                                                                        \
   hipLaunchKernelGGL((pt_segmax_kernel<ST_>), dim3(pn_blocks(L.G * L.h2 / 4)), dim3(256), 0, s, reinterpret_cast<const ST_*>(L.y2),               \
                      (const int32_t*)L.goff, L.G, L.h2, L.nd, (const int32_t*)pt->cell_of_obj, (const float*)L.mean2, (const float*)L.rstd2,       \
-                     (const float*)T_(st, L.prefix + ".1.1.weight").data, (const float*)T_(st, L.prefix + ".1.1.bias").data, L.xout, L.arg, L.ysel)
+                     (const float*)PT(pt, L.prefix + ".1.1.weight").data, (const float*)PT(pt, L.prefix + ".1.1.bias").data, L.xout, L.arg, L.ysel)
     if (pt->half) T2L_PN_SEGMAX(pn_bf16);
     else T2L_PN_SEGMAX(float);
 #undef T2L_PN_SEGMAX
@@ -1075,9 +1091,9 @@ int pn_train_forward_impl(t2l_ctx* ctx, const float* pos, const float* rgb, cons
     }
   }
   pt->f0 = pt->lv[3].xout;
-  gemm_nt(pt->f0, T_(st, P + "lin1.weight").data, T_(st, P + "lin1.bias").data, pt->f1, n_obj, 512, 1024, 1, s);
-  gemm_nt(pt->f1, T_(st, P + "lin2.weight").data, T_(st, P + "lin2.bias").data, pt->f2, n_obj, 256, 512, 1, s);
-  T2L_HIP(ctx, hipMemcpyAsync(out_f2, pt->f2, sizeof(float) * (size_t)n_obj * 256, hipMemcpyDeviceToDevice, s));
+  gemm_nt(pt->f0, PT(pt, P + "lin1.weight").data, PT(pt, P + "lin1.bias").data, pt->f1, n_obj, 512, 1024, 1, s);
+  gemm_nt(pt->f1, PT(pt, P + "lin2.weight").data, PT(pt, P + "lin2.bias").data, pt->f2, n_obj, 256, 512, 1, s);
+  if (out_f2) T2L_HIP(ctx, hipMemcpyAsync(out_f2, pt->f2, sizeof(float) * (size_t)n_obj * 256, hipMemcpyDeviceToDevice, s));
   event_end(ctx, "pointnet_train_forward", s);
   T2L_HIP(ctx, hipGetLastError());
   T2L_HIP(ctx, hipStreamSynchronize(s));  // the host tables above go out of scope
@@ -1085,19 +1101,25 @@ int pn_train_forward_impl(t2l_ctx* ctx, const float* pos, const float* rgb, cons
   return T2L_OK;
 }
 
-int pn_train_backward_impl(t2l_ctx* ctx, const float* grad_f2, hipStream_t s) {
-  using namespace train;
+int pn_train_forward_impl(t2l_ctx* ctx, const float* pos, const float* rgb, const int32_t* cell_offsets, int n_cells, float* out_f2,
+                          hipStream_t s) {
   TrainState* st = state(ctx);
   PnTrain* pt = st ? pn_state(st) : nullptr;
-  if (!pt || !pt->have_forward) return fail(ctx, T2L_ESTATE, "t2l_pointnet_backward: no training-mode forward to differentiate");
-  st->pn_touched = true;  // the backbone's gradients carry this batch: its tensors take part in the next t2l_adam_step
-  if (!pt->trainable)
-    return fail(ctx, T2L_ESTATE, "t2l_pointnet_backward: the backbone was bound without gradient buffers (frozen)");
-  if (!grad_f2) return fail(ctx, T2L_EINVAL, "t2l_pointnet_backward: null gradient");
+  if (!pt || !pt->bound)
+    return fail(ctx, T2L_ESTATE, "t2l_pointnet_features_train: bind the object_encoder.pointnet.* tensors first (t2l_train_bind)");
+  if (!out_f2) return fail(ctx, T2L_EINVAL, "t2l_pointnet_features_train: bad arguments");
+  return pn_forward_core(ctx, pt, "t2l_pointnet_features_train", pos, rgb, cell_offsets, n_cells, out_f2, s);
+}
+
+// The backward of the last forward of a bound backbone state (pt->have_forward): parameter gradients ADDED to its buffers.
+static int pn_backward_core(t2l_ctx* ctx, PnTrain* pt, const std::string& who, const float* grad_f2, hipStream_t s) {
+  using namespace train;
+  if (!pt->trainable) return fail(ctx, T2L_ESTATE, who + ": the backbone was bound without gradient buffers (frozen)");
+  if (!grad_f2) return fail(ctx, T2L_EINVAL, who + ": null gradient");
   const int n_obj = pt->n_obj;
   if ((ctx->train_bf16 == 1) != pt->half)
-    return fail(ctx, T2L_ESTATE, "t2l_pointnet_backward: option train_bf16 changed between the forward and the backward (the saved edge rows are "
-                                 "bf16 exactly when the forward ran with train_bf16 = 1)");
+    return fail(ctx, T2L_ESTATE, who + ": option train_bf16 changed between the forward and the backward (the saved edge rows are "
+                                       "bf16 exactly when the forward ran with train_bf16 = 1)");
   tl_gemm_bf16 = ctx->train_bf16;
   const size_t es = pt->half ? 2 : 4;
   const std::string P = "object_encoder.pointnet.";
@@ -1109,31 +1131,31 @@ int pn_train_backward_impl(t2l_ctx* ctx, const float* grad_f2, hipStream_t s) {
   float* dx_next = pn_bump<float>(pt, (size_t)n_obj * 8192);  // ... and w.r.t. the output of the level below
   T2L_HIP(ctx, hipMemcpyAsync(d2, grad_f2, sizeof(float) * (size_t)n_obj * 256, hipMemcpyDeviceToDevice, s));
   hipLaunchKernelGGL(pt_relu_mask_kernel, dim3(pn_blocks((size_t)n_obj * 256)), dim3(256), 0, s, d2, (const float*)pt->f2, (size_t)n_obj * 256);
-  gemm_tn(d2, pt->f1, T_(st, P + "lin2.weight").grad, T_(st, P + "lin2.bias").grad, n_obj, 256, 512, s);
-  gemm_nn(d2, T_(st, P + "lin2.weight").data, d1, n_obj, 256, 512, 0, s);
+  gemm_tn(d2, pt->f1, PT(pt, P + "lin2.weight").grad, PT(pt, P + "lin2.bias").grad, n_obj, 256, 512, s);
+  gemm_nn(d2, PT(pt, P + "lin2.weight").data, d1, n_obj, 256, 512, 0, s);
   hipLaunchKernelGGL(pt_relu_mask_kernel, dim3(pn_blocks((size_t)n_obj * 512)), dim3(256), 0, s, d1, (const float*)pt->f1, (size_t)n_obj * 512);
-  gemm_tn(d1, pt->f0, T_(st, P + "lin1.weight").grad, T_(st, P + "lin1.bias").grad, n_obj, 512, 1024, s);
-  gemm_nn(d1, T_(st, P + "lin1.weight").data, dx, n_obj, 512, 1024, 0, s);
+  gemm_tn(d1, pt->f0, PT(pt, P + "lin1.weight").grad, PT(pt, P + "lin1.bias").grad, n_obj, 512, 1024, s);
+  gemm_nn(d1, PT(pt, P + "lin1.weight").data, dx, n_obj, 512, 1024, 0, s);
   for (int l = 3; l >= 0; --l) {
     const PnLevel& L = pt->lv[l];
     const size_t lmark = pt->ws_off;
     float* dA2 = reinterpret_cast<float*>(pn_bump<char>(pt, L.E * L.h2 * es));  // (edge-row tensors: pn_store_t)
     float* dA1 = reinterpret_cast<float*>(pn_bump<char>(pt, L.E * L.h1 * es));
-    pn_block_bwd(st, pt, L, 1, dA2, L.y2, nullptr, L.h2, L.mean2, L.rstd2, nullptr, dx, s);
-    const float* be1 = T_(st, L.prefix + ".0.1.bias").data;
+    pn_block_bwd(pt, L, 1, dA2, L.y2, nullptr, L.h2, L.mean2, L.rstd2, nullptr, dx, s);
+    const float* be1 = PT(pt, L.prefix + ".0.1.bias").data;
     {  // a1 = relu(bn(y1)) is rebuilt while y1 is staged
-      if (!gemm_tn2(dA2, L.a1 ? L.a1 : L.y1, T_(st, L.prefix + ".1.0.weight").grad, T_(st, L.prefix + ".1.0.bias").grad, L.E, L.h2, L.h1, L.h1,
+      if (!gemm_tn2(dA2, L.a1 ? L.a1 : L.y1, PT(pt, L.prefix + ".1.0.weight").grad, PT(pt, L.prefix + ".1.0.bias").grad, L.E, L.h2, L.h1, L.h1,
                     L.h1, L.a1 ? nullptr : L.mean1, L.a1 ? nullptr : L.rg1, L.a1 ? nullptr : be1, L.row_cell, s))
-        return fail(ctx, T2L_EHIP, "t2l_pointnet_backward: no tn2_kernel instance for this layer shape (internal error)");
+        return fail(ctx, T2L_EHIP, who + ": no tn2_kernel instance for this layer shape (internal error)");
       hipLaunchKernelGGL(pt_transpose_kernel, dim3((unsigned)((L.h2 * L.h1 + 255) / 256)), dim3(256), 0, s,
-                         (const float*)T_(st, L.prefix + ".1.0.weight").data, L.h2, L.h1, pt->wt);
+                         (const float*)PT(pt, L.prefix + ".1.0.weight").data, L.h2, L.h1, pt->wt);
       gemm_rows2(dA2, pt->wt, nullptr, dA1, L.E, L.h1, L.h2, nullptr, nullptr, nullptr, nullptr, nullptr, s);
     }
-    pn_block_bwd(st, pt, L, 0, dA1, L.y1, L.a1, L.h1, L.mean1, L.rstd1, L.rg1, nullptr, s);
+    pn_block_bwd(pt, L, 0, dA1, L.y1, L.a1, L.h1, L.mean1, L.rstd1, L.rg1, nullptr, s);
     {  // straight into the unpadded gradient: the padding columns of X are not written
-      if (!gemm_tn2(dA1, L.X, T_(st, L.prefix + ".0.0.weight").grad, T_(st, L.prefix + ".0.0.bias").grad, L.E, L.h1, L.kp, L.kin, L.kin,
+      if (!gemm_tn2(dA1, L.X, PT(pt, L.prefix + ".0.0.weight").grad, PT(pt, L.prefix + ".0.0.bias").grad, L.E, L.h1, L.kp, L.kin, L.kin,
                     nullptr, nullptr, nullptr, nullptr, s))
-        return fail(ctx, T2L_EHIP, "t2l_pointnet_backward: no tn2_kernel instance for this layer shape (internal error)");
+        return fail(ctx, T2L_EHIP, who + ": no tn2_kernel instance for this layer shape (internal error)");
     }
     if (l > 0) {  // the input gradient: features of the level below (positions are data)
       const PnLevel& Lb = pt->lv[l - 1];
@@ -1159,12 +1181,43 @@ int pn_train_backward_impl(t2l_ctx* ctx, const float* grad_f2, hipStream_t s) {
       std::swap(dx, dx_next);
     }
     if (pt->ws_off > pt->scratch_off + pt->scratch_bytes || pt->ws_off > pt->ws_cap)
-      return fail(ctx, T2L_ENOMEM, "t2l_pointnet_backward: scratch bound exceeded (internal error)");
+      return fail(ctx, T2L_ENOMEM, who + ": scratch bound exceeded (internal error)");
     pt->ws_off = lmark;
   }
   event_end(ctx, "pointnet_train_backward", s);
   T2L_HIP(ctx, hipGetLastError());
   return T2L_OK;
 }
+
+int pn_train_backward_impl(t2l_ctx* ctx, const float* grad_f2, hipStream_t s) {
+  TrainState* st = state(ctx);
+  PnTrain* pt = st ? pn_state(st) : nullptr;
+  if (!pt || !pt->have_forward) return fail(ctx, T2L_ESTATE, "t2l_pointnet_backward: no training-mode forward to differentiate");
+  st->pn_touched = true;  // the backbone's gradients carry this batch: its tensors take part in the next t2l_adam_step
+  return pn_backward_core(ctx, pt, "t2l_pointnet_backward", grad_f2, s);
+}
+
+// ---- a backbone state owned by another context member (the fine step: ft::FineTrain::pn, fine_train.hip) ----------------
+int pn_train_bind_group(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n, const char* who, PnTrain** out) {
+  std::unordered_map<std::string, TTensor> src;
+  for (int i = 0; i < n; ++i)
+    if (tensors[i].name && tensors[i].data) src[tensors[i].name] = TTensor{tensors[i].data, tensors[i].grad, tensors[i].numel};
+  return pn_bind_core(ctx, src, who, out, nullptr);
+}
+int pn_train_forward_on(t2l_ctx* ctx, PnTrain* pt, const char* who, const float* pos, const float* rgb, const int32_t* cell_offsets,
+                        int n_cells, const float** features2, hipStream_t s) {
+  // the GEMM block choice of the training step's forward (train_forward_impl), for lin1 / lin2
+  tl_gemm_block64 = ctx->train_gemm_block == 64 || (ctx->train_gemm_block == 0 && ctx->train_bf16 != 0);
+  const int rc = pn_forward_core(ctx, pt, who, pos, rgb, cell_offsets, n_cells, nullptr, s);
+  *features2 = rc == T2L_OK ? pt->f2 : nullptr;
+  return rc;
+}
+int pn_train_backward_on(t2l_ctx* ctx, PnTrain* pt, const char* who, const float* grad_f2, hipStream_t s) {
+  if (!pt->have_forward) return fail(ctx, T2L_ESTATE, std::string(who) + ": no training-mode forward of the backbone to differentiate");
+  tl_gemm_block64 = ctx->train_gemm_block == 64 || (ctx->train_gemm_block == 0 && ctx->train_bf16 != 0);
+  return pn_backward_core(ctx, pt, who, grad_f2, s);
+}
+bool pn_train_trainable(const PnTrain* pt) { return pt && pt->trainable; }
+void pn_train_release(PnTrain* pt) { pn_train_free(pt); }
 
 }  // namespace t2l

@@ -207,6 +207,16 @@ int zero_grad_impl(t2l_ctx* ctx, hipStream_t s);
 int pn_train_forward_impl(t2l_ctx* ctx, const float* pos, const float* rgb, const int32_t* cell_offsets, int n_cells, float* out_f2,
                           hipStream_t s);
 int pn_train_backward_impl(t2l_ctx* ctx, const float* grad_f2, hipStream_t s);
+// the same backbone code on a state owned elsewhere (pointnet_train.h; the fine step binds one of its own): bind the
+// object_encoder.pointnet.* group of `tensors` (*out = null when the group is absent), training-mode forward (features2 in the
+// state until its next forward: *features2), backward of that forward (ADDS into the bound gradient buffers), release
+struct PnTrain;
+int pn_train_bind_group(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n, const char* who, PnTrain** out);
+int pn_train_forward_on(t2l_ctx* ctx, PnTrain* pt, const char* who, const float* pos, const float* rgb, const int32_t* cell_offsets,
+                        int n_cells, const float** features2, hipStream_t s);
+int pn_train_backward_on(t2l_ctx* ctx, PnTrain* pt, const char* who, const float* grad_f2, hipStream_t s);
+bool pn_train_trainable(const PnTrain* pt);
+void pn_train_release(PnTrain* pt);
 int search_lanes_impl(t2l_ctx* ctx, const float* q, int Q, int K, int32_t* out_idx, double* out_score, hipStream_t s);
 int search_join_impl(t2l_ctx* ctx, hipStream_t s);
 void free_lanes(t2l_ctx* ctx);
@@ -248,6 +258,8 @@ void free_fine(t2l_ctx* ctx);
 int fine_train_bind_impl(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n, const t2l_model_config* cfg);
 int fine_train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, const float* pn_feat, const float* hint_desc, int n_pairs,
                             int n_hints, float p, uint32_t seed, float* out, hipStream_t s);
+int fine_train_forward_points_impl(t2l_ctx* ctx, const t2l_packed_cells* in, const float* pos, const float* rgb, const float* hint_desc,
+                                   int n_pairs, int n_hints, float p, uint32_t seed, float* out, hipStream_t s);
 int fine_train_backward_impl(t2l_ctx* ctx, const float* grad_offsets, float* grad_hint, float* grad_pn, hipStream_t s);
 void free_fine_train(t2l_ctx* ctx);
 // text_head.hip

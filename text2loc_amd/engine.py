@@ -88,6 +88,8 @@ EXPORTS = {
     "t2l_fine_train_bind": (C.c_int, [C.c_void_p, C.POINTER(_TrainTensor), C.c_int32, C.POINTER(_ModelConfig)]),
     "t2l_fine_train_forward": (C.c_int, [C.c_void_p, C.POINTER(_PackedCells), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float,
                                          C.c_uint32, C.c_void_p, C.c_void_p]),
+    "t2l_fine_train_forward_points": (C.c_int, [C.c_void_p, C.POINTER(_PackedCells), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]),
     "t2l_fine_train_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "t2l_text_train_bind": (C.c_int, [C.c_void_p, C.POINTER(_TrainTensor), C.c_int32, C.c_char_p]),
     "t2l_text_head_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]),
@@ -390,6 +392,25 @@ class Engine:
                                                     self._ptr(hint_desc, torch.float32, "hint_desc"), pc.n_cells, int(hint_desc.shape[1]),
                                                     float(dropout_p), int(seed) & 0xFFFFFFFF, out.data_ptr(), _stream_ptr(self.device)))
         self._fine_train_inputs = (packed, pn_feat, hint_desc)
+        return out
+
+    def fine_train_forward_points(self, packed: Dict[str, torch.Tensor], pos: torch.Tensor, rgb: torch.Tensor, hint_desc: torch.Tensor,
+                                  dropout_p: float = 0.1, seed: int = 0) -> torch.Tensor:
+        """The same step with features2 from the PointNet++ backbone bound by ``fine_train_bind`` (class_embed off): pos, rgb
+        f32[16*n_pairs,256,3], object-major (each pair's 16 objects, pads included). The backbone runs in training mode, one
+        cell per pair (its BatchNorm running statistics move once per pair); the caller bumps num_batches_tracked."""
+        pc = self._packed_struct(packed)
+        if hint_desc.dim() != 3 or hint_desc.shape[0] != pc.n_cells or hint_desc.shape[2] != 128:
+            raise T2LError(f"fine_train_forward_points: hint_desc must be [n_pairs={pc.n_cells},n_hints,128], got {tuple(hint_desc.shape)}")
+        n = 16 * pc.n_cells
+        if tuple(pos.shape) != (n, 256, 3) or tuple(rgb.shape) != (n, 256, 3):
+            raise T2LError(f"fine_train_forward_points: pos and rgb must be [16*n_pairs={n},256,3], got {tuple(pos.shape)}, {tuple(rgb.shape)}")
+        out = torch.empty((pc.n_cells, 2), dtype=torch.float32, device=hint_desc.device)
+        self._check(self.lib.t2l_fine_train_forward_points(self._h, C.byref(pc), self._ptr(pos, torch.float32, "pos"),
+                                                           self._ptr(rgb, torch.float32, "rgb"), self._ptr(hint_desc, torch.float32, "hint_desc"),
+                                                           pc.n_cells, int(hint_desc.shape[1]), float(dropout_p), int(seed) & 0xFFFFFFFF,
+                                                           out.data_ptr(), _stream_ptr(self.device)))
+        self._fine_train_inputs = (packed, None, hint_desc)
         return out
 
     def fine_train_backward(self, grad_offsets: torch.Tensor, grad_hint_desc: Optional[torch.Tensor] = None,

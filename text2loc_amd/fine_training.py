@@ -3,8 +3,10 @@
 
 Batches are in ``Kitti360FineDataset.collate_fn`` format: ``objects`` (per pose, the cell's objects padded / cut to 16),
 ``texts``, ``offsets`` (target offsets [B,2]), ``poses`` (objects with a ``.pose`` attribute) and ``object_points`` (per pose,
-PointNet++ features2 [16,256] as tensors in the published feature mode; ignored when class_embed is on). The reference reads
-the optimizer and the MSE criterion from module globals; here they are passed in.
+in the published feature mode: the cell's point batch — ``.pos`` / ``.x`` [16*256,3] or a dict with those keys, as the
+reference's dataloader builds it — which trains the PointNet++ backbone jointly unless ``--pointnet_freeze``, or precomputed
+features2 [16,256] as tensors; ignored when class_embed is on). The reference reads the optimizer and the MSE criterion from
+module globals; here they are passed in.
 """
 from __future__ import annotations
 

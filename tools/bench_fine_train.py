@@ -4,7 +4,12 @@ parameter containers (nn.Linear / nn.BatchNorm1d / nn.TransformerDecoderLayer, f
 models/cross_matcher.py:86-135 runs them. Same weights, inputs and batch. Device events around `--iters` steps after
 `--warmup` steps; the median of `--reps` repetitions. Prints one JSON line.
 
-    python tools/bench_fine_train.py [--batches 32,256] [--iters 20] [--warmup 10] [--reps 5]
+`--points`: the published configuration instead — features2 from the PointNet++ backbone on each pair's point batch
+(t2l_fine_train_forward_points), trained jointly (the backward continues into it, Adam steps it too). Engine only: the
+reference's backbone needs torch_geometric, which this machine does not have, so there is no PyTorch column. The row also
+gives the device memory the first step claimed (the backbone's saved activations and scratch plus the fine step's arena).
+
+    python tools/bench_fine_train.py [--batches 32,256] [--iters 20] [--warmup 10] [--reps 5] [--points]
 """
 from __future__ import annotations
 
@@ -117,14 +122,65 @@ def bench(embed, B, iters, warmup, reps):
             "speedup": round(ms_torch / ms_engine, 3)}
 
 
+def bench_points(B, iters, warmup, reps):
+    args = make_args(False)
+    args.pointnet_freeze = False  # the published fine command: the backbone trains with everything else
+    model = CrossMatch(synth.KNOWN_CLASS, synth.COLOR_NAMES, args, language_encoder=torch.nn.Identity())
+    sd = dict(synth.make_fine_weights(0))
+    sd.update(synth.make_pointnet_weights(0))
+    model.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=False)
+    model = model.cuda().train()
+    cells = synth.make_cells(B, seed=1, min_obj=16, max_obj=16)
+    packed = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in cells.items() if k != "counts"}
+    pos, rgb = (torch.from_numpy(a).cuda() for a in synth.make_sampled_points(cells, 3))
+    rng = np.random.default_rng(2)
+    hints = torch.from_numpy(rng.standard_normal((B, 6, 128)).astype(np.float32)).cuda()
+    target = torch.from_numpy(rng.random((B, 2)).astype(np.float32)).cuda()
+    eng = Engine(torch.cuda.current_device())
+    tensors = model._fine_train_tensors()
+    eng.fine_train_bind(tensors, class_embed=False, color_embed=False, use_features=tuple(model.args.use_features), num_layers=2)
+    for t, g in model._fine_train_pn_live:  # the backbone's buffers as .grad: every step's backward goes through it
+        t.grad = g
+    opt = torch.optim.Adam([p for n, p in model.named_parameters() if p.grad is not None], lr=1e-4)
+    gh = torch.empty_like(hints)
+    seed = [0]
+
+    def engine_step():
+        opt.zero_grad(set_to_none=False)
+        seed[0] += 1
+        out = eng.fine_train_forward_points(packed, pos, rgb, hints, dropout_p=0.1, seed=seed[0]).requires_grad_(True)
+        loss = LAMBDA * F.mse_loss(out, target)
+        loss.backward()
+        eng.fine_train_backward(out.grad, gh, None)
+        opt.step()
+
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    engine_step()
+    torch.cuda.synchronize()
+    claimed = free0 - torch.cuda.mem_get_info()[0]
+    ms = time_steps(engine_step, iters, warmup, reps)
+    eng.close()
+    return {"mode": "points (backbone trained)", "B": B, "objects": 16 * B, "ms_engine": round(ms, 4), "ms_pytorch": None,
+            "first_step_device_gb": round(claimed / 1e9, 3)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default="32,256")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--points", action="store_true", help="features2 from the jointly trained PointNet++ backbone (engine only)")
     a = ap.parse_args()
     torch.manual_seed(0)
+    if a.points:
+        rows = [bench_points(int(B), a.iters, a.warmup, a.reps) for B in a.batches.split(",")]
+        print(json.dumps({"metric": "fine-stage training step with the PointNet++ backbone trained jointly (backbone fwd + fwd + "
+                                    "offset_lambda*MSE + bwd + backbone bwd + Adam), L=2, 6 hints, dropout 0.1, 256 points per object",
+                          "unit": "ms/step", "rows": rows,
+                          "pytorch": "no PyTorch column: the reference's PointNet++ needs torch_geometric, which is not installed"}))
+        return
     rows = [bench(embed, int(B), a.iters, a.warmup, a.reps) for embed in (True, False) for B in a.batches.split(",")]
     print(json.dumps({"metric": "fine-stage training step (fwd + offset_lambda*MSE + bwd + Adam), L=2, 6 hints, dropout 0.1",
                       "unit": "ms/step", "rows": rows}))
