@@ -16,11 +16,27 @@ The index structure (FPS order, neighbour lists, the extra self-loop source) com
 both oracles see identical edges. Gradients: d loss / d every ``object_encoder.pointnet.*`` parameter the path uses, given
 d loss / d features2 (the classifier heads are not on the path: object_encoder.py:60-61 uses features2).
 Checked against central differences of its own forward in tests/test_oracle_train.py.
+
+Reduced-precision arithmetic (``arith``, oracle/arith.py; the engine's option ``train_bf16``, text2loc_amd/csrc/pointnet_train.h):
+every product of the path runs on a bf16-capable GEMM and takes the operand arithmetic here —
+* edge MLPs: rows2_kernel (gemm_rows2.h:118-306, operands converted in rows2_fill / step) for y1 = X W1^T and y2 = a1 W2^T
+  (pn_block_fwd, pointnet_train.h:858, 1078-1079), dA1 = dA2 W2 (:1152) and the input gradient dA1 W1 (:1168 / :1174); tn2_kernel
+  (gemm_rows2.h:330-490, conversion at :420-443) for dW2 = dA2^T a1 (:1147) and dW1 = dA1^T X (:1156);
+* lin1 / lin2: gemm_f32.h (gemm_nt :1094-1095, gemm_tn / gemm_nn :1134-1138).
+In mode 1 the edge-row tensors are also STORED as bf16, rounded once when written (gemm_rows2.h:26-32, pn_store_t; ``store`` here):
+X (pt_gather_kernel), y1, y2, a1 (stored at the global level, rebuilt from the stored y1 and rounded as an operand at the SA levels —
+the same value), dA2 and dA1 (each the gradient w.r.t. the Linear output after the BatchNorm backward) and the global level's input
+gradient. The BatchNorm statistics of the forward come from the float32 accumulators BEFORE the rounding (rows2_kernel's epilogue,
+gemm_rows2.h:252, 277-299); everything after them — normalisation, ReLU, the first-maximum arg-max of a group, the BatchNorm
+backward's sums and closed form — reads the rounded values. Float32 (exact here): the SA levels' input gradient (scattered by
+rows2_kernel's epilogue), the per-group tensors (xout, arg, ysel, dxout), lin1 / lin2 activations, the bias gradients (column sums of
+the stored dY).
 """
 from __future__ import annotations
 
 import numpy as np
 
+from . import arith as A
 from . import t2l_oracle_pointnet as OP
 
 BN_EPS = 1e-5
@@ -28,12 +44,13 @@ MOMENTUM = 0.1
 P = "object_encoder.pointnet."
 
 
-def _bn_train(h, gamma, beta):
+def _bn_train(h, gamma, beta, hs):
+    """Statistics of h; the normalisation reads hs (h as stored: bf16 in mode 1)."""
     n = h.shape[0]
     mean = h.mean(axis=0)
     var = h.var(axis=0)  # biased
     rstd = 1.0 / np.sqrt(var + BN_EPS)
-    xhat = (h - mean) * rstd
+    xhat = (hs - mean) * rstd
     return xhat * gamma + beta, (xhat, rstd, n, mean, var)
 
 
@@ -49,8 +66,9 @@ def _bn_bwd(dy, cache, gamma):
 class _Mlp:
     """get_mlp([cin, h1, h2]) in training mode over ONE BatchNorm domain (the rows of one cell)."""
 
-    def __init__(self, sd, prefix):
+    def __init__(self, sd, prefix, arith=0):
         self.prefix = prefix
+        self.arith = arith
         self.w = [sd[f"{prefix}.{i}.0.weight"].astype(np.float64) for i in range(2)]
         self.b = [sd[f"{prefix}.{i}.0.bias"].astype(np.float64) for i in range(2)]
         self.g = [sd[f"{prefix}.{i}.1.weight"].astype(np.float64) for i in range(2)]
@@ -59,23 +77,27 @@ class _Mlp:
     def forward(self, x):
         cache = []
         for i in range(2):
-            h = x @ self.w[i].T + self.b[i]
-            y, bn = _bn_train(h, self.g[i], self.be[i])
+            h = A.product(x, self.w[i].T, self.arith) + self.b[i]
+            y, bn = _bn_train(h, self.g[i], self.be[i], A.store(h, self.arith))
             a = np.maximum(y, 0.0)
             cache.append((x, bn, a))
             x = a
         return x, cache
 
-    def backward(self, da, cache, grads, need_dx=True):
+    def backward(self, da, cache, grads, need_dx=True, store_dx=False):
+        """store_dx: the input gradient is an edge-row tensor too (the global level's; the SA levels scatter theirs in float32)."""
         for i in (1, 0):
             x, bn, a = cache[i]
             dy = da * (a > 0)
             dh, dg, db = _bn_bwd(dy, bn, self.g[i])
+            dh = A.store(dh, self.arith)
             grads[f"{self.prefix}.{i}.1.weight"] = grads.get(f"{self.prefix}.{i}.1.weight", 0) + dg
             grads[f"{self.prefix}.{i}.1.bias"] = grads.get(f"{self.prefix}.{i}.1.bias", 0) + db
-            grads[f"{self.prefix}.{i}.0.weight"] = grads.get(f"{self.prefix}.{i}.0.weight", 0) + dh.T @ x
+            grads[f"{self.prefix}.{i}.0.weight"] = grads.get(f"{self.prefix}.{i}.0.weight", 0) + A.product(dh.T, x, self.arith)
             grads[f"{self.prefix}.{i}.0.bias"] = grads.get(f"{self.prefix}.{i}.0.bias", 0) + dh.sum(axis=0)
-            da = dh @ self.w[i] if (need_dx or i == 1) else None
+            da = A.product(dh, self.w[i], self.arith) if (need_dx or i == 1) else None
+            if i == 1 or store_dx:
+                da = A.store(da, self.arith)
         return da
 
 
@@ -106,9 +128,9 @@ def build_edges(pos, cell_offsets, pyg_self_loops=True):
     return levels
 
 
-def forward_backward(pos, rgb, cell_offsets, sd, grad_f2=None, pyg_self_loops=True):
+def forward_backward(pos, rgb, cell_offsets, sd, grad_f2=None, pyg_self_loops=True, arith=0):
     """pos, rgb f32[n_obj,256,3]. Returns (features2 f64[n_obj,256], info) with info["grads"] (when grad_f2 is given),
-    info["running"] = name -> value after the per-cell sequential updates, info["features0"]."""
+    info["running"] = name -> value after the per-cell sequential updates, info["features0"]. ``arith``: module docstring."""
     sd64 = {k: np.asarray(v, dtype=np.float64) for k, v in sd.items() if np.asarray(v).dtype.kind == "f"}
     n_obj = pos.shape[0]
     n_cells = len(cell_offsets) - 1
@@ -125,7 +147,7 @@ def forward_backward(pos, rgb, cell_offsets, sd, grad_f2=None, pyg_self_loops=Tr
     fwd = []  # per level, per cell: (mlp cache, row -> (object, centre), argmax rows)
     for li, (radius, name) in enumerate(OP.LEVELS):
         sel, src, src_pos, new_pos = levels[li]
-        mlp = _Mlp(sd64, f"{P}{name}.point_conv.local_nn")
+        mlp = _Mlp(sd64, f"{P}{name}.point_conv.local_nn", arith)
         x_prev = x_levels[-1]
         nd = sel.shape[1]
         h2 = mlp.w[1].shape[0]
@@ -142,7 +164,7 @@ def forward_backward(pos, rgb, cell_offsets, sd, grad_f2=None, pyg_self_loops=Tr
                     rows_ctr.extend([(o, t)] * len(src[o][t]))
             rows_src = np.array(rows_src, dtype=np.int64)
             ctr = np.array(rows_ctr, dtype=np.int64)
-            xin = np.concatenate([xs[rows_src], ps[rows_src] - new_pos[ctr[:, 0], ctr[:, 1]].astype(np.float64)], axis=1)
+            xin = A.store(np.concatenate([xs[rows_src], ps[rows_src] - new_pos[ctr[:, 0], ctr[:, 1]].astype(np.float64)], axis=1), arith)
             a, cache = mlp.forward(xin)
             update_running(mlp.prefix, cache)
             amax = {}
@@ -159,14 +181,14 @@ def forward_backward(pos, rgb, cell_offsets, sd, grad_f2=None, pyg_self_loops=Tr
         fwd.append((mlp, per_cell))
         x_levels.append(new_x)
     # global abstraction, per cell
-    ga = _Mlp(sd64, P + "ga.mlp")
+    ga = _Mlp(sd64, P + "ga.mlp", arith)
     pos3 = levels[-1][3].astype(np.float64)
     x3 = x_levels[-1]
     f0 = np.zeros((n_obj, ga.w[1].shape[0]))
     ga_cells = []
     for c in range(n_cells):
         lo, hi = int(cell_offsets[c]), int(cell_offsets[c + 1])
-        xin = np.concatenate([x3[lo:hi], pos3[lo:hi]], axis=2).reshape(-1, x3.shape[2] + 3)
+        xin = A.store(np.concatenate([x3[lo:hi], pos3[lo:hi]], axis=2).reshape(-1, x3.shape[2] + 3), arith)
         a, cache = ga.forward(xin)
         update_running(ga.prefix, cache)
         a3 = a.reshape(hi - lo, pos3.shape[1], -1)
@@ -175,24 +197,24 @@ def forward_backward(pos, rgb, cell_offsets, sd, grad_f2=None, pyg_self_loops=Tr
         ga_cells.append((cache, arg, lo, hi))
     w1, b1 = sd64[P + "lin1.weight"], sd64[P + "lin1.bias"]
     w2, b2 = sd64[P + "lin2.weight"], sd64[P + "lin2.bias"]
-    f1 = np.maximum(f0 @ w1.T + b1, 0.0)
-    f2 = np.maximum(f1 @ w2.T + b2, 0.0)
+    f1 = np.maximum(A.product(f0, w1.T, arith) + b1, 0.0)
+    f2 = np.maximum(A.product(f1, w2.T, arith) + b2, 0.0)
     info = {"running": running, "features0": f0, "features1": f1}
     if grad_f2 is None:
         return f2, info
 
     grads = {}
     d2 = np.asarray(grad_f2, dtype=np.float64) * (f2 > 0)
-    grads[P + "lin2.weight"], grads[P + "lin2.bias"] = d2.T @ f1, d2.sum(axis=0)
-    d1 = (d2 @ w2) * (f1 > 0)
-    grads[P + "lin1.weight"], grads[P + "lin1.bias"] = d1.T @ f0, d1.sum(axis=0)
-    df0 = d1 @ w1
+    grads[P + "lin2.weight"], grads[P + "lin2.bias"] = A.product(d2.T, f1, arith), d2.sum(axis=0)
+    d1 = A.product(d2, w2, arith) * (f1 > 0)
+    grads[P + "lin1.weight"], grads[P + "lin1.bias"] = A.product(d1.T, f0, arith), d1.sum(axis=0)
+    df0 = A.product(d1, w1, arith)
     dx = np.zeros_like(x3)
     for cache, arg, lo, hi in ga_cells:
         npts = pos3.shape[1]
         da = np.zeros((hi - lo, npts, f0.shape[1]))
         np.put_along_axis(da, arg[:, None, :], df0[lo:hi][:, None, :], axis=1)
-        dxin = ga.backward(da.reshape(-1, f0.shape[1]), cache, grads)
+        dxin = ga.backward(da.reshape(-1, f0.shape[1]), cache, grads, store_dx=True)
         dx[lo:hi] = dxin.reshape(hi - lo, npts, -1)[:, :, : x3.shape[2]]
     for li in (2, 1, 0):
         mlp, per_cell = fwd[li]

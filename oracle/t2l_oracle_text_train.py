@@ -11,6 +11,14 @@ the dropout sites: 0 -> sites 0-3, 1 -> sites 4-7, the masks are this build's co
 Only ``tests/`` may import this module. Pinning: tests/test_oracle_train.py checks it against tests/golden/train_step_text.npz (the
 imported reference's own forward / backward with the dropout sites at p = 0, oracle/gen_golden_text_train.py) and against central
 differences of its own forward.
+
+Reduced-precision arithmetic (``arith``, oracle/arith.py; the engine's option ``text_train_bf16``): EVERY Linear product of the head —
+forward, dW and dX of intra_module.0, inter_mlp and inter_module.0 — takes the operand arithmetic, through ``OT._Tape.mm``. Products with
+>= 64 output rows (t_fast, text2loc_amd/csrc/train.hip:998-1000) run on fast_gemm (text_head.hip:990-1054): th_split_bf16_kernel
+(text_head.hip:593-603) forms hi = bf16(v) and lo = bf16(v - hi) planes of both operands and th_gemm_kernel<.., BF16> adds wh*xh,
+plus wh*xl + wl*xh unless ``single`` (mode 1) (text_head.hip:274-277); the smaller ones run on gemm_f32.h with tl_gemm_bf16 =
+text_train_bf16 (train.hip:1003, 1021-1022, 1061, 1117, 1185) — the same arithmetic. Exact on the device and here: the attention cores,
+LayerNorms, the BatchNorm, the max poolings and the bias gradients (float32 column sums of the unrounded dY).
 """
 from __future__ import annotations
 
@@ -20,10 +28,11 @@ from . import t2l_oracle_train as OT
 
 
 def text_head_train(hidden: np.ndarray, sd: dict, n_desc: int, grad_out=None, p_drop: float = 0.0, seed: int = 0, dtype=np.float64,
-                    prefix: str = "language_encoder."):
+                    prefix: str = "language_encoder.", arith=0):
     """hidden f32[n_sent, L, 1024] (description-major) -> (out [n_desc, 256] — not normalised —, info). With ``grad_out``
-    [n_desc, 256]: info["grads"][name] = dLoss/dparameter, info["bn_stats"]["<prefix>inter_mlp.0.1"] = (mean, biased var, n)."""
-    t = OT._Tape(sd, dtype)
+    [n_desc, 256]: info["grads"][name] = dLoss/dparameter, info["bn_stats"]["<prefix>inter_mlp.0.1"] = (mean, biased var, n).
+    ``arith``: operand arithmetic of the Linear products (module docstring; float64 only)."""
+    t = OT._Tape(sd, dtype, arith)
     w = t.w
     x = np.asarray(hidden).astype(dtype)
     n_sent, L, _ = x.shape
@@ -32,7 +41,7 @@ def text_head_train(hidden: np.ndarray, sd: dict, n_desc: int, grad_out=None, p_
     tok_arg = x2.argmax(axis=1)                                                              # :133 (first maximal token wins)
     pooled = np.take_along_axis(x2, tok_arg[:, None, :], axis=1)[:, 0]
     mp = prefix + "inter_mlp.0"
-    y = pooled @ w[mp + ".0.weight"].T + w[mp + ".0.bias"]                                  # :135
+    y = t.mm(pooled, w[mp + ".0.weight"].T) + w[mp + ".0.bias"]                                  # :135
     z, bc = OT._bn_fwd(y, w[mp + ".1.weight"], w[mp + ".1.bias"])
     t.bn_stats[mp + ".1"] = (bc[2], bc[3], y.shape[0])
     xi = z.reshape(n_desc, S, -1)                                                            # :136
@@ -51,9 +60,9 @@ def text_head_train(hidden: np.ndarray, sd: dict, n_desc: int, grad_out=None, p_
     dy, dg, db = OT._bn_bwd(dz, w[mp + ".1.weight"], bc)
     t.add(mp + ".1.weight", dg)
     t.add(mp + ".1.bias", db)
-    t.add(mp + ".0.weight", dy.T @ pooled)
+    t.add(mp + ".0.weight", t.mm(dy.T, pooled))
     t.add(mp + ".0.bias", dy.sum(0))
-    dpooled = dy @ w[mp + ".0.weight"]
+    dpooled = t.mm(dy, w[mp + ".0.weight"])
     dx2 = np.zeros_like(x2)
     np.put_along_axis(dx2, tok_arg[:, None, :], dpooled[:, None, :], axis=1)
     OT._layer_bwd(t, dx2, prefix + "intra_module.0", 4, c1)

@@ -13,10 +13,23 @@ against ``tests/golden/train_step_{embed,pn}.npz`` (the imported reference run w
 oracle/gen_golden_train.py) and checks the analytic backward against central differences of the forward.
 Dropout masks are this build's own counter-based masks (``dropout_keep``): torch's RNG stream is not reproducible,
 so with p>0 the oracle pins the build's arithmetic, not the reference's random draw.
+
+Reduced-precision arithmetic (``arith``, oracle/arith.py; the engine's option ``train_bf16``): ``tl_gemm_bf16`` reaches exactly the
+products of the gemm_f32.h GEMMs (text2loc_amd/csrc/train.hip), and ``_Tape.mm`` applies ``product(.., arith)`` exactly there:
+* forward: the Linears with more than 3 inputs — mlp_pointnet, mlp_merge (mlp_layer_fwd -> gemm_nt, train.hip:346), the second layer
+  of the colour / position / count encoders (small_branches_fwd, train.hip:416), in_proj / out_proj / linear1 / linear2 of every
+  transformer layer (train.hip:610, 612, 616, 628);
+* backward: dW and dX of the same Linears (mlp_layer_bwd -> gemm_tn_nn / gemm_tn, train.hip:667-671; small_branches_bwd,
+  train.hip:465-467; the layers' gemm_tn_nn, train.hip:718, 721, 726, 730).
+Exact on the device and here: the [1|3 -> 64] first layers of the small encoders (smallk_* kernels, train.hip:343, 421, 489, 664), the
+attention cores, every bias gradient (float32 column sums of the UNROUNDED dY, gemm_f32.h:122-131), normalisations, BatchNorm and
+LayerNorm. ``arith=0`` is the plain ``@`` of before (every default output unchanged bit for bit).
 """
 from __future__ import annotations
 
 import numpy as np
+
+from .arith import product
 
 BN_EPS = 1e-5
 LN_EPS = 1e-5
@@ -102,15 +115,21 @@ def _ln_bwd(dy, g, cache):
 
 
 class _Tape:
-    """Weights in the working dtype + gradient accumulators + BatchNorm batch statistics seen in forward."""
+    """Weights in the working dtype + gradient accumulators + BatchNorm batch statistics seen in forward + the operand arithmetic
+    of the GEMM-served products (module docstring)."""
 
-    def __init__(self, sd, dtype):
+    def __init__(self, sd, dtype, arith=0):
         self.w = {k: np.asarray(v).astype(dtype) for k, v in sd.items() if np.asarray(v).dtype.kind == "f"}
         self.grads = {}
         self.bn_stats = {}  # prefix -> (mean, biased var, n)
+        self.arith = arith
 
     def add(self, name, g):
         self.grads[name] = self.grads.get(name, 0) + g
+
+    def mm(self, a, b, gemm=True):
+        """a @ b; under the operand arithmetic when the device runs this product on a bf16-capable GEMM (``gemm``)."""
+        return product(a, b, self.arith if gemm else 0)
 
 
 def _mlp_fwd(t: _Tape, x, prefix, n_layers):
@@ -118,7 +137,7 @@ def _mlp_fwd(t: _Tape, x, prefix, n_layers):
     caches = []
     for i in range(n_layers):
         w, b = t.w[f"{prefix}.{i}.0.weight"], t.w[f"{prefix}.{i}.0.bias"]
-        y = x @ w.T + b
+        y = t.mm(x, w.T, x.shape[1] > 3) + b  # (1 or 3 inputs: smallk_fwd_kernel, float32)
         z, bc = _bn_fwd(y, t.w[f"{prefix}.{i}.1.weight"], t.w[f"{prefix}.{i}.1.bias"])
         t.bn_stats[f"{prefix}.{i}.1"] = (bc[2], bc[3], y.shape[0])
         out = np.maximum(z, 0)
@@ -130,14 +149,15 @@ def _mlp_fwd(t: _Tape, x, prefix, n_layers):
 def _mlp_bwd(t: _Tape, d, prefix, caches, need_dx=False):
     for i in reversed(range(len(caches))):
         x, bc, pos = caches[i]
+        gemm = x.shape[1] > 3  # (1 or 3 inputs: smallk_bwd_kernel, float32)
         d = d * pos
         d, dg, db = _bn_bwd(d, t.w[f"{prefix}.{i}.1.weight"], bc)
         t.add(f"{prefix}.{i}.1.weight", dg)
         t.add(f"{prefix}.{i}.1.bias", db)
-        t.add(f"{prefix}.{i}.0.weight", d.T @ x)
+        t.add(f"{prefix}.{i}.0.weight", t.mm(d.T, x, gemm))
         t.add(f"{prefix}.{i}.0.bias", d.sum(0))
         if i > 0 or need_dx:
-            d = d @ t.w[f"{prefix}.{i}.0.weight"]
+            d = t.mm(d, t.w[f"{prefix}.{i}.0.weight"], gemm)
     return d
 
 
@@ -146,7 +166,7 @@ def _layer_fwd(t: _Tape, x, prefix, H, p, seed, layer):
     B, S, D = x.shape
     hd = D // H
     w = t.w
-    qkv = x @ w[prefix + ".self_attn.in_proj_weight"].T + w[prefix + ".self_attn.in_proj_bias"]
+    qkv = t.mm(x, w[prefix + ".self_attn.in_proj_weight"].T) + w[prefix + ".self_attn.in_proj_bias"]
 
     def heads(a):
         return a.reshape(B, S, H, hd).transpose(0, 2, 1, 3)  # [B,H,S,hd]
@@ -158,12 +178,12 @@ def _layer_fwd(t: _Tape, x, prefix, H, p, seed, layer):
     pr = pr / pr.sum(-1, keepdims=True)
     prd, m0 = _drop(pr, seed, layer * 4 + 0, p)  # attention-probability dropout (MultiheadAttention.dropout)
     o = (prd @ v).transpose(0, 2, 1, 3).reshape(B, S, D)
-    a = o @ w[prefix + ".self_attn.out_proj.weight"].T + w[prefix + ".self_attn.out_proj.bias"]
+    a = t.mm(o, w[prefix + ".self_attn.out_proj.weight"].T) + w[prefix + ".self_attn.out_proj.bias"]
     ad, m1 = _drop(a, seed, layer * 4 + 1, p)  # dropout1
     x1, ln1 = _ln_fwd(x + ad, w[prefix + ".norm1.weight"], w[prefix + ".norm1.bias"])
-    h = np.maximum(x1 @ w[prefix + ".linear1.weight"].T + w[prefix + ".linear1.bias"], 0)
+    h = np.maximum(t.mm(x1, w[prefix + ".linear1.weight"].T) + w[prefix + ".linear1.bias"], 0)
     hdp, m2 = _drop(h, seed, layer * 4 + 2, p)  # dropout
-    f = hdp @ w[prefix + ".linear2.weight"].T + w[prefix + ".linear2.bias"]
+    f = t.mm(hdp, w[prefix + ".linear2.weight"].T) + w[prefix + ".linear2.bias"]
     fd, m3 = _drop(f, seed, layer * 4 + 3, p)  # dropout2
     x2, ln2 = _ln_fwd(x1 + fd, w[prefix + ".norm2.weight"], w[prefix + ".norm2.bias"])
     return x2, (x, q, k, v, pr, prd, m0, o, m1, ln1, x1, h, hdp, m2, m3, ln2)
@@ -178,22 +198,22 @@ def _layer_bwd(t: _Tape, d, prefix, H, cache):
     t.add(prefix + ".norm2.weight", dg)
     t.add(prefix + ".norm2.bias", db)
     dfd = dz2 if m3 is None else dz2 * m3
-    t.add(prefix + ".linear2.weight", dfd.reshape(-1, D).T @ hdp.reshape(-1, hdp.shape[-1]))
+    t.add(prefix + ".linear2.weight", t.mm(dfd.reshape(-1, D).T, hdp.reshape(-1, hdp.shape[-1])))
     t.add(prefix + ".linear2.bias", dfd.reshape(-1, D).sum(0))
-    dh = dfd @ w[prefix + ".linear2.weight"]
+    dh = t.mm(dfd, w[prefix + ".linear2.weight"])
     if m2 is not None:
         dh = dh * m2
     dh = dh * (h > 0)
-    t.add(prefix + ".linear1.weight", dh.reshape(-1, dh.shape[-1]).T @ x1.reshape(-1, D))
+    t.add(prefix + ".linear1.weight", t.mm(dh.reshape(-1, dh.shape[-1]).T, x1.reshape(-1, D)))
     t.add(prefix + ".linear1.bias", dh.reshape(-1, dh.shape[-1]).sum(0))
-    dx1 = dz2 + dh @ w[prefix + ".linear1.weight"]
+    dx1 = dz2 + t.mm(dh, w[prefix + ".linear1.weight"])
     dz1, dg, db = _ln_bwd(dx1, w[prefix + ".norm1.weight"], ln1)
     t.add(prefix + ".norm1.weight", dg)
     t.add(prefix + ".norm1.bias", db)
     da = dz1 if m1 is None else dz1 * m1
-    t.add(prefix + ".self_attn.out_proj.weight", da.reshape(-1, D).T @ o.reshape(-1, D))
+    t.add(prefix + ".self_attn.out_proj.weight", t.mm(da.reshape(-1, D).T, o.reshape(-1, D)))
     t.add(prefix + ".self_attn.out_proj.bias", da.reshape(-1, D).sum(0))
-    do = (da @ w[prefix + ".self_attn.out_proj.weight"]).reshape(B, S, H, hd).transpose(0, 2, 1, 3)
+    do = t.mm(da, w[prefix + ".self_attn.out_proj.weight"]).reshape(B, S, H, hd).transpose(0, 2, 1, 3)
     dv = prd.transpose(0, 1, 3, 2) @ do
     dprd = do @ v.transpose(0, 1, 3, 2)
     dpr = dprd if m0 is None else dprd * m0
@@ -205,9 +225,9 @@ def _layer_bwd(t: _Tape, d, prefix, H, cache):
         return a.transpose(0, 2, 1, 3).reshape(B, S, D)
 
     dqkv = np.concatenate([unheads(dq), unheads(dk), unheads(dv)], axis=-1)
-    t.add(prefix + ".self_attn.in_proj_weight", dqkv.reshape(-1, 3 * D).T @ x.reshape(-1, D))
+    t.add(prefix + ".self_attn.in_proj_weight", t.mm(dqkv.reshape(-1, 3 * D).T, x.reshape(-1, D)))
     t.add(prefix + ".self_attn.in_proj_bias", dqkv.reshape(-1, 3 * D).sum(0))
-    return dz1 + dqkv @ w[prefix + ".self_attn.in_proj_weight"]
+    return dz1 + t.mm(dqkv, w[prefix + ".self_attn.in_proj_weight"])
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -215,11 +235,11 @@ def _layer_bwd(t: _Tape, d, prefix, H, cache):
 # ----------------------------------------------------------------------------------------------------------------
 def encode_cells_train(cells: dict, sd: dict, class_embed: bool, color_embed: bool, grad_out=None, p_drop: float = 0.0,
                        seed: int = 0, object_size: int = 28, n_heads: int = 4, n_layers: int = 2,
-                       use_features=FEATURES, dtype=np.float64):
+                       use_features=FEATURES, dtype=np.float64, arith=0):
     """Returns (out [B,D], info). ``info['bn_stats']``: BatchNorm prefix -> (batch mean, biased var, n rows).
     With ``grad_out`` [B,D] (dLoss/d out) also ``info['grads']`` (state_dict names) and, in the PointNet mode,
-    ``info['grad_pn_feat']``."""
-    t = _Tape(sd, dtype)
+    ``info['grad_pn_feat']``. ``arith``: operand arithmetic of the GEMM-served products (module docstring; float64 only)."""
+    t = _Tape(sd, dtype, arith)
     p = "object_encoder."
     counts, offsets = np.asarray(cells["counts"]), np.asarray(cells["offsets"])
     B = len(counts)
