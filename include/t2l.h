@@ -16,7 +16,9 @@
  *     that stream unless stated otherwise. A context is not thread-safe: the reference is a single
  *     thread / single process per device, and so is this (one process per GPU; shards meet in RCCL).
  *   - row ids are int32 (N < 2^31) and GLOBAL: local row + the shard's row_offset (t2l_db_set).
- *   - embed dim is fixed at 256 (coarse_embed_dim of the published config, README.md:87-99).
+ *   - the search, the loss, the text entry points and the training step work on rows of T2L_EMBED_DIM = 256 floats
+ *     (coarse_embed_dim of the published config, README.md:87-99). The eval-mode cell encoder also serves the other
+ *     shapes the reference builds from its arguments (t2l_load_weights_shaped); t2l_embed_dim gives its row width.
  */
 #ifndef T2L_H_
 #define T2L_H_
@@ -75,6 +77,28 @@ typedef struct {
  * "object_encoder.pointnet.*" tensors are optional as a group: when present they are folded and packed for
  * t2l_pointnet_features (the two classifier heads, unused on this path, are ignored). */
 int t2l_load_weights(t2l_ctx* ctx, const t2l_weight_desc* w, int32_t n, const t2l_model_config* cfg);
+
+/* The shape arguments the reference builds its coarse model from (models/cell_retrieval.py:22-49): */
+typedef struct {
+  int32_t embed_dim;   /* args.coarse_embed_dim (training/args.py:47): 128 or 256 */
+  int32_t object_size; /* args.object_size (training/args.py:60): 1..32, one 32-row MFMA tile */
+} t2l_model_shape;
+
+/* t2l_load_weights for a model built with other shape arguments. Replaces: CellRetrievalNetwork.__init__ reading
+ * args.coarse_embed_dim / args.object_size / args.object_inter_module_num_heads (models/cell_retrieval.py:22-49,
+ * training/args.py:47,60-62) + load_state_dict. t2l_load_weights(ctx, w, n, cfg) is this call with {256, 28}.
+ * Compiled set: embed_dim 128 or 256; cfg->num_heads with head_dim = embed_dim / num_heads of 32 or 64 (2 or 4 heads at
+ * 128, 4 or 8 at 256); object_size 1..32; cfg->num_layers 1..4; dim_feedforward = 2 * embed_dim as in the reference.
+ * Anything else is T2L_EINVAL and the message names the set, as is a tensor whose size contradicts the declared shape.
+ * {256, 28} with 4 heads runs the kernels of the published model, every other shape one shape-templated kernel (one cell
+ * per workgroup; split-f16 MFMA, or the f32 MFMA under the same range guard / option "encoder_f32"). Options
+ * "encoder_f16" and "encoder_two_cells" are accepted at every shape and act on the published shape only.
+ * The training entry points (t2l_train_bind and what follows it) are built for the published shape only. */
+int t2l_load_weights_shaped(t2l_ctx* ctx, const t2l_weight_desc* w, int32_t n, const t2l_model_config* cfg,
+                            const t2l_model_shape* shape);
+/* Replaces: model.embed_dim (models/cell_retrieval.py:26). Row width of t2l_encode_cells' output for the loaded weights
+ * (T2L_EMBED_DIM before any load). */
+int t2l_embed_dim(const t2l_ctx* ctx);
 
 /* ---- per-object reductions over raw points (a1) ------------------------------------------------ */
 /* Replaces the host reductions the reference redoes inside every ObjectEncoder.forward call
@@ -149,9 +173,9 @@ typedef struct {
 } t2l_packed_cells;
 
 /* Replaces: CellRetrievalNetwork.encode_objects (models/cell_retrieval.py:65-110) in eval mode.
- * out_emb: dev f32[n_cells,256], unit rows. Objects beyond the first 28 of a cell are ignored
- * (cell_retrieval.py:94-98); the zero pad slots take part in attention and in the max-pool, as in
- * the reference (no padding mask). */
+ * out_emb: dev f32[n_cells, D] dense, unit rows, D = t2l_embed_dim(ctx) (256 after t2l_load_weights). Objects beyond the
+ * first object_size (28) of a cell are ignored (cell_retrieval.py:94-98); the zero pad slots below object_size take part in
+ * attention and in the max-pool, as in the reference (no padding mask). */
 int t2l_encode_cells(t2l_ctx* ctx, const t2l_packed_cells* in, float* out_emb, void* stream);
 
 /* ---- database + search (a6) ------------------------------------------------------------------ */

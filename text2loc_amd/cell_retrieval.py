@@ -4,8 +4,8 @@ on the boundary that ``training.coarse.eval_epoch`` / ``evaluation.pipeline.run_
     CellRetrievalNetwork(known_classes, known_colors, args)
         .embed_dim  .eval()  .train()  .to(device)  .device / .get_device()
         .state_dict() / .load_state_dict(strict=False)     (same parameter names as the reference checkpoint)
-        .encode_objects(objects, object_points) -> Tensor[B,256]   # fused HIP kernel (libt2l.so)
-        .encode_text(descriptions)              -> Tensor[B,256]   # frozen T5 + head, PyTorch-ROCm (unchanged path)
+        .encode_objects(objects, object_points) -> Tensor[B,D]     # fused HIP kernel (libt2l.so), D = coarse_embed_dim
+        .encode_text(descriptions)              -> Tensor[B,D]     # frozen T5 + head, PyTorch-ROCm (unchanged path)
         .forward() raises, as in the reference (cell_retrieval.py:112-113)
 
 The object branch's modules below are PARAMETER CONTAINERS only (so that checkpoints load and save with the
@@ -31,7 +31,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import packing
-from .engine import EMBED_DIM, OBJECT_SIZE, Engine, T2LError
+from .engine import EMBED_DIM, OBJECT_SIZE, TRAIN_SHAPE_MSG, Engine, T2LError, check_compiled_shape, is_published_shape
 
 
 def get_mlp(channels: Sequence[int], add_batchnorm: bool = True, last_relu: bool = True) -> nn.Sequential:
@@ -559,11 +559,11 @@ class CellRetrievalNetwork(nn.Module):
         super().__init__()
         self.args = args
         self.embed_dim = args.coarse_embed_dim
-        if self.embed_dim != EMBED_DIM:
-            raise T2LError(f"the engine is built for coarse_embed_dim={EMBED_DIM}, got {self.embed_dim}")
-        if args.object_size != OBJECT_SIZE:
-            raise T2LError(f"the engine is built for object_size={OBJECT_SIZE}, got {args.object_size}")
+        # the shapes the fused encoder is compiled for (engine.COMPILED_SHAPES); anything else has no kernel and no fallback
+        check_compiled_shape(int(self.embed_dim), int(args.object_inter_module_num_heads), int(args.object_size),
+                             int(args.object_inter_module_num_layers))
         self.object_size = args.object_size
+        self.published_shape = is_published_shape(int(self.embed_dim), int(args.object_inter_module_num_heads), int(args.object_size))
         self.object_encoder = ObjectEncoderParams(self.embed_dim, known_classes, args, known_colors)
         self.obj_inter_module = nn.ModuleList([
             nn.TransformerEncoderLayer(self.embed_dim, args.object_inter_module_num_heads,
@@ -611,6 +611,8 @@ class CellRetrievalNetwork(nn.Module):
 
     def encode_objects(self, objects, object_points=None):
         if self.training and torch.is_grad_enabled():
+            if not self.published_shape:
+                raise T2LError("encode_objects under model.train(): " + TRAIN_SHAPE_MSG)
             return self._encode_objects_train(objects, object_points)
         with torch.no_grad():
             return self._encode_objects_eval(objects, object_points)
@@ -706,6 +708,8 @@ class CellRetrievalNetwork(nn.Module):
 
     def train_engine(self) -> Engine:
         """The engine with the training path bound to the CURRENT parameter / gradient / buffer storage."""
+        if not self.published_shape:
+            raise T2LError("train_engine: " + TRAIN_SHAPE_MSG)
         dev = self.device
         idx = dev.index if dev.index is not None else torch.cuda.current_device()
         if self._engine is None or self._engine.device != idx:
@@ -793,7 +797,7 @@ class CellRetrievalNetwork(nn.Module):
     @torch.no_grad()
     def encode_cell_set(self, cell_set, points: bool = False, transform: str = "fixed", seed: int = 0,
                         chunk_cells: int = 4096) -> torch.Tensor:
-        """Eval-mode ``encode_objects`` over a whole ``packing.PackedCellSet`` -> f32[n_cells,256] unit rows on the GPU: what
+        """Eval-mode ``encode_objects`` over a whole ``packing.PackedCellSet`` -> f32[n_cells,embed_dim] unit rows on the GPU: what
         ``eval_epoch``'s database loop (training/coarse.py:99-113) computes with one ``encode_objects`` call per ``args.batch_size``
         cells (1 by default, evaluation/args.py:11), here from the flattened dataset in chunks of ``chunk_cells`` cells. In eval mode
         a cell's embedding is a function of that cell alone (no batch statistics, no dropout), so the chunking cannot change it —
@@ -889,4 +893,5 @@ class CellRetrievalNetwork(nn.Module):
         self._engine.load_weights(sd, class_embed=bool(getattr(a, "class_embed", False)),
                                   color_embed=bool(getattr(a, "color_embed", False)),
                                   use_features=tuple(a.use_features), num_layers=a.object_inter_module_num_layers,
-                                  num_heads=a.object_inter_module_num_heads)
+                                  num_heads=a.object_inter_module_num_heads, embed_dim=self.embed_dim,
+                                  object_size=self.object_size)

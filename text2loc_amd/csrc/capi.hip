@@ -126,9 +126,19 @@ int t2l_load_weights(t2l_ctx* ctx, const t2l_weight_desc* w, int32_t n, const t2
   if (!ctx) return T2L_EINVAL;
   if (!w || n <= 0 || !cfg) return fail(ctx, T2L_EINVAL, "t2l_load_weights: null/empty arguments");
   T2L_HIP(ctx, hipSetDevice(ctx->device));
-  const int rc = load_weights_impl(ctx, w, n, cfg);
+  const int rc = load_weights_impl(ctx, w, n, cfg, T2L_EMBED_DIM, T2L_OBJECT_SIZE);
   return rc ? rc : pointnet_load_impl(ctx, w, n);
 }
+
+int t2l_load_weights_shaped(t2l_ctx* ctx, const t2l_weight_desc* w, int32_t n, const t2l_model_config* cfg, const t2l_model_shape* shape) {
+  if (!ctx) return T2L_EINVAL;
+  if (!w || n <= 0 || !cfg || !shape) return fail(ctx, T2L_EINVAL, "t2l_load_weights_shaped: null/empty arguments");
+  T2L_HIP(ctx, hipSetDevice(ctx->device));
+  const int rc = load_weights_impl(ctx, w, n, cfg, shape->embed_dim, shape->object_size);
+  return rc ? rc : pointnet_load_impl(ctx, w, n);
+}
+
+int t2l_embed_dim(const t2l_ctx* ctx) { return ctx ? encoder_embed_dim(ctx) : T2L_EINVAL; }
 
 int t2l_sample_object_points(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets, int32_t n_objects,
                              uint32_t seed, int32_t transform_flags, float rotate_deg, float* out_pos, float* out_rgb, void* stream) {

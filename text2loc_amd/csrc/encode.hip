@@ -28,6 +28,7 @@
 
 #include "t2l_internal.h"
 #include "mfma_h3.h"
+#include "encode_shared.h"
 
 #ifndef T2L_ENC_UNROLL
 #define T2L_ENC_UNROLL 4
@@ -43,71 +44,9 @@
 
 namespace t2l {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kLdX = kD + 4;        // 260: row stride of every 256-wide LDS buffer
 constexpr int kLdH = 64 + 4;        // 68   (hidden layer of the small MLPs)
 constexpr int kXFloats = kSP * kLdX;
-constexpr float kNumMean = 1826.6844940968194f;  // models/object_encoder.py:43
-constexpr float kNumStd = 2516.8905096993817f;   // models/object_encoder.py:44
-
-struct SmallMlp {  // get_mlp([in, 64, 256]) with BN folded (language_encoder.py:16-41)
-  const float* w1;   // [64][in]
-  const float* b1;   // [64]
-  const float4* w2p; // packed [8 tiles][8][64] float4   (N=256, K=64)
-  const float* b2;   // [256]
-};
-
-struct LayerW {
-  const float4 *in_wp, *out_wp, *ff1_wp, *ff2_wp;
-  const uint4 *in_hp, *out_hp, *ff1_hp, *ff2_hp;  // the same matrices as split-f16 fragments (pack_h)
-  const float *in_b, *out_b, *ff1_b, *ff2_b, *ln1_w, *ln1_b, *ln2_w, *ln2_b;
-};
-
-struct EncParams {
-  const float* class_tab;  // [n_class][256] rows already L2-normalised
-  const float* color_tab;  // [n_color][256]
-  int n_class, n_color;
-  SmallMlp pos, color, num;
-  const float4* pn_wp;     // mlp_pointnet packed (N=256,K=256)
-  const uint4* pn_hp;
-  const float* pn_b;
-  const float4* merge_wp;  // nfeat consecutive packings (N=256, K=256), one per 256-wide feature slot
-  const uint4* merge_hp;
-  const float* merge_b;
-  LayerW layer[4];
-  int num_layers;
-  int class_embed, color_embed, use_class, use_color, use_pos, use_num, nfeat;
-  int split_ok;  // every activation entering a split-f16 GEMM is provably below the f16 range for these weights
-};
-
-struct EncoderWeights {
-  EncParams p;
-  float* blob = nullptr;
-};
-
-// ---- device helpers ----------------------------------------------------------------------------
-// all-reduce sum over the 64 lanes on the VALU (DPP + v_permlane swaps): __shfl_xor lowers to ds_bpermute_b32 — six dependent
-// LDS round trips per sum
-template <int CTRL>
-__device__ __forceinline__ float wave_sum_dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float wave_sum(float v) {
-  v += wave_sum_dpp<0xB1>(v);   // quad_perm [1,0,3,2]
-  v += wave_sum_dpp<0x4E>(v);   // quad_perm [2,3,0,1]
-  v += wave_sum_dpp<0x141>(v);  // row_half_mirror
-  v += wave_sum_dpp<0x140>(v);  // row_mirror
-  {
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  }
-  {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  }
-  return v;
-}
 
 // out[32][N] = A[32][K] @ W^T ; the 4 waves split N in 32-column tiles, two tiles at a time per wave
 // (tiles w+8p and w+8p+4) sharing the A fragments. epi(t, r, row, col, value) is called for every element
@@ -1354,13 +1293,13 @@ std::vector<float> pack_h(const std::vector<float>& W, int N, int K) { return pa
 float max_abs(const float* v, size_t n) { return h3_max_abs(v, n); }
 float max_row_norm(const float* W, int rows, int cols) { return h3_max_row_norm(W, rows, cols); }
 
-std::vector<float> normalized_rows(const float* t, int rows) {
-  std::vector<float> o((size_t)rows * kD);
+std::vector<float> normalized_rows(const float* t, int rows, int D) {
+  std::vector<float> o((size_t)rows * D);
   for (int r = 0; r < rows; ++r) {
     float ss = 0.f;
-    for (int c = 0; c < kD; ++c) ss += t[r * kD + c] * t[r * kD + c];
+    for (int c = 0; c < D; ++c) ss += t[r * D + c] * t[r * D + c];
     const float inv = 1.f / fmaxf(sqrtf(ss), 1e-12f);
-    for (int c = 0; c < kD; ++c) o[(size_t)r * kD + c] = t[r * kD + c] * inv;
+    for (int c = 0; c < D; ++c) o[(size_t)r * D + c] = t[r * D + c] * inv;
   }
   return o;
 }
@@ -1369,13 +1308,13 @@ struct SmallOff {
   size_t w1, b1, w2p, b2;
 };
 
-bool add_small(t2l_ctx* ctx, const WMap& m, const std::string& pre, int in, Blob* blob, SmallOff* off, int* rc) {
+bool add_small(t2l_ctx* ctx, const WMap& m, const std::string& pre, int in, int D, Blob* blob, SmallOff* off, int* rc) {
   std::vector<float> W1, b1, W2, b2;
   if (!fold(ctx, m, pre + ".0.0", pre + ".0.1", 64, in, &W1, &b1, rc)) return false;
-  if (!fold(ctx, m, pre + ".1.0", pre + ".1.1", kD, 64, &W2, &b2, rc)) return false;
+  if (!fold(ctx, m, pre + ".1.0", pre + ".1.1", D, 64, &W2, &b2, rc)) return false;
   off->w1 = blob->add(W1);
   off->b1 = blob->add(b1);
-  off->w2p = blob->add(pack(W2, kD, 64));
+  off->w2p = blob->add(pack(W2, D, 64));
   off->b2 = blob->add(b2);
   return true;
 }
@@ -1389,8 +1328,12 @@ void free_weights(t2l_ctx* ctx) {
   ctx->enc = nullptr;
 }
 
-int load_weights_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const t2l_model_config* cfg) {
-  if (cfg->num_heads != 4) return fail(ctx, T2L_EINVAL, "t2l_load_weights: only num_heads == 4 (head_dim 64) is built");
+int encoder_embed_dim(const t2l_ctx* ctx) { return ctx->enc ? ctx->enc->embed_dim : kD; }
+
+int load_weights_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const t2l_model_config* cfg, int D, int object_size) {
+  if (!shape_is_compiled(D, cfg->num_heads, object_size))
+    return fail(ctx, T2L_EINVAL, "t2l_load_weights: embed_dim " + std::to_string(D) + ", num_heads " + std::to_string(cfg->num_heads) +
+                                     ", object_size " + std::to_string(object_size) + " is not built (" + compiled_shapes_text() + ")");
   if (cfg->num_layers < 1 || cfg->num_layers > 4) return fail(ctx, T2L_EINVAL, "t2l_load_weights: num_layers must be 1..4");
   const int nfeat = (cfg->use_class != 0) + (cfg->use_color != 0) + (cfg->use_position != 0) + (cfg->use_num != 0);
   if (nfeat < 1) return fail(ctx, T2L_EINVAL, "t2l_load_weights: use_features is empty");
@@ -1410,13 +1353,13 @@ int load_weights_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const t2l_m
   if (cfg->use_class) {
     if (cfg->class_embed) {
       auto it = m.find(oe + "class_embedding.weight");
-      if (it == m.end() || it->second->numel % kD) return fail(ctx, T2L_EINVAL, "missing/odd class_embedding.weight");
-      n_class = (int)(it->second->numel / kD);
-      class_tab = blob.add(normalized_rows(it->second->data, n_class));
+      if (it == m.end() || it->second->numel % D) return fail(ctx, T2L_EINVAL, "missing/odd class_embedding.weight");
+      n_class = (int)(it->second->numel / D);
+      class_tab = blob.add(normalized_rows(it->second->data, n_class, D));
     } else {
       std::vector<float> W, b;
-      if (!fold(ctx, m, oe + "mlp_pointnet.0.0", oe + "mlp_pointnet.0.1", kD, kD, &W, &b, &rc)) return rc;
-      pn_wp = blob.add(pack(W, kD, kD));
+      if (!fold(ctx, m, oe + "mlp_pointnet.0.0", oe + "mlp_pointnet.0.1", D, 256, &W, &b, &rc)) return rc;  // features2 is 256 wide at every D
+      pn_wp = blob.add(pack(W, D, 256));
       pn_b = blob.add(b);
       w_absmax = fmaxf(w_absmax, max_abs(W.data(), W.size()));
     }
@@ -1424,27 +1367,27 @@ int load_weights_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const t2l_m
   if (cfg->use_color) {
     if (cfg->color_embed) {
       auto it = m.find(oe + "color_embedding.weight");
-      if (it == m.end() || it->second->numel % kD) return fail(ctx, T2L_EINVAL, "missing/odd color_embedding.weight");
-      n_color = (int)(it->second->numel / kD);
-      color_tab = blob.add(normalized_rows(it->second->data, n_color));
-    } else if (!add_small(ctx, m, oe + "color_encoder", 3, &blob, &color, &rc)) {
+      if (it == m.end() || it->second->numel % D) return fail(ctx, T2L_EINVAL, "missing/odd color_embedding.weight");
+      n_color = (int)(it->second->numel / D);
+      color_tab = blob.add(normalized_rows(it->second->data, n_color, D));
+    } else if (!add_small(ctx, m, oe + "color_encoder", 3, D, &blob, &color, &rc)) {
       return rc;
     }
   }
-  if (cfg->use_position && !add_small(ctx, m, oe + "pos_encoder", 3, &blob, &pos, &rc)) return rc;
-  if (cfg->use_num && !add_small(ctx, m, oe + "num_encoder", 1, &blob, &num, &rc)) return rc;
+  if (cfg->use_position && !add_small(ctx, m, oe + "pos_encoder", 3, D, &blob, &pos, &rc)) return rc;
+  if (cfg->use_num && !add_small(ctx, m, oe + "num_encoder", 1, D, &blob, &num, &rc)) return rc;
   if (nfeat > 1) {
     std::vector<float> W, b;
-    if (!fold(ctx, m, oe + "mlp_merge.0.0", oe + "mlp_merge.0.1", kD, nfeat * kD, &W, &b, &rc)) return rc;
+    if (!fold(ctx, m, oe + "mlp_merge.0.0", oe + "mlp_merge.0.1", D, nfeat * D, &W, &b, &rc)) return rc;
     {  // one (N=256, K=256) packing per feature slot, consecutive
       std::vector<float> all, all_h;
       for (int sl = 0; sl < nfeat; ++sl) {
-        std::vector<float> Ws((size_t)kD * kD);
-        for (int n = 0; n < kD; ++n)
-          for (int k = 0; k < kD; ++k) Ws[(size_t)n * kD + k] = W[(size_t)n * nfeat * kD + sl * kD + k];
-        const std::vector<float> ps = pack(Ws, kD, kD);
+        std::vector<float> Ws((size_t)D * D);
+        for (int n = 0; n < D; ++n)
+          for (int k = 0; k < D; ++k) Ws[(size_t)n * D + k] = W[(size_t)n * nfeat * D + sl * D + k];
+        const std::vector<float> ps = pack(Ws, D, D);
         all.insert(all.end(), ps.begin(), ps.end());
-        const std::vector<float> ph = pack_h(Ws, kD, kD);
+        const std::vector<float> ph = pack_h(Ws, D, D);
         all_h.insert(all_h.end(), ph.begin(), ph.end());
       }
       merge_wp = blob.add(all);
@@ -1472,15 +1415,15 @@ int load_weights_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const t2l_m
       return true;
     };
     auto vec = [&](const std::string& name, size_t* o) -> bool {
-      const float* v = need(ctx, m, p + name, kD, &rc);
+      const float* v = need(ctx, m, p + name, D, &rc);
       if (!v) return false;
-      *o = blob.add(std::vector<float>(v, v + kD));
+      *o = blob.add(std::vector<float>(v, v + D));
       return true;
     };
-    if (!lin("self_attn.in_proj_weight", "self_attn.in_proj_bias", 3 * kD, kD, &lo[l].in_wp, &lo[l].in_hp, &lo[l].in_b)) return rc;
-    if (!lin("self_attn.out_proj.weight", "self_attn.out_proj.bias", kD, kD, &lo[l].out_wp, &lo[l].out_hp, &lo[l].out_b)) return rc;
-    if (!lin("linear1.weight", "linear1.bias", 2 * kD, kD, &lo[l].ff1_wp, &lo[l].ff1_hp, &lo[l].ff1_b)) return rc;
-    if (!lin("linear2.weight", "linear2.bias", kD, 2 * kD, &lo[l].ff2_wp, &lo[l].ff2_hp, &lo[l].ff2_b)) return rc;
+    if (!lin("self_attn.in_proj_weight", "self_attn.in_proj_bias", 3 * D, D, &lo[l].in_wp, &lo[l].in_hp, &lo[l].in_b)) return rc;
+    if (!lin("self_attn.out_proj.weight", "self_attn.out_proj.bias", D, D, &lo[l].out_wp, &lo[l].out_hp, &lo[l].out_b)) return rc;
+    if (!lin("linear1.weight", "linear1.bias", 2 * D, D, &lo[l].ff1_wp, &lo[l].ff1_hp, &lo[l].ff1_b)) return rc;
+    if (!lin("linear2.weight", "linear2.bias", D, 2 * D, &lo[l].ff2_wp, &lo[l].ff2_hp, &lo[l].ff2_b)) return rc;
     if (!vec("norm1.weight", &lo[l].ln1_w) || !vec("norm1.bias", &lo[l].ln1_b) || !vec("norm2.weight", &lo[l].ln2_w) ||
         !vec("norm2.bias", &lo[l].ln2_b))
       return rc;
@@ -1490,14 +1433,14 @@ int load_weights_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const t2l_m
       const float* W1 = m.at(p + "linear1.weight")->data;
       const float* b1 = m.at(p + "linear1.bias")->data;
       auto ln_elem = [&](const char* wn, const char* bn) {
-        return 16.f * max_abs(m.at(p + wn)->data, kD) + max_abs(m.at(p + bn)->data, kD);
+        return 16.f * max_abs(m.at(p + wn)->data, D) + max_abs(m.at(p + bn)->data, D);
       };
       act_bound = fmaxf(act_bound, x_norm);                                                                   // q/k/v input
-      act_bound = fmaxf(act_bound, x_norm * max_row_norm(Wi, 2 * kD, kD) + max_abs(bi, 2 * kD));              // q, k: operands of the split S = K Q^T
-      act_bound = fmaxf(act_bound, x_norm * max_row_norm(Wi + (size_t)2 * kD * kD, kD, kD) + max_abs(bi + 2 * kD, kD));  // v (operand of P V) and out_proj input: convex combinations of v
+      act_bound = fmaxf(act_bound, x_norm * max_row_norm(Wi, 2 * D, D) + max_abs(bi, 2 * D));              // q, k: operands of the split S = K Q^T
+      act_bound = fmaxf(act_bound, x_norm * max_row_norm(Wi + (size_t)2 * D * D, D, D) + max_abs(bi + 2 * D, D));  // v (operand of P V) and out_proj input: convex combinations of v
       const float ln1 = ln_elem("norm1.weight", "norm1.bias");
       act_bound = fmaxf(act_bound, ln1);                                                                      // linear1 input (element bound)
-      act_bound = fmaxf(act_bound, 16.f * ln1 * max_row_norm(W1, 2 * kD, kD) + max_abs(b1, 2 * kD));          // linear2 input
+      act_bound = fmaxf(act_bound, 16.f * ln1 * max_row_norm(W1, 2 * D, D) + max_abs(b1, 2 * D));          // linear2 input
       x_norm = 16.f * ln_elem("norm2.weight", "norm2.bias");                                                 // next layer's rows
     }
   }
@@ -1546,6 +1489,9 @@ int load_weights_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const t2l_m
   P.use_pos = cfg->use_position;
   P.use_num = cfg->use_num;
   P.nfeat = nfeat;
+  ew->embed_dim = D;
+  ew->object_size = object_size;
+  ew->num_heads = cfg->num_heads;
   ctx->enc = ew;
   return T2L_OK;
 }
@@ -1557,6 +1503,7 @@ int encode_impl(t2l_ctx* ctx, const t2l_packed_cells* in, float* out, hipStream_
   if ((P.use_class && P.class_embed && !in->class_idx) || (P.use_color && P.color_embed && !in->color_idx) ||
       (P.use_color && !P.color_embed && !in->rgb) || (P.use_pos && !in->center) || (P.use_num && !in->n_pts))
     return fail(ctx, T2L_EINVAL, "t2l_encode_cells: a per-object input required by the loaded config is NULL");
+  if (!ctx->enc->published()) return encode_shaped_impl(ctx, in, out, s);  // every other compiled shape: encode_shaped.hip
   const size_t lds = (size_t)(2 * kXFloats + 8) * sizeof(float);  // 66.6 KB: two cells per CU
   static PerDeviceOnce attr_done;
   if (attr_done.need(ctx->device)) {

@@ -195,7 +195,8 @@ int search_small_impl(t2l_ctx* ctx, const float* q, int Q, int K, int32_t* out_i
 int exact_stage_impl(t2l_ctx* ctx, const float* db, int n_rows, int row_offset, const float* q, int Q, int K, int32_t* out_idx,
                      double* out_score, hipStream_t s);
 // encode.hip
-int load_weights_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const t2l_model_config* cfg);
+int load_weights_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const t2l_model_config* cfg, int embed_dim, int object_size);
+int encoder_embed_dim(const t2l_ctx* ctx);  // of the loaded object branch (T2L_EMBED_DIM before any load)
 int encode_impl(t2l_ctx* ctx, const t2l_packed_cells* in, float* out, hipStream_t s);
 void free_weights(t2l_ctx* ctx);
 // train.hip

@@ -221,7 +221,7 @@ static int check_mlp_layer(t2l_ctx* ctx, TrainState* st, const std::string& p, i
 
 int train_bind_impl(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n, const t2l_model_config* cfg) {
   if (!tensors || n <= 0 || !cfg) return fail(ctx, T2L_EINVAL, "t2l_train_bind: null argument");
-  if (cfg->num_heads != kTH) return fail(ctx, T2L_EINVAL, "t2l_train_bind: the engine is built for 4 attention heads");
+  if (cfg->num_heads != kTH) return fail(ctx, T2L_EINVAL, "t2l_train_bind: the training step is built for the published shape only (embed dim 256, 4 attention heads, object_size 28)");
   const int n_feat = (cfg->use_class != 0) + (cfg->use_color != 0) + (cfg->use_position != 0) + (cfg->use_num != 0);
   if (n_feat < 2) return fail(ctx, T2L_EINVAL, "t2l_train_bind: training needs at least two of the class/color/position/num features");
   // a re-bind of the SAME model (model.to(), an externally assigned .grad, ...) only moves POINTERS: with option

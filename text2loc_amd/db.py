@@ -6,9 +6,10 @@ build-once artefact the engine loads straight into HBM.
     db.save("k360_val.t2ldb.npz");  db = CellDatabase.load("k360_val.t2ldb.npz")
     idx, score = db.search(engine, text_embeddings, k=10)        # row ids -> db.cell_ids[idx]
 
-File format (``numpy.savez``; little-endian, row-major): ``cell_ids <U[N]``, ``embeddings f32[N,256]`` (unit rows, the
-coarse encodings), optional ``fine_desc f32[N,16,128]`` (the query-independent half of the fine stage), ``bbox_w f64[N,6]``,
-``cell_size f64[N]``, ``meta`` (format version, feature mode). 1 KiB per cell without, 9 KiB with the fine descriptors.
+File format (``numpy.savez``; little-endian, row-major): ``cell_ids <U[N]``, ``embeddings f32[N,D]`` (unit rows, the
+coarse encodings; D = the model's coarse_embed_dim, 256 or 128), optional ``fine_desc f32[N,16,128]`` (the query-independent half of the fine stage), ``bbox_w f64[N,6]``,
+``cell_size f64[N]``, ``meta`` (format version, feature mode). 1 KiB per cell without, 9 KiB with the fine descriptors
+(at D = 256).
 """
 from __future__ import annotations
 
@@ -64,7 +65,7 @@ class CellDatabase:
         a = model.args
         meta = {"format": FORMAT_VERSION, "class_embed": bool(getattr(a, "class_embed", False)),
                 "color_embed": bool(getattr(a, "color_embed", False)), "use_features": list(a.use_features)}
-        return cls(np.array(ids), np.concatenate(embs) if embs else np.zeros((0, 256), np.float32), np.array(bboxes),
+        return cls(np.array(ids), np.concatenate(embs) if embs else np.zeros((0, int(model.embed_dim)), np.float32), np.array(bboxes),
                    np.array(sizes), np.concatenate(fines) if fines else None, meta)
 
     # ---- persistence ------------------------------------------------------------------------------------------

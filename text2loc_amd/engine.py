@@ -17,6 +17,13 @@ import torch
 
 EMBED_DIM = 256
 OBJECT_SIZE = 28
+# what the eval-mode cell encoder is compiled for (include/t2l.h: t2l_load_weights_shaped); the search, the text entry points and the
+# training step stay at EMBED_DIM / OBJECT_SIZE
+COMPILED_EMBED_DIMS = (128, 256)
+COMPILED_HEAD_DIMS = (32, 64)
+MAX_OBJECT_SIZE = 32
+COMPILED_SHAPES = ("coarse_embed_dim in {128, 256}; object_inter_module_num_heads with head_dim 32 or 64 (2 or 4 heads at 128, 4 or 8 at "
+                   "256); object_size 1..32; object_inter_module_num_layers 1..4")
 MAX_TOPK = 26
 # (T2L_LIB: a dev build beside the shipped one — the stamped or an experiment library of csrc/Makefile; never a fallback)
 _LIB_PATH = os.environ.get("T2L_LIB") or osp.join(osp.dirname(osp.abspath(__file__)), "libt2l.so")
@@ -26,6 +33,23 @@ class T2LError(RuntimeError):
     pass
 
 
+def check_compiled_shape(embed_dim: int, num_heads: int, object_size: int, num_layers: int):
+    """Raises unless the cell encoder is compiled for this shape (no GPU needed: the same rule as t2l_load_weights_shaped)."""
+    ok = (embed_dim in COMPILED_EMBED_DIMS and num_heads > 0 and embed_dim % num_heads == 0
+          and embed_dim // num_heads in COMPILED_HEAD_DIMS and 1 <= object_size <= MAX_OBJECT_SIZE and 1 <= num_layers <= 4)
+    if not ok:
+        raise T2LError(f"the cell encoder is not built for coarse_embed_dim={embed_dim}, object_inter_module_num_heads={num_heads}, "
+                       f"object_size={object_size}, object_inter_module_num_layers={num_layers}. Compiled set: {COMPILED_SHAPES}")
+
+
+def is_published_shape(embed_dim: int, num_heads: int, object_size: int) -> bool:
+    return embed_dim == EMBED_DIM and num_heads == 4 and object_size == OBJECT_SIZE
+
+
+TRAIN_SHAPE_MSG = ("the training step is built for the published shape only (coarse_embed_dim=256, 4 heads, object_size=28); "
+                   "eval-mode encoding works at every compiled shape")
+
+
 class _WeightDesc(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
@@ -33,6 +57,10 @@ class _WeightDesc(C.Structure):
 class _ModelConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("class_embed", "color_embed", "use_class", "use_color", "use_position",
                                          "use_num", "num_layers", "num_heads")]
+
+
+class _ModelShape(C.Structure):
+    _fields_ = [("embed_dim", C.c_int32), ("object_size", C.c_int32)]
 
 
 class _TrainTensor(C.Structure):
@@ -51,6 +79,8 @@ EXPORTS = {
     "t2l_destroy": (None, [C.c_void_p]),
     "t2l_last_error": (C.c_char_p, [C.c_void_p]),
     "t2l_load_weights": (C.c_int, [C.c_void_p, C.POINTER(_WeightDesc), C.c_int32, C.POINTER(_ModelConfig)]),
+    "t2l_load_weights_shaped": (C.c_int, [C.c_void_p, C.POINTER(_WeightDesc), C.c_int32, C.POINTER(_ModelConfig), C.POINTER(_ModelShape)]),
+    "t2l_embed_dim": (C.c_int, [C.c_void_p]),
     "t2l_encode_cells": (C.c_int, [C.c_void_p, C.POINTER(_PackedCells), C.c_void_p, C.c_void_p]),
     "t2l_sample_object_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.c_float,
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -185,8 +215,11 @@ class Engine:
 
     # ------------------------------------------------------------------ weights
     def load_weights(self, state_dict: Dict[str, object], class_embed: bool, color_embed: bool,
-                     use_features=("class", "color", "position", "num"), num_layers: int = 2, num_heads: int = 4):
-        """state_dict: name -> torch.Tensor | np.ndarray (fp32), keys as in the reference checkpoint."""
+                     use_features=("class", "color", "position", "num"), num_layers: int = 2, num_heads: int = 4,
+                     embed_dim: int = EMBED_DIM, object_size: int = OBJECT_SIZE):
+        """state_dict: name -> torch.Tensor | np.ndarray (fp32), keys as in the reference checkpoint. ``embed_dim`` /
+        ``object_size`` / ``num_heads``: any compiled shape (``COMPILED_SHAPES``); ``encode_cells`` then returns ``embed_dim`` columns."""
+        check_compiled_shape(int(embed_dim), int(num_heads), int(object_size), int(num_layers))
         keep, descs = [], []
         for name, v in state_dict.items():
             if not (name.startswith("object_encoder.") or name.startswith("obj_inter_module.")):
@@ -201,7 +234,13 @@ class Engine:
         cfg = _ModelConfig(int(class_embed), int(color_embed), int("class" in use_features),
                            int("color" in use_features), int("position" in use_features), int("num" in use_features),
                            int(num_layers), int(num_heads))
-        self._check(self.lib.t2l_load_weights(self._h, arr, len(descs), C.byref(cfg)))
+        shape = _ModelShape(int(embed_dim), int(object_size))
+        self._check(self.lib.t2l_load_weights_shaped(self._h, arr, len(descs), C.byref(cfg), C.byref(shape)))
+
+    @property
+    def embed_dim(self) -> int:
+        """Row width of ``encode_cells`` for the loaded object branch (256 before any load)."""
+        return int(self.lib.t2l_embed_dim(self._h))
 
     # ------------------------------------------------------------------ per-object reductions (a1)
     def reduce_objects(self, xyz: torch.Tensor, rgb: torch.Tensor, point_offsets: torch.Tensor,
@@ -261,11 +300,11 @@ class Engine:
     # ------------------------------------------------------------------ cell encoding
     def encode_cells(self, packed: Dict[str, torch.Tensor]) -> torch.Tensor:
         """packed: offsets i32[B+1], class_idx/color_idx i32[n], rgb/center f32[n,3], n_pts f32[n],
-        optional pn_feat f32[n,256] — all on the GPU. Returns f32[B,256] unit rows."""
+        optional pn_feat f32[n,256] — all on the GPU. Returns f32[B,D] unit rows, D = ``self.embed_dim``."""
         offsets = packed["offsets"]
         n_cells = int(offsets.numel()) - 1
         n_obj = int(packed["n_pts"].numel()) if packed.get("n_pts") is not None else int(packed["class_idx"].numel())
-        out = torch.empty((max(n_cells, 0), EMBED_DIM), dtype=torch.float32, device=offsets.device)
+        out = torch.empty((max(n_cells, 0), self.embed_dim), dtype=torch.float32, device=offsets.device)
         if n_cells <= 0:
             return out
         pc = _PackedCells(
@@ -436,7 +475,11 @@ class Engine:
                    color_embed: bool, use_features=("class", "color", "position", "num"), num_layers: int = 2,
                    num_heads: int = 4):
         """tensors: state_dict key -> (live fp32 CUDA tensor, its gradient buffer or None for BatchNorm buffers).
-        The engine keeps the POINTERS (no copies): keep the tensors alive and re-bind if they are re-allocated."""
+        The engine keeps the POINTERS (no copies): keep the tensors alive and re-bind if they are re-allocated.
+        Published shape only: tensors of another embed dim or head count are refused, not re-interpreted."""
+        ln = tensors.get("obj_inter_module.0.norm1.weight")
+        if int(num_heads) != 4 or (ln is not None and int(ln[0].numel()) != EMBED_DIM):
+            raise T2LError("train_bind: " + TRAIN_SHAPE_MSG)
         descs, keep = [], []
         for name, (data, grad) in tensors.items():
             keep.append((data, grad))

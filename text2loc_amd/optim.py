@@ -42,6 +42,10 @@ class Adam(torch.optim.Optimizer):
         launch, moments inside the library — instead of a torch.optim.Adam beside the engine."""
         if grad_reduce not in ("sum", "mean"):
             raise ValueError("grad_reduce must be 'sum' or 'mean'")
+        if not getattr(model, "published_shape", True):
+            from .engine import TRAIN_SHAPE_MSG, T2LError
+
+            raise T2LError("optim.Adam: " + TRAIN_SHAPE_MSG)
         self._group, self._grad_reduce, self._dp = group, grad_reduce, bool(data_parallel) or group is not None
         obj, rest, text = [], [], []
         le = getattr(model, "language_encoder", None)
