@@ -555,6 +555,11 @@ int t2l_adam_state(t2l_ctx* ctx, int32_t set, float* m, float* v, int64_t* step,
  *                     enter the lane's list, the third travels as the record's decodable bound B1; the re-rank re-scores that group's 8
  *                     rows when a query's certificate fails on B1 alone). 0 = every score inserted into the list (round 5's form; A/B).
  *                     Results are identical either way.
+ * "search_epilogue"   (default 1): the paired scan's tail. 1 = the last tile of every wave goes through the tile-local selection like
+ *                     the tiles before it, every lane half merges only the query group it carries, and the merged records of the splits
+ *                     one XCD owns (search_xcd_qgroups) are contiguous, so every 128-byte line of the record buffer is written by one
+ *                     XCD's L2. 0 = round 6's epilogue and record order (A/B; both arms run in one process). Applies to merged records
+ *                     (the layout) with search_tile_sel = 1 (the epilogue). Ids and float64 scores are bit-identical either way.
  * "search_pair_ll"    (default 6): per-lane list length of the paired scan (5: experiment, halves the certificate's margin).
  * "profile_events"    (default 0): n >= 1 records hipEvents around every n-th launch of each kernel (t2l_kernel_stats);
  *                     two records cost ~6 us of queue time per bracketed kernel, which matters beside a 30 us kernel.

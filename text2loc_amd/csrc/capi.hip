@@ -369,9 +369,9 @@ int t2l_search_fallbacks(t2l_ctx* ctx, int32_t* out_count) {
 }
 
 #ifdef T2L_STAMPS
-int t2l_debug_stamps(t2l_ctx* ctx, long long* out8) {  // dev builds only: s_memrealtime stamps a kernel left in fb_count[16..]
+int t2l_debug_stamps(t2l_ctx* ctx, long long* out24) {  // dev builds only: s_memrealtime stamps a kernel left in fb_count[16..63]
   T2L_HIP(ctx, hipDeviceSynchronize());
-  T2L_HIP(ctx, hipMemcpy(out8, ctx->fb_count + 16, 16 * sizeof(long long), hipMemcpyDeviceToHost));
+  T2L_HIP(ctx, hipMemcpy(out24, ctx->fb_count + 16, 24 * sizeof(long long), hipMemcpyDeviceToHost));
   const long long init[8] = {0, 0, 0, 0, LLONG_MAX, 0, LLONG_MAX, 0};  // re-arm the min / max slots
   T2L_HIP(ctx, hipMemcpy(ctx->fb_count + 16, init, sizeof(init), hipMemcpyHostToDevice));
   return T2L_OK;
@@ -632,6 +632,9 @@ int t2l_set_option(t2l_ctx* ctx, const char* name, double value) {
     ctx->wide_repair = (int)value;
   } else if (!strcmp(name, "search_tile_sel")) {
     ctx->search_tile_sel = value != 0;
+  } else if (!strcmp(name, "search_epilogue")) {
+    if (value != 0 && value != 1) return fail(ctx, T2L_EINVAL, "search_epilogue: 0 (round 6's epilogue and record layout) or 1 (default)");
+    ctx->search_epilogue = (int)value;
   } else if (!strcmp(name, "search_pair_ll")) {
     if (value != 5 && value != 6) return fail(ctx, T2L_EINVAL, "search_pair_ll must be 5 or 6");
     ctx->pair_ll = (int)value;

@@ -1,27 +1,32 @@
 // Coarse retrieval: all-pairs query x submap-DB similarity + top-k, fused (gfx950 / CDNA4).
 //
-// Replaces the host loop of training/coarse.py:119-125 — per query a float64 `cell_encodings @ t`
-// (N x 256) and a full argsort — by three launches on one stream, no host round trip:
+// Replaces the host loop of training/coarse.py:119-125 — per query a float64 `cell_encodings @ t` (N x 256) and a full argsort — by
+// TWO launches on one stream, no host round trip:
 //
-//   scan_kernel      f32 MFMA (v_mfma_f32_32x32x2_f32, bit-exact f32 FMA chains) over [128 queries] x
-//                    [DB split]. A lane owns (1 query, half of each 32-row tile) and keeps its top-L as a
-//                    sorted register list of KEYS = f32 score with the low `code_bits` mantissa bits
-//                    replaced by the row's position inside the split, so one v_med3_f32 per list element
-//                    inserts a score branch-free, in the shadow of the serially dependent MFMA chain.
-//                    Scores are never written to HBM.
-//   rerank_kernel    one wave per query: merges the 2*nsplit sorted lists to the top-L keys, re-scores
-//                    those rows in float64 (what the reference ranks by), orders them by (score desc,
-//                    row asc) and CERTIFIES: every row that was not re-scored has key <= g, so
-//                    s64_K > g + key-truncation + f32-rounding bound  ==> the top-K equals the float64
-//                    ranking exactly.
-//                    A failed certificate is usually repaired inside the wave (the lists are still in registers: re-score
-//                    the few keys that can still reach the top-K); what is left — about one query in a million on
-//                    unit-Gaussian data — gets the exact float64 ranking from the re-rank's own workgroup (wg_exact_scan).
+//   scanp_kernel     (the default, batches of >= 256 queries) f16 MFMA (v_mfma_f32_32x32x16_f16, operands scaled by powers of two,
+//                    f32 accumulation) over [256 queries] x [DB split]: one 512-thread workgroup per CU, two waves per SIMD that hold
+//                    the same 64 queries and take alternate 32-row tiles of an f16 plane of the database streamed through an LDS ring
+//                    by LDS-DMA. A lane owns (1 query, half of each tile) and keeps its top 6 as a sorted register list of KEYS = f32
+//                    score with the low mantissa bits replaced by the row's position inside the split; scores meet in a local top 3 per
+//                    group of 8 first (search_dev.h: TileSelLists), in the shadow of the MFMA stream. The workgroup's four lists per query
+//                    leave as ONE 32-byte record: 6 keys + B1 (a decodable bound) + B2 (a bound on everything else). Scores are never
+//                    written to HBM.
+//                    scanh_kernel (one wave per SIMD: small batches, tiny shards, k > 10) and scanw_kernel (split-bf16 operands, three
+//                    MFMAs per product: what the auto mode escalates to when f16 certificates fail wholesale) hand over plain lists.
+//   rerank_kernel    one wave per query: merges the records (or lists) to the top-L keys, re-scores those rows in float64 (what the
+//                    reference ranks by), orders them by (score desc, row asc) and CERTIFIES: every row that was not re-scored has
+//                    key <= g, so s64_K > g + key-truncation + operand-rounding bound  ==> the top-K equals the float64 ranking exactly.
+//                    A failed certificate is usually repaired inside the wave (B1's group of 8 rows; the keys that can still reach the
+//                    top-K; a wide repair of up to 1,024 rows); what is left — about one query in a million on unit-Gaussian data — gets
+//                    the exact float64 ranking from the re-rank's own workgroup (wg_exact_scan).
 //                    No third launch: an empty fallback kernel cost ~5 us of every ~55 us step in round 1.
 //   (heavy mode)     databases that defeat the certificates wholesale: search_exact.hip (float64 MFMA stage).
+//   (elsewhere)      <= 16 queries: one launch, exact from the start (search_small.hip); <= 64 queries against a large shard: the
+//                    HBM-streaming scan (search_stream.hip); shards of several segments: search_merge.hip.
 //
-// HBM layout: DB f32[n_pad,256] row-major (n_pad = n rounded up to 32, tail rows zero and masked by
-// row >= n); queries f32[Q,256]; candidate keys f32 [Q][nsplit][2][L].
+// HBM layout: DB f32[n_pad,256] row-major (n_pad = n rounded up to 32, tail rows zero and masked by row >= n) + its f16 plane (rows
+// dealt to tiles strided, plane_row) or split-bf16 plane; queries f32[Q,256]; candidates f32 [Q][nsplit][8] (merged records, slot order
+// by record_slot) or [Q][2*nsplit][L] (plain lists).
 #include <float.h>
 #include <limits.h>
 
@@ -411,6 +416,7 @@ struct RerankArgs {
   int32_t* host_stat;
   int seq, wide_cap;
   int rec6;  // merged records of the tile-local selection: 6 keys, B1 (a key: the largest third-best key of the record's lanes), B2
+  int slot_bits = 0;  // merged records: the record of part p sits in slot record_slot(p, parts, slot_bits) of its query
 };
 
 // MERGE: the workgroup's four lists per query (two lane halves x two waves, 24 keys) leave as ONE record of 8 floats — the best 7 keys,
@@ -422,13 +428,20 @@ constexpr int kMergedLL = 8;
 #ifndef T2L_SEL_RD
 #define T2L_SEL_RD 2  // fragment-ring depth of the SEL = 1 loop (the tile-local registers come out of the ring's)
 #endif
+// SEL = 2: the tile-local selection with round 6's epilogue (option "search_epilogue" = 0, kept for the A/B). SEL = 1 (EPI below, what
+// ships — so the shipped kernel keeps the name the committed profiles and bench.py's roofline know it by): the workgroup's tail as work removed, not overlapped — the last tile goes through the
+// tile-local selection like every other tile, every lane half merges ONE query group's lists instead of both, and the last
+// compare-exchange of the cross-quad sort (whose two outputs only ever meet again in a max) is dropped. Records are bit-identical to
+// SEL = 2 in their merge; the drain moves keys of the last tile from the lists into (B1, B2), which the re-rank's certificate covers.
+// slot_bits: the merged record of split sp sits in slot record_slot(sp, nsplit, slot_bits) of its query (search_dev.h).
 template <int LL, int NS, bool MERGE = false, int SEL = 0>
 __global__ __launch_bounds__(512, 1) void scanp_kernel(const uint4* __restrict__ dbt, int n_rows, int n_tiles, int code_bits,
                                                        const float* __restrict__ q, int Q, int nsplit,
                                                        float* __restrict__ cand, int32_t* __restrict__ fb_count, int32_t* __restrict__ fb_prev,
                                                        int zero_counts, float pinf, unsigned long long* __restrict__ span,
-                                                       unsigned span_seq, int xcd_qgroups) {
+                                                       unsigned span_seq, int xcd_qgroups, int slot_bits) {
   static_assert(NS == 4, "the step loop below is unrolled for a ring of 4 slots");
+  constexpr bool EPI = SEL == 1;  // the short epilogue (it drains the last tile through the tile-local selection)
   static_assert(!MERGE || LL == 6, "the in-workgroup list merge is written for lists of 6");
   static_assert(!SEL || MERGE, "the tile-local selection's dropped-bound leaves through the merged record's bound");
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -478,9 +491,17 @@ __global__ __launch_bounds__(512, 1) void scanp_kernel(const uint4* __restrict__
     if (k == 3) atomicMax(reinterpret_cast<unsigned long long*>(fb_count + 16) + 7, (unsigned long long)t_);           \
   }
 #define T2L_STAMP2(k) if (tid == 0 && blockIdx.x == 37) reinterpret_cast<long long*>(fb_count + 32)[k] = __builtin_amdgcn_s_memrealtime()
+// the epilogue's parts (fb_count[48..63]); the scheduling fences keep each part's instructions on its own side of the stamp
+#define T2L_STAMP3(k)                                                                                                  \
+  {                                                                                                                    \
+    __builtin_amdgcn_sched_barrier(0);                                                                                 \
+    if (tid == 0 && blockIdx.x == 37) reinterpret_cast<long long*>(fb_count + 48)[k] = __builtin_amdgcn_s_memrealtime(); \
+    __builtin_amdgcn_sched_barrier(0);                                                                                 \
+  }
 #else
 #define T2L_STAMP(k)
 #define T2L_STAMP2(k)
+#define T2L_STAMP3(k)
 #endif
   T2L_STAMP(0);
 
@@ -614,22 +635,43 @@ __global__ __launch_bounds__(512, 1) void scanp_kernel(const uint4* __restrict__
     if (i + 2 < steps) step(std::integral_constant<int, 2>{}, later, i + 2, accA0, accA1, accB0, accB1);
     if (i + 3 < steps) step(std::integral_constant<int, 3>{}, later, i + 3, accB0, accB1, accA0, accA1);
   }
+  T2L_STAMP3(0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // over-issued DMA pieces must not land in LDS after the workgroup is gone
   T2L_STAMP(2);
+  T2L_STAMP3(1);
 
   if (nt == steps) {  // the wave's last tile's scores are still in registers; only here can rows be >= n_rows. (A wave with
                       // nt == steps - 1 ran its last step on a clamped tile: that step inserted the real last tile's scores.)
     const int row0 = (vs + (nt - 1) * vn) * kTileRows + 4 * half;
     const int code0 = ((nt - 1) << (4 + kCS)) | code_q;
     const bool odd = nt & 1;
+    if constexpr (EPI) {
+      // the last tile takes the loop's road: two tile-local groups of 8 per query group, 43 ops each instead of 8 x 9. Rows at or
+      // beyond n_rows are -inf instead of keys (a plain -inf, as in round 6's drain: it falls through every op of the selection; a
+      // masked SCORE would turn into the NaN -inf | code), so (dA, dB) account for this tile exactly as for every other one and the
+      // exactness argument of the tile-local selection ("Round 6") holds unchanged: what a lane dropped without passing
+      // it through its list lies at or below dA. The two query groups use separate temporaries: two independent chains to issue from.
+      f32x16 m0, m1;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const bool ok = row0 + (r & 3) + 8 * (r >> 2) < n_rows;
-      const float s0 = odd ? accA0[r] : accB0[r], s1 = odd ? accA1[r] : accB1[r];
-      ins_key<LL>(w.ls0, ok ? make_key(s0, mask, code0 + (r << kCS)) : T2L_NEG_INF);
-      ins_key<LL>(w.ls1, ok ? make_key(s1, mask, code0 + (r << kCS)) : T2L_NEG_INF);
+      for (int r = 0; r < 16; ++r) {
+        const bool ok = row0 + (r & 3) + 8 * (r >> 2) < n_rows;
+        m0[r] = ok ? make_key(odd ? accA0[r] : accB0[r], mask, code0 + (r << kCS)) : T2L_NEG_INF;
+        m1[r] = ok ? make_key(odd ? accA1[r] : accB1[r], mask, code0 + (r << kCS)) : T2L_NEG_INF;
+      }
+      TileSelLists<LL> w1;  // (its temporaries only)
+      tile_sel_ops<LL, 0, kTileSelOps, kCS, true>(w.ls0, w.dA0, w.dB0, w, m0, vmask, code0, pinf);
+      tile_sel_ops<LL, 0, kTileSelOps, kCS, true>(w.ls1, w.dA1, w.dB1, w1, m1, vmask, code0, pinf);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const bool ok = row0 + (r & 3) + 8 * (r >> 2) < n_rows;
+        const float s0 = odd ? accA0[r] : accB0[r], s1 = odd ? accA1[r] : accB1[r];
+        ins_key<LL>(w.ls0, ok ? make_key(s0, mask, code0 + (r << kCS)) : T2L_NEG_INF);
+        ins_key<LL>(w.ls1, ok ? make_key(s1, mask, code0 + (r << kCS)) : T2L_NEG_INF);
+      }
     }
   }
+  T2L_STAMP3(2);
   const int part = 2 * vs + half, parts = 2 * vn;
   const int qrow0 = qb * kWideQPerBlock + wq * kWideQPerWave + col, qrow1 = qrow0 + 32;
   auto put_list = [&](int qrow, const float* ls) {  // (measured: non-temporal stores here cost +2 us per step)
@@ -672,17 +714,47 @@ __global__ __launch_bounds__(512, 1) void scanp_kernel(const uint4* __restrict__
       O0[i] = with_half(w.ls0[i]);
       O1[i] = with_half(w.ls1[i]);
     }
+    float M[kMergedLL], fl, DA = T2L_NEG_INF, DB = T2L_NEG_INF;
+    auto top2 = [&](float& a, float& b, float oa, float ob) {
+      const float lo = __builtin_amdgcn_fmed3f(a, oa, ninf);
+      a = __builtin_amdgcn_fmed3f(a, oa, pinf);
+      b = __builtin_amdgcn_fmed3f(__builtin_amdgcn_fmed3f(b, ob, pinf), lo, pinf);
+    };
+    if constexpr (EPI) {
+      // Lane half h carries query group h from here on, so it needs the two lists of THAT group only: one v_permlane32_swap of
+      // (group-0 value, group-1 value) leaves every lane with its own and its partner's value of its group (in either order: every
+      // merge below is symmetric in its two inputs) — 10 swaps, one 6 + 6 -> 8 merge and one top2 where round 6's form runs 18 swaps + selects,
+      // two merges, two top2 and then discards the half it does not carry. Same keys into the same networks: the same M, fl, DA, DB.
+      auto swap_halves = [&](float& a0, float& a1) {
+        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a0), __float_as_uint(a1), false, false);
+        a0 = __uint_as_float(r[0]);
+        a1 = __uint_as_float(r[1]);
+      };
+#pragma unroll
+      for (int i = 0; i < LL; ++i) swap_halves(O0[i], O1[i]);
+      float fa = w.ls0[LL - 1] == T2L_NEG_INF ? T2L_NEG_INF : __int_as_float(__float_as_int(w.ls0[LL - 1]) | half);
+      float fb = w.ls1[LL - 1] == T2L_NEG_INF ? T2L_NEG_INF : __int_as_float(__float_as_int(w.ls1[LL - 1]) | half);
+      swap_halves(fa, fb);
+      fl = fmaxf(fa, fb);
+      if constexpr (SEL) {
+        float oa = with_half(w.dA1), ob = with_half(w.dB1);
+        DA = with_half(w.dA0); DB = with_half(w.dB0);
+        swap_halves(DA, oa);
+        swap_halves(DB, ob);
+        top2(DA, DB, oa, ob);
+      }
+      static_assert(LL == 6 && kMergedLL == 8, "the half merge below is written out for 6 + 6 -> 8");
+      M[0] = O0[0]; M[1] = O0[1]; M[6] = O1[1]; M[7] = O1[0];
+#pragma unroll
+      for (int i = 2; i < 6; ++i) M[i] = __builtin_amdgcn_fmed3f(O0[i], O1[7 - i], pinf);
+      sort_bitonic8(M);
+    } else {
     // a lane's FLOOR (its 6th key: every row the lane saw and dropped lies at or below it) bounds what the record cannot list
     float f0 = O0[LL - 1], f1 = O1[LL - 1];
     f0 = fmaxf(f0, xor32_f32(f0, half));
     f1 = fmaxf(f1, xor32_f32(f1, half));
     // SEL: (dA >= dB) = the two largest third-best keys of the lane's tile-local groups — real keys whose code names their group. The four
     // lanes of a query meet in (DA >= DB), the two largest of their eight: two sorted pairs -> top 2 = (max heads, max(min heads, max seconds))
-    auto top2 = [&](float& a, float& b, float oa, float ob) {
-      const float lo = __builtin_amdgcn_fmed3f(a, oa, ninf);
-      a = __builtin_amdgcn_fmed3f(a, oa, pinf);
-      b = __builtin_amdgcn_fmed3f(__builtin_amdgcn_fmed3f(b, ob, pinf), lo, pinf);
-    };
     float DA0 = T2L_NEG_INF, DB0 = T2L_NEG_INF, DA1 = T2L_NEG_INF, DB1 = T2L_NEG_INF;
     if constexpr (SEL) {
       DA0 = with_half(w.dA0); DB0 = with_half(w.dB0); DA1 = with_half(w.dA1); DB1 = with_half(w.dB1);
@@ -708,11 +780,12 @@ __global__ __launch_bounds__(512, 1) void scanp_kernel(const uint4* __restrict__
       sort_bitonic8(A1);
     }
     // both halves now hold the same two merged lists; half h carries query col + 32 h from here on
-    float M[kMergedLL];
 #pragma unroll
     for (int i = 0; i < kMergedLL; ++i) M[i] = half ? A1[i] : A0[i];
-    float fl = half ? f1 : f0;
-    float DA = half ? DA1 : DA0, DB = half ? DB1 : DB0;
+    fl = half ? f1 : f0;
+    DA = half ? DA1 : DA0, DB = half ? DB1 : DB0;
+    }
+    T2L_STAMP3(3);
     // 11-float records (conflict-free) in their own 11 KB BEHIND the tile ring: no barrier between the last tile and the exchange
     float* xch = smem + NS * kSlotBytes / sizeof(float) + ((size_t)wq * 64 + lane) * (kMergedLL + 3);
     if (quad == 1) {
@@ -725,10 +798,21 @@ __global__ __launch_bounds__(512, 1) void scanp_kernel(const uint4* __restrict__
       }
     }
     __syncthreads();
+    T2L_STAMP3(4);
     if (quad == 0) {
 #pragma unroll
       for (int i = 0; i < kMergedLL; ++i) M[i] = __builtin_amdgcn_fmed3f(M[i], xch[kMergedLL - 1 - i], pinf);
-      sort_bitonic8(M);
+      if constexpr (EPI) {
+        // the record reads the best 6 keys and max(7th, 8th): the sort's last compare-exchange of (6, 7) would only order two
+        // values that meet again in the max below
+#pragma unroll
+        for (int d = 4; d >= 1; d >>= 1)
+#pragma unroll
+          for (int i = 0; i < kMergedLL; ++i)
+            if ((i & d) == 0 && !(d == 1 && i == kMergedLL - 2)) cx(M[i], M[i + d]);
+      } else {
+        sort_bitonic8(M);
+      }
       fl = fmaxf(fl, xch[kMergedLL]);
       // everything evicted on the way lies at or below the 8th merged key; everything a lane dropped at or below its floor
       M[kMergedLL - 1] = fmaxf(M[kMergedLL - 1], fl);
@@ -740,12 +824,14 @@ __global__ __launch_bounds__(512, 1) void scanp_kernel(const uint4* __restrict__
         M[kMergedLL - 1] = fmaxf(fmaxf(M[kMergedLL - 1], M[kMergedLL - 2]), DB);
         M[kMergedLL - 2] = DA;
       }
+      T2L_STAMP3(5);
       const int qrow = qb * kWideQPerBlock + wq * kWideQPerWave + lane;
       if (qrow < Q) {
-        float4* out = reinterpret_cast<float4*>(cand + ((size_t)qrow * nsplit + sp) * kMergedLL);
+        float4* out = reinterpret_cast<float4*>(cand + ((size_t)qrow * nsplit + record_slot(sp, nsplit, slot_bits)) * kMergedLL);
         out[0] = make_float4(M[0], M[1], M[2], M[3]);
         out[1] = make_float4(M[4], M[5], M[6], M[7]);
       }
+      T2L_STAMP3(6);
     }
   } else {
     put_list(qrow0, w.ls0);
@@ -943,7 +1029,9 @@ __device__ __forceinline__ void rerank_query(const RerankArgs& a, const int qid,
   // ---- every lane pulls its whole sorted key list into registers (one memory latency for the merge)
   float lst[LL];
   {
-    const float* mine = cand + ((size_t)qid * parts + min(lane, parts - 1)) * LL;
+    // (merged records: the lane holds the record of part = lane, wherever the scan's layout put it)
+    const int mslot = MG ? record_slot(min(lane, parts - 1), parts, a.slot_bits) : min(lane, parts - 1);
+    const float* mine = cand + ((size_t)qid * parts + mslot) * LL;
     if constexpr (MG) {
       const float4 v0 = reinterpret_cast<const float4*>(mine)[0], v1 = reinterpret_cast<const float4*>(mine)[1];
       lst[0] = v0.x; lst[1] = v0.y; lst[2] = v0.z; lst[3] = v0.w;
@@ -1472,12 +1560,12 @@ __global__ __launch_bounds__(256, (MG ? 4 : 1)) void rerank_kernel(const float* 
                                                      int32_t* __restrict__ out_idx, double* __restrict__ out_score,
                                                      int32_t* __restrict__ flags, int32_t* __restrict__ fb_count,
                                                      float eps_rel_probe, float pinf, int n_rows, int defer, int stat_mode,
-                                                     int32_t* __restrict__ host_stat, int seq, int wide_cap, int rec6) {
+                                                     int32_t* __restrict__ host_stat, int seq, int wide_cap, int rec6, int slot_bits) {
   __shared__ WgExactShared exact_sh;
   __shared__ int wg_flag[4];
   __shared__ int wide_rows[4][kWideCap];  // per wave: the rows a wide repair re-scores
   const RerankArgs a{db, q, Q, K, parts, code_bits, cand, row_offset, eps_rel, db_norm_max, half_mode, out_idx, out_score, flags, fb_count,
-                     eps_rel_probe, pinf, n_rows, defer, stat_mode, host_stat, seq, wide_cap, rec6};
+                     eps_rel_probe, pinf, n_rows, defer, stat_mode, host_stat, seq, wide_cap, rec6, slot_bits};
   const int lane = threadIdx.x & 63;
   const int qid = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (threadIdx.x < 4) wg_flag[threadIdx.x] = 0;
@@ -1616,6 +1704,7 @@ static int launch_search(t2l_ctx* ctx, const float* db, const uint4* dbs, const 
   const int seq = first ? ++ctx->stat_seq : 0;  // the report card goes out once per call
   const int defer = ctx->heavy ? 1 : 0;
   bool merged = false;  // the candidate lists are merged records (scanp_kernel<..., MERGE>)
+  int rec_slot_bits = 0;  // ... laid out by record_slot(part, parts, rec_slot_bits)
   if constexpr (LL <= 6) {  // paired f16 MFMA scan (default): one 512-thread workgroup per CU, 256 queries each; `nsplit`
     // counts VIRTUAL splits here: the kernel takes physical ones (2 virtual splits per workgroup)
     const dim3 grid((Q + kWideQPerBlock - 1) / kWideQPerBlock * (nsplit / 2));
@@ -1626,6 +1715,7 @@ static int launch_search(t2l_ctx* ctx, const float* db, const uint4* dbs, const 
       allow_lds(&scanp_kernel<LL, 4>, lds);
       if constexpr (LL == 6) allow_lds(&scanp_kernel<LL, 4, true>, lds);
       if constexpr (LL == 6) allow_lds(&scanp_kernel<LL, 4, true, 1>, lds);
+      if constexpr (LL == 6) allow_lds(&scanp_kernel<LL, 4, true, 2>, lds);
       once.mark(ctx->device);
     }
     const unsigned span_seq = ++ctx->span_seq;
@@ -1637,15 +1727,21 @@ static int launch_search(t2l_ctx* ctx, const float* db, const uint4* dbs, const 
       const int nqb = (Q + kWideQPerBlock - 1) / kWideQPerBlock, ns = nsplit / 2;
       if (xq < 2 || 8 % xq || nqb % xq || ns % (8 / xq) || (nqb * ns) % 8) xq = 1;
     }
+    // option "search_epilogue" = 1: the splits one XCD owns for a query block (sp % GS == x / GQ, GS = 8 / GQ of them interleaved) are
+    // contiguous in the query's records — every 128-byte line of the record buffer is written by ONE XCD's L2 (record_slot)
+    int slot_bits = 0;
+    if (ctx->search_epilogue && xq > 1)
+      for (int gs = 8 / xq; gs > 1; gs >>= 1) ++slot_bits;
+    rec_slot_bits = slot_bits;
     hipEvent_t ea, eb;
     const bool ev = event_pair(ctx, "search_scan", &ea, &eb);  // sampled launch: the dispatch carries its own start / stop events
     auto launch = [&](auto kern) {
       if (ev)
         hipExtLaunchKernelGGL(kern, grid, dim3(512), (uint32_t)lds, s, ea, eb, 0u, dbh, n_rows, n_tiles, code_bits, q, Q, nsplit / 2, ctx->cand_score,
-                              ctx->fb_count, ctx->fb_prev, zero, __builtin_inff(), span, span_seq, xq);
+                              ctx->fb_count, ctx->fb_prev, zero, __builtin_inff(), span, span_seq, xq, slot_bits);
       else
         hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, dbh, n_rows, n_tiles, code_bits, q, Q, nsplit / 2, ctx->cand_score, ctx->fb_count,
-                           ctx->fb_prev, zero, __builtin_inff(), span, span_seq, xq);
+                           ctx->fb_prev, zero, __builtin_inff(), span, span_seq, xq, slot_bits);
     };
     if constexpr (LL == 6 && L == 16) {
       // merged records (option "search_merge_lists"): the workgroup's four lists per query leave as one 32-byte record
@@ -1653,7 +1749,8 @@ static int launch_search(t2l_ctx* ctx, const float* db, const uint4* dbs, const 
       merged = (ctx->search_merge == 1 || (ctx->search_merge == 2 && ctx->merge_live && !ctx->heavy)) && code_bits <= 9;
     }
     if constexpr (LL == 6) {
-      if (merged && ctx->search_tile_sel) launch(scanp_kernel<LL, 4, true, 1>);
+      if (merged && ctx->search_tile_sel && ctx->search_epilogue) launch(scanp_kernel<LL, 4, true, 1>);
+      else if (merged && ctx->search_tile_sel) launch(scanp_kernel<LL, 4, true, 2>);
       else if (merged) launch(scanp_kernel<LL, 4, true>);
     }
     if (!merged) launch(scanp_kernel<LL, 4>);
@@ -1694,12 +1791,12 @@ static int launch_search(t2l_ctx* ctx, const float* db, const uint4* dbs, const 
         hipExtLaunchKernelGGL((rerank_kernel<kMergedLL, L, true>), dim3((Q + 3) / 4), dim3(256), 0u, s, ea, eb, 0u, db, q, Q, K, nsplit / 2,
                               code_bits, (const float*)ctx->cand_score, row_offset, eps_rel, (const float*)ctx->db_norm_max, half_mode, out_idx,
                               out_score, ctx->flags, ctx->fb_count, eps_probe, __builtin_inff(), n_rows, defer, stat_mode,
-                              ctx->host_stat_dev, seq, min(ctx->wide_repair, kWideCap), ctx->search_tile_sel ? 1 : 0);
+                              ctx->host_stat_dev, seq, min(ctx->wide_repair, kWideCap), ctx->search_tile_sel ? 1 : 0, rec_slot_bits);
       else
         hipLaunchKernelGGL((rerank_kernel<kMergedLL, L, true>), dim3((Q + 3) / 4), dim3(256), 0, s, db, q, Q, K, nsplit / 2, code_bits,
                            ctx->cand_score, row_offset, eps_rel, ctx->db_norm_max, half_mode, out_idx, out_score, ctx->flags,
                            ctx->fb_count, eps_probe, __builtin_inff(), n_rows, defer, stat_mode, ctx->host_stat_dev, seq,
-                           min(ctx->wide_repair, kWideCap), ctx->search_tile_sel ? 1 : 0);
+                           min(ctx->wide_repair, kWideCap), ctx->search_tile_sel ? 1 : 0, rec_slot_bits);
       T2L_HIP(ctx, hipGetLastError());
       if (ctx->heavy) return exact_stage_impl(ctx, db, n_rows, row_offset, q, Q, K, out_idx, out_score, s);
       return T2L_OK;
@@ -1709,12 +1806,12 @@ static int launch_search(t2l_ctx* ctx, const float* db, const uint4* dbs, const 
     hipExtLaunchKernelGGL((rerank_kernel<LL, L>), dim3((Q + 3) / 4), dim3(256), 0u, s, ea, eb, 0u, db, q, Q, K, parts, code_bits,
                           (const float*)ctx->cand_score, row_offset, eps_rel, (const float*)ctx->db_norm_max, half_mode, out_idx,
                           out_score, ctx->flags, ctx->fb_count, eps_probe, __builtin_inff(), n_rows, defer, stat_mode,
-                          ctx->host_stat_dev, seq, min(ctx->wide_repair, kWideCap), 0);
+                          ctx->host_stat_dev, seq, min(ctx->wide_repair, kWideCap), 0, 0);
   else
     hipLaunchKernelGGL((rerank_kernel<LL, L>), dim3((Q + 3) / 4), dim3(256), 0, s, db, q, Q, K, parts, code_bits,
                        ctx->cand_score, row_offset, eps_rel, ctx->db_norm_max, half_mode, out_idx, out_score, ctx->flags,
                        ctx->fb_count, eps_probe, __builtin_inff(), n_rows, defer, stat_mode, ctx->host_stat_dev, seq,
-                       min(ctx->wide_repair, kWideCap), 0);
+                       min(ctx->wide_repair, kWideCap), 0, 0);
   T2L_HIP(ctx, hipGetLastError());
   if (ctx->heavy) return exact_stage_impl(ctx, db, n_rows, row_offset, q, Q, K, out_idx, out_score, s);
   return T2L_OK;

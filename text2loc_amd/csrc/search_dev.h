@@ -340,12 +340,16 @@ struct TileSelLists {
 constexpr int kTileSelGroup = 8;                     // scores per tile-local group: the 16 accumulator registers of a lane-tile are two groups
 constexpr int kTileSelGroupOps = 43;                 // VALU ops per group: 29 selection + 12 list insertion + 2 for (dA, dB)
 constexpr int kTileSelOps = 2 * kTileSelGroupOps;    // per lane-tile and query group
-template <int LL, int O, int CS>
+// KEYS: `prev` holds finished keys (the scan's epilogue: rows past the end are -inf there, never a NaN), not scores.
+template <int LL, int O, int CS, bool KEYS = false>
 __device__ __forceinline__ void tile_sel_op(float (&ls)[LL], float& dA, float& dB, TileSelLists<LL>& w, const f32x16& prev, int vmask,
                                             int code0, float pinf) {
   static_assert(LL == 6, "op table written for lists of 6");
   constexpr int B = (O / kTileSelGroupOps) * kTileSelGroup, o = O % kTileSelGroupOps;  // first accumulator register of the group, op within it
-  auto key = [&](int i) { return __int_as_float((__float_as_int(prev[B + i]) & vmask) | __builtin_amdgcn_readfirstlane(code0 + ((B + i) << CS))); };
+  auto key = [&](int i) {
+    if constexpr (KEYS) return prev[B + i];
+    else return __int_as_float((__float_as_int(prev[B + i]) & vmask) | __builtin_amdgcn_readfirstlane(code0 + ((B + i) << CS)));
+  };
   if constexpr (o == 0) w.k = key(0);
   else if constexpr (o == 1) w.t0 = __builtin_amdgcn_fmed3f(w.k, -pinf, pinf);
   else if constexpr (o == 2) w.k = key(1);
@@ -372,12 +376,21 @@ __device__ __forceinline__ void tile_sel_op(float (&ls)[LL], float& dA, float& d
     dA = __builtin_amdgcn_fmed3f(dA, w.t2, pinf);
   }
 }
-template <int LL, int O, int O_END, int CS>
+// Slot of split (part) `sp`'s merged record among the `nsplit` records of a query. With the XCD rectangle (search_xcd_qgroups = GQ > 1)
+// XCD x owns the splits sp % GS == x / GQ (GS = 8 / GQ = 1 << bits): they sit side by side, residue after residue — at the default
+// GQ = 4 the slot is (sp & 1) * (nsplit / 2) + (sp >> 1), so a query's 128-byte lines are each written by one XCD's L2 instead of
+// half by one and half by another. bits = 0 (the rectangle off, or the layout not asked for): the identity. The scan's store and the
+// re-rank's load both come through here; the re-rank's lane p still holds part p's record.
+__device__ __forceinline__ int record_slot(int sp, int nsplit, int bits) {
+  return (sp & ((1 << bits) - 1)) * (nsplit >> bits) + (sp >> bits);
+}
+
+template <int LL, int O, int O_END, int CS, bool KEYS = false>
 __device__ __forceinline__ void tile_sel_ops(float (&ls)[LL], float& dA, float& dB, TileSelLists<LL>& w, const f32x16& prev, int vmask,
                                              int code0, float pinf) {
   if constexpr (O < O_END) {
-    tile_sel_op<LL, O, CS>(ls, dA, dB, w, prev, vmask, code0, pinf);
-    tile_sel_ops<LL, O + 1, O_END, CS>(ls, dA, dB, w, prev, vmask, code0, pinf);
+    tile_sel_op<LL, O, CS, KEYS>(ls, dA, dB, w, prev, vmask, code0, pinf);
+    tile_sel_ops<LL, O + 1, O_END, CS, KEYS>(ls, dA, dB, w, prev, vmask, code0, pinf);
   }
 }
 // k-steps [S, S_END) of one step of the paired scan with the tile-local selection. RD: depth of the fragment ring (k-steps of

@@ -110,6 +110,7 @@ struct t2l_ctx {
   int encoder_f16 = 0;   // 1: plain-f16 products (one MFMA per operand pair) instead of split-f16: ~1e-4 instead of 2e-7, 28 % faster
   int search_auto = 1;
   int pair_ll = 6;       // per-lane list length of the paired scan (5 or 6)
+  int search_epilogue = 1;  // paired scan: 1 = the short epilogue + records laid out by XCD (scanp_kernel<..., SEL = 1>, record_slot), 0 = round 6's (SEL = 2)
   int search_tile_sel = 1;  // paired scan with the tile-local top-3 selection (scanp_kernel<..., SEL = 1>; merged records only)
   int search_small = 1;      // batches of <= 16 queries against <= 65,536 rows: the one-launch exact float64 search (search_small.hip)
   int search_small_wgs = 0;  // ... its workgroups per 4-query slice (0 = by query count: 128 for Q <= 2 or Q > 8, else 192)
