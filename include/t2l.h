@@ -440,6 +440,15 @@ int t2l_fine_train_backward(t2l_ctx* ctx, const float* grad_offsets, float* grad
  * without grad) and `<prefix>inter_module.0.*` (d_model 256, 4 heads, ff 1024); prefix NULL = "language_encoder.". No copies: the
  * kernels read the parameters and accumulate (+=) into the gradient buffers the caller's optimizer owns (torch.optim.Adam steps
  * them). Pointers must stay valid until the next bind.
+ * A second layout is accepted, the FINE head (LanguageEncoder(is_fine=True) of models/cross_matcher.py, fine_embed_dim = 128): NO
+ * `<prefix>inter_module.*` tensor at all and `<prefix>inter_mlp.0.*` of width D = 128 (0.weight [128,1024]). The names decide: one
+ * inter_module tensor asks for the coarse layout, all of it at the sizes above. Every other combination (another width, a partial
+ * or mis-sized inter_module) is refused with T2L_EINVAL and a message that names both layouts. In the fine layout the head stops
+ * behind inter_mlp's BatchNorm (language_encoder.py:137-141 returns the view [B, n_hints, D]): t2l_text_head_train runs the token
+ * layer (dropout sites 0-3), the max over the tokens, Linear(1024 -> D) and the batch-statistics BatchNorm with the running-buffer
+ * update, and writes out = dev f32[n_sentences, D]; n_descriptions must still divide n_sentences (<= 32 sentences each), though no
+ * kernel depends on it. t2l_text_head_backward then takes grad_out = dev f32[n_sentences, D] and starts at the BatchNorm backward.
+ * The cross-rank BatchNorm slots, "text_train_bf16" and the workspace bound are those of the coarse layout.
  * t2l_text_head_train: hidden = dev f32[n_sentences, n_tokens, 1024], sentence-major and description-major (sentence j of
  * description i is row i * S + j, S = n_sentences / n_descriptions — the reference's own order); out = dev f32[n_descriptions, 256],
  * not normalised. Training-mode semantics: the four dropout sites of both TransformerEncoderLayers drop with probability

@@ -125,7 +125,8 @@ class ObjectEncoderParams(nn.Module):
 
 
 class _TextHeadTrainFn(torch.autograd.Function):
-    """The head after T5 under model.train(): forward and backward are HIP (t2l_text_head_train / t2l_text_head_backward). Parameter
+    """The head after T5 under model.train(): forward and backward are HIP (t2l_text_head_train / t2l_text_head_backward); -> [B, 256],
+    or, for the fine head, [n_sentences, D] (one row per hint: ``head`` views it [B, n_hints, D]). Parameter
     gradients do not flow through autograd: the engine accumulates them straight into the parameters' ``.grad`` buffers (bound by
     pointer), which torch's Adam steps; the hidden states are constants (T5 is frozen). ``hook`` is a dummy leaf that makes
     autograd call ``backward``."""
@@ -303,23 +304,32 @@ class LanguageEncoder(nn.Module):
     def _train_gate(self, hidden: torch.Tensor, batch_size: int):
         """-> dropout p when the engine's training head can serve this call, else None (the PyTorch modules do)."""
         if not (self.use_engine_head and self.use_engine_train_head and self.training and torch.is_grad_enabled() and hidden.is_cuda
-                and not hidden.requires_grad and not self.is_fine and hidden.dim() == 3 and hidden.shape[-1] == 1024
+                and not hidden.requires_grad and hidden.dim() == 3 and hidden.shape[-1] == 1024
                 and 1 <= hidden.shape[1] <= 32 and hidden.shape[0] % batch_size == 0 and hidden.shape[0] // batch_size <= 32):
             return None
         return self._train_structure_gate()
 
     def _train_structure_gate(self):
-        """The call-independent half of _train_gate: is this the published head (one stock layer each side of inter_mlp, one dropout
-        probability, nothing frozen)? -> that probability, else None."""
-        if not (self.use_engine_head and self.use_engine_train_head and not self.is_fine):
+        """The call-independent half of _train_gate: is this one of the two published heads (coarse: one stock layer each side of a
+        256-wide inter_mlp; fine: one stock layer in front of a 128-wide inter_mlp and nothing behind it), with one dropout probability
+        and nothing frozen? -> that probability, else None."""
+        if not (self.use_engine_head and self.use_engine_train_head):
             return None
-        if not (len(self.intra_module) == 1 and len(self.inter_module) == 1 and self.inter_mlp[0][0].out_features == 256
-                and self._layer_is_stock(self.intra_module[0], 1024, 4096, 4) and self._layer_is_stock(self.inter_module[0], 256, 1024, 4)
+        if not (len(self.intra_module) == 1 and self._layer_is_stock(self.intra_module[0], 1024, 4096, 4)
                 and isinstance(self.inter_mlp[0][1], nn.BatchNorm1d) and abs(self.inter_mlp[0][1].eps - 1e-5) < 1e-12
                 and self.inter_mlp[0][1].momentum == 0.1 and self.inter_mlp[0][1].track_running_stats):
             return None
+        if self.is_fine:  # (t2l_text_train_bind's second layout: the width the engine is tested at, no inter_module)
+            if self.inter_mlp[0][0].out_features != 128 or hasattr(self, "inter_module"):
+                return None
+            layers = (self.intra_module[0],)
+        else:
+            if not (len(self.inter_module) == 1 and self.inter_mlp[0][0].out_features == 256
+                    and self._layer_is_stock(self.inter_module[0], 256, 1024, 4)):
+                return None
+            layers = (self.intra_module[0], self.inter_module[0])
         ps = set()
-        for layer in (self.intra_module[0], self.inter_module[0]):
+        for layer in layers:
             ps.update((float(layer.dropout.p), float(layer.dropout1.p), float(layer.dropout2.p), float(layer.self_attn.dropout)))
         if len(ps) != 1 or not all(p.requires_grad for p in self._head_params() if p.dtype == torch.float32 and p.dim() > 0 and p.is_leaf
                                    and isinstance(p, nn.Parameter)):
@@ -329,8 +339,9 @@ class LanguageEncoder(nn.Module):
     # ---- the head's optimizer on the engine (t2l_text_adam_step; text2loc_amd.optim.Adam routes the head's parameters here)
     def engine_optimizer_params(self):
         """[(name, parameter)] of the head parameters the engine's training path binds — what ``optim.Adam`` hands to
-        ``engine_adam_step`` instead of a torch optimizer — or [] when this head stays on the PyTorch modules in training."""
-        if self._train_structure_gate() is None:
+        ``engine_adam_step`` instead of a torch optimizer — or [] when this head stays on the PyTorch modules in training, and for a
+        fine head: the engine trains it, but ``torch.optim.Adam(model.parameters())`` steps it with the rest of CrossMatch."""
+        if self.is_fine or self._train_structure_gate() is None:
             return []
         return [(n, p) for n, p in self.named_parameters()
                 if n.startswith(("intra_module.0.", "inter_mlp.0.", "inter_module.0.")) and p.requires_grad]
@@ -369,7 +380,8 @@ class LanguageEncoder(nn.Module):
         _apply_sync_bn(self._th_train_engine, getattr(self, "_sync_bn_cfg", None))
 
     def head(self, hidden: torch.Tensor, batch_size: int) -> torch.Tensor:
-        """hidden: last_hidden_state [n_sentences_total, L, C] -> [B, D] (language_encoder.py:127-148)."""
+        """hidden: last_hidden_state [n_sentences_total, L, C] -> [B, D], or [B, n_hints, D] for the fine head
+        (language_encoder.py:127-148)."""
         p_drop = self._train_gate(hidden, batch_size)
         if p_drop is not None:
             self._bind_text_train(hidden.device)
@@ -380,7 +392,8 @@ class LanguageEncoder(nn.Module):
             bn = self.inter_mlp[0][1]
             if bn.num_batches_tracked is not None:
                 bn.num_batches_tracked += 1
-            return _TextHeadTrainFn.apply(hook, hidden.contiguous().float(), self, batch_size, p_drop, seed)
+            out = _TextHeadTrainFn.apply(hook, hidden.contiguous().float(), self, batch_size, p_drop, seed)
+            return out.view(batch_size, hidden.shape[0] // batch_size, -1) if self.is_fine else out
         self._open_call(hidden.device)
         n_eng = LanguageEncoder.head_engine_calls
         x = self._head_first_half(hidden)

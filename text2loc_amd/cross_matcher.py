@@ -7,15 +7,19 @@
         .encode_cells(objects, object_points) -> Tensor[B,16,128]   (new: the query-independent half, cacheable per cell)
         .match(cell_desc, hint_desc, cell_index, hint_index) -> Tensor[P,2]
 
-The text branch (``LanguageEncoder(is_fine=True)``: T5 + one Transformer layer over tokens + Linear/BN) stays on
-PyTorch-ROCm; the 3D-submap branch (ObjectEncoder at fine_embed_dim incl. PointNet++ in the published mode), the cascaded
-cross-attention decoder layers and the offset head run in the engine (t2l_fine_*). The nn.Modules below are PARAMETER
-CONTAINERS for the engine-side tensors.
+Of the text branch (``LanguageEncoder(is_fine=True)``: T5 + one Transformer layer over tokens + Linear/BN) only T5 stays on
+PyTorch-ROCm: the head behind it runs in the engine, in eval mode (t2l_text_head) and under ``model.train()``
+(t2l_text_head_train / _backward in their fine layout, out [B, n_hints, 128]; ``LanguageEncoder.head`` keeps the PyTorch modules
+for what the engine does not take: site-specific dropout probabilities, a trainable T5, ``use_engine_train_head = False``). The
+3D-submap branch (ObjectEncoder at fine_embed_dim incl. PointNet++ in the published mode), the cascaded cross-attention decoder
+layers and the offset head run in the engine (t2l_fine_*). The nn.Modules below are PARAMETER CONTAINERS for the engine-side
+tensors.
 
 Under ``model.train()``, ``forward`` is one training step's forward in the engine (t2l_fine_train_*): BatchNorm over the
 batch's objects, the decoder layers' dropout, and a backward that adds every parameter gradient straight into the live
 ``.grad`` tensors and hands d loss / d hint encodings (and d features2) back to autograd, so ``loss.backward()`` continues into
-the text branch and ``torch.optim.Adam(model.parameters())`` steps everything (training/fine.py:38-91). ``encode_cells`` /
+the text branch — the engine's text-head backward, which adds the head's gradients into its ``.grad`` tensors the same way — and
+``torch.optim.Adam(model.parameters())`` steps everything (training/fine.py:38-91). ``encode_cells`` /
 ``match`` stay eval-only.
 
 With class_embed off (the published fine command) ``object_points`` holds per cell EITHER features2 [16,256] as tensors OR the
@@ -310,7 +314,7 @@ class CrossMatch(nn.Module):
             packed = packing.pack_cells_gpu(eng, objects, oe.known_classes, oe.known_colors, dev)
         else:
             packed = packing.to_device(packing.pack_cells(objects, oe.known_classes, oe.known_colors), dev)
-        hint_enc = self.language_encoder(hints)  # [B, n_hints, 128]  (cross_matcher.py:95), on torch autograd
+        hint_enc = self.language_encoder(hints)  # [B, n_hints, 128]  (cross_matcher.py:95): the engine's training head behind T5
         if hint_enc.dim() != 3 or hint_enc.shape[0] != len(objects) or not 1 <= hint_enc.shape[1] <= 8 or hint_enc.shape[2] != FINE_DIM:
             raise T2LError(f"hint encodings must be [B={len(objects)}, 1..8, 128], got {tuple(hint_enc.shape)}")
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())        # torch.manual_seed governs the masks

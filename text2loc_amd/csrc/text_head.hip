@@ -586,7 +586,8 @@ __global__ __launch_bounds__(256) void th_ln_kernel(const float* __restrict__ y,
 // ---------------------------------------------------------------------------------------------------------------
 // Operand planes of the TRAINING GEMMs (fast_gemm below): row-major f32 -> T16 planes of bf16 hi / lo halves.
 //   TRANS = false: A [R][C] -> planes of A      (rows R -> padded to a multiple of 256, contraction C a multiple of 32)
-//   TRANS = true : A [R][C] -> planes of A^T    (rows C a multiple of 256, contraction R -> padded to a multiple of 32)
+//   TRANS = true : A [R][C] -> planes of A^T    (rows C a multiple of 4 -> padded to a multiple of 256: the fine head's dW has 128;
+//                                                contraction R -> padded to a multiple of 64)
 // Through LDS, whole-line reads and 512-byte plane blocks on both sides; rows / columns beyond the matrix are zeros.
 // ---------------------------------------------------------------------------------------------------------------
 template <bool TRANS>

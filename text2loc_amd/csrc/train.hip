@@ -843,6 +843,8 @@ int zero_grad_impl(t2l_ctx* ctx, hipStream_t s) {
 //   max over tokens -> Linear(1024 -> 256) + BatchNorm1d with the statistics of THIS batch of sentences (running buffers
 //   updated) -> view [n_desc, S, 256] -> x += TransformerEncoderLayer(256, 4 heads, ff 1024)(x) over the S sentences -> max
 //   over the sentences -> out [n_desc, 256]  (F.normalize stays with the caller: cell_retrieval.py:57-63).
+// The FINE head (LanguageEncoder(is_fine=True), fine_embed_dim 128: language_encoder.py:137-141) is the same pipeline cut off behind
+// the BatchNorm at width 128: bound without inter_module tensors, out [n_sent, 128], the backward starts at the BatchNorm.
 // Forward keeps the activations; backward accumulates (+=) into the bound .grad buffers — the parameters stay torch's and are
 // stepped by t2l_text_adam_step (one launch over the 13.6 M head parameters; torch.optim.Adam when the caller prefers). The same
 // modular f32 kernels as the object branch (gemm_f32.h products, option train_bf16 for bf16 / split-bf16 operands), with the
@@ -863,6 +865,8 @@ struct TextTrain {
   size_t ws_cap = 0, ws_off = 0;
   bool have_forward = false;
   int n_sent = 0, L = 0, n_desc = 0, S = 0;
+  int D = 256;        // width of inter_mlp: 256 (the coarse head) or 128 (the fine head)
+  bool fine = false;  // the fine layout: no inter_module, the head ends behind inter_mlp's BatchNorm (out [n_sent, D])
   float p = 0.f;
   uint32_t seed = 0;
   TextLayer intra, inter;
@@ -900,13 +904,17 @@ __global__ void add_inplace_kernel(float* __restrict__ a, const float* __restric
   if (i < n) a[i] += b[i];
 }
 
-int text_train_bind_impl(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n, const char* prefix) {
+static int text_train_bind_body(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n, const char* prefix) {
   if (!tensors || n <= 0) return fail(ctx, T2L_EINVAL, "t2l_text_train_bind: null argument");
   // a re-bind of the same parameter list (moved storage: model.to(), re-assigned .grad) keeps the optimizer state, as t2l_train_bind does
   std::vector<std::string> old_names;
   std::vector<int64_t> old_numel;
   float* old_mv = nullptr;
   int64_t old_total = 0, old_step = 0;
+  struct MvGuard {  // the detached moments are freed on every path that does not adopt them (a refused re-bind included)
+    float* p = nullptr;
+    ~MvGuard() { if (p) (void)hipFree(p); }
+  } old_guard;
   if (TextTrain* o = tstate(ctx)) {
     if (ctx->train_keep_adam && o->mv) {
       old_names = o->adam_names;
@@ -915,6 +923,7 @@ int text_train_bind_impl(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n, c
       old_total = o->mv_total;
       old_step = o->step;
       o->mv = nullptr;  // (free_text_train below must not free it)
+      old_guard.p = old_mv;
     }
   }
   free_text_train(ctx);
@@ -930,8 +939,9 @@ int text_train_bind_impl(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n, c
     auto it = st->t.find(st->prefix + name);
     if (it == st->t.end() || it->second.numel != numel || (grad && !it->second.grad))
       return fail(ctx, T2L_EINVAL, "t2l_text_train_bind: tensor '" + st->prefix + name + "' missing, mis-sized or without a gradient buffer "
-                                   "(the engine trains the published head: intra_module 1 x (1024, 4 heads, 4096), inter_mlp 1024 -> 256, "
-                                   "inter_module 1 x (256, 4 heads, 1024))");
+                                   "(the engine trains the two published heads: the coarse one — intra_module 1 x (1024, 4 heads, 4096), "
+                                   "inter_mlp 1024 -> 256, inter_module 1 x (256, 4 heads, 1024) — and the fine one — the same intra_module, "
+                                   "inter_mlp 1024 -> 128, no inter_module tensors at all)");
     return T2L_OK;
   };
   int rc;
@@ -946,10 +956,17 @@ int text_train_bind_impl(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n, c
       if ((rc = need_t(lp + r.first, r.second, true))) return rc;
     return T2L_OK;
   };
-  if ((rc = layer("intra_module.0", 1024, 4096)) || (rc = layer("inter_module.0", 256, 1024))) return rc;
-  if ((rc = need_t("inter_mlp.0.0.weight", 256 * 1024, true)) || (rc = need_t("inter_mlp.0.0.bias", 256, true)) ||
-      (rc = need_t("inter_mlp.0.1.weight", 256, true)) || (rc = need_t("inter_mlp.0.1.bias", 256, true)) ||
-      (rc = need_t("inter_mlp.0.1.running_mean", 256, false)) || (rc = need_t("inter_mlp.0.1.running_var", 256, false)))
+  // the layout follows from the names alone: ANY <prefix>inter_module.* tensor asks for the coarse head (and then all of
+  // inter_module.0 must be there at 256 / 1024); none at all asks for the fine head, whose inter_mlp is 128 wide
+  st->fine = true;
+  for (auto& kv : st->t)
+    if (kv.first.compare(0, st->prefix.size() + 13, st->prefix + "inter_module.") == 0) st->fine = false;
+  st->D = st->fine ? 128 : 256;
+  const int64_t D = st->D;
+  if ((rc = layer("intra_module.0", 1024, 4096)) || (!st->fine && (rc = layer("inter_module.0", 256, 1024)))) return rc;
+  if ((rc = need_t("inter_mlp.0.0.weight", D * 1024, true)) || (rc = need_t("inter_mlp.0.0.bias", D, true)) ||
+      (rc = need_t("inter_mlp.0.1.weight", D, true)) || (rc = need_t("inter_mlp.0.1.bias", D, true)) ||
+      (rc = need_t("inter_mlp.0.1.running_mean", D, false)) || (rc = need_t("inter_mlp.0.1.running_var", D, false)))
     return rc;
   {  // Adam tables over every bound tensor that has a gradient buffer, in bind order; moments zero-initialised
     std::vector<AdamTensor> ts;
@@ -964,8 +981,10 @@ int text_train_bind_impl(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n, c
     if (same) {
       st->mv = old_mv;
       st->step = old_step;
+      old_guard.p = nullptr;
     } else {
       if (old_mv) (void)hipFree(old_mv);
+      old_guard.p = nullptr;
       T2L_HIP(ctx, hipMalloc(&st->mv, sizeof(float) * 2 * (size_t)st->mv_total));
       T2L_HIP(ctx, hipMemset(st->mv, 0, sizeof(float) * 2 * (size_t)st->mv_total));
     }
@@ -989,6 +1008,12 @@ int text_train_bind_impl(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n, c
     once.mark(ctx->device);
   }
   return T2L_OK;
+}
+
+int text_train_bind_impl(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n, const char* prefix) {
+  const int rc = text_train_bind_body(ctx, tensors, n, prefix);
+  if (rc != T2L_OK) free_text_train(ctx);  // a refused bind leaves nothing half-bound behind: the next forward reports "bind first"
+  return rc;
 }
 
 // The head's Linear products run on the tiled LDS-ring GEMM of text_head.hip (fast_gemm: 256 x 256 tiles, bf16 planes, split-bf16 by
@@ -1141,13 +1166,15 @@ int text_train_forward_impl(t2l_ctx* ctx, const float* hidden, int n_sent, int L
   st->tok_arg = tbump<int32_t>(st, (size_t)n_sent * 1024);
   hipLaunchKernelGGL(seq_max_fwd_kernel, dim3((unsigned)(((size_t)n_sent * 1024 + 255) / 256)), dim3(256), 0, s, (const float*)A.x2, (const float*)nullptr,
                      n_sent, L, 1024, st->pooled, st->tok_arg);
-  st->mlp_y = tbump<float>(st, (size_t)n_sent * 256);
-  st->mlp_out = tbump<float>(st, (size_t)n_sent * 256);
-  st->bn_mean = tbump<float>(st, 256);
-  st->bn_rstd = tbump<float>(st, 256);
-  t_gemm_nt(st, st->pooled, TT(st, "inter_mlp.0.0.weight").data, TT(st, "inter_mlp.0.0.bias").data, st->mlp_y, n_sent, 256, 1024, 0, s);
+  const int D = st->D;
+  st->mlp_y = tbump<float>(st, (size_t)n_sent * D);
+  st->mlp_out = tbump<float>(st, (size_t)n_sent * D);
+  st->bn_mean = tbump<float>(st, D);
+  st->bn_rstd = tbump<float>(st, D);
+  // (D = 128 is no multiple of the fast GEMM's 256-column tile: the fine head's Linear runs on the gemm_f32.h product, same operands)
+  t_gemm_nt(st, st->pooled, TT(st, "inter_mlp.0.0.weight").data, TT(st, "inter_mlp.0.0.bias").data, st->mlp_y, n_sent, D, 1024, 0, s);
 #define T2L_TEXT_BN_FWD(PHASE, ACC)                                                                                                       \
-  hipLaunchKernelGGL((bn_plain_fwd_kernel<PHASE>), dim3(64), dim3(256), 0, s, (const float*)st->mlp_y, n_sent, 256,                       \
+  hipLaunchKernelGGL((bn_plain_fwd_kernel<PHASE>), dim3(D / 4), dim3(256), 0, s, (const float*)st->mlp_y, n_sent, D,                      \
                      TT(st, "inter_mlp.0.1.weight").data, TT(st, "inter_mlp.0.1.bias").data, TT(st, "inter_mlp.0.1.running_mean").data,   \
                      TT(st, "inter_mlp.0.1.running_var").data, 0.1f, st->mlp_out, st->bn_mean, st->bn_rstd, ACC)
   if (ctx->sync_fn) {  // statistics | sum over the ranks | apply (t2l_train_sync_bn)
@@ -1160,6 +1187,15 @@ int text_train_forward_impl(t2l_ctx* ctx, const float* hidden, int n_sent, int L
     T2L_TEXT_BN_FWD(0, (double*)nullptr);
   }
 #undef T2L_TEXT_BN_FWD
+  if (st->fine) {  // the fine head ends here: one vector per hint, viewed [n_desc, S, D] by the caller (language_encoder.py:137-141)
+    T2L_HIP(ctx, hipMemcpyAsync(out, st->mlp_out, sizeof(float) * (size_t)n_sent * D, hipMemcpyDeviceToDevice, s));
+    event_end(ctx, "text_train_forward", s);
+    T2L_HIP(ctx, hipGetLastError());
+    if (st->ws_off > st->ws_cap) return fail(ctx, T2L_ENOMEM, "t2l_text_head_train: workspace bound exceeded (internal error)");
+    if (ctx->sync_failed) return fail(ctx, T2L_ESTATE, "t2l_text_head_train: the cross-rank sum callback (t2l_train_sync_bn) failed");
+    st->have_forward = true;
+    return T2L_OK;
+  }
   TextLayer& I = st->inter;
   I = TextLayer{};
   I.prefix = "inter_module.0"; I.T = n_sent; I.B = n_desc; I.S = S; I.site0 = 4; I.x_in = st->mlp_out;
@@ -1186,16 +1222,23 @@ int text_train_backward_impl(t2l_ctx* ctx, const float* grad_out, hipStream_t s)
   tl_gemm_block64 = ctx->train_gemm_block == 64 || (ctx->train_gemm_block == 0 && ctx->text_train_bf16 != 0);
   const size_t mark = st->ws_off;
   const int n_sent = st->n_sent, n_desc = st->n_desc, S = st->S, L = st->L;
+  const int D = st->D;
   event_begin(ctx, "text_train_backward", s);
-  // max over the sentences: the gradient goes to the arg-max row of (x + layer(x)) — to the layer's output AND to the residual x
-  float* dY2 = tbump<float>(st, (size_t)n_sent * 256);
-  hipLaunchKernelGGL(seq_max_bwd_kernel, dim3((unsigned)(((size_t)n_sent * 256 + 255) / 256)), dim3(256), 0, s, grad_out, (const int32_t*)st->sent_arg,
-                     n_desc, S, 256, dY2);
-  float* dX = text_layer_bwd<256>(st, st->inter, dY2, true, s);
-  hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)(((size_t)n_sent * 256 + 255) / 256)), dim3(256), 0, s, dX, (const float*)dY2, (size_t)n_sent * 256);
+  float* dX;
+  if (st->fine) {  // grad_out IS the gradient behind the BatchNorm; its backward works in place, so on a copy
+    dX = tbump<float>(st, (size_t)n_sent * D);
+    T2L_HIP(ctx, hipMemcpyAsync(dX, grad_out, sizeof(float) * (size_t)n_sent * D, hipMemcpyDeviceToDevice, s));
+  } else {
+    // max over the sentences: the gradient goes to the arg-max row of (x + layer(x)) — to the layer's output AND to the residual x
+    float* dY2 = tbump<float>(st, (size_t)n_sent * 256);
+    hipLaunchKernelGGL(seq_max_bwd_kernel, dim3((unsigned)(((size_t)n_sent * 256 + 255) / 256)), dim3(256), 0, s, grad_out, (const int32_t*)st->sent_arg,
+                       n_desc, S, 256, dY2);
+    dX = text_layer_bwd<256>(st, st->inter, dY2, true, s);
+    hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)(((size_t)n_sent * 256 + 255) / 256)), dim3(256), 0, s, dX, (const float*)dY2, (size_t)n_sent * 256);
+  }
   // inter_mlp: BatchNorm (batch statistics), Linear
 #define T2L_TEXT_BN_BWD(PHASE, ACC)                                                                                                    \
-  hipLaunchKernelGGL((bn_plain_bwd_kernel<PHASE>), dim3(64), dim3(256), 0, s, dX, (const float*)st->mlp_y, n_sent, 256,                 \
+  hipLaunchKernelGGL((bn_plain_bwd_kernel<PHASE>), dim3(D / 4), dim3(256), 0, s, dX, (const float*)st->mlp_y, n_sent, D,                \
                      TT(st, "inter_mlp.0.1.weight").data, (const float*)st->bn_mean, (const float*)st->bn_rstd,                         \
                      TT(st, "inter_mlp.0.1.weight").grad, TT(st, "inter_mlp.0.1.bias").grad, ACC)
   if (ctx->sync_fn) {
@@ -1210,7 +1253,7 @@ int text_train_backward_impl(t2l_ctx* ctx, const float* grad_out, hipStream_t s)
 #undef T2L_TEXT_BN_BWD
   float* dpool = tbump<float>(st, (size_t)n_sent * 1024);
   t_gemm_tn_nn(st, dX, st->pooled, TT(st, "inter_mlp.0.0.weight").grad, TT(st, "inter_mlp.0.0.bias").grad, TT(st, "inter_mlp.0.0.weight").data, dpool,
-               n_sent, 256, 1024, 0, nullptr, nullptr, s);
+               n_sent, D, 1024, 0, nullptr, nullptr, s);
   // max over the tokens, then the d = 1024 layer (its input, T5's hidden states, is a constant: no dX)
   float* dX2 = tbump<float>(st, (size_t)n_sent * L * 1024);
   hipLaunchKernelGGL(seq_max_bwd_kernel, dim3((unsigned)(((size_t)n_sent * L * 1024 + 255) / 256)), dim3(256), 0, s, (const float*)dpool,

@@ -508,29 +508,46 @@ class Engine:
     # ------------------------------------------------------------------ the text head in training mode (f-4)
     def text_train_bind(self, tensors: Dict[str, Tuple[torch.Tensor, Optional[torch.Tensor]]], prefix: str = "language_encoder."):
         """tensors: ``<prefix>intra_module.0.* / inter_mlp.0.* / inter_module.0.*`` -> (live fp32 CUDA tensor, its .grad buffer or None
-        for the BatchNorm running buffers). POINTERS are kept, not copies."""
+        for the BatchNorm running buffers). POINTERS are kept, not copies. Two layouts (include/t2l.h): the coarse head (inter_mlp 256
+        wide + inter_module.0) and the fine head (inter_mlp 128 wide, no inter_module tensor at all); the library refuses the rest."""
         descs, keep = [], []
         for name, (data, grad) in tensors.items():
             keep.append((data, grad))
             descs.append(_TrainTensor(name.encode(), self._ptr(data, torch.float32, name),
                                       self._ptr(grad, torch.float32, name + ".grad"), data.numel()))
         arr = (_TrainTensor * len(descs))(*descs)
+        self._text_train_shape = self._text_train_out = None  # (a refused bind leaves nothing bound; a new one forgets the last forward)
         self._check(self.lib.t2l_text_train_bind(self._h, arr, len(descs), prefix.encode()))
         self._text_train_keepalive = keep
+        # what the library just accepted, for the output shapes below: (fine layout?, width of inter_mlp)
+        # The library decided the layout (text_train_bind_body: any inter_module name -> coarse) and accepted exactly two shapes; the
+        # width is read off the bound tensor, and anything but those two means this wrapper and the library disagree: loud, not a
+        # mis-sized output buffer
+        fine = not any(n.startswith(prefix + "inter_module.") for n in tensors)
+        shape = (fine, int(tensors[prefix + "inter_mlp.0.1.weight"][0].numel()))
+        if shape not in ((True, 128), (False, 256)):
+            raise T2LError(f"text_train_bind: the library accepted a layout this wrapper does not know: fine={shape[0]}, width {shape[1]}")
+        self._text_train_shape = shape
 
     def text_head_train(self, hidden: torch.Tensor, n_descriptions: int, dropout_p: float = 0.1, seed: int = 0) -> torch.Tensor:
         """hidden f32[n_sentences, n_tokens, 1024] -> f32[n_descriptions, 256] (not normalised): LanguageEncoder.forward after T5 under
-        model.train() (models/language_encoder.py:127-147); activations stay in the context for ``text_head_backward``."""
+        model.train() (models/language_encoder.py:127-147); with the fine head bound -> f32[n_sentences, 128], one row per hint
+        (:137-141). Activations stay in the context for ``text_head_backward``."""
         if hidden.dim() != 3 or hidden.shape[2] != 1024:
             raise T2LError(f"text_head_train: expected [n_sentences, n_tokens, 1024], got {tuple(hidden.shape)}")
-        out = torch.empty((int(n_descriptions), 256), dtype=torch.float32, device=hidden.device)
+        fine, D = getattr(self, "_text_train_shape", None) or (False, 256)  # (unbound: the library raises below)
+        out = torch.empty((int(hidden.shape[0]) if fine else int(n_descriptions), D), dtype=torch.float32, device=hidden.device)
         self._check(self.lib.t2l_text_head_train(self._h, self._ptr(hidden, torch.float32, "hidden"), int(hidden.shape[0]), int(hidden.shape[1]),
                                                  int(n_descriptions), float(dropout_p), int(seed) & 0xFFFFFFFF, out.data_ptr(),
                                                  _stream_ptr(self.device)))
         self._text_train_input = hidden  # must outlive the backward call
+        self._text_train_out = tuple(out.shape)
         return out
 
     def text_head_backward(self, grad_out: torch.Tensor):
+        want = getattr(self, "_text_train_out", None)
+        if want is not None and tuple(grad_out.shape) != want:  # (the library reads want[0] * want[1] floats behind the pointer)
+            raise T2LError(f"text_head_backward: grad_out must be {want} like the last forward's output, got {tuple(grad_out.shape)}")
         self._check(self.lib.t2l_text_head_backward(self._h, self._ptr(grad_out, torch.float32, "grad_out"), _stream_ptr(self.device)))
 
     def pointnet_features_train(self, pos: torch.Tensor, rgb: torch.Tensor, cell_offsets) -> torch.Tensor:

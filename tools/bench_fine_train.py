@@ -9,7 +9,14 @@ models/cross_matcher.py:86-135 runs them. Same weights, inputs and batch. Device
 reference's backbone needs torch_geometric, which this machine does not have, so there is no PyTorch column. The row also
 gives the device memory the first step claimed (the backbone's saved activations and scratch plus the fine step's arena).
 
-    python tools/bench_fine_train.py [--batches 32,256] [--iters 20] [--warmup 10] [--reps 5] [--points]
+`--text`: the WHOLE step, text branch included — ``CrossMatch.forward`` under ``train()`` with a real ``LanguageEncoder(is_fine=True)``
+behind a stub T5 that hands back fixed hidden states [B * 6, --tokens, 1024] (T5 itself is frozen and out of scope), offset_lambda * MSE,
+``backward`` and ``torch.optim.Adam(model.parameters())``. Two rows per batch size: ``use_engine_train_head`` on (t2l_text_head_train /
+_backward) and off (the head on its PyTorch modules: exactly the step before the engine served the fine head); everything else —
+the packing of the objects, the engine's decoder step, the optimizer — is the same code in both. Every row gives the five
+repetitions' medians' median and their spread (max - min). ``--text-only on|off`` runs one of the two (a kernel trace of its own).
+
+    python tools/bench_fine_train.py [--batches 32,256] [--iters 20] [--warmup 10] [--reps 5] [--points | --text [--tokens 12]]
 """
 from __future__ import annotations
 
@@ -64,7 +71,7 @@ def torch_forward(model, packed, hints, pn):
     return model.mlp_offsets(hint.max(dim=0).values)
 
 
-def time_steps(step, iters, warmup, reps):
+def time_steps(step, iters, warmup, reps, all_reps=False):
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
@@ -77,7 +84,7 @@ def time_steps(step, iters, warmup, reps):
         b.record()
         b.synchronize()
         ms.append(a.elapsed_time(b) / iters)
-    return float(np.median(ms))
+    return [float(x) for x in ms] if all_reps else float(np.median(ms))
 
 
 def bench(embed, B, iters, warmup, reps):
@@ -165,6 +172,61 @@ def bench_points(B, iters, warmup, reps):
             "first_step_device_gb": round(claimed / 1e9, 3)}
 
 
+class _Obj:  # duck-types the reference's Object3d (xyz, rgb, label)
+    def __init__(self, label, xyz, rgb):
+        self.label, self.xyz, self.rgb = label, xyz, rgb
+
+
+class _StubT5:
+    def __init__(self, hidden):
+        self.hidden = hidden
+
+    def __call__(self, input_ids=None, attention_mask=None, output_attentions=False):
+        return argparse.Namespace(last_hidden_state=self.hidden)
+
+
+def _stub_tokenizer(sentences, return_tensors="pt", padding="longest"):
+    ids = torch.zeros((len(sentences), 4), dtype=torch.long)
+    return {"input_ids": ids, "attention_mask": torch.ones_like(ids)}
+
+
+def bench_text(B, L, engine_head, iters, warmup, reps, H=6):
+    from text2loc_amd.cell_retrieval import LanguageEncoder
+    from text2loc_amd.cross_matcher import pad_objects
+
+    hidden = torch.from_numpy(synth.make_t5_hidden(B * H, L, seed=3)).cuda()
+    enc = LanguageEncoder(128, fixed_embedding=True, intra_module_num_layers=1, is_fine=True, llm_model=_StubT5(hidden),
+                          tokenizer=_stub_tokenizer, input_dim=1024)
+    head = {k[len("language_encoder."):]: torch.from_numpy(v) for k, v in synth.make_language_head_weights(1, embed_dim=128).items()
+            if ".inter_module." not in k}
+    enc.load_state_dict(head, strict=False)
+    enc.use_engine_train_head = bool(engine_head)
+    model = CrossMatch(synth.KNOWN_CLASS, synth.COLOR_NAMES, make_args(True), language_encoder=enc)
+    model.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in synth.make_fine_weights(0).items()}, strict=False)
+    model = model.cuda().train()
+    cells = synth.make_cells(B, seed=1, min_obj=16, max_obj=16)
+    objects = [[] for _ in range(B)]
+    for b, o, label, xyz, rgb in synth.make_object_points(cells, 1):
+        objects[b].append(_Obj(label, xyz, rgb))
+    objects = [pad_objects(o) for o in objects]
+    texts = [" ".join(["The pose is north of a gray pole."] * H)] * B
+    target = torch.from_numpy(np.random.default_rng(2).random((B, 2)).astype(np.float32)).cuda()
+    opt = torch.optim.Adam(model.parameters(), lr=1e-4)
+    n0 = LanguageEncoder.train_engine_calls
+
+    def step():
+        opt.zero_grad(set_to_none=False)
+        loss = LAMBDA * F.mse_loss(model(objects, texts, None), target)
+        loss.backward()
+        opt.step()
+
+    ms = time_steps(step, iters, warmup, reps, all_reps=True)
+    served = LanguageEncoder.train_engine_calls - n0
+    assert served == ((warmup + iters * reps) if engine_head else 0), served  # the row measures the path it names
+    return {"B": B, "sentences": B * H, "tokens": L, "text_head": "engine" if engine_head else "pytorch", "ms_step": round(float(np.median(ms)), 4),
+            "spread_ms": round(max(ms) - min(ms), 4), "reps_ms": [round(x, 4) for x in ms]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default="32,256")
@@ -172,8 +234,24 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--points", action="store_true", help="features2 from the jointly trained PointNet++ backbone (engine only)")
+    ap.add_argument("--text", action="store_true", help="the whole step with a real LanguageEncoder(is_fine) behind fixed hidden states")
+    ap.add_argument("--tokens", type=int, default=12, help="--text: tokens per hint sentence")
+    ap.add_argument("--text-only", choices=["on", "off"], default=None, help="--text: only the row with the engine head on / off")
     a = ap.parse_args()
     torch.manual_seed(0)
+    if a.text:
+        heads = [True, False] if a.text_only is None else [a.text_only == "on"]
+        rows = [bench_text(int(B), a.tokens, h, a.iters, a.warmup, a.reps) for B in a.batches.split(",") for h in heads]
+        by = {(r["B"], r["text_head"]): r for r in rows}
+        for B in {r["B"] for r in rows}:
+            if (B, "engine") in by and (B, "pytorch") in by:
+                e, t = by[(B, "engine")], by[(B, "pytorch")]
+                e["gain_ms"] = round(t["ms_step"] - e["ms_step"], 4)
+                e["beats_pytorch_head_by_more_than_the_spread"] = bool(e["gain_ms"] > max(e["spread_ms"], t["spread_ms"]))
+        print(json.dumps({"metric": "full fine-stage training step with the text head (CrossMatch.forward under train(): text head fwd + "
+                                    "decoder fwd + offset_lambda*MSE + bwd + text head bwd + Adam), 2 decoder layers, 6 hints of --tokens tokens, dropout 0.1, embedding mode",
+                          "unit": "ms/step", "rows": rows}))
+        return
     if a.points:
         rows = [bench_points(int(B), a.iters, a.warmup, a.reps) for B in a.batches.split(",")]
         print(json.dumps({"metric": "fine-stage training step with the PointNet++ backbone trained jointly (backbone fwd + fwd + "
