@@ -15,6 +15,11 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream). Calls are asynchronous on
  *     that stream unless stated otherwise. A context is not thread-safe: the reference is a single
  *     thread / single process per device, and so is this (one process per GPU; shards meet in RCCL).
+ *   - Alignment: a typed dev array needs the alignment of its element type, and any run of whole rows of one (emb + lo * 256,
+ *     rgb + 5 * 3) is as good an argument as the array itself. The kernels may read arrays whose rows are a multiple of 16 bytes —
+ *     embeddings, queries, hidden states, descriptors, pn_feat, point batches, pair records — in 16-byte units and rely on the
+ *     16-byte alignment every such run of rows inherits from its allocation; per-point and per-object arrays (xyz, rgb, center,
+ *     n_pts, class_idx, color_idx, offsets, result ids / scores, index lists) are read element by element.
  *   - row ids are int32 (N < 2^31) and GLOBAL: local row + the shard's row_offset (t2l_db_set).
  *   - the search, the loss, the text entry points and the training step work on rows of T2L_EMBED_DIM = 256 floats
  *     (coarse_embed_dim of the published config, README.md:87-99). The eval-mode cell encoder also serves the other
@@ -236,6 +241,8 @@ int t2l_merge_pairs(t2l_ctx* ctx, const double* pairs, int32_t parts, int32_t n_
 /* Same exchange with ONE collective and NO pack launch: a rank hands t2l_search output pointers into ONE block —
  * ids i32[n_queries][k] at offset 0, scores f64[n_queries][k] at score_offset (8-byte aligned, >= 4 * n_queries * k) — the
  * blocks of all ranks are all-gathered back to back (block_bytes each, 12 bytes per candidate on the wire) and merged here.
+ * `blocks` is a byte buffer read as int32 and float64: it must start on an 8-byte boundary, and block_bytes and score_offset must
+ * be multiples of 8 — T2L_EINVAL otherwise, before anything is launched (the one alignment requirement beyond "Alignment" above).
  * (text2loc_amd.sharded.ShardedSearcher: search -> all_gather -> this; the per-rank work of an 8-GPU step is three launches.) */
 int t2l_merge_gathered(t2l_ctx* ctx, const void* blocks, int64_t block_bytes, int64_t score_offset, int32_t parts,
                        int32_t n_queries, int32_t k, int32_t* out_idx, double* out_score, void* stream);
@@ -248,7 +255,9 @@ int t2l_search_rescored(t2l_ctx* ctx, int32_t* out_count);
 /* All counters of the last t2l_search call (synchronises): out8[0] queries that ended in a float64 VALU scan of the shard,
  * [1] queries re-scored beyond the first L candidates (in the re-rank wave or by the fallback kernel), [2] queries the
  * re-rank handed to the fallback kernel, [3] auto-mode probe count, [4] queries deferred to the float64 MFMA stage (heavy
- * mode), [5] = [0] + [4] of the previous call, [6] queries the MFMA stage could not certify, [7] queries it served. */
+ * mode), [5] queries a wide in-wave repair settled, [6] queries the MFMA stage could not certify, [7] queries it served.
+ * Every path answers for the last call alone: the one-launch path reports zeros, the streaming scan counts its exact scans in [0]
+ * and reports zeros elsewhere. */
 int t2l_search_counters(t2l_ctx* ctx, int32_t* out8);
 
 /* ---- contrastive loss (a8) ------------------------------------------------------------------- */

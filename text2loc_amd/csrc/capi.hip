@@ -336,6 +336,8 @@ int t2l_merge_gathered(t2l_ctx* ctx, const void* blocks, int64_t block_bytes, in
     return fail(ctx, T2L_EINVAL, "t2l_merge_gathered: bad parts / n_queries / k");
   if (n_queries == 0) return T2L_OK;
   if (!blocks || !out_idx) return fail(ctx, T2L_EINVAL, "t2l_merge_gathered: null buffer");
+  if (reinterpret_cast<uintptr_t>(blocks) % 8)  // (int32 ids and float64 scores are read out of a byte buffer)
+    return fail(ctx, T2L_EINVAL, "t2l_merge_gathered: blocks must start on an 8-byte boundary");
   T2L_HIP(ctx, hipSetDevice(ctx->device));
   return merge_gathered_impl(ctx, blocks, block_bytes, score_offset, parts, n_queries, k, out_idx, out_score, (hipStream_t)stream);
 }

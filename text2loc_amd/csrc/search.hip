@@ -1879,7 +1879,10 @@ int search_impl(t2l_ctx* ctx, const float* q, int Q, int K, int32_t* out_idx, do
     if (done > ctx->stat_seen) {
       ctx->stat_seen = done;
       const int64_t flagged = hs[1], total = hs[2], exact_prev = hs[3], rescored = hs[5];
-      if (ctx->search_mode == 0 && ctx->search_auto && hs[4]) {
+      // (total == 0: the bank of a call that keeps no report card — the streaming scan clears its bank and counts its exact scans
+      // only — or of no call at all: nothing to learn from)
+      const bool counted = total > 0;
+      if (counted && ctx->search_mode == 0 && ctx->search_auto && hs[4]) {
         // ... or more than 1 in 2 failed the first certificate: the in-wave repairs settle them, but a wide repair re-scores
         // dozens to hundreds of rows per query — measured on a clustered database with 92 % of the queries repaired: 185 us per
         // step on the f16 scan against 133 us on the split-bf16 scan, whose 50x tighter band certifies them outright
@@ -1890,11 +1893,11 @@ int search_impl(t2l_ctx* ctx, const float* q, int Q, int K, int32_t* out_idx, do
       }
       // merged candidate records pay while repairs are rare: more than 1 query in 64 failing its first certificate -> plain lists
       // (their repairs re-score a quarter of the rows), back below 1 in 256
-      if (hs[4] == 1) {
+      if (counted && hs[4] == 1) {
         if (ctx->merge_live && rescored * 64 > total) ctx->merge_live = false;
         else if (!ctx->merge_live && rescored * 256 <= total) ctx->merge_live = true;
       }
-      if (ctx->search_auto) {
+      if (counted && ctx->search_auto) {
         if (!ctx->heavy && exact_prev * 64 > total) ctx->heavy = true;
         else if (ctx->heavy && exact_prev * 256 < total) ctx->heavy = false;
         // 7 in 8 queries end in the exact stage whatever the candidate scan says: stop paying for the scan and the re-rank

@@ -360,7 +360,9 @@ static int stream_launch(t2l_ctx* ctx, const float* q, int Q, int K, int32_t* ou
     attr_done.mark(ctx->device);
   }
   const float eps_rel = (float)(ctx->eps_scale * ((kD + 8) * 5.9604644775390625e-08 + 9.85e-4));  // f16 operands (search.hip)
-  T2L_HIP(ctx, hipMemsetAsync(ctx->fb_count, 0, 2 * sizeof(int32_t), s));
+  // all 16 counters of the bank, not only the two this path counts in: the bank still holds the last batched call's [2..15], and
+  // t2l_search_counters / t2l_search_fallbacks answer for THIS call (a cleared bank is what a first call finds, search.hip: reset_counts)
+  T2L_HIP(ctx, hipMemsetAsync(ctx->fb_count, 0, 16 * sizeof(int32_t), s));
   for (int q0 = 0; q0 < Q; q0 += kStreamQ) {
     const int nq = min(kStreamQ, Q - q0);
     event_begin(ctx, "search_scan", s);

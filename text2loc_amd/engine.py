@@ -165,24 +165,30 @@ def _stream_ptr(device=None) -> int:
     return int(torch.cuda.current_stream(device).cuda_stream)
 
 
-def _dev_ptr(t: Optional[torch.Tensor], dtype, name: str) -> Optional[int]:
+def _dev_ptr(t: Optional[torch.Tensor], dtype, name: str, align: int = 1) -> Optional[int]:
+    """``align``: for the one argument the kernels read in units wider than its elements and whose rows are no multiple of that unit
+    (include/t2l.h states the requirement beside the entry point); everything else needs the alignment of its elements only, which a
+    contiguous tensor has (alignment contract)."""
     if t is None:
         return None
     if not t.is_cuda:
         raise T2LError(f"{name}: expected a CUDA (HIP) tensor; the engine has no CPU path")
     if t.dtype != dtype or not t.is_contiguous():
         raise T2LError(f"{name}: expected contiguous {dtype}, got {t.dtype} contiguous={t.is_contiguous()}")
-    return t.data_ptr()
+    ptr = t.data_ptr()
+    if ptr % align:
+        raise T2LError(f"{name}: must start on a {align}-byte boundary (include/t2l.h), this one starts {ptr % align} bytes behind one")
+    return ptr
 
 
 class Engine:
     """One context per GPU (one process per GPU)."""
 
-    def _ptr(self, t: Optional[torch.Tensor], dtype, name: str) -> Optional[int]:
+    def _ptr(self, t: Optional[torch.Tensor], dtype, name: str, align: int = 1) -> Optional[int]:
         """Device pointer of a contiguous tensor of ``dtype`` that lives on THIS engine's GPU (anything else raises)."""
         if t is not None and t.is_cuda and t.device.index != self.device:
             raise T2LError(f"{name}: tensor is on cuda:{t.device.index}, this engine drives cuda:{self.device}")
-        return _dev_ptr(t, dtype, name)
+        return _dev_ptr(t, dtype, name, align)
 
     def __init__(self, device: Optional[int] = None):
         self.lib = load_library()
@@ -766,13 +772,15 @@ class Engine:
         return buf, idx, sc, block_bytes, score_offset
 
     def merge_gathered(self, blocks: torch.Tensor, block_bytes: int, score_offset: int, parts: int, Q: int, k: int, out=None):
-        """blocks u8[parts * block_bytes] (all-gathered ``result_block``s) -> (idx i32[Q,k], score f64[Q,k])."""
+        """blocks u8[parts * block_bytes] (all-gathered ``result_block``s) -> (idx i32[Q,k], score f64[Q,k]). The kernel reads int32 ids
+        and float64 scores out of the byte buffer: it must start on an 8-byte boundary (a byte slice such as ``buf[1:]`` is refused)."""
+        blocks_ptr = self._ptr(blocks, torch.uint8, "blocks", align=8)
         if out is None:
             out_i = torch.empty((Q, k), dtype=torch.int32, device=blocks.device)
             out_s = torch.empty((Q, k), dtype=torch.float64, device=blocks.device)
         else:
             out_i, out_s = out
-        self._check(self.lib.t2l_merge_gathered(self._h, self._ptr(blocks, torch.uint8, "blocks"), int(block_bytes), int(score_offset),
+        self._check(self.lib.t2l_merge_gathered(self._h, blocks_ptr, int(block_bytes), int(score_offset),
                                                 int(parts), int(Q), int(k), out_i.data_ptr(), out_s.data_ptr(), _stream_ptr(self.device)))
         return out_i, out_s
 
