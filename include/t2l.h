@@ -95,8 +95,8 @@ typedef struct {
  * Compiled set: embed_dim 128 or 256; cfg->num_heads with head_dim = embed_dim / num_heads of 32 or 64 (2 or 4 heads at
  * 128, 4 or 8 at 256); object_size 1..32; cfg->num_layers 1..4; dim_feedforward = 2 * embed_dim as in the reference.
  * Anything else is T2L_EINVAL and the message names the set, as is a tensor whose size contradicts the declared shape.
- * {256, 28} with 4 heads runs the kernels of the published model, every other shape one shape-templated kernel (one cell
- * per workgroup; split-f16 MFMA, or the f32 MFMA under the same range guard / option "encoder_f32"). Options
+ * Every shape runs one shape-templated kernel (one cell per workgroup; split-f16 MFMA, or the f32 MFMA under the same range
+ * guard / option "encoder_f32"); {256, 28} with 4 heads, the published model, has the two-cell kernel in front of it. Options
  * "encoder_f16" and "encoder_two_cells" are accepted at every shape and act on the published shape only.
  * The training entry points (t2l_train_bind and what follows it) are built for the published shape only. */
 int t2l_load_weights_shaped(t2l_ctx* ctx, const t2l_weight_desc* w, int32_t n, const t2l_model_config* cfg,
@@ -561,9 +561,10 @@ int t2l_adam_state(t2l_ctx* ctx, int32_t set, float* m, float* v, int64_t* step,
  *                     handed to an exact scan of the whole shard; 0 = off (tests of the exact stages).
  * "encoder_two_cells" (default 1): t2l_encode_cells with two cells per eight-wave workgroup, activations as split-f16 planes in LDS and the
  *                     merge / out_proj / feed-forward weight fragments shared by both cells (split-f16 and plain-f16 arithmetic, two or
- *                     more feature slots). 0 = one cell per four-wave workgroup on f32 tiles — the kernel that serves models with ONE
- *                     feature slot (and, in its f32 form, "encoder_f32"); the option exists so that the tests can hold that kernel
- *                     to the reference goldens, which are four-feature models. Same results to rounding.
+ *                     more feature slots). 0 = one cell per four-wave workgroup on f32 tiles — the shape-templated kernel that serves every
+ *                     other shape, models with ONE feature slot and, in its f32 form, "encoder_f32"; the option exists so that the
+ *                     tests can hold its published-shape instances to the reference goldens, which are four-feature models. Same
+ *                     results to rounding.
  * "search_merge_lists" (default 2): the paired scan's candidate hand-off to the re-rank. 0 = four 24-byte lists per (query, workgroup);
  *                     1 = ONE 32-byte record (the best 7 of their 24 keys, the source list in two more code bits, + a bound on every other
  *                     key): a third of the bytes written back at the end of the launch, -0.7 us per step at Q = 4096; 2 = records while the

@@ -166,3 +166,27 @@ def test_plain_f16_option_meets_the_north_star_bar(golden, name, embed):
         assert np.abs(np.linalg.norm(out, axis=1) - 1).max() < 1e-5
     finally:
         e.close()
+
+
+@pytest.mark.parametrize("name,embed", [("encoder_embed", True), ("encoder_pn", False)])
+def test_plain_f16_option_on_the_one_cell_kernel(golden, name, embed):
+    """Option encoder_f16 with encoder_two_cells = 0: the plain-f16 instance of the one-cell kernel, held to the same bar as the
+    two-cell form above (1e-3 is the north star's; asserted at 3e-4), and really plain f16 (above 1e-6)."""
+    from text2loc_amd.engine import Engine
+
+    g = golden(name)
+    sd = synth.make_object_branch_weights(int(g["weight_seed"]))
+    e = Engine(0)
+    try:
+        e.set_option("encoder_two_cells", 0)
+        e.set_option("encoder_f16", 1)
+        e.load_weights(sd, class_embed=embed, color_embed=embed)
+        cells = _cells(g)
+        if not embed:
+            cells["pn_feat"] = synth.make_cells(int(g["n_cells"]), seed=int(g["cell_seed"]), with_pn_feat=True)["pn_feat"]
+        out = e.encode_cells(_to_gpu(cells)).cpu().numpy()
+        err = np.abs(out - g["cell_embeddings"]).max()
+        assert 1e-6 < err < 3e-4, err
+        assert np.abs(np.linalg.norm(out, axis=1) - 1).max() < 1e-5
+    finally:
+        e.close()

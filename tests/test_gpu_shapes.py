@@ -151,6 +151,34 @@ def test_shapes_interleave_on_one_context_and_side_by_side(eng, golden):
         other.close()
 
 
+@pytest.mark.parametrize("f32", [0, 1], ids=["split-f16", "f32"])
+def test_published_one_cell_is_the_shaped_instance(f32):
+    """The published shape with encoder_two_cells = 0 runs the <256, 64> instance of the one-cell kernel with object_size 28, the
+    instance the same state_dict gets when the shape is spelled out: equal bits on cells of 0, 1, 27, 28 and 29 objects."""
+    from text2loc_amd.engine import Engine
+
+    sd = synth.make_object_branch_weights(0)
+    src = synth.make_cells(1, seed=2, min_obj=86, max_obj=86)
+    counts = np.array([0, 1, 27, 28, 29], dtype=np.int32)
+    cells = {"counts": counts, "offsets": np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)}
+    cells.update({k: src[k][: counts.sum()] for k in OBJ_KEYS if k in src})
+    a, b = Engine(0), Engine(0)
+    try:
+        for e in (a, b):
+            e.set_option("encoder_f32", f32)
+            e.set_option("encoder_two_cells", 0)
+        a.load_weights(sd, class_embed=True, color_embed=True)
+        b.load_weights(sd, class_embed=True, color_embed=True, embed_dim=256, num_heads=4, object_size=28)
+        out_a = a.encode_cells(to_gpu(cells)).cpu().numpy()
+        out_b = b.encode_cells(to_gpu(cells)).cpu().numpy()
+        assert out_a.shape == (5, 256) and np.isfinite(out_a).all()
+        assert np.array_equal(out_a, out_b)
+        assert np.abs(out_a - O.encode_cells(cells, sd, True, True)).max() < TOL
+    finally:
+        a.close()
+        b.close()
+
+
 def test_c_entry_point_refuses_what_is_not_compiled(eng):
     """T2L_EINVAL from t2l_load_weights_shaped itself (the binding's own check is bypassed), the message names the compiled set."""
     import ctypes as C

@@ -1,6 +1,10 @@
-// Fused per-cell encoder: ObjectEncoder.forward (models/object_encoder.py:66-153, eval mode) +
-// CellRetrievalNetwork.encode_objects (models/cell_retrieval.py:65-110) as ONE kernel, one workgroup
-// (4 waves) per cell, every intermediate resident in LDS.
+// The cell encoder at the published shape (256, 4 heads, 28 slots) in its default form, the fused t2l_text_inter layer, and the
+// weight loader of every encoder kernel.
+//
+// encode_cells2_kernel: ObjectEncoder.forward (models/object_encoder.py:66-153, eval mode) +
+// CellRetrievalNetwork.encode_objects (models/cell_retrieval.py:65-110) as ONE kernel, two cells per eight-wave workgroup, every
+// intermediate resident in LDS. The one-cell kernel — every other compiled shape, the all-f32 arithmetic, single-feature models,
+// option encoder_two_cells = 0 — is encode_shaped.hip; encode_impl below chooses.
 //
 //   per object (<= 28 kept, cell_retrieval.py:94-98):
 //     class  = normalize(class_embedding[idx])           | normalize(mlp_pointnet(features2))
@@ -16,7 +20,7 @@
 // ~5e-7 relative, well inside the 1e-3 parity budget (measured 2e-6 on the goldens) at 1/5 of the matrix-pipe time of
 // v_mfma_f32_32x32x2_f32. Activations are split on the fly (20 VALU per 8 values), weights at load time. f16 overflows at
 // 65504: t2l_load_weights bounds every activation that enters a split GEMM from the weights (LayerNorm gain/bias,
-// row norms) and keeps the all-f32 kernel for models that could exceed it (option encoder_f32 forces it).
+// row norms) and sends models that could exceed it to the all-f32 one-cell kernel (option encoder_f32 forces it).
 // The attention core (S = K Q^T, P V) and the small MLPs stay on the f32 MFMA.
 // M = 32 rows = the 28 slots + 4 dead rows (masked out of the softmax keys and the max-pool).
 // Weights are BN-folded and re-laid out on the host into MFMA B-fragment order
@@ -46,7 +50,6 @@ namespace t2l {
 
 constexpr int kLdX = kD + 4;        // 260: row stride of every 256-wide LDS buffer
 constexpr int kLdH = 64 + 4;        // 68   (hidden layer of the small MLPs)
-constexpr int kXFloats = kSP * kLdX;
 
 // out[32][N] = A[32][K] @ W^T ; the 4 waves split N in 32-column tiles, two tiles at a time per wave
 // (tiles w+8p and w+8p+4) sharing the A fragments. epi(t, r, row, col, value) is called for every element
@@ -90,64 +93,6 @@ __device__ __forceinline__ void gemm32(const float* __restrict__ A, int lda, int
   }
 }
 
-// acc0 += A * W0^T, acc1 += A * W1^T over qn packed k-steps (8 k each): A = this lane's LDS row half (arow), W0 / W1 =
-// packed weight tiles already offset to their first step and to this lane. The caller owns initialisation and epilogue.
-__device__ __forceinline__ void mm_pair(const float* __restrict__ arow, int qn, const float4* __restrict__ w0,
-                                        const float4* __restrict__ w1, f32x16& acc0, f32x16& acc1) {
-#pragma unroll 4
-  for (int q = 0; q < qn; ++q) {
-    const float4 a = *reinterpret_cast<const float4*>(arow + 4 * q);
-    const float4 b0 = w0[q * 64];
-    const float4 b1 = w1[q * 64];
-    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b0.x, acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b1.x, acc1, 0, 0, 0);
-    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b0.y, acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b1.y, acc1, 0, 0, 0);
-    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b0.z, acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b1.z, acc1, 0, 0, 0);
-    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b0.w, acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b1.w, acc1, 0, 0, 0);
-  }
-}
-
-// ---- split-f16 forms of gemm32 / mm_pair (fragments and packing: mfma_h3.h)
-// acc0 += A * W0^T, acc1 += A * W1^T over `steps` k-steps of 16: arow = this lane's LDS row half, w0 / w1 = the two weight
-// tiles already offset to their first step and to this lane (2 uint4 per lane and step, 128 uint4 per step)
-template <bool SG = false>
-__device__ __forceinline__ void mm_pair_h(const float* __restrict__ arow, int steps, const uint4* __restrict__ w0,
-                                          const uint4* __restrict__ w1, f32x16& acc0, f32x16& acc1) {
-#pragma unroll T2L_ENC_UNROLL
-  for (int s = 0; s < steps; ++s) {
-    const HFrag a = split_h<SG>(arow + 8 * s);
-    const HFrag b0 = load_h1<SG>(w0 + T2L_WSTEP(s) * 128), b1 = load_h1<SG>(w1 + T2L_WSTEP(s) * 128);
-    mfma_h3<SG>(acc0, a, b0);
-    mfma_h3<SG>(acc1, a, b1);
-  }
-}
-template <bool SG = false, typename Epi>
-__device__ __forceinline__ void gemm32_h(const float* __restrict__ A, int lda, int K, const uint4* __restrict__ Wp, int N,
-                                         int wave, int lane, Epi epi) {
-  const int col = lane & 31, half = lane >> 5;
-  const int steps = K >> 4;
-  const float* arow = A + col * lda + half * (K >> 1);
-  for (int p = 0; p < (N >> 8); ++p) {
-    const int nt0 = wave + 8 * p, nt1 = nt0 + 4;
-    f32x16 acc0, acc1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      acc0[r] = 0.f;
-      acc1[r] = 0.f;
-    }
-    mm_pair_h<SG>(arow, steps, Wp + ((size_t)nt0 * steps * 64 + lane) * 2, Wp + ((size_t)nt1 * steps * 64 + lane) * 2, acc0, acc1);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
-      epi(0, r, row, nt0 * 32 + col, acc0[r]);
-      epi(1, r, row, nt1 * 32 + col, acc1[r]);
-    }
-  }
-}
-
 // F.normalize over 256 columns of `rows` rows starting at buf (row stride ld); rows >= nvalid are zeroed.
 __device__ __forceinline__ void normalize_rows(float* buf, int ld, int nvalid, int wave, int lane) {
   for (int i = wave; i < kSP; i += 4) {
@@ -163,29 +108,6 @@ __device__ __forceinline__ void normalize_rows(float* buf, int ld, int nvalid, i
     } else {
       v = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    *p = v;
-  }
-}
-
-// torch.nn.LayerNorm(256, eps=1e-5) in place over the 32 rows of x
-__device__ __forceinline__ void layer_norm_rows(float* x, const float* __restrict__ w, const float* __restrict__ b,
-                                                int wave, int lane) {
-  const float4 wv = reinterpret_cast<const float4*>(w)[lane];
-  const float4 bv = reinterpret_cast<const float4*>(b)[lane];
-  for (int i = wave; i < kSP; i += 4) {
-    float4* p = reinterpret_cast<float4*>(x + i * kLdX) + lane;
-    float4 v = *p;
-    const float mean = wave_sum(v.x + v.y + v.z + v.w) * (1.f / kD);
-    v.x -= mean;
-    v.y -= mean;
-    v.z -= mean;
-    v.w -= mean;
-    const float var = wave_sum(v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w) * (1.f / kD);
-    const float inv = 1.f / sqrtf(var + 1e-5f);
-    v.x = v.x * inv * wv.x + bv.x;
-    v.y = v.y * inv * wv.y + bv.y;
-    v.z = v.z * inv * wv.z + bv.z;
-    v.w = v.w * inv * wv.w + bv.w;
     *p = v;
   }
 }
@@ -219,414 +141,10 @@ __device__ __forceinline__ void small_mlp(const SmallMlp& m, const float* __rest
   normalize_rows(dst, kLdX, nobj, wave, lane);
 }
 
-// LDS: x [32][260] + buf [32][260] = 66.6 KB per cell, one cell per workgroup, so TWO workgroups (cells) are in flight per CU:
-// while one sits in a barrier, a LayerNorm or a softmax, the other keeps the MFMA pipe busy.
-// (Measured and rejected in round 2: TWO cells per workgroup sharing every weight fragment in registers — 133 KB, one
-// workgroup per CU, bit-identical output — 5.35 ms against 3.70 ms for 11,259 cells: what it saves on the weight stream it loses
-// twice over by leaving each SIMD a single wave to hide the L2 latency of that stream.)
-// What makes a cell fit 66.6 KB:
-//  * the concatenated features never exist: every 256-wide slot is produced in `buf` and immediately contracted with its
-//    256-column slice of the merge weight into register accumulators;
-//  * q, k, v never touch LDS: head h = wave h computes q_h^T and k_h^T TRANSPOSED (A = packed weights, B = the x rows) and
-//    v_h straight (A = x rows, B = packed weights); in those MFMA output layouts k_h^T / q_h^T registers ARE the A / B
-//    operands of S^T = K Q^T and the v_h registers ARE the B operand of P V, so the whole head runs from registers;
-//  * the feed-forward hidden layer goes through `buf` in two halves of 256 units (chosen as the units that one half of the
-//    half-split weight packing covers), the second Linear accumulating over both halves in registers.
-template <int H, int NC = 1>  // H = 1: split-f16 MFMAs for the big contractions (see the file header); 2: plain f16 (one product,
-                            // the high halves of the same packing); 0: everything on the f32 MFMA
-__global__ __launch_bounds__(256, NC == 1 ? 2 : 1) void encode_cells_kernel(EncParams P, t2l_packed_cells in,
-                                                                           float* __restrict__ out) {
-  static_assert(NC == 1, "one cell per workgroup (the two-cell form was measured and rejected, see above)");
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* x[NC];    // [32][260] token buffer; scratch (small-MLP hidden / features2 staging) before it is live
-  float* buf[NC];  // [32][260] feature slot -> attention output -> feed-forward hidden half
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    x[c] = smem + c * 2 * kXFloats;
-    buf[c] = x[c] + kXFloats;
-  }
-  float* red = smem + NC * 2 * kXFloats;  // [8 * NC]
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int col = lane & 31, half = lane >> 5;
-  int cell[NC], obj0[NC], nobj[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    cell[c] = min((int)blockIdx.x * NC + c, in.n_cells - 1);  // an odd tail workgroup computes its last cell twice
-    obj0[c] = in.offsets[cell[c]];
-    nobj[c] = min(in.offsets[cell[c] + 1] - obj0[c], kS);  // objects beyond 28 are dropped (cell_retrieval.py:94-98)
-  }
-
-  // ------------------------------------------------------------------ per-object features, merged slot by slot
-  f32x16 keep0[NC], keep1[NC];  // merge output tiles (wave, wave + 4)
-#pragma unroll
-  for (int c = 0; c < NC; ++c)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) keep0[c][r] = keep1[c][r] = 0.f;
-  int slot = 0;
-  auto merge_slot = [&]() {  // buf holds slot `slot` (normalised rows): keep += buf @ Wmerge[:, 256*slot : 256*slot+256]^T
-    __syncthreads();
-    if (P.nfeat > 1) {
-      if constexpr (H != 0) {
-        const uint4* hp = P.merge_hp + (size_t)slot * (kD * kD / 4);
-        const uint4* w0 = hp + ((size_t)wave * (kD / 16) * 64 + lane) * 2;
-        const uint4* w1 = hp + ((size_t)(wave + 4) * (kD / 16) * 64 + lane) * 2;
-        mm_pair_h(buf[0] + col * kLdX + half * 128, kD / 16, w0, w1, keep0[0], keep1[0]);
-      } else {
-        const float4* wp = P.merge_wp + (size_t)slot * (kD * kD / 4);
-        mm_pair(buf[0] + col * kLdX + half * 128, kD / 8, wp + (size_t)wave * (kD / 8) * 64 + lane,
-                wp + (size_t)(wave + 4) * (kD / 8) * 64 + lane, keep0[0], keep1[0]);
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < NC; ++c)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
-          keep0[c][r] = buf[c][row * kLdX + wave * 32 + col];
-          keep1[c][r] = buf[c][row * kLdX + (wave + 4) * 32 + col];
-        }
-    }
-    ++slot;
-    __syncthreads();  // every wave is done reading buf (and the x-region scratch) before the next slot rewrites them
-  };
-  if (P.use_class) {
-    if (P.class_embed) {  // object_encoder.py:103-110 (table rows pre-normalised on the host)
-#pragma unroll
-      for (int c = 0; c < NC; ++c)
-        for (int o = 0; o < kSP; ++o) {
-          float v = 0.f;
-          if (o < nobj[c]) {
-            const int ci = min(max(in.class_idx[obj0[c] + o], 0), P.n_class - 1);
-            v = P.class_tab[ci * kD + tid];
-          }
-          buf[c][o * kLdX + tid] = v;
-        }
-    } else {  // object_encoder.py:86-99,112: features2 -> mlp_pointnet -> normalize
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        float* stage = x[c];  // park features2 in the (not yet live) token buffer
-        for (int o = wave; o < kSP; o += 4) {
-          float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (o < nobj[c]) v = reinterpret_cast<const float4*>(in.pn_feat + (size_t)(obj0[c] + o) * kD)[lane];
-          reinterpret_cast<float4*>(stage + o * kLdX)[lane] = v;
-        }
-      }
-      __syncthreads();
-      const float* pb = P.pn_b;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        float* dst = buf[c];
-        auto pn_epi = [&](int, int, int row, int cc, float v) { dst[row * kLdX + cc] = fmaxf(v + pb[cc], 0.f); };
-        // (features2 is an input: its magnitude is not bounded by the weights, so this GEMM stays f32)
-        gemm32(x[c], kLdX, kD, P.pn_wp, kD, wave, lane, pn_epi);
-      }
-      __syncthreads();
-#pragma unroll
-      for (int c = 0; c < NC; ++c) normalize_rows(buf[c], kLdX, nobj[c], wave, lane);
-    }
-    merge_slot();
-  }
-  if (P.use_color) {
-    if (P.color_embed) {  // object_encoder.py:116-120
-#pragma unroll
-      for (int c = 0; c < NC; ++c)
-        for (int o = 0; o < kSP; ++o) {
-          float v = 0.f;
-          if (o < nobj[c]) {
-            const int ci = min(max(in.color_idx[obj0[c] + o], 0), P.n_color - 1);
-            v = P.color_tab[ci * kD + tid];
-          }
-          buf[c][o * kLdX + tid] = v;
-        }
-    } else {  // object_encoder.py:121-128
-#pragma unroll
-      for (int c = 0; c < NC; ++c)
-        small_mlp<3>(P.color, in.rgb + (size_t)obj0[c] * 3, false, nobj[c], x[c], buf[c], tid, wave, lane);
-    }
-    merge_slot();
-  }
-  if (P.use_pos) {  // object_encoder.py:130-136
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-      small_mlp<3>(P.pos, in.center + (size_t)obj0[c] * 3, false, nobj[c], x[c], buf[c], tid, wave, lane);
-    merge_slot();
-  }
-  if (P.use_num) {  // object_encoder.py:138-145
-#pragma unroll
-    for (int c = 0; c < NC; ++c) small_mlp<1>(P.num, in.n_pts + obj0[c], true, nobj[c], x[c], buf[c], tid, wave, lane);
-    merge_slot();
-  }
-  // merge epilogue (object_encoder.py:148-149: Linear+BN folded, ReLU) + normalize (cell_retrieval.py:92)
-  {
-    const float* mb = P.merge_b;
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
-        const int c0 = wave * 32 + col, c1 = (wave + 4) * 32 + col;
-        x[c][row * kLdX + c0] = P.nfeat > 1 ? fmaxf(keep0[c][r] + mb[c0], 0.f) : keep0[c][r];
-        x[c][row * kLdX + c1] = P.nfeat > 1 ? fmaxf(keep1[c][r] + mb[c1], 0.f) : keep1[c][r];
-      }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int c = 0; c < NC; ++c) normalize_rows(x[c], kLdX, nobj[c], wave, lane);  // rows >= nobj: the zero pad slots (cell_retrieval.py:85)
-  __syncthreads();
-
-  // ------------------------------------------------------------------ set transformer (cell_retrieval.py:101-103)
-  for (int l = 0; l < P.num_layers; ++l) {
-    const LayerW& W = P.layer[l];
-    {  // head h = wave, registers only
-      const int h = wave;
-      constexpr int QN = kD / 8;  // 32 packed k-steps
-      const float* ib = W.in_b;
-      // ---- pass 1: q_h^T and k_h^T of every cell (the packed weights are the A operand, the token rows the B operand); one
-      // load of a weight fragment feeds every cell. v_h follows in its own pass: 12 live accumulators would not fit.
-      f32x16 st[NC];  // becomes S^T, then the unnormalised probabilities
-      float inv[NC];
-      {
-        f32x16 qT0[NC], qT1[NC], kT0[NC], kT1[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) qT0[c][r] = qT1[c][r] = kT0[c][r] = kT1[c][r] = 0.f;
-        if constexpr (H != 0) {
-          constexpr int HS = kD / 16;
-          const uint4* hq0 = W.in_hp + ((size_t)(2 * h) * HS * 64 + lane) * 2;
-          const uint4* hq1 = W.in_hp + ((size_t)(2 * h + 1) * HS * 64 + lane) * 2;
-          const uint4* hk0 = W.in_hp + ((size_t)(8 + 2 * h) * HS * 64 + lane) * 2;
-          const uint4* hk1 = W.in_hp + ((size_t)(9 + 2 * h) * HS * 64 + lane) * 2;
-#pragma unroll 2
-          for (int s = 0; s < HS; ++s) {
-            HFrag xf[NC];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) xf[c] = split_h<H == 2>(x[c] + col * kLdX + half * 128 + 8 * s);
-            {
-              const HFrag f = load_h1<H == 2>(hq0 + T2L_WSTEP(s) * 128);
-#pragma unroll
-              for (int c = 0; c < NC; ++c) mfma_h3<H == 2>(qT0[c], f, xf[c]);
-            }
-            {
-              const HFrag f = load_h1<H == 2>(hq1 + T2L_WSTEP(s) * 128);
-#pragma unroll
-              for (int c = 0; c < NC; ++c) mfma_h3<H == 2>(qT1[c], f, xf[c]);
-            }
-            {
-              const HFrag f = load_h1<H == 2>(hk0 + T2L_WSTEP(s) * 128);
-#pragma unroll
-              for (int c = 0; c < NC; ++c) mfma_h3<H == 2>(kT0[c], f, xf[c]);
-            }
-            {
-              const HFrag f = load_h1<H == 2>(hk1 + T2L_WSTEP(s) * 128);
-#pragma unroll
-              for (int c = 0; c < NC; ++c) mfma_h3<H == 2>(kT1[c], f, xf[c]);
-            }
-          }
-        } else {
-          const float* xr = x[0] + col * kLdX + half * 128;
-          const float4* wq0 = W.in_wp + (size_t)(2 * h) * QN * 64 + lane;
-          const float4* wq1 = W.in_wp + (size_t)(2 * h + 1) * QN * 64 + lane;
-          const float4* wk0 = W.in_wp + (size_t)(8 + 2 * h) * QN * 64 + lane;
-          const float4* wk1 = W.in_wp + (size_t)(9 + 2 * h) * QN * 64 + lane;
-#pragma unroll 2
-          for (int q = 0; q < QN; ++q) {
-            const float4 xv = *reinterpret_cast<const float4*>(xr + 4 * q);
-            const float4 a0 = wq0[q * 64], a1 = wq1[q * 64], c0 = wk0[q * 64], c1 = wk1[q * 64];
-#define T2L_QK(C)                                                                   \
-  qT0[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.C, xv.C, qT0[0], 0, 0, 0);       \
-  qT1[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.C, xv.C, qT1[0], 0, 0, 0);       \
-  kT0[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(c0.C, xv.C, kT0[0], 0, 0, 0);       \
-  kT1[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(c1.C, xv.C, kT1[0], 0, 0, 0);
-            T2L_QK(x) T2L_QK(y) T2L_QK(z) T2L_QK(w)
-#undef T2L_QK
-          }
-        }
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-          // in_proj bias: q^T / k^T rows are features (register index)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int f = (r & 3) + 8 * (r >> 2) + 4 * half;
-            qT0[c][r] += ib[h * 64 + f];
-            qT1[c][r] += ib[h * 64 + 32 + f];
-            kT0[c][r] += ib[kD + h * 64 + f];
-            kT1[c][r] += ib[kD + h * 64 + 32 + f];
-          }
-          // S^T[j][i] = k_j . q_i: k_h^T (token j = lane col, feature pair (f, f+4) = the two lane halves) is the A operand,
-          // q_h^T the B operand, one MFMA per register
-#pragma unroll
-          for (int r = 0; r < 16; ++r) st[c][r] = 0.f;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) st[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(kT0[c][r], qT0[c][r], st[c], 0, 0, 0);
-#pragma unroll
-          for (int r = 0; r < 16; ++r) st[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(kT1[c][r], qT1[c][r], st[c], 0, 0, 0);
-          // lane: query i = col, keys j = (r&3) + 8*(r>>2) + 4*half ; keys >= 28 are the dead rows
-          float m = -__builtin_inff();
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int j = (r & 3) + 8 * (r >> 2) + 4 * half;
-            st[c][r] = (j < kS) ? st[c][r] * 0.125f : -__builtin_inff();  // 1/sqrt(head_dim = 64)
-            m = fmaxf(m, st[c][r]);
-          }
-          m = fmaxf(m, __shfl_xor(m, 32));
-          float sum = 0.f;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            st[c][r] = __expf(st[c][r] - m);
-            sum += st[c][r];
-          }
-          sum += __shfl_xor(sum, 32);
-          inv[c] = 1.f / sum;
-        }
-      }
-      // ---- pass 2: v_h straight (A = token rows, B = packed weights), then o = P V from registers
-      {
-        f32x16 v0[NC], v1[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) v0[c][r] = v1[c][r] = 0.f;
-        if constexpr (H != 0) {
-          constexpr int HS = kD / 16;
-          const uint4* hv0 = W.in_hp + ((size_t)(16 + 2 * h) * HS * 64 + lane) * 2;
-          const uint4* hv1 = W.in_hp + ((size_t)(17 + 2 * h) * HS * 64 + lane) * 2;
-#pragma unroll 4
-          for (int s = 0; s < HS; ++s) {
-            const HFrag f0 = load_h1<H == 2>(hv0 + T2L_WSTEP(s) * 128), f1 = load_h1<H == 2>(hv1 + T2L_WSTEP(s) * 128);
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-              const HFrag xf = split_h<H == 2>(x[c] + col * kLdX + half * 128 + 8 * s);
-              mfma_h3<H == 2>(v0[c], xf, f0);
-              mfma_h3<H == 2>(v1[c], xf, f1);
-            }
-          }
-        } else {
-          const float* xr = x[0] + col * kLdX + half * 128;
-          const float4* wv0 = W.in_wp + (size_t)(16 + 2 * h) * QN * 64 + lane;
-          const float4* wv1 = W.in_wp + (size_t)(17 + 2 * h) * QN * 64 + lane;
-          mm_pair(xr, QN, wv0, wv1, v0[0], v1[0]);
-        }
-        const float bv0 = ib[2 * kD + h * 64 + col], bv1 = ib[2 * kD + h * 64 + 32 + col];  // v columns are features (lane)
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-          // o[i][n] = sum_j P[i][j] v[j][n]: P (lane = query i, register = key j) is the A operand, v_h registers (lane =
-          // column n, register = key j) the B operand
-          f32x16 o0, o1;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) o0[r] = o1[r] = 0.f;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const float p = st[c][r] * inv[c];
-            o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(p, v0[c][r] + bv0, o0, 0, 0, 0);
-            o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(p, v1[c][r] + bv1, o1, 0, 0, 0);
-          }
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int i = (r & 3) + 8 * (r >> 2) + 4 * half;
-            buf[c][i * kLdX + h * 64 + col] = o0[r];
-            buf[c][i * kLdX + h * 64 + 32 + col] = o1[r];
-          }
-        }
-      }
-    }
-    __syncthreads();
-    {  // x = LN1(x + o @ out_proj^T + b)
-      const float* b = W.out_b;
-      {
-        float* xd = x[0];
-        auto out_epi = [&](int, int, int row, int c, float v) { xd[row * kLdX + c] += v + b[c]; };
-        if constexpr (H != 0) gemm32_h<H == 2>(buf[0], kLdX, kD, W.out_hp, kD, wave, lane, out_epi);
-        else gemm32(buf[0], kLdX, kD, W.out_wp, kD, wave, lane, out_epi);
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < NC; ++c) layer_norm_rows(x[c], W.ln1_w, W.ln1_b, wave, lane);
-    __syncthreads();
-    {  // x = LN2(x + relu(x W1^T + b1) W2^T + b2), hidden units in two halves through buf
-      f32x16 acc0[NC], acc1[NC];  // output tiles (wave, wave + 4)
-#pragma unroll
-      for (int c = 0; c < NC; ++c)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc0[c][r] = acc1[c][r] = 0.f;
-      const float* b1 = W.ff1_b;
-      for (int hf = 0; hf < 2; ++hf) {
-        // half hf = hidden units [128 hf, 128 hf + 128) and [256 + 128 hf, 256 + 128 hf + 128): exactly what k-steps
-        // [32 hf, 32 hf + 32) of the half-split packing of W2 (K = 512) cover
-        const int tA = 4 * hf + wave, tB = 8 + 4 * hf + wave;
-        f32x16 h0[NC], h1[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) h0[c][r] = h1[c][r] = 0.f;
-        if constexpr (H != 0) {
-          const uint4* w0 = W.ff1_hp + ((size_t)tA * (kD / 16) * 64 + lane) * 2;
-          const uint4* w1 = W.ff1_hp + ((size_t)tB * (kD / 16) * 64 + lane) * 2;
-          mm_pair_h<H == 2>(x[0] + col * kLdX + half * 128, kD / 16, w0, w1, h0[0], h1[0]);
-        } else {
-          mm_pair(x[0] + col * kLdX + half * 128, kD / 8, W.ff1_wp + (size_t)tA * (kD / 8) * 64 + lane,
-                  W.ff1_wp + (size_t)tB * (kD / 8) * 64 + lane, h0[0], h1[0]);
-        }
-        if (hf) __syncthreads();  // every wave has consumed the first half from buf
-        const float bA = b1[tA * 32 + col], bB = b1[tB * 32 + col];
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
-            buf[c][row * kLdX + 32 * wave + col] = fmaxf(h0[c][r] + bA, 0.f);
-            buf[c][row * kLdX + 128 + 32 * wave + col] = fmaxf(h1[c][r] + bB, 0.f);
-          }
-        __syncthreads();
-        if constexpr (H != 0) {  // K = 512: 32 steps per tile, half hf = steps [16 hf, 16 hf + 16)
-          const uint4* w0 = W.ff2_hp + (((size_t)wave * (2 * kD / 16) + 16 * hf) * 64 + lane) * 2;
-          const uint4* w1 = W.ff2_hp + (((size_t)(wave + 4) * (2 * kD / 16) + 16 * hf) * 64 + lane) * 2;
-          mm_pair_h<H == 2>(buf[0] + col * kLdX + half * 128, kD / 16, w0, w1, acc0[0], acc1[0]);
-        } else {
-          mm_pair(buf[0] + col * kLdX + half * 128, kD / 8, W.ff2_wp + ((size_t)wave * (2 * kD / 8) + 32 * hf) * 64 + lane,
-                  W.ff2_wp + ((size_t)(wave + 4) * (2 * kD / 8) + 32 * hf) * 64 + lane, acc0[0], acc1[0]);
-        }
-      }
-      const float* b2 = W.ff2_b;
-#pragma unroll
-      for (int c = 0; c < NC; ++c)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
-          const int c0 = wave * 32 + col, c1 = (wave + 4) * 32 + col;
-          x[c][row * kLdX + c0] += acc0[c][r] + b2[c0];
-          x[c][row * kLdX + c1] += acc1[c][r] + b2[c1];
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < NC; ++c) layer_norm_rows(x[c], W.ln2_w, W.ln2_b, wave, lane);
-    __syncthreads();
-  }
-
-  // ------------------------------------------------------------------ max over ALL 28 slots, pads included (cell_retrieval.py:107-108)
-  float mx[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    mx[c] = x[c][tid];
-    for (int i = 1; i < kS; ++i) mx[c] = fmaxf(mx[c], x[c][i * kLdX + tid]);
-    const float ss = wave_sum(mx[c] * mx[c]);
-    if (lane == 0) red[c * 4 + wave] = ss;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const float nrm = sqrtf(red[c * 4 + 0] + red[c * 4 + 1] + red[c * 4 + 2] + red[c * 4 + 3]);
-    if ((int)blockIdx.x * NC + c < in.n_cells) out[(size_t)cell[c] * kD + tid] = mx[c] / fmaxf(nrm, 1e-12f);
-  }
-}
-
 // ------------------------------------------------------------------------------------------------
 // t2l_text_inter as ONE launch (models/language_encoder.py:137-147): x = sent.view(B, S, 256); x += TransformerEncoderLayer(256, 4 heads,
 // ff 1024, post-norm, ReLU)(x) over the S sentences of a description; max over the sentences. The layer is the cell encoder's
-// (above) with three differences: a 32-row tile holds floor(32 / S) whole DESCRIPTIONS and a query attends to the keys of its own
+// (encode_shaped.hip) with three differences: a 32-row tile holds floor(32 / S) whole DESCRIPTIONS and a query attends to the keys of its own
 // description only (block-diagonal mask; rows past the tile's last description are zero rows that form groups of their own: every
 // softmax has its own row as a key, nothing is NaN); the feed-forward hidden layer is 1,024 wide = four passes through `buf`
 // (pass c = hidden units [128c, 128c+128) and [512+128c, 512+128c+128): what k-steps [16c, 16c+16) of W2's half-split packing at
@@ -644,7 +162,7 @@ __global__ __launch_bounds__(256, NC == 1 ? 2 : 1) void encode_cells_kernel(EncP
 //    output features and multiplies it into both token tiles (products computed transposed: A = weight fragment, B = token fragment);
 //  * no operand is split in a GEMM loop: a token fragment is two ds_read_b128; the splitting happens once per produced element in the
 //    epilogues, which hold 4 consecutive features per register quad (transposed C layout) and store 8-byte plane pieces;
-//  * the attention runs as in the first form, one wave per (tile, head), q/k/v projected per tile (their fragments are not shared), with
+//  * the attention runs as in the one-cell encoder, one wave per (tile, head), q/k/v projected per tile (their fragments are not shared), with
 //    O^T = V^T P^T so that its output has the same store-friendly layout.
 // 135 KB of LDS: one workgroup (two waves per SIMD) per CU. The residual is rebuilt from hi + lo (22 significand bits).
 #ifndef T2L_RING_DEPTH
@@ -1056,12 +574,12 @@ __global__ __launch_bounds__(512, 1) void text_inter_fused2_kernel(InterFusedW W
 // encode_cells, second form (option encoder_two_cells, split-f16 / plain-f16 arithmetic, at least two feature slots): the recipe that
 // t2l_text_inter's second form proved — TWO cells per workgroup of EIGHT waves, activations as split-f16 planes in LDS,
 // the weight fragments of the feature merge, out_proj and both feed-forward Linears loaded once for both cells and requested ahead of
-// the MFMAs, nothing split inside a GEMM loop. The feature stage keeps the first form's code: waves 4t .. 4t+3 build cell t's feature
+// the MFMAs, nothing split inside a GEMM loop. The feature stage is the one-cell kernel's (small_mlp, gemm32, normalize_rows above): waves 4t .. 4t+3 build cell t's feature
 // slot as a normalised f32 tile (in the cell's X-plane region, not live before the merge epilogue), convert it to the cell's B planes,
 // and all eight waves contract both cells' slot with its slice of the merge weight.
 template <int H>
 __global__ __launch_bounds__(512, 1) void encode_cells2_kernel(EncParams P, t2l_packed_cells in, float* __restrict__ out) {
-  static_assert(H == 1 || H == 2, "split-f16 or plain f16 (the all-f32 encoder keeps the first form)");
+  static_assert(H == 1 || H == 2, "split-f16 or plain f16 (the all-f32 encoder is the one-cell kernel)");
   constexpr bool SG = H == 2;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   _Float16* base = reinterpret_cast<_Float16*>(smem);
@@ -1503,43 +1021,24 @@ int encode_impl(t2l_ctx* ctx, const t2l_packed_cells* in, float* out, hipStream_
   if ((P.use_class && P.class_embed && !in->class_idx) || (P.use_color && P.color_embed && !in->color_idx) ||
       (P.use_color && !P.color_embed && !in->rgb) || (P.use_pos && !in->center) || (P.use_num && !in->n_pts))
     return fail(ctx, T2L_EINVAL, "t2l_encode_cells: a per-object input required by the loaded config is NULL");
-  if (!ctx->enc->published()) return encode_shaped_impl(ctx, in, out, s);  // every other compiled shape: encode_shaped.hip
-  const size_t lds = (size_t)(2 * kXFloats + 8) * sizeof(float);  // 66.6 KB: two cells per CU
-  static PerDeviceOnce attr_done;
-  if (attr_done.need(ctx->device)) {
-    T2L_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&encode_cells_kernel<1>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    T2L_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&encode_cells_kernel<2>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    T2L_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&encode_cells_kernel<0>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_done.mark(ctx->device);
+  // the published shape with split-f16 / plain-f16 arithmetic and at least two feature slots: two cells per eight-wave workgroup on
+  // planes (option encoder_two_cells, default on); everything else: the one-cell kernel of encode_shaped.hip
+  if (!(ctx->enc->published() && P.split_ok && !ctx->encoder_f32 && ctx->encoder_two_cells && P.nfeat > 1))
+    return encode_shaped_impl(ctx, in, out, s);
+  const size_t lds2 = (size_t)8 * kPlane * sizeof(_Float16) + (size_t)(2 * kSP * kLdH + 8) * sizeof(float);
+  static PerDeviceOnce attr2;
+  if (attr2.need(ctx->device)) {
+    T2L_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&encode_cells2_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+    T2L_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&encode_cells2_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+    attr2.mark(ctx->device);
   }
   event_begin(ctx, "encode_cells", s);
-  if (P.split_ok && !ctx->encoder_f32 && ctx->encoder_two_cells && P.nfeat > 1) {  // second form: two cells per eight-wave workgroup on planes
-    const size_t lds2 = (size_t)8 * kPlane * sizeof(_Float16) + (size_t)(2 * kSP * kLdH + 8) * sizeof(float);
-    static PerDeviceOnce attr2;
-    if (attr2.need(ctx->device)) {
-      T2L_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&encode_cells2_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-      T2L_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&encode_cells2_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-      attr2.mark(ctx->device);
-    }
-    if (ctx->encoder_f16)
-      hipLaunchKernelGGL(encode_cells2_kernel<2>, dim3((in->n_cells + 1) / 2), dim3(512), lds2, s, P, *in, out);
-    else
-      hipLaunchKernelGGL(encode_cells2_kernel<1>, dim3((in->n_cells + 1) / 2), dim3(512), lds2, s, P, *in, out);
-    event_end(ctx, "encode_cells", s);
-    T2L_HIP(ctx, hipGetLastError());
-    return T2L_OK;
-  }
   // encoder_f16 (option, off by default): ONE f16 product per operand pair instead of the three of the split form — embeddings
   // within ~1e-4 of the reference's (the north star asks for 1e-3) instead of 2e-7, 28 % less time
-  if (P.split_ok && !ctx->encoder_f32 && ctx->encoder_f16)
-    hipLaunchKernelGGL(encode_cells_kernel<2>, dim3(in->n_cells), dim3(256), lds, s, P, *in, out);
-  else if (P.split_ok && !ctx->encoder_f32)
-    hipLaunchKernelGGL(encode_cells_kernel<1>, dim3(in->n_cells), dim3(256), lds, s, P, *in, out);
+  if (ctx->encoder_f16)
+    hipLaunchKernelGGL(encode_cells2_kernel<2>, dim3((in->n_cells + 1) / 2), dim3(512), lds2, s, P, *in, out);
   else
-    hipLaunchKernelGGL(encode_cells_kernel<0>, dim3(in->n_cells), dim3(256), lds, s, P, *in, out);
+    hipLaunchKernelGGL(encode_cells2_kernel<1>, dim3((in->n_cells + 1) / 2), dim3(512), lds2, s, P, *in, out);
   event_end(ctx, "encode_cells", s);
   T2L_HIP(ctx, hipGetLastError());
   return T2L_OK;

@@ -1,17 +1,22 @@
-// The fused per-cell encoder of encode.hip (ObjectEncoder.forward, models/object_encoder.py:66-153, +
-// CellRetrievalNetwork.encode_objects, models/cell_retrieval.py:65-110, eval mode) for the shapes the reference builds from
-// `args` other than the published one (models/cell_retrieval.py:22-49, training/args.py:47,60-62):
+// The one-cell cell encoder: ObjectEncoder.forward (models/object_encoder.py:66-153) + CellRetrievalNetwork.encode_objects
+// (models/cell_retrieval.py:65-110), eval mode, as ONE kernel, one workgroup of four waves per cell, for every shape the reference
+// builds from `args` (models/cell_retrieval.py:22-49, training/args.py:47,60-62) that is compiled:
 //
 //   coarse_embed_dim D in {128, 256};  head_dim HD in {32, 64} (object_inter_module_num_heads = D / HD);
 //   object_size 1..32 (a run-time value);  1..4 layers;  dim_feedforward = 2 D.
 //
-// The published shape (256, 4 heads, 28 slots) never comes here: encode_impl keeps it on the kernels of encode.hip.
+// The published shape (256, 4 heads, 28 slots) is the <256, 64> instance with object_size = 28. encode_impl (encode.hip) puts the
+// two-cell kernel in front of it when that one applies (split-f16 or plain-f16 arithmetic, two or more feature slots, option
+// encoder_two_cells); its f32 arithmetic, single-feature models and encoder_two_cells = 0 run here.
 //
-// One workgroup of four waves per cell, every intermediate in LDS as f32 rows of D + 4 floats, the arithmetic of
-// encode_cells_kernel: the big contractions (feature merge, q/k/v, out_proj, both feed-forward products) as split-f16 on
-// v_mfma_f32_32x32x16_f16 (hi*hi + hi*lo + lo*hi, f32 accumulation; mfma_h3.h), or everything on the f32 MFMA when the weights
-// do not bound the activations below the f16 range (EncParams::split_ok) or option encoder_f32 asks for it. The attention core
-// and the small MLPs are f32 MFMA in both.
+// Every intermediate lives in LDS as f32 rows of D + 4 floats. Arithmetic, template value H:
+//   1  the big contractions (feature merge, q/k/v, out_proj, both feed-forward products) as split-f16 on
+//      v_mfma_f32_32x32x16_f16 (hi*hi + hi*lo + lo*hi, f32 accumulation; mfma_h3.h);
+//   2  plain f16, one product per operand pair on the high halves of the same fragments (option encoder_f16; compiled for
+//      <256, 64> and offered at the published shape only). The feature merge keeps its three products;
+//   0  everything on the f32 MFMA: when the weights do not bound the activations below the f16 range (EncParams::split_ok) or
+//      option encoder_f32 asks for it.
+// The attention core and the small MLPs are f32 MFMA in all three.
 //
 // Tile ownership. A D-wide output is D / 32 column tiles; wave w owns tiles w, w + 4, ... (one at D = 128, two at 256, sharing
 // the A fragments). A head is HD / 32 tiles of q, k and v; wave w runs heads w, w + 4, ... from registers only: q_h^T and k_h^T
@@ -22,11 +27,15 @@
 // The feed-forward hidden layer (2 D wide) goes through `buf` in two halves of D units: half hf = units [hf D/2, hf D/2 + D/2)
 // and [D + hf D/2, ...), what k-steps [hf D/16, (hf + 1) D/16) of the half-split packing of linear2 (K = 2 D) cover.
 //
-// LDS: x [32][D + 4] + buf [32][D + 4] + 8 floats = 33.8 KB at D = 128, 66.6 KB at D = 256 (two workgroups per CU, as the
-// published one-cell form). Row stride D + 4: a lane (col, half) reads 16 bytes at col (D + 4) + const; over the 16 lanes of a
-// ds_read_b128 group the word address is 4 col + const mod 64 for D a multiple of 64 (132 = 2*64 + 4, 260 = 4*64 + 4), sixteen
-// disjoint runs of four banks: conflict-free at both widths. features2 (256 wide at every D) is staged over x AND buf
-// (32 x 260 floats <= 2 x 32 x 132), so mlp_pointnet keeps its output in registers until every wave is done reading the stage.
+// LDS: x [32][D + 4] + buf [32][D + 4] + 8 floats = 33.8 KB at D = 128, 66.6 KB at D = 256: two workgroups per CU at 256, so
+// while one sits in a barrier, a LayerNorm or a softmax, the other keeps the MFMA pipe busy. The compiler does not see the
+// dynamic LDS size: at D = 256 the kernel states its two waves per SIMD itself (amdgpu_waves_per_eu), or the register
+// allocator squeezes the split-f16 instance into the 168 VGPRs of a third wave that never comes and serialises every weight
+// fragment load with its use; there mm_tiles asks for a step's fragments one step ahead (profiles/shapes_encoder.md).
+// Row stride D + 4: a lane (col, half) reads 16 bytes at col (D + 4) + const; over the 16 lanes of a ds_read_b128 group the
+// word address is 4 col + const mod 64 for D a multiple of 64 (132 = 2*64 + 4, 260 = 4*64 + 4), sixteen disjoint runs of four
+// banks: conflict-free at both widths. features2 (256 wide at every D) is staged over x AND buf (32 x 260 floats <=
+// 2 x 32 x 132), so mlp_pointnet keeps its output in registers until every wave is done reading the stage.
 //
 // object_size: rows [nobj, object_size) are the reference's zero pad slots: attended to, attending, and in the max-pool (there
 // is no padding mask). Rows [object_size, 32) are dead: masked out of the softmax keys and the max-pool. object_size = 32 has
@@ -51,12 +60,14 @@ constexpr int kLdHid = 64 + 4;     // hidden layer of the small MLPs
 
 // acc[t] += X W_t^T (WA = false: this lane's LDS row half is the A operand) or W_t X^T (WA = true: the packed weight tile is the
 // A operand, the product comes out transposed), over `khalf` k-values per lane half starting at per-half offset `koff` of a
-// matrix packed for K = ktot. F32: f32 packing (pack) on v_mfma_f32_32x32x2_f32, else split-f16 fragments (pack_h).
-template <bool F32, bool WA, int NT>
+// matrix packed for K = ktot. H = 0: f32 packing (pack) on v_mfma_f32_32x32x2_f32; 1: split-f16 fragments (pack_h), three
+// products; 2: plain f16, the high halves of the same fragments, one product. AHEAD (the f16 forms at D = 256, where a SIMD
+// holds two waves): the NT weight fragments of the next k-step are in flight behind the MFMAs of the current one.
+template <int H, bool WA, int NT, bool AHEAD = false>
 __device__ __forceinline__ void mm_tiles(const float* __restrict__ arow, int khalf, const float4* __restrict__ wp,
                                          const uint4* __restrict__ hp, int ktot, int koff, const int (&tile)[NT],
                                          f32x16 (&acc)[NT], int lane) {
-  if constexpr (F32) {
+  if constexpr (H == 0) {
     const int qn = ktot >> 3, q0 = koff >> 2, nq = khalf >> 2;
     const float4* w[NT];
 #pragma unroll
@@ -79,14 +90,40 @@ __device__ __forceinline__ void mm_tiles(const float* __restrict__ arow, int kha
     const uint4* w[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) w[t] = hp + (((size_t)tile[t] * steps + s0) * 64 + lane) * 2;
-#pragma unroll T2L_ENC_UNROLL
-    for (int s = 0; s < ns; ++s) {
-      const HFrag a = split_h(arow + 8 * s);
+    if constexpr (AHEAD) {
+      // the four-tile q/k pass unrolls half as far: at most eight fragments of 8 VGPRs named per body
+      constexpr int kUnroll = NT > 2 ? (T2L_ENC_UNROLL > 1 ? T2L_ENC_UNROLL / 2 : 1) : T2L_ENC_UNROLL;
+      HFrag b[NT];
 #pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        const HFrag b = load_h1(w[t] + s * 128);
-        if constexpr (WA) mfma_h3(acc[t], b, a);
-        else mfma_h3(acc[t], a, b);
+      for (int t = 0; t < NT; ++t) b[t] = load_h1<H == 2>(w[t]);
+#pragma unroll kUnroll
+      for (int s = 0; s < ns; ++s) {
+        const HFrag a = split_h<H == 2>(arow + 8 * s);
+        // the next step's fragments are requested before this step's MFMAs (the last step asks for its own again); the
+        // scheduling barrier keeps the compiler from sinking the loads to their uses, where each would wait vmcnt(0)
+        const int sn = min(s + 1, ns - 1);
+        HFrag nb[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) nb[t] = load_h1<H == 2>(w[t] + sn * 128);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          if constexpr (WA) mfma_h3<H == 2>(acc[t], b[t], a);
+          else mfma_h3<H == 2>(acc[t], a, b[t]);
+        }
+#pragma unroll
+        for (int t = 0; t < NT; ++t) b[t] = nb[t];
+      }
+    } else {
+#pragma unroll T2L_ENC_UNROLL
+      for (int s = 0; s < ns; ++s) {
+        const HFrag a = split_h<H == 2>(arow + 8 * s);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          const HFrag b = load_h1<H == 2>(w[t] + s * 128);
+          if constexpr (WA) mfma_h3<H == 2>(acc[t], b, a);
+          else mfma_h3<H == 2>(acc[t], a, b);
+        }
       }
     }
   }
@@ -110,12 +147,11 @@ __device__ __forceinline__ void normalize_rows_d(float* buf, int ld, int nvalid,
   for (int i = wave; i < kSP; i += 4) {
     float* p = buf + i * ld + lane * EL;
     float v[EL];
-    float ss = 0.f;
 #pragma unroll
-    for (int e = 0; e < EL; ++e) {
-      v[e] = p[e];
-      ss += v[e] * v[e];
-    }
+    for (int e = 0; e < EL; ++e) v[e] = p[e];
+    float ss = v[0] * v[0];
+#pragma unroll
+    for (int e = 1; e < EL; ++e) ss += v[e] * v[e];
     ss = wave_sum(ss);
     const float inv = i < nvalid ? 1.f / fmaxf(sqrtf(ss), 1e-12f) : 0.f;
 #pragma unroll
@@ -137,19 +173,17 @@ __device__ __forceinline__ void layer_norm_rows_d(float* x, const float* __restr
   for (int i = wave; i < kSP; i += 4) {
     float* p = x + i * LD + lane * EL;
     float v[EL];
-    float sum = 0.f;
 #pragma unroll
-    for (int e = 0; e < EL; ++e) {
-      v[e] = p[e];
-      sum += v[e];
-    }
+    for (int e = 0; e < EL; ++e) v[e] = p[e];
+    float sum = v[0];
+#pragma unroll
+    for (int e = 1; e < EL; ++e) sum += v[e];
     const float mean = wave_sum(sum) * (1.f / D);
-    float sq = 0.f;
 #pragma unroll
-    for (int e = 0; e < EL; ++e) {
-      v[e] -= mean;
-      sq += v[e] * v[e];
-    }
+    for (int e = 0; e < EL; ++e) v[e] -= mean;
+    float sq = v[0] * v[0];
+#pragma unroll
+    for (int e = 1; e < EL; ++e) sq += v[e] * v[e];
     const float var = wave_sum(sq) * (1.f / D);
     const float inv = 1.f / sqrtf(var + 1e-5f);
 #pragma unroll
@@ -157,9 +191,9 @@ __device__ __forceinline__ void layer_norm_rows_d(float* x, const float* __restr
   }
 }
 
-template <int D, int HD, bool F32>
-__global__ __launch_bounds__(256, 2) void encode_cells_shaped_kernel(EncParams P, t2l_packed_cells in, int object_size,
-                                                                     float* __restrict__ out) {
+template <int D, int HD, int H>
+__global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, D == 256 ? 2 : 4))) void encode_cells_shaped_kernel(
+    EncParams P, t2l_packed_cells in, int object_size, float* __restrict__ out) {
   static_assert(D == 128 || D == 256, "tile ownership is written for 4 or 8 column tiles over four waves");
   static_assert(HD == 32 || HD == 64, "a head is one or two 32-column tiles");
   constexpr int LD = D + 4;       // row stride of x and buf (see the file header for the bank arithmetic)
@@ -188,8 +222,8 @@ __global__ __launch_bounds__(256, 2) void encode_cells_shaped_kernel(EncParams P
   int slot = 0;
   auto merge_slot = [&]() {  // buf holds slot `slot` (normalised rows): keep += buf @ Wmerge[:, D*slot : D*slot + D]^T
     __syncthreads();
-    if (P.nfeat > 1) {
-      mm_tiles<F32, false, NT>(buf + col * LD + half * KH, KH, P.merge_wp + (size_t)slot * (D * D / 4),
+    if (P.nfeat > 1) {  // (split-f16 also under plain f16)
+      mm_tiles<(H ? 1 : 0), false, NT, D == 256>(buf + col * LD + half * KH, KH, P.merge_wp + (size_t)slot * (D * D / 4),
                                P.merge_hp + (size_t)slot * (D * D / 4), D, 0, own, keep, lane);
     } else {
 #pragma unroll
@@ -228,7 +262,7 @@ __global__ __launch_bounds__(256, 2) void encode_cells_shaped_kernel(EncParams P
     __syncthreads();
     f32x16 acc[NT];
     zero_tiles(acc);
-    mm_tiles<true, false, NT>(hbuf + col * kLdHid + half * 32, 32, m.w2p, nullptr, 64, 0, own, acc, lane);
+    mm_tiles<0, false, NT>(hbuf + col * kLdHid + half * 32, 32, m.w2p, nullptr, 64, 0, own, acc, lane);
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       const int c = own[t] * 32 + col;
@@ -254,7 +288,7 @@ __global__ __launch_bounds__(256, 2) void encode_cells_shaped_kernel(EncParams P
       f32x16 acc[NT];
       zero_tiles(acc);
       // (features2 is an input: its magnitude is not bounded by the weights, so this product stays f32)
-      mm_tiles<true, false, NT>(stage + col * kLdStage + half * 128, 128, P.pn_wp, nullptr, 256, 0, own, acc, lane);
+      mm_tiles<0, false, NT>(stage + col * kLdStage + half * 128, 128, P.pn_wp, nullptr, 256, 0, own, acc, lane);
       __syncthreads();  // the stage overlaps buf
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
@@ -311,7 +345,7 @@ __global__ __launch_bounds__(256, 2) void encode_cells_shaped_kernel(EncParams P
           qk[TPH + t] = DT + h * TPH + t;
         }
         zero_tiles(qkT);
-        mm_tiles<F32, true, 2 * TPH>(xrow, KH, W.in_wp, W.in_hp, D, 0, qk, qkT, lane);
+        mm_tiles<H, true, 2 * TPH, D == 256>(xrow, KH, W.in_wp, W.in_hp, D, 0, qk, qkT, lane);
         // in_proj bias: q^T / k^T rows are features (register index)
 #pragma unroll
         for (int t = 0; t < TPH; ++t)
@@ -353,7 +387,7 @@ __global__ __launch_bounds__(256, 2) void encode_cells_shaped_kernel(EncParams P
 #pragma unroll
         for (int t = 0; t < TPH; ++t) vt[t] = 2 * DT + h * TPH + t;
         zero_tiles(v);
-        mm_tiles<F32, false, TPH>(xrow, KH, W.in_wp, W.in_hp, D, 0, vt, v, lane);
+        mm_tiles<H, false, TPH, D == 256>(xrow, KH, W.in_wp, W.in_hp, D, 0, vt, v, lane);
 #pragma unroll
         for (int t = 0; t < TPH; ++t) {
           const float bv = ib[2 * D + h * HD + t * 32 + col];  // v columns are features (lane)
@@ -373,7 +407,7 @@ __global__ __launch_bounds__(256, 2) void encode_cells_shaped_kernel(EncParams P
     {  // x = LN1(x + o @ out_proj^T + b)
       f32x16 acc[NT];
       zero_tiles(acc);
-      mm_tiles<F32, false, NT>(buf + col * LD + half * KH, KH, W.out_wp, W.out_hp, D, 0, own, acc, lane);
+      mm_tiles<H, false, NT, D == 256>(buf + col * LD + half * KH, KH, W.out_wp, W.out_hp, D, 0, own, acc, lane);
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         const int c = own[t] * 32 + col;
@@ -395,7 +429,7 @@ __global__ __launch_bounds__(256, 2) void encode_cells_shaped_kernel(EncParams P
 #pragma unroll
         for (int t = 0; t < NT; ++t) ht[t] = own[t] < DT / 2 ? hf * (DT / 2) + own[t] : DT + hf * (DT / 2) + own[t] - DT / 2;
         zero_tiles(hh);
-        mm_tiles<F32, false, NT>(xrow, KH, W.ff1_wp, W.ff1_hp, D, 0, ht, hh, lane);
+        mm_tiles<H, false, NT, D == 256>(xrow, KH, W.ff1_wp, W.ff1_hp, D, 0, ht, hh, lane);
         if (hf) __syncthreads();  // every wave has consumed the first half from buf
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
@@ -404,7 +438,7 @@ __global__ __launch_bounds__(256, 2) void encode_cells_shaped_kernel(EncParams P
           for (int r = 0; r < 16; ++r) buf[acc_row(r, half) * LD + own[t] * 32 + col] = fmaxf(hh[t][r] + b1, 0.f);
         }
         __syncthreads();
-        mm_tiles<F32, false, NT>(buf + col * LD + half * KH, KH, W.ff2_wp, W.ff2_hp, 2 * D, hf * KH, own, acc, lane);
+        mm_tiles<H, false, NT, D == 256>(buf + col * LD + half * KH, KH, W.ff2_wp, W.ff2_hp, 2 * D, hf * KH, own, acc, lane);
       }
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
@@ -432,17 +466,17 @@ __global__ __launch_bounds__(256, 2) void encode_cells_shaped_kernel(EncParams P
   if (tid < D) out[(size_t)cell * D + tid] = mx / fmaxf(nrm, 1e-12f);
 }
 
-template <int D, int HD, bool F32>
+template <int D, int HD, int H>
 int launch_shaped(t2l_ctx* ctx, const EncParams& P, const t2l_packed_cells* in, int object_size, float* out, hipStream_t s) {
   const size_t lds = (size_t)(2 * kSP * (D + 4) + 8) * sizeof(float);
   static PerDeviceOnce attr_done;
   if (attr_done.need(ctx->device)) {
-    T2L_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&encode_cells_shaped_kernel<D, HD, F32>),
+    T2L_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&encode_cells_shaped_kernel<D, HD, H>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr_done.mark(ctx->device);
   }
   event_begin(ctx, "encode_cells", s);
-  hipLaunchKernelGGL((encode_cells_shaped_kernel<D, HD, F32>), dim3(in->n_cells), dim3(256), lds, s, P, *in, object_size, out);
+  hipLaunchKernelGGL((encode_cells_shaped_kernel<D, HD, H>), dim3(in->n_cells), dim3(256), lds, s, P, *in, object_size, out);
   event_end(ctx, "encode_cells", s);
   T2L_HIP(ctx, hipGetLastError());
   return T2L_OK;
@@ -465,11 +499,13 @@ const char* compiled_shapes_text() {
 int encode_shaped_impl(t2l_ctx* ctx, const t2l_packed_cells* in, float* out, hipStream_t s) {
   const EncoderWeights& ew = *ctx->enc;
   const EncParams& P = ew.p;
-  const bool f32 = !P.split_ok || ctx->encoder_f32;  // options encoder_f16 / encoder_two_cells: the published shape only
+  // 0: everything on the f32 MFMA; 1: split-f16; 2: plain f16 (option encoder_f16: the published shape only, as encoder_two_cells)
+  const int H = (!P.split_ok || ctx->encoder_f32) ? 0 : (ctx->encoder_f16 && ew.published()) ? 2 : 1;
   const int D = ew.embed_dim, hd = ew.embed_dim / ew.num_heads, S = ew.object_size;
+  if (H == 2) return launch_shaped<256, 64, 2>(ctx, P, in, S, out, s);
 #define T2L_SHAPED(DD, HH)                                                        \
   if (D == DD && hd == HH)                                                        \
-    return f32 ? launch_shaped<DD, HH, true>(ctx, P, in, S, out, s) : launch_shaped<DD, HH, false>(ctx, P, in, S, out, s);
+    return H ? launch_shaped<DD, HH, 1>(ctx, P, in, S, out, s) : launch_shaped<DD, HH, 0>(ctx, P, in, S, out, s);
   T2L_SHAPED(128, 32)
   T2L_SHAPED(128, 64)
   T2L_SHAPED(256, 32)

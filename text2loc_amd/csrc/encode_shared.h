@@ -1,5 +1,6 @@
 // What the two cell-encoder translation units share: the packed-weight parameter block that t2l_load_weights builds
-// (encode.hip) and both kernels read (encode.hip: the published shape; encode_shaped.hip: every other compiled shape).
+// (encode.hip) and both kernels read (encode.hip: two cells per workgroup at the published shape; encode_shaped.hip: one cell per
+// workgroup at every compiled shape).
 #pragma once
 #include "t2l_internal.h"
 
@@ -43,8 +44,8 @@ struct EncParams {
 struct EncoderWeights {
   EncParams p;
   float* blob = nullptr;
-  // the shape the weights were loaded for (t2l_load_weights_shaped); the published one runs the kernels of encode.hip,
-  // every other compiled shape the shape-templated kernel of encode_shaped.hip
+  // the shape the weights were loaded for (t2l_load_weights_shaped); the published one has the two-cell kernel of encode.hip in
+  // front of the shape-templated kernel of encode_shaped.hip
   int embed_dim = kD, object_size = kS, num_heads = 4;
   bool published() const { return embed_dim == kD && object_size == kS && num_heads == 4; }
 };
@@ -72,7 +73,7 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-// the shape-templated kernel (encode_shaped.hip): true when (embed_dim, num_heads, object_size) is a compiled shape
+// the one-cell kernel (encode_shaped.hip): true when (embed_dim, num_heads, object_size) is a compiled shape
 bool shape_is_compiled(int embed_dim, int num_heads, int object_size);
 const char* compiled_shapes_text();
 int encode_shaped_impl(t2l_ctx* ctx, const t2l_packed_cells* in, float* out, hipStream_t s);

@@ -106,7 +106,7 @@ struct t2l_ctx {
   // count to mapped host memory; no stream operation, no synchronisation) and, when that is more than one in eight —
   // scores packed tighter than the f16 error band — searches with the split-bf16 scan (50x tighter bound) until fewer than
   // one in sixteen would be flagged again
-  int encoder_f32 = 0;   // 1: the all-f32-MFMA encoder kernel even when the split-f16 one is safe (encode.hip)
+  int encoder_f32 = 0;   // 1: the all-f32-MFMA encoder kernel even when the split-f16 one is safe (encode_shaped.hip)
   int encoder_f16 = 0;   // 1: plain-f16 products (one MFMA per operand pair) instead of split-f16: ~1e-4 instead of 2e-7, 28 % faster
   int search_auto = 1;
   int pair_ll = 6;       // per-lane list length of the paired scan (5 or 6)
@@ -120,7 +120,7 @@ struct t2l_ctx {
   void* small_part = nullptr;             // published per-workgroup top-K lists {f64 score | i32 row}
   size_t small_part_cap = 0;
   int wide_repair = 512;  // rows a re-rank wave may re-score in a wide repair before the query goes to an exact scan (0: never)
-  int encoder_two_cells = 1;  // encode_cells: two cells per eight-wave workgroup on LDS planes (encode.hip: encode_cells2_kernel); 0: first form
+  int encoder_two_cells = 1;  // encode_cells: two cells per eight-wave workgroup on LDS planes (encode.hip: encode_cells2_kernel); 0: the one-cell kernel (encode_shaped.hip)
   int search_merge = 2;    // the paired scan merges a workgroup's four lists per query into one 32-byte record (search.hip: MERGE / MG):
                            // 0 never, 1 always, 2 while the f16 report cards show next to no failed first certificates (a repair behind
                            // a merged record re-scores 4x the rows of a plain list's)

@@ -1,6 +1,6 @@
 """ms per `t2l_encode_cells` over the 11,259-cell synthetic database at each compiled shape of the cell encoder, beside the
-published shape's one-cell split-f16 instance (`encoder_two_cells = 0`) measured in the SAME run — the baseline every ratio in
-the table is taken against — and its default two-cell instance for orientation.
+published shape on the one-cell kernel (`encoder_two_cells = 0`: the <256, 64> instance with object_size 28) measured in the SAME
+run — the baseline every ratio in the table is taken against — and its default two-cell kernel for orientation.
 
 Kernel time comes from the library's device events around the launch (`profile_events = 1`, `Engine.kernel_stats("encode_cells")`).
 Every case is warmed up (`--warmup` calls), then timed `--reps` times over `--iters` calls each; the cases are ALTERNATED inside
@@ -8,8 +8,10 @@ every repetition, so drift of the machine lands on all of them alike. Reported: 
 per-repetition means, the ratio of medians to the baseline, and the MFMA work of one cell relative to the published shape
 (counted from the shapes: projections and feed-forward ~ D^2, attention core ~ 32 * 32 * D).
 
-    python tools/bench_shapes.py [--cells 11259] [--iters 20] [--warmup 5] [--reps 7] [--f32] [--markdown OUT.md]
+    python tools/bench_shapes.py [--cells 11259] [--iters 20] [--warmup 5] [--reps 7] [--f32 | --f16] [--markdown OUT.md]
 
+`--f16` sets option `encoder_f16`, which acts on the two published rows only. `T2L_LIB=path/to/libt2l.so` in the environment times
+another build of the library (engine.py).
 Prints one JSON line; `--markdown` also writes the table. Bar (asserted, exit status 1): the (128, 4 heads) split-f16 time must
 not exceed the baseline's — a quarter of the D^2 work on the same 32-row tiles; it catches a non-MFMA or badly occupied kernel.
 """
@@ -52,7 +54,9 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--f32", action="store_true", help="the all-f32 instances (option encoder_f32) instead of split-f16")
+    arith = ap.add_mutually_exclusive_group()
+    arith.add_argument("--f32", action="store_true", help="the all-f32 instances (option encoder_f32) instead of split-f16")
+    arith.add_argument("--f16", action="store_true", help="plain f16 (option encoder_f16) at the published shape")
     ap.add_argument("--markdown", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -64,6 +68,7 @@ def main():
         e = Engine(0)
         e.set_option("profile_events", 1)
         e.set_option("encoder_f32", 1 if a.f32 else 0)
+        e.set_option("encoder_f16", 1 if a.f16 else 0)
         e.set_option("encoder_two_cells", two)
         sd = synth.make_object_branch_weights(0, embed_dim=D, num_layers=layers)
         e.load_weights(sd, class_embed=True, color_embed=True, num_layers=layers, num_heads=heads, embed_dim=D, object_size=osz)
@@ -92,7 +97,7 @@ def main():
                          ms_min=round(float(min(t)), 4), ms_max=round(float(max(t)), 4), ratio_to_baseline=round(med / base, 3),
                          mfma_work_ratio=round(mfma_work(D, layers) / pub_work, 3)))
     ok = rows[2]["ms"] <= rows[0]["ms"]
-    out = dict(tool="bench_shapes", cells=a.cells, iters=a.iters, reps=a.reps, arithmetic="f32" if a.f32 else "split-f16",
+    out = dict(tool="bench_shapes", cells=a.cells, iters=a.iters, reps=a.reps, arithmetic="f32" if a.f32 else "plain-f16" if a.f16 else "split-f16",
                device=torch.cuda.get_device_name(0), rows=rows, d128_bar_holds=bool(ok))
     if a.markdown:
         with open(a.markdown, "w") as f:
