@@ -52,7 +52,10 @@ def test_golden_e2e_ids(eng, golden):
 
 
 @pytest.mark.parametrize("n,q,k", [(1, 1, 1), (5, 3, 10), (31, 7, 5), (32, 128, 10), (33, 129, 10), (1000, 257, 26),
-                                   (4097, 64, 16), (11259, 300, 10)])
+                                   (4097, 64, 16), (11259, 300, 10),
+                                   # the smallest shape of each scan instance (csrc/search_plan.h: ScanKernel): one wave per SIMD with
+                                   # lists of 16 and of 8, the smallest paired launch (32 tiles at 256 queries) and one tile short of it
+                                   (33, 17, 10), (11259, 255, 10), (993, 256, 10), (992, 256, 10)])
 def test_ragged_shapes_vs_oracle(eng, n, q, k):
     db, qs, _ = synth.make_retrieval_problem(n, q, seed=100 + n, noise=2.0)
     idx, sc = _search(eng, db, qs, k)
@@ -699,8 +702,9 @@ def test_merged_candidate_records_equal_the_plain_lists(kind, n, q, k):
         e.db_set(torch.from_numpy(db).cuda())
         qd = torch.from_numpy(qs).cuda()
         got = {}
-        for merge in (0, 1):
-            e.set_option("search_merge_lists", merge)
+        for merge in (0, 1, "lists of 5"):  # (the third arm: plain lists of 5 keys per lane, option search_pair_ll)
+            e.set_option("search_merge_lists", 0 if merge == "lists of 5" else merge)
+            e.set_option("search_pair_ll", 5 if merge == "lists of 5" else 6)
             idx, sc = e.search(qd, k)
             torch.cuda.synchronize()
             got[merge] = (idx.cpu().numpy().astype(np.int64), sc.cpu().numpy(), e.search_counters())

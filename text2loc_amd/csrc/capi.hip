@@ -75,17 +75,17 @@ int t2l_create(t2l_ctx** out, int device_id) {
   t2l_ctx* ctx = new t2l_ctx();
   ctx->device = device_id;
   if (hipMalloc(&ctx->db_norm_max, (2 + 256) * sizeof(float)) != hipSuccess ||
-      hipMalloc(&ctx->fb_count, 256 * sizeof(int32_t)) != hipSuccess) {
+      hipMalloc(&ctx->fb_count, 2 * kBankInts * sizeof(int32_t)) != hipSuccess) {
     delete ctx;
     return T2L_ENOMEM;
   }
   (void)hipMemset(ctx->db_norm_max, 0, (2 + 256) * sizeof(float));
-  if (hipHostMalloc((void**)&ctx->host_stat, 8 * sizeof(int32_t), hipHostMallocMapped) == hipSuccess) {
-    memset(ctx->host_stat, 0, 8 * sizeof(int32_t));
+  if (hipHostMalloc((void**)&ctx->host_stat, kStatInts * sizeof(int32_t), hipHostMallocMapped) == hipSuccess) {
+    memset(ctx->host_stat, 0, kStatInts * sizeof(int32_t));
     if (hipHostGetDevicePointer((void**)&ctx->host_stat_dev, ctx->host_stat, 0) != hipSuccess) ctx->host_stat_dev = nullptr;
   }
-  (void)hipMemset(ctx->fb_count, 0, 256 * sizeof(int32_t));
-  ctx->fb_prev = ctx->fb_count + 128;  // two banks (search.hip: reset_counts)
+  (void)hipMemset(ctx->fb_count, 0, 2 * kBankInts * sizeof(int32_t));
+  ctx->fb_prev = ctx->fb_count + kBankInts;  // two banks (t2l_internal.h: CounterSlot)
   if (hipMalloc(&ctx->scan_span, sizeof(unsigned long long) * 2 * kSpanWgs * kSpanRing) == hipSuccess) {
     (void)hipMemset(ctx->scan_span, 0, sizeof(unsigned long long) * 2 * kSpanWgs * kSpanRing);
     ctx->span_grid = new unsigned[kSpanRing]();
@@ -206,13 +206,7 @@ int t2l_db_set(t2l_ctx* ctx, const float* emb, int64_t n_rows, int64_t row_offse
   ctx->db_rows = n_rows;
   // a new database: what earlier report cards said about the previous one (split-bf16 stand-in, heavy / all-exact mode) is void,
   // and so is every report of a search still in flight
-  if (ctx->search_auto) {
-    ctx->escalated = false;
-    ctx->heavy = false;
-    ctx->all_exact = false;
-    ctx->merge_live = true;
-    ctx->stat_seen = ctx->stat_seq + 1;  // (the NEXT call's re-rank still publishes the report of the last call on the old rows)
-  }
+  if (ctx->search_auto) ctx->policy.reset(true);  // (the NEXT call's re-rank still publishes the report of the last call on the old rows)
   ctx->db_pad = pad;
   ctx->row_offset = row_offset;
   if (n_rows > 0) {
@@ -231,17 +225,14 @@ int t2l_db_set(t2l_ctx* ctx, const float* emb, int64_t n_rows, int64_t row_offse
   // 3.4 with the prior), and t2l_db_set voids the report cards that would have said so. The prior only picks the starting MODE
   // (split-bf16 stand-in scan, unsettled queries deferred to the float64 MFMA stage); results are exact in every mode and the first
   // report cards correct a wrong guess within two calls (cost of a wrong guess: one near-empty launch per call).
-  if (ctx->search_auto && ctx->search_mode == 0 && n_rows >= 64) {
+  if (ctx->search_auto && ctx->knobs.search_mode == 0 && n_rows >= 64) {
     float cols[256];
     T2L_HIP(ctx, hipMemcpy(cols, ctx->db_norm_max + 2, sizeof(cols), hipMemcpyDeviceToHost));
     double ss = 0.0;
     for (float c : cols) ss += (double)c * c;
     const double n = (double)std::min<int64_t>(n_rows, 1024);
     const double mean_cos = (ss - n) / (n * (n - 1.0));
-    if (mean_cos > 0.9) {  // (NaN compares false)
-      ctx->escalated = true;
-      ctx->heavy = true;
-    }
+    ctx->policy.seed_from_prior(mean_cos);
   }
   return T2L_OK;
 }
@@ -366,7 +357,7 @@ int t2l_search_fallbacks(t2l_ctx* ctx, int32_t* out_count) {
   T2L_HIP(ctx, hipDeviceSynchronize());
   int32_t c[8];
   T2L_HIP(ctx, read_counters(ctx, c));
-  *out_count = c[0] + (c[7] - c[6]);  // float64 VALU scans + queries the float64 MFMA stage certified (search_exact.hip)
+  *out_count = c[kCntExactScan] + (c[kCntExactServed] - c[kCntExactUncert]);  // float64 VALU scans + queries the float64 MFMA stage certified (search_exact.hip)
   return T2L_OK;
 }
 
@@ -394,7 +385,7 @@ int t2l_search_rescored(t2l_ctx* ctx, int32_t* out_count) {
   T2L_HIP(ctx, hipDeviceSynchronize());
   int32_t c[8];
   T2L_HIP(ctx, read_counters(ctx, c));
-  *out_count = c[1];
+  *out_count = c[kCntRescored];
   return T2L_OK;
 }
 
@@ -582,14 +573,14 @@ int t2l_set_option(t2l_ctx* ctx, const char* name, double value) {
   if (!ctx || !name) return T2L_EINVAL;
   if (!strcmp(name, "certify_eps_scale")) {
     if (!(value >= 0)) return fail(ctx, T2L_EINVAL, "certify_eps_scale must be >= 0");
-    ctx->eps_scale = value;
+    ctx->knobs.eps_scale = value;
   } else if (!strcmp(name, "search_nsplit")) {
     if (value < 0 || value > kMaxParts / 2) return fail(ctx, T2L_EINVAL, "search_nsplit out of range [0,32]");
-    ctx->nsplit_override = (int)value;
+    ctx->knobs.nsplit_override = (int)value;
   } else if (!strcmp(name, "search_mode")) {
     if (value != 0 && value != 2)
       return fail(ctx, T2L_EINVAL, "search_mode must be 0 (f16 scan) or 2 (split-bf16 scan); 1 (the exact-f32 MFMA scan: 7x slower, same results) was removed in round 5");
-    ctx->search_mode = (int)value;
+    ctx->knobs.search_mode = (int)value;
   } else if (!strcmp(name, "encoder_f32")) {
     ctx->encoder_f32 = value != 0;
   } else if (!strcmp(name, "encoder_f16")) {
@@ -599,15 +590,9 @@ int t2l_set_option(t2l_ctx* ctx, const char* name, double value) {
     ctx->text_head_rows = (int)value;
   } else if (!strcmp(name, "search_auto")) {
     ctx->search_auto = value != 0;
-    if (!ctx->search_auto) {  // forget the state and every report of a search launched so far
-      ctx->escalated = false;
-      ctx->heavy = false;
-      ctx->all_exact = false;
-      ctx->merge_live = true;
-      ctx->stat_seen = ctx->stat_seq;
-    }
+    if (!ctx->search_auto) ctx->policy.reset(false);  // forget the state and every report of a search launched so far
   } else if (!strcmp(name, "search_heavy")) {  // force (1) / release (0) the float64 MFMA exact stage (tests)
-    ctx->heavy = value != 0;
+    ctx->policy.heavy = value != 0;
   } else if (!strcmp(name, "search_small")) {
     ctx->search_small = value != 0;
   } else if (!strcmp(name, "search_small_wgs")) {
@@ -615,7 +600,7 @@ int t2l_set_option(t2l_ctx* ctx, const char* name, double value) {
     ctx->search_small_wgs = (int)value;
   } else if (!strcmp(name, "search_xcd_qgroups")) {
     if (value != 1 && value != 2 && value != 4 && value != 8) return fail(ctx, T2L_EINVAL, "search_xcd_qgroups must be 1, 2, 4 or 8");
-    ctx->xcd_qgroups = (int)value;
+    ctx->knobs.xcd_qgroups = (int)value;
   } else if (!strcmp(name, "text_train_bf16")) {
     // (0 = f32 MFMA operands was an option until round 5: 7.6 ms per step against 5.6 ms for PyTorch on the same GPU — a trap, removed.
     // Split-bf16 is the f32-class arithmetic of the head: relative product error <= 2^-16 + 2^-18, meets the f32 goldens to 1e-4.)
@@ -627,19 +612,19 @@ int t2l_set_option(t2l_ctx* ctx, const char* name, double value) {
     ctx->encoder_two_cells = value != 0;
   } else if (!strcmp(name, "search_merge_lists")) {
     if (value != 0 && value != 1 && value != 2) return fail(ctx, T2L_EINVAL, "search_merge_lists: 0 (plain lists), 1 (merged records), 2 (default: by report card)");
-    ctx->search_merge = (int)value;
-    ctx->merge_live = true;
+    ctx->knobs.search_merge = (int)value;
+    ctx->policy.merge_live = true;
   } else if (!strcmp(name, "search_wide_repair")) {
     if (value < 0 || value > 1024) return fail(ctx, T2L_EINVAL, "search_wide_repair: 0 (off) .. 1024 rows");
-    ctx->wide_repair = (int)value;
+    ctx->knobs.wide_repair = (int)value;
   } else if (!strcmp(name, "search_tile_sel")) {
-    ctx->search_tile_sel = value != 0;
+    ctx->knobs.search_tile_sel = value != 0;
   } else if (!strcmp(name, "search_epilogue")) {
     if (value != 0 && value != 1) return fail(ctx, T2L_EINVAL, "search_epilogue: 0 (round 6's epilogue and record layout) or 1 (default)");
-    ctx->search_epilogue = (int)value;
+    ctx->knobs.search_epilogue = (int)value;
   } else if (!strcmp(name, "search_pair_ll")) {
     if (value != 5 && value != 6) return fail(ctx, T2L_EINVAL, "search_pair_ll must be 5 or 6");
-    ctx->pair_ll = (int)value;
+    ctx->knobs.pair_ll = (int)value;
   } else if (!strcmp(name, "train_gemm_block")) {
     if (value != 0 && value != 32 && value != 64) return fail(ctx, T2L_EINVAL, "train_gemm_block must be 0 (auto), 32 or 64");
     ctx->train_gemm_block = (int)value;
@@ -649,7 +634,7 @@ int t2l_set_option(t2l_ctx* ctx, const char* name, double value) {
   } else if (!strcmp(name, "train_keep_adam_state")) {
     ctx->train_keep_adam = value != 0;
   } else if (!strcmp(name, "profile_rerank")) {
-    ctx->profile_rerank = value != 0;
+    ctx->knobs.profile_rerank = value != 0;
   } else if (!strcmp(name, "stats_reset")) {  // forget every kernel-time sample so far (host-only: no stream operation, no sync)
     for (auto& kv : ctx->events) {
       kv.second.count = 0;

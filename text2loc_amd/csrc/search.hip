@@ -43,25 +43,16 @@ namespace t2l {
 // latency, so the VALU work below needs two independent chains to hide behind. After every 8th MFMA one
 // score of the PREVIOUS tile is turned into a key and inserted into the lane's list: ~L+4 VALU instructions
 // spread over the gaps (sched_group_barrier pins the interleave).
-// fb_count (dev i32[128]), per t2l_search call: [0] queries that ended in an exact float64 VALU scan, [1] queries re-scored
-// beyond the first L candidates, [2] queries the first certificate + in-wave re-score left unsettled, [3] f16-probe count
-// (auto mode), [4] queries deferred to the float64 MFMA stage (heavy mode), [5] queries a WIDE in-wave repair settled,
-// [6] queries the MFMA stage could not certify,
-// [7] queries it served, [9] Q and [10] stat mode of the call (rerank_kernel). The first scan launch of a call
-// (zero_counts) copies the finished call's [0..15] to [64..79] — rerank_kernel publishes that copy to the host's report
-// card — and clears the counters.
-// Two banks (round 4): a call counts in `fb_count`, which the call before it left zeroed; `fb_prev` is that earlier call's bank — its
-// final counts are parked at fb_count[64..79] (the report card) and it is cleared for the call after this one. The host swaps the two
-// per call. No workgroup of a call ever waits for this reset (a launch may count from its first finished query
-// block on, whatever workgroup 0 is doing).
+// The first scan launch of a call parks the finished call's counters and clears its bank; a later segment's folds the per-segment
+// counts away (t2l_internal.h: CounterSlot).
 __device__ __forceinline__ void reset_counts(int32_t* fb_count, int32_t* fb_prev, int zero_counts, int tid) {
-  if (zero_counts && tid < 16) {
-    fb_count[64 + tid] = fb_prev[tid];
+  if (zero_counts && tid < kCntCleared) {
+    fb_count[kReportBase + tid] = fb_prev[tid];
     fb_prev[tid] = 0;
   }
   if (!zero_counts && tid == 0) {  // a later segment of a multi-segment shard: the deferred lists are per segment
-    fb_count[12] += fb_count[4];
-    fb_count[4] = fb_count[6] = 0;
+    fb_count[kCntDeferredSegs] += fb_count[kCntDeferred];
+    fb_count[kCntDeferred] = fb_count[kCntExactUncert] = 0;
   }
 }
 
@@ -104,8 +95,6 @@ __global__ __launch_bounds__(256) void split_db_kernel(const float* __restrict__
 // shadow. One barrier per tile, placed where nothing waits on it (the tile it releases landed a tile-time ago).
 //   grid = ceil(Q/256) * nsplit; block b -> split b % nsplit (tiles sp, sp + nsplit, ...); LDS NBUF x 33 KiB.
 // ------------------------------------------------------------------------------------------------
-constexpr int kWideQPerWave = 64;
-constexpr int kWideQPerBlock = 4 * kWideQPerWave;
 
 template <int LL, int NBUF>
 __global__ __launch_bounds__(256, 1) void scanw_kernel(const uint4* __restrict__ dbs, int n_rows, int n_tiles, int code_bits,
@@ -208,16 +197,8 @@ __global__ __launch_bounds__(256, 1) void scanw_kernel(const uint4* __restrict__
     }
   }
   const int part = 2 * sp + half, parts = 2 * nsplit;
-  if (qrow0 < Q) {
-    float4* out = reinterpret_cast<float4*>(cand + ((size_t)qrow0 * parts + part) * LL);
-#pragma unroll
-    for (int i = 0; i < LL / 4; ++i) out[i] = make_float4(w.ls0[4 * i], w.ls0[4 * i + 1], w.ls0[4 * i + 2], w.ls0[4 * i + 3]);
-  }
-  if (qrow1 < Q) {
-    float4* out = reinterpret_cast<float4*>(cand + ((size_t)qrow1 * parts + part) * LL);
-#pragma unroll
-    for (int i = 0; i < LL / 4; ++i) out[i] = make_float4(w.ls1[4 * i], w.ls1[4 * i + 1], w.ls1[4 * i + 2], w.ls1[4 * i + 3]);
-  }
+  put_list4<LL>(cand, qrow0, Q, parts, part, w.ls0);
+  put_list4<LL>(cand, qrow1, Q, parts, part, w.ls1);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -365,16 +346,8 @@ __global__ __launch_bounds__(256, 1) void scanh_kernel(const uint4* __restrict__
     }
   }
   const int part = 2 * sp + half, parts = 2 * nsplit;
-  if (qrow0 < Q) {
-    float4* out = reinterpret_cast<float4*>(cand + ((size_t)qrow0 * parts + part) * LL);
-#pragma unroll
-    for (int i = 0; i < LL / 4; ++i) out[i] = make_float4(w.ls0[4 * i], w.ls0[4 * i + 1], w.ls0[4 * i + 2], w.ls0[4 * i + 3]);
-  }
-  if (qrow1 < Q) {
-    float4* out = reinterpret_cast<float4*>(cand + ((size_t)qrow1 * parts + part) * LL);
-#pragma unroll
-    for (int i = 0; i < LL / 4; ++i) out[i] = make_float4(w.ls1[4 * i], w.ls1[4 * i + 1], w.ls1[4 * i + 2], w.ls1[4 * i + 3]);
-  }
+  put_list4<LL>(cand, qrow0, Q, parts, part, w.ls0);
+  put_list4<LL>(cand, qrow1, Q, parts, part, w.ls1);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -412,9 +385,7 @@ struct RerankArgs {
   int32_t* flags;
   int32_t* fb_count;
   float eps_rel_probe, pinf;
-  int n_rows, defer, stat_mode;
-  int32_t* host_stat;
-  int seq, wide_cap;
+  int n_rows, defer, wide_cap;
   int rec6;  // merged records of the tile-local selection: 6 keys, B1 (a key: the largest third-best key of the record's lanes), B2
   int slot_bits = 0;  // merged records: the record of part p sits in slot record_slot(p, parts, slot_bits) of its query
 };
@@ -422,7 +393,7 @@ struct RerankArgs {
 // MERGE: the workgroup's four lists per query (two lane halves x two waves, 24 keys) leave as ONE record of 8 floats — the best 7 keys,
 // re-keyed so that the source list rides in two more code bits, + a bound on every key that did not make it (kMergedLL; the
 // re-rank's MG form reads it): a third of the bytes written back at the end of the launch and read by the re-rank.
-constexpr int kMergedLL = 8;
+// (kMergedLL = 8 floats: search_plan.h)
 // SEL = 1: the tile-local selection (search_dev.h, TileSelLists): 86 instead of 112 selection VALU per lane-tile and query group;
 // the third-best key of every group of 8 accumulator registers goes into the lane's (dA, dB), which leave in the record as B1 / B2.
 #ifndef T2L_SEL_RD
@@ -860,9 +831,6 @@ struct WgExactSharedN {
 };
 typedef WgExactSharedN<4> WgExactShared;
 
-// Rows one wave re-scores in a WIDE repair (rerank_kernel) before the query is handed to an exact scan of the whole shard.
-constexpr int kWideCap = 1024;
-
 // A wave's running top-32 as a list spread over lanes 0..31 (lane i = i-th best by (score desc, row asc); empty = -inf / INT_MAX):
 // insert (cd, cr) unless that row is already in the list. Wave-uniform control flow.
 __device__ __forceinline__ void top32_insert(double& ts, int& tr, double cd, int cr, int lane) {
@@ -982,18 +950,16 @@ __device__ __forceinline__ void wg_exact_scan(const float* __restrict__ db, int 
 // later call — no stream operation, no synchronisation (it only steers heuristics); the sequence number is published LAST with
 // system-scope release ordering, the host reads it first with an acquire load, so a new sequence number is never paired with the
 // previous call's counts. One thread of one workgroup per call.
-__device__ __forceinline__ void publish_report(const RerankArgs& a) {
-  int32_t* fb_count = a.fb_count;
-  if (a.host_stat && a.seq > 0) {
-    a.host_stat[1] = fb_count[64 + 10] == 2 ? fb_count[64 + 3] : fb_count[64 + 2];  // f16-certificate failures (or the probe's)
-    a.host_stat[2] = fb_count[64 + 9];
-    a.host_stat[3] = fb_count[64 + 0] + fb_count[64 + 4] + fb_count[64 + 12];  // exact-stage queries
-    a.host_stat[4] = fb_count[64 + 10];  // 0: not an f16-certificate count, 1: the f16 scan's own, 2: the split-bf16 stand-in's probe
-    a.host_stat[5] = fb_count[64 + 10] == 2 ? fb_count[64 + 3] : fb_count[64 + 1];  // first-certificate failures (settled in the wave or not)
-    __hip_atomic_store(&a.host_stat[0], a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+__device__ __forceinline__ void publish_report(int32_t* fb_count, int32_t* host_stat, int seq) {
+  if (host_stat && seq > 0) {
+    const int32_t* prev = fb_count + kReportBase;
+    host_stat[kStatFlagged] = prev[kCntStatMode] == 2 ? prev[kCntProbe] : prev[kCntUnsettled];  // f16-certificate failures (or the probe's)
+    host_stat[kStatTotal] = prev[kCntQ];
+    host_stat[kStatExact] = prev[kCntExactScan] + prev[kCntDeferred] + prev[kCntDeferredSegs];  // exact-stage queries
+    host_stat[kStatMode] = prev[kCntStatMode];  // 0: not an f16-certificate count, 1: the f16 scan's own, 2: the split-bf16 stand-in's probe
+    host_stat[kStatRescored] = prev[kCntStatMode] == 2 ? prev[kCntProbe] : prev[kCntRescored];  // first-certificate failures (settled in the wave or not)
+    __hip_atomic_store(&host_stat[kStatSeq], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
-  fb_count[9] = a.Q;
-  fb_count[10] = a.stat_mode;  // 0: not an f16-certificate count, 1: f16 scan, 2: split-bf16 stand-in probing for it
 }
 
 // One query, one wave. `my_wg_flag`: this wave's slot of the workgroup's "rank exactly" flags; `wr_buf`: kWideCap ints of LDS.
@@ -1298,7 +1264,7 @@ __device__ __forceinline__ void rerank_query(const RerankArgs& a, const int qid,
           emit(valid2, rank2);
           if (lane == 0) {
             flags[qid] = 0;
-            atomicAdd(&fb_count[1], 1);  // re-scored beyond the first L candidates (the group repair)
+            atomicAdd(&fb_count[kCntRescored], 1);  // re-scored beyond the first L candidates (the group repair)
           }
           fast_done = true;
         }
@@ -1330,7 +1296,7 @@ __device__ __forceinline__ void rerank_query(const RerankArgs& a, const int qid,
       // the f16 error band would still flag: the host goes back to the f16 scan when they become rare
       if (eps_rel_probe > 0.f && lane == 0 &&
           !(dK > (double)g * kscale + key_slack(g, slack_bits, (double)eps_rel_probe * sqrt(qn) * (double)(*db_norm_max), kscale)))
-        atomicAdd(&fb_count[3], 1);
+        atomicAdd(&fb_count[kCntProbe], 1);
       // a row with key k has score <= k*kscale + |k|*kscale*2^(cb-22) + eps32; with S = 2*(|dK|*2^(cb-22) + eps32) every
       // key below (dK - S)/kscale is therefore below the current K-th best score dK (and the final K-th is >= dK)
       const double S = 2.0 * (fabs(dK) * ldexp(1.0, slack_bits - 22) + eps32);
@@ -1525,7 +1491,7 @@ __device__ __forceinline__ void rerank_query(const RerankArgs& a, const int qid,
           out_idx[(size_t)qid * K + lane] = tr == INT_MAX ? -1 : tr + row_offset;
           if (out_score) out_score[(size_t)qid * K + lane] = ts;
         }
-        if (lane == 0) atomicAdd(&fb_count[5], 1);
+        if (lane == 0) atomicAdd(&fb_count[kCntWideRepair], 1);
         settled = true;
       }
     }
@@ -1534,12 +1500,12 @@ __device__ __forceinline__ void rerank_query(const RerankArgs& a, const int qid,
   if (lane == 0) {
     const int flag = !representable ? 2 : ((certified || settled) ? 0 : 1);
     flags[qid] = flag;
-    if (!certified || !representable) atomicAdd(&fb_count[1], 1);  // first certificate failed (settled in the wave or not)
+    if (!certified || !representable) atomicAdd(&fb_count[kCntRescored], 1);  // first certificate failed (settled in the wave or not)
     if (flag) {
-      atomicAdd(&fb_count[2], 1);
+      atomicAdd(&fb_count[kCntUnsettled], 1);
       if (!defer) *my_wg_flag = flag;  // settled below, by this workgroup
-      else if (flag == 2) flags[4 * Q + atomicAdd(&fb_count[6], 1)] = qid;  // heavy mode: -> exact_list_kernel
-      else flags[3 * Q + atomicAdd(&fb_count[4], 1)] = qid;                  //             -> exactd_kernel
+      else if (flag == 2) flags[4 * Q + atomicAdd(&fb_count[kCntExactUncert], 1)] = qid;  // heavy mode: -> exact_list_kernel
+      else flags[3 * Q + atomicAdd(&fb_count[kCntDeferred], 1)] = qid;                  //             -> exactd_kernel
     }
   }
   }  // !fast_done
@@ -1565,11 +1531,15 @@ __global__ __launch_bounds__(256, (MG ? 4 : 1)) void rerank_kernel(const float* 
   __shared__ int wg_flag[4];
   __shared__ int wide_rows[4][kWideCap];  // per wave: the rows a wide repair re-scores
   const RerankArgs a{db, q, Q, K, parts, code_bits, cand, row_offset, eps_rel, db_norm_max, half_mode, out_idx, out_score, flags, fb_count,
-                     eps_rel_probe, pinf, n_rows, defer, stat_mode, host_stat, seq, wide_cap, rec6, slot_bits};
+                     eps_rel_probe, pinf, n_rows, defer, wide_cap, rec6, slot_bits};
   const int lane = threadIdx.x & 63;
   const int qid = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (threadIdx.x < 4) wg_flag[threadIdx.x] = 0;
-  if (blockIdx.x == 0 && threadIdx.x == 0) publish_report(a);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    publish_report(fb_count, host_stat, seq);
+    fb_count[kCntQ] = Q;
+    fb_count[kCntStatMode] = stat_mode;  // 0: not an f16-certificate count, 1: f16 scan, 2: split-bf16 stand-in probing for it
+  }
   __syncthreads();
   if (qid < Q) rerank_query<LL, L, MG>(a, qid, lane, &wg_flag[threadIdx.x >> 6], wide_rows[threadIdx.x >> 6]);
   // ---- unsettled queries of this workgroup: the exact float64 ranking, all 4 waves on one query at a time
@@ -1578,7 +1548,7 @@ __global__ __launch_bounds__(256, (MG ? 4 : 1)) void rerank_kernel(const float* 
   for (int w = 0; w < 4; ++w) {
     if (!wg_flag[w]) continue;  // workgroup-uniform
     const int fq = blockIdx.x * 4 + w;
-    if (threadIdx.x == 0) atomicAdd(&fb_count[0], 1);
+    if (threadIdx.x == 0) atomicAdd(&fb_count[kCntExactScan], 1);
     wg_exact_scan(db, n_rows, q + (size_t)fq * kD, K, row_offset, out_idx + (size_t)fq * K,
                   out_score ? out_score + (size_t)fq * K : nullptr, exact_sh);
   }
@@ -1683,141 +1653,92 @@ static void allow_lds(Kern* kern, size_t lds) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 }
 
-// scan (by search_mode) -> re-rank -> fallback on one stream. LL = per-lane list length the scan keeps, L = rows the
-// re-rank re-scores per query.
-template <int LL, int L>
-static int launch_search(t2l_ctx* ctx, const float* db, const uint4* dbs, const uint4* dbh, int n_rows, int row_offset,
-                         const float* q, int Q, int K, int nsplit, int code_bits, int32_t* out_idx, double* out_score,
-                         bool first, bool pair, hipStream_t s) {
-  const int n_tiles = (n_rows + kTileRows - 1) / kTileRows;
-  const int parts = 2 * nsplit;
+// One kernel launch that a sampled call times: the dispatch carries its own start / stop events (event_pair, capi.hip) when
+// `enabled` and this launch is a sampled one, and is a plain launch otherwise. The arguments convert to the kernel's parameter types.
+template <typename... P>
+static void launch_timed(t2l_ctx* ctx, const char* name, bool enabled, void (*kern)(P...), dim3 grid, dim3 block, size_t lds,
+                         hipStream_t s, std::common_type_t<P>... args) {
+  hipEvent_t ea, eb;
+  if (enabled && event_pair(ctx, name, &ea, &eb)) hipExtLaunchKernelGGL(kern, grid, block, (uint32_t)lds, s, ea, eb, 0u, args...);
+  else hipLaunchKernelGGL(kern, grid, block, lds, s, args...);
+}
+
+// scan -> re-rank on one stream, as the plan says (search_plan.h: plan_segment).
+static int launch_search(t2l_ctx* ctx, const SegmentPlan& p, const float* db, const uint4* dbs, const uint4* dbh, int n_rows,
+                         int row_offset, const float* q, int Q, int K, int32_t* out_idx, double* out_score, bool first, hipStream_t s) {
   const int zero = first;
-  const int half_mode = ctx->eff_mode == 0;
-  const bool probing = ctx->search_mode == 0 && ctx->eff_mode == 2;  // standing in for the f16 scan (search_impl)
-  // f32 dot-product error bound: gamma_n * |a||b| with n = 256 terms (+ slack for the MFMA's k order), plus the operand
-  // rounding of the scan that produced the keys: f16 (RNE, both operands) 2^-10 + 2^-21 and 2^-20 for denormal
-  // elements, rounded up to 9.85e-4; split-bf16 2^-16 + 2^-18, rounded up to 2e-5; f32: none
-  const double operand_eps = ctx->eff_mode == 0 ? 9.85e-4 : (ctx->eff_mode == 2 ? 2.0e-5 : 0.0);
-  const float eps_rel = (float)(ctx->eps_scale * ((kD + 8) * 5.9604644775390625e-08 + operand_eps));
-  const float eps_probe = probing ? (float)(ctx->eps_scale * ((kD + 8) * 5.9604644775390625e-08 + 9.85e-4)) : 0.f;
-  const int stat_mode = probing ? 2 : (half_mode ? 1 : 0);
-  const int seq = first ? ++ctx->stat_seq : 0;  // the report card goes out once per call
-  const int defer = ctx->heavy ? 1 : 0;
-  bool merged = false;  // the candidate lists are merged records (scanp_kernel<..., MERGE>)
-  int rec_slot_bits = 0;  // ... laid out by record_slot(part, parts, rec_slot_bits)
-  if constexpr (LL <= 6) {  // paired f16 MFMA scan (default): one 512-thread workgroup per CU, 256 queries each; `nsplit`
-    // counts VIRTUAL splits here: the kernel takes physical ones (2 virtual splits per workgroup)
-    const dim3 grid((Q + kWideQPerBlock - 1) / kWideQPerBlock * (nsplit / 2));
-    // (the tile ring + the merged records' exchange area: 256 records of 11 floats)
-    const size_t lds = (size_t)4 * 2 * kHalfTileBytes + (size_t)256 * (kMergedLL + 3) * sizeof(float);
-    static PerDeviceOnce once;
-    if (once.need(ctx->device)) {
-      allow_lds(&scanp_kernel<LL, 4>, lds);
-      if constexpr (LL == 6) allow_lds(&scanp_kernel<LL, 4, true>, lds);
-      if constexpr (LL == 6) allow_lds(&scanp_kernel<LL, 4, true, 1>, lds);
-      if constexpr (LL == 6) allow_lds(&scanp_kernel<LL, 4, true, 2>, lds);
-      once.mark(ctx->device);
-    }
+  const int seq = first ? ++ctx->policy.stat_seq : 0;  // the report card goes out once per call
+  static PerDeviceOnce once;
+  if (once.need(ctx->device)) {
+    const size_t pair_lds = (size_t)4 * 2 * kHalfTileBytes + (size_t)256 * (kMergedLL + 3) * sizeof(float);
+    allow_lds(&scanp_kernel<5, 4>, pair_lds);
+    allow_lds(&scanp_kernel<6, 4>, pair_lds);
+    allow_lds(&scanp_kernel<6, 4, true>, pair_lds);
+    allow_lds(&scanp_kernel<6, 4, true, 1>, pair_lds);
+    allow_lds(&scanp_kernel<6, 4, true, 2>, pair_lds);
+    allow_lds(&scanh_kernel<8>, (size_t)4 * kHalfTileBytes);
+    allow_lds(&scanh_kernel<16>, (size_t)4 * kHalfTileBytes);
+    allow_lds(&scanh_kernel<32>, (size_t)4 * kHalfTileBytes);
+    allow_lds(&scanw_kernel<8, 4>, (size_t)4 * kTileFloats * sizeof(float));
+    allow_lds(&scanw_kernel<16, 4>, (size_t)4 * kTileFloats * sizeof(float));
+    allow_lds(&scanw_kernel<32, 4>, (size_t)4 * kTileFloats * sizeof(float));
+    once.mark(ctx->device);
+  }
+  const dim3 grid(p.grid), block(p.block);
+  if (p.pair) {
     const unsigned span_seq = ++ctx->span_seq;
     unsigned long long* span = ctx->scan_span && grid.x <= (unsigned)kSpanWgs ? ctx->scan_span + (size_t)2 * kSpanWgs * (span_seq % kSpanRing) : nullptr;
     if (ctx->span_grid) ctx->span_grid[span_seq % kSpanRing] = span ? grid.x : 0;
-    // the XCD rectangle needs whole query-block groups and split groups on every XCD (else: splits only, as before)
-    int xq = ctx->xcd_qgroups;
-    {
-      const int nqb = (Q + kWideQPerBlock - 1) / kWideQPerBlock, ns = nsplit / 2;
-      if (xq < 2 || 8 % xq || nqb % xq || ns % (8 / xq) || (nqb * ns) % 8) xq = 1;
-    }
-    // option "search_epilogue" = 1: the splits one XCD owns for a query block (sp % GS == x / GQ, GS = 8 / GQ of them interleaved) are
-    // contiguous in the query's records — every 128-byte line of the record buffer is written by ONE XCD's L2 (record_slot)
-    int slot_bits = 0;
-    if (ctx->search_epilogue && xq > 1)
-      for (int gs = 8 / xq; gs > 1; gs >>= 1) ++slot_bits;
-    rec_slot_bits = slot_bits;
-    hipEvent_t ea, eb;
-    const bool ev = event_pair(ctx, "search_scan", &ea, &eb);  // sampled launch: the dispatch carries its own start / stop events
-    auto launch = [&](auto kern) {
-      if (ev)
-        hipExtLaunchKernelGGL(kern, grid, dim3(512), (uint32_t)lds, s, ea, eb, 0u, dbh, n_rows, n_tiles, code_bits, q, Q, nsplit / 2, ctx->cand_score,
-                              ctx->fb_count, ctx->fb_prev, zero, __builtin_inff(), span, span_seq, xq, slot_bits);
-      else
-        hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, dbh, n_rows, n_tiles, code_bits, q, Q, nsplit / 2, ctx->cand_score, ctx->fb_count,
-                           ctx->fb_prev, zero, __builtin_inff(), span, span_seq, xq, slot_bits);
+    auto launch = [&](auto kern) {  // sampled launch: the dispatch carries its own start / stop events
+      launch_timed(ctx, "search_scan", true, kern, grid, block, p.lds, s, dbh, n_rows, p.n_tiles, p.code_bits, q, Q, p.scan_nsplit, ctx->cand_score,
+                   ctx->fb_count, ctx->fb_prev, zero, __builtin_inff(), span, span_seq, p.xq, p.slot_bits);
     };
-    if constexpr (LL == 6 && L == 16) {
-      // merged records (option "search_merge_lists"): the workgroup's four lists per query leave as one 32-byte record
-      // (two more code bits come out of the key's score: kept to shards whose keys still hold 12 score bits below the exponent)
-      merged = (ctx->search_merge == 1 || (ctx->search_merge == 2 && ctx->merge_live && !ctx->heavy)) && code_bits <= 9;
+    switch (p.scan) {
+      case ScanKernel::kPair5: launch(&scanp_kernel<5, 4>); break;
+      case ScanKernel::kPair6: launch(&scanp_kernel<6, 4>); break;
+      case ScanKernel::kPairMerged0: launch(&scanp_kernel<6, 4, true>); break;
+      case ScanKernel::kPairMerged1: launch(&scanp_kernel<6, 4, true, 1>); break;
+      default: launch(&scanp_kernel<6, 4, true, 2>); break;
     }
-    if constexpr (LL == 6) {
-      if (merged && ctx->search_tile_sel && ctx->search_epilogue) launch(scanp_kernel<LL, 4, true, 1>);
-      else if (merged && ctx->search_tile_sel) launch(scanp_kernel<LL, 4, true, 2>);
-      else if (merged) launch(scanp_kernel<LL, 4, true>);
-    }
-    if (!merged) launch(scanp_kernel<LL, 4>);
   } else {
-  event_begin(ctx, "search_scan", s);
-  if (ctx->eff_mode == 0) {  // f16 MFMA scan, one wave per SIMD (tiny shards, k > 10): 256 queries per workgroup
-    const dim3 grid((Q + kWideQPerBlock - 1) / kWideQPerBlock * nsplit);
-    const size_t lds = (size_t)4 * kHalfTileBytes;
-    static PerDeviceOnce once;
-    if (once.need(ctx->device)) {
-      allow_lds(&scanh_kernel<LL>, (size_t)4 * kHalfTileBytes);
-      once.mark(ctx->device);
+    auto launch = [&](auto ll) {
+      constexpr int LL = decltype(ll)::value;
+      event_begin(ctx, "search_scan", s);
+      if (p.scan == ScanKernel::kWaveF16)
+        hipLaunchKernelGGL((scanh_kernel<LL>), grid, block, p.lds, s, dbh, n_rows, p.n_tiles, p.code_bits, q, Q, p.scan_nsplit,
+                           ctx->cand_score, ctx->fb_count, ctx->fb_prev, zero, __builtin_inff());
+      else
+        hipLaunchKernelGGL((scanw_kernel<LL, 4>), grid, block, p.lds, s, dbs, n_rows, p.n_tiles, p.code_bits, q, Q, p.scan_nsplit,
+                           ctx->cand_score, ctx->fb_count, ctx->fb_prev, zero, __builtin_inff());
+      event_end(ctx, "search_scan", s);
+    };
+    switch (p.LL) {
+      case 8: launch(std::integral_constant<int, 8>{}); break;
+      case 16: launch(std::integral_constant<int, 16>{}); break;
+      default: launch(std::integral_constant<int, 32>{}); break;
     }
-    hipLaunchKernelGGL((scanh_kernel<LL>), grid, dim3(256), lds, s, dbh, n_rows, n_tiles, code_bits, q, Q, nsplit,
-                       ctx->cand_score, ctx->fb_count, ctx->fb_prev, zero, __builtin_inff());
-  } else if (ctx->eff_mode == 2) {  // split-bf16 MFMA scan, same structure, three MFMAs per product
-    const dim3 grid((Q + kWideQPerBlock - 1) / kWideQPerBlock * nsplit);
-    const size_t lds = (size_t)4 * kTileFloats * sizeof(float);
-    static PerDeviceOnce once;
-    if (once.need(ctx->device)) {
-      allow_lds(&scanw_kernel<LL, 4>, (size_t)4 * kTileFloats * sizeof(float));
-      once.mark(ctx->device);
-    }
-    hipLaunchKernelGGL((scanw_kernel<LL, 4>), grid, dim3(256), lds, s, dbs, n_rows, n_tiles, code_bits, q, Q, nsplit,
-                       ctx->cand_score, ctx->fb_count, ctx->fb_prev, zero, __builtin_inff());
-  }
-  event_end(ctx, "search_scan", s);
   }
   T2L_HIP(ctx, hipGetLastError());
   // Two launches per search. Queries the certificate and the in-wave re-score leave unsettled are ranked exactly by
   // their own re-rank workgroup (wg_exact_scan) — there is no separate fallback launch to pay for when, as usual, there
   // are none. (Heavy mode: they are deferred to the float64 MFMA stage instead, search_exact.hip.)
-  hipEvent_t ea, eb;
-  if constexpr (LL == 6 && L == 16) {
-    if (merged) {
-      const bool evr = ctx->profile_rerank && event_pair(ctx, "search_rerank", &ea, &eb);
-      if (evr)
-        hipExtLaunchKernelGGL((rerank_kernel<kMergedLL, L, true>), dim3((Q + 3) / 4), dim3(256), 0u, s, ea, eb, 0u, db, q, Q, K, nsplit / 2,
-                              code_bits, (const float*)ctx->cand_score, row_offset, eps_rel, (const float*)ctx->db_norm_max, half_mode, out_idx,
-                              out_score, ctx->flags, ctx->fb_count, eps_probe, __builtin_inff(), n_rows, defer, stat_mode,
-                              ctx->host_stat_dev, seq, min(ctx->wide_repair, kWideCap), ctx->search_tile_sel ? 1 : 0, rec_slot_bits);
-      else
-        hipLaunchKernelGGL((rerank_kernel<kMergedLL, L, true>), dim3((Q + 3) / 4), dim3(256), 0, s, db, q, Q, K, nsplit / 2, code_bits,
-                           ctx->cand_score, row_offset, eps_rel, ctx->db_norm_max, half_mode, out_idx, out_score, ctx->flags,
-                           ctx->fb_count, eps_probe, __builtin_inff(), n_rows, defer, stat_mode, ctx->host_stat_dev, seq,
-                           min(ctx->wide_repair, kWideCap), ctx->search_tile_sel ? 1 : 0, rec_slot_bits);
-      T2L_HIP(ctx, hipGetLastError());
-      if (ctx->heavy) return exact_stage_impl(ctx, db, n_rows, row_offset, q, Q, K, out_idx, out_score, s);
-      return T2L_OK;
-    }
+  auto rerank = [&](auto kern) {
+    launch_timed(ctx, "search_rerank", p.time_rerank, kern, dim3((Q + 3) / 4), dim3(256), 0, s, db, q, Q, K, p.rerank_parts, p.code_bits,
+                 ctx->cand_score, row_offset, p.eps_rel, ctx->db_norm_max, p.half_mode, out_idx, out_score, ctx->flags, ctx->fb_count,
+                 p.eps_probe, __builtin_inff(), n_rows, p.defer, p.stat_mode, ctx->host_stat_dev, seq, p.wide_cap, p.rec6, p.rerank_slot_bits);
+  };
+  switch (p.rerank) {
+    case RerankKernel::kLists5: rerank(&rerank_kernel<5, 16>); break;
+    case RerankKernel::kLists6: rerank(&rerank_kernel<6, 16>); break;
+    case RerankKernel::kLists8: rerank(&rerank_kernel<8, 16>); break;
+    case RerankKernel::kLists16: rerank(&rerank_kernel<16, 16>); break;
+    case RerankKernel::kLists32: rerank(&rerank_kernel<32, 32>); break;
+    case RerankKernel::kRecords: rerank(&rerank_kernel<kMergedLL, 16, true>); break;
   }
-  if (ctx->profile_rerank && event_pair(ctx, "search_rerank", &ea, &eb))
-    hipExtLaunchKernelGGL((rerank_kernel<LL, L>), dim3((Q + 3) / 4), dim3(256), 0u, s, ea, eb, 0u, db, q, Q, K, parts, code_bits,
-                          (const float*)ctx->cand_score, row_offset, eps_rel, (const float*)ctx->db_norm_max, half_mode, out_idx,
-                          out_score, ctx->flags, ctx->fb_count, eps_probe, __builtin_inff(), n_rows, defer, stat_mode,
-                          ctx->host_stat_dev, seq, min(ctx->wide_repair, kWideCap), 0, 0);
-  else
-    hipLaunchKernelGGL((rerank_kernel<LL, L>), dim3((Q + 3) / 4), dim3(256), 0, s, db, q, Q, K, parts, code_bits,
-                       ctx->cand_score, row_offset, eps_rel, ctx->db_norm_max, half_mode, out_idx, out_score, ctx->flags,
-                       ctx->fb_count, eps_probe, __builtin_inff(), n_rows, defer, stat_mode, ctx->host_stat_dev, seq,
-                       min(ctx->wide_repair, kWideCap), 0, 0);
   T2L_HIP(ctx, hipGetLastError());
-  if (ctx->heavy) return exact_stage_impl(ctx, db, n_rows, row_offset, q, Q, K, out_idx, out_score, s);
+  if (p.defer) return exact_stage_impl(ctx, db, n_rows, row_offset, q, Q, K, out_idx, out_score, s);
   return T2L_OK;
 }
-
-// (rows one scan launch can cover — kSegmentRows = 32 splits x 512 tiles (13 code bits) x 32 rows — t2l_internal.h)
 
 // an empty shard (legal under ragged row-sharding: shard_bounds hands the tail ranks nothing) answers -1 / -inf everywhere
 __global__ __launch_bounds__(256) void empty_result_kernel(int n, int32_t* __restrict__ out_idx, double* __restrict__ out_score) {
@@ -1837,17 +1758,10 @@ __global__ __launch_bounds__(256) void all_exact_prep_kernel(int Q, int32_t* __r
     reset_counts(fb_count, fb_prev, 1, threadIdx.x);
     __syncthreads();
     if (threadIdx.x == 0) {
-      if (host_stat && seq > 0) {
-        host_stat[1] = fb_count[64 + 10] == 2 ? fb_count[64 + 3] : fb_count[64 + 2];
-        host_stat[2] = fb_count[64 + 9];
-        host_stat[3] = fb_count[64 + 0] + fb_count[64 + 4] + fb_count[64 + 12];
-        host_stat[4] = fb_count[64 + 10];
-        host_stat[5] = fb_count[64 + 10] == 2 ? fb_count[64 + 3] : fb_count[64 + 1];
-        __hip_atomic_store(&host_stat[0], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-      fb_count[9] = Q;
-      fb_count[10] = 0;
-      fb_count[1] = fb_count[2] = fb_count[4] = Q;  // every query counts as flagged and deferred
+      publish_report(fb_count, host_stat, seq);
+      fb_count[kCntQ] = Q;
+      fb_count[kCntStatMode] = 0;
+      fb_count[kCntRescored] = fb_count[kCntUnsettled] = fb_count[kCntDeferred] = Q;  // every query counts as flagged and deferred
     }
   }
   for (int i = blockIdx.x * 256 + threadIdx.x; i < Q; i += gridDim.x * 256) list[i] = i;
@@ -1862,71 +1776,33 @@ int search_impl(t2l_ctx* ctx, const float* q, int Q, int K, int32_t* out_idx, do
     return T2L_OK;
   }
   ctx->last_search_small = false;
+  const SearchKnobs& knobs = ctx->knobs;
+  SearchPolicy& policy = ctx->policy;
   // few queries against a large shard: stream the DB once through every CU (search_stream.hip)
-  if (Q <= 64 && n_rows >= ctx->stream_min_rows && n_rows > 0 && ctx->search_mode == 0 && ctx->nsplit_override == 0)
+  if (Q <= 64 && n_rows >= ctx->stream_min_rows && n_rows > 0 && knobs.search_mode == 0 && knobs.nsplit_override == 0)
     return search_stream_impl(ctx, q, Q, K, out_idx, out_score, s);
   // a handful of queries against a shard that fits the caches: ONE launch, exact float64 from the start (search_small.hip)
   if (search_small_applies(ctx, Q, K)) return search_small_impl(ctx, q, Q, K, out_idx, out_score, s);
-  // the f16 scan's report card of an earlier call on this DB (see t2l_internal.h): more than 1 in 8 queries flagged ->
-  // the split-bf16 scan from now on
-  // ... and back when fewer than 1 in 16 would be (the stand-in counts them, rerank_kernel)
-  // ... and its exact-stage count: when more than 1 in 64 queries of a call ended in the float64 scan, the database
-  // defeats the certificates wholesale ("heavy"): later calls defer those queries to the float64 MFMA stage
-  // (search_exact.hip) instead of the fallback kernel's VALU scan, until fewer than 1 in 256 need it
+  // the report card of an earlier call on this DB steers this one (search_plan.h: SearchPolicy)
   if (ctx->host_stat) {
     const volatile int32_t* hs = ctx->host_stat;
-    const int done = __atomic_load_n(ctx->host_stat, __ATOMIC_ACQUIRE);  // pairs with the kernel's system-scope release store
-    if (done > ctx->stat_seen) {
-      ctx->stat_seen = done;
-      const int64_t flagged = hs[1], total = hs[2], exact_prev = hs[3], rescored = hs[5];
-      // (total == 0: the bank of a call that keeps no report card — the streaming scan clears its bank and counts its exact scans
-      // only — or of no call at all: nothing to learn from)
-      const bool counted = total > 0;
-      if (counted && ctx->search_mode == 0 && ctx->search_auto && hs[4]) {
-        // ... or more than 1 in 2 failed the first certificate: the in-wave repairs settle them, but a wide repair re-scores
-        // dozens to hundreds of rows per query — measured on a clustered database with 92 % of the queries repaired: 185 us per
-        // step on the f16 scan against 133 us on the split-bf16 scan, whose 50x tighter band certifies them outright
-        // (a report is two calls old: only a report of the f16 scan escalates, only one of the stand-in's probe releases —
-        // an f16 report that arrives after the switch must not undo it)
-        if (hs[4] == 1 && !ctx->escalated && (flagged * 8 > total || rescored * 2 > total)) ctx->escalated = true;
-        else if (hs[4] == 2 && ctx->escalated && flagged * 16 < total) ctx->escalated = false;
-      }
-      // merged candidate records pay while repairs are rare: more than 1 query in 64 failing its first certificate -> plain lists
-      // (their repairs re-score a quarter of the rows), back below 1 in 256
-      if (counted && hs[4] == 1) {
-        if (ctx->merge_live && rescored * 64 > total) ctx->merge_live = false;
-        else if (!ctx->merge_live && rescored * 256 <= total) ctx->merge_live = true;
-      }
-      if (counted && ctx->search_auto) {
-        if (!ctx->heavy && exact_prev * 64 > total) ctx->heavy = true;
-        else if (ctx->heavy && exact_prev * 256 < total) ctx->heavy = false;
-        // 7 in 8 queries end in the exact stage whatever the candidate scan says: stop paying for the scan and the re-rank
-        // (0.26 ms of a 1.0 ms step on such a database) and hand EVERY query to the float64 MFMA stage; one call in 8 still
-        // takes the long way and its report decides whether that remains true
-        // (only on the word of the split-bf16 stand-in, whose band is the tightest a candidate scan has: a database that defeats
-        // the f16 scan alone gets the stand-in first; reports of all-exact calls themselves carry no scan and change nothing)
-        if (hs[4] == 2) ctx->all_exact = ctx->heavy && exact_prev * 8 >= total * 7;
-        else if (hs[4] == 1) ctx->all_exact = false;
-      }
-    }
+    int32_t report[kStatInts];
+    report[kStatSeq] = __atomic_load_n(ctx->host_stat, __ATOMIC_ACQUIRE);  // pairs with the kernel's system-scope release store
+    for (int i = 1; i < kStatInts; ++i) report[i] = hs[i];
+    policy.observe(report, knobs.search_mode, ctx->search_auto != 0);
   }
-  ctx->eff_mode = (ctx->search_mode == 0 && ctx->escalated) ? 2 : ctx->search_mode;
-  const int qpb = kWideQPerBlock;
-  const int n_qblocks = (Q + qpb - 1) / qpb;
-  // rows re-scored per query: K + margin (the margin only has to absorb key-truncation ties; the certificate catches
-  // the rest). (L = 12 was measured: second-stage re-scores multiply.)
-  const int L = (K <= 10) ? 16 : 32;
-  const int n_seg = max(1, (n_rows + kSegmentRows - 1) / kSegmentRows);
-  if (n_seg * K > 256)
+  const int eff_mode = policy.eff_mode(knobs.search_mode);
+  const Segments segs = segments_of(n_rows, K);
+  const int n_seg = segs.n_seg;
+  if (segs.too_large)
     return fail(ctx, T2L_EINVAL, "t2l_search: shard too large (more than 256/k segments of 524,288 rows); shard the "
                                  "database over more ranks");
   int rc;
   // flags[Q] + f32 thresholds[Q] + flagged list[Q] + deferred list[Q] + uncertified list[Q] (search_exact.hip)
   if ((rc = grow(ctx, (void**)&ctx->flags, &ctx->flag_cap, (size_t)5 * Q * sizeof(int32_t))) != T2L_OK) return rc;
   std::swap(ctx->fb_count, ctx->fb_prev);  // this call counts in the bank the previous call cleared (reset_counts)
-  ctx->last_search_small = false;
-  if (ctx->search_auto && ctx->heavy && ctx->all_exact && n_seg == 1 && (ctx->all_exact_calls++ & 7) != 7) {
-    const int seq = ++ctx->stat_seq;
+  if (policy.take_all_exact(n_seg)) {
+    const int seq = ++policy.stat_seq;
     // (block 0 parks the counters before any block's exactd successor reads them: the launches are stream-ordered)
     hipLaunchKernelGGL(all_exact_prep_kernel, dim3(min((Q + 255) / 256, 64)), dim3(256), 0, s, Q, ctx->flags + (size_t)3 * Q, ctx->fb_count,
                        ctx->fb_prev, ctx->host_stat_dev, seq);
@@ -1940,41 +1816,11 @@ int search_impl(t2l_ctx* ctx, const float* q, int Q, int K, int32_t* out_idx, do
         (rc = grow(ctx, (void**)&ctx->seg_score, &ctx->seg_score_cap, (size_t)n_seg * Q * K * sizeof(double))) != T2L_OK)
       return rc;
   }
-  for (int seg = 0; seg < n_seg; ++seg) {
+  for (int seg = 0; seg < n_seg; ++seg) {  // (rows one scan launch can cover: kSegmentRows, search_plan.h)
     const int row0 = seg * kSegmentRows;
-    const int rows = min(kSegmentRows, n_rows - row0);
-    const int n_tiles = (max(rows, 0) + kTileRows - 1) / kTileRows;
-    // the paired scan (two waves per SIMD, scanp_kernel) serves the f16 mode whenever the shard gives every query at least
-    // 32 per-lane lists (>= 8 physical splits: 256+ rows); its splits below are VIRTUAL ones (two per workgroup)
-    // (small batches keep the one-wave-per-SIMD kernel: twice the workgroups, and its prologue is the shorter one)
-    const bool pair_ok = ctx->eff_mode == 0 && L == 16 && n_tiles >= 16 && Q >= 256;
-    int nsplit = ctx->nsplit_override;
-    if (nsplit <= 0) {
-      // fill 256 CUs with one (wide scan) or two workgroups each; multiples of 8 keep a split on one XCD's L2
-      nsplit = (256 + n_qblocks - 1) / n_qblocks;
-      nsplit = ((nsplit + 7) / 8) * 8;
-    }
-    nsplit = max(1, min(nsplit, kMaxParts / 2));
-    nsplit = max(1, min(nsplit, max(1, n_tiles)));
-    nsplit = max(nsplit, (n_tiles + kMaxPerTiles - 1) / kMaxPerTiles);  // keep the key code within 13 bits
-    bool pair = pair_ok;
-    if (pair) {  // physical splits = workgroups per query block (<= 16), virtual = twice that
-      int phys = ctx->nsplit_override > 0 ? max(1, ctx->nsplit_override / 2) : min(16, nsplit);
-      phys = max(phys, (n_tiles + 2 * kMaxPerTiles - 1) / (2 * kMaxPerTiles));
-      phys = min(phys, 16);
-      if (2 * phys > n_tiles || 4 * phys < 32) pair = false;
-      else nsplit = 2 * phys;
-    }
-    const int per = max(1, (n_tiles + nsplit - 1) / nsplit);
-    int code_bits = 4;
-    while ((1 << code_bits) < per * 16) ++code_bits;
-    // per-lane list length of the wide scan: the global top-L spreads over 2*nsplit lists (tiles are dealt round-robin
-    // to the splits, 4-row groups alternate between the lane halves), so 8 per list hold it unless more than 8 of a
-    // query's best 16 fall into ONE list — with >= 16 lists a ~1e-8 event on unstructured data; the certificate
-    // (floors of full lists) catches it and the fallback re-scores. Few lists (tiny shards): keep 16.
-    const int LL = pair ? ctx->pair_ll : (L == 32 ? 32 : (2 * nsplit >= 16 ? 8 : 16));
-    const size_t need = (size_t)n_qblocks * qpb * 2 * nsplit * LL * sizeof(float);
-    if ((rc = grow(ctx, (void**)&ctx->cand_score, &ctx->cand_cap, need)) != T2L_OK) return rc;
+    const int rows = max(min(kSegmentRows, n_rows - row0), 0);
+    const SegmentPlan p = plan_segment(knobs, eff_mode, policy.merge_live, policy.heavy, Q, K, rows);
+    if ((rc = grow(ctx, (void**)&ctx->cand_score, &ctx->cand_cap, p.cand_bytes)) != T2L_OK) return rc;
     if (n_seg > 1) {
       seg_idx = ctx->seg_idx + (size_t)seg * Q * K;
       seg_score = ctx->seg_score + (size_t)seg * Q * K;
@@ -1983,11 +1829,7 @@ int search_impl(t2l_ctx* ctx, const float* q, int Q, int K, int32_t* out_idx, do
     const uint4* dbs = ctx->db_split ? ctx->db_split + (size_t)row0 * 64 : nullptr;
     const uint4* dbh = ctx->db_half ? ctx->db_half + (size_t)row0 * 32 : nullptr;
     const int off = (int)ctx->row_offset + row0;
-#define T2L_SEARCH(LLv, Lv) \
-  launch_search<LLv, Lv>(ctx, db, dbs, dbh, max(rows, 0), off, q, Q, K, nsplit, code_bits, seg_idx, seg_score, seg == 0, pair, s)
-    rc = LL == 5 ? T2L_SEARCH(5, 16) : LL == 6 ? T2L_SEARCH(6, 16) : (LL == 8 ? T2L_SEARCH(8, 16) : (L == 16 ? T2L_SEARCH(16, 16) : T2L_SEARCH(32, 32)));
-#undef T2L_SEARCH
-    if (rc != T2L_OK) return rc;
+    if ((rc = launch_search(ctx, p, db, dbs, dbh, rows, off, q, Q, K, seg_idx, seg_score, seg == 0, s)) != T2L_OK) return rc;
   }
   if (n_seg > 1) return merge_impl(ctx, ctx->seg_idx, ctx->seg_score, n_seg, Q, K, out_idx, out_score, s);
   return T2L_OK;
@@ -2007,7 +1849,7 @@ static void swap_lane(t2l_ctx* ctx, t2l_ctx::SearchLane& L) {
   std::swap(ctx->fb_prev, L.fb_prev);
   std::swap(ctx->host_stat, L.host_stat);
   std::swap(ctx->host_stat_dev, L.host_stat_dev);
-  std::swap(ctx->stat_seen, L.stat_seen);
+  std::swap(ctx->policy.stat_seen, L.stat_seen);
 }
 
 int search_join_impl(t2l_ctx* ctx, hipStream_t s) {
@@ -2036,7 +1878,7 @@ void free_lanes(t2l_ctx* ctx) {
 int search_lanes_impl(t2l_ctx* ctx, const float* q, int Q, int K, int32_t* out_idx, double* out_score, hipStream_t s) {
   // one launch pair per call is what pipelines; everything else (small batches on the streaming scan, multi-segment shards,
   // databases in heavy mode with their extra stages, empty shards) runs in the caller's stream after a join
-  const bool plain = ctx->n_lanes <= 1 || Q < 256 || ctx->heavy || ctx->db_rows <= 0 || (int)ctx->db_rows > kSegmentRows;
+  const bool plain = ctx->n_lanes <= 1 || Q < 256 || ctx->policy.heavy || ctx->db_rows <= 0 || (int)ctx->db_rows > kSegmentRows;
   if (plain) {
     int rc = search_join_impl(ctx, s);
     return rc != T2L_OK ? rc : search_impl(ctx, q, Q, K, out_idx, out_score, s);
@@ -2046,11 +1888,11 @@ int search_lanes_impl(t2l_ctx* ctx, const float* q, int Q, int K, int32_t* out_i
     T2L_HIP(ctx, hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
     T2L_HIP(ctx, hipEventCreateWithFlags(&L.done, hipEventDisableTiming));
     if (!ctx->lane_fork) T2L_HIP(ctx, hipEventCreateWithFlags(&ctx->lane_fork, hipEventDisableTiming));
-    T2L_HIP(ctx, hipMalloc(&L.fb_count, 256 * sizeof(int32_t)));  // two banks (reset_counts)
-    T2L_HIP(ctx, hipMemset(L.fb_count, 0, 256 * sizeof(int32_t)));
-    L.fb_prev = L.fb_count + 128;
-    if (hipHostMalloc((void**)&L.host_stat, 8 * sizeof(int32_t), hipHostMallocMapped) == hipSuccess) {
-      for (int i = 0; i < 8; ++i) L.host_stat[i] = 0;
+    T2L_HIP(ctx, hipMalloc(&L.fb_count, 2 * kBankInts * sizeof(int32_t)));  // two banks (t2l_internal.h: CounterSlot)
+    T2L_HIP(ctx, hipMemset(L.fb_count, 0, 2 * kBankInts * sizeof(int32_t)));
+    L.fb_prev = L.fb_count + kBankInts;
+    if (hipHostMalloc((void**)&L.host_stat, kStatInts * sizeof(int32_t), hipHostMallocMapped) == hipSuccess) {
+      for (int i = 0; i < kStatInts; ++i) L.host_stat[i] = 0;
       if (hipHostGetDevicePointer((void**)&L.host_stat_dev, L.host_stat, 0) != hipSuccess) L.host_stat_dev = nullptr;
     }
     L.ready = true;

@@ -194,7 +194,7 @@ __device__ __forceinline__ void tilew_steps(const char* tb, const char* tbn, con
 // shift 0 here and are sent to the exact float64 scan by the re-rank, which evaluates the same predicate.
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 constexpr int kHalfShiftMax = 100;
-constexpr int kHalfTileBytes = kTileRows * 512;  // 32 rows x 256 f16 = 16 KiB, tile-chunk-major (below)
+// (kHalfTileBytes = 32 rows x 256 f16 = 16 KiB, tile-chunk-major (below): search_plan.h)
 
 __device__ __forceinline__ bool half_shift_of(float absmax, int& shift) {  // false = not representable (see above)
   const int e = (int)((__float_as_uint(absmax) >> 23) & 0xffu) - 127;
@@ -340,6 +340,17 @@ struct TileSelLists {
 constexpr int kTileSelGroup = 8;                     // scores per tile-local group: the 16 accumulator registers of a lane-tile are two groups
 constexpr int kTileSelGroupOps = 43;                 // VALU ops per group: 29 selection + 12 list insertion + 2 for (dA, dB)
 constexpr int kTileSelOps = 2 * kTileSelGroupOps;    // per lane-tile and query group
+
+// a plain list of LL keys (a multiple of 4) to its place in the candidate buffer [Q][parts][LL] (scanw / scanh, search.hip)
+template <int LL>
+__device__ __forceinline__ void put_list4(float* __restrict__ cand, int qrow, int Q, int parts, int part, const float (&ls)[LL]) {
+  if (qrow < Q) {
+    float4* out = reinterpret_cast<float4*>(cand + ((size_t)qrow * parts + part) * LL);
+#pragma unroll
+    for (int i = 0; i < LL / 4; ++i) out[i] = make_float4(ls[4 * i], ls[4 * i + 1], ls[4 * i + 2], ls[4 * i + 3]);
+  }
+}
+
 // KEYS: `prev` holds finished keys (the scan's epilogue: rows past the end are -inf there, never a NaN), not scores.
 template <int LL, int O, int CS, bool KEYS = false>
 __device__ __forceinline__ void tile_sel_op(float (&ls)[LL], float& dA, float& dB, TileSelLists<LL>& w, const f32x16& prev, int vmask,

@@ -222,7 +222,7 @@ __global__ __launch_bounds__(256) void exact_list_kernel(const float* __restrict
     const int qid = list[i];
     __syncthreads();
     qs[threadIdx.x] = (double)q[(size_t)qid * kD + threadIdx.x];
-    if (threadIdx.x == 0) atomicAdd(&fb_count[0], 1);
+    if (threadIdx.x == 0) atomicAdd(&fb_count[kCntExactScan], 1);
     __syncthreads();
     exact_scan<32>(db, n_rows, qs, K, row_offset, out_idx + (size_t)qid * K, out_score ? out_score + (size_t)qid * K : nullptr,
                    red_s, red_i, red_t);
@@ -248,11 +248,11 @@ int exact_stage_impl(t2l_ctx* ctx, const float* db, int n_rows, int row_offset, 
   int32_t* list4 = ctx->flags + (size_t)4 * Q;
   event_begin(ctx, "search_exact", s);
   hipLaunchKernelGGL(exactd_kernel, dim3(min((Q + kExactQ - 1) / kExactQ, 256)), dim3(256), lds, s, db, n_rows, q, K, L, row_offset,
-                     code_bits, list3, ctx->fb_count + 4, ctx->db_norm_max, out_idx, out_score, list4, ctx->fb_count + 6,
-                     ctx->fb_count + 7);
+                     code_bits, list3, ctx->fb_count + kCntDeferred, ctx->db_norm_max, out_idx, out_score, list4, ctx->fb_count + kCntExactUncert,
+                     ctx->fb_count + kCntExactServed);
   T2L_HIP(ctx, hipGetLastError());
   hipLaunchKernelGGL(exact_list_kernel, dim3(min(Q, 128)), dim3(256), 0, s, db, n_rows, q, K, row_offset, list4,
-                     ctx->fb_count + 6, out_idx, out_score, ctx->fb_count);
+                     ctx->fb_count + kCntExactUncert, out_idx, out_score, ctx->fb_count);
   event_end(ctx, "search_exact", s);
   T2L_HIP(ctx, hipGetLastError());
   return T2L_OK;

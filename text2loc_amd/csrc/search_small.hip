@@ -400,7 +400,7 @@ __global__ __launch_bounds__(256) void smallq_kernel(const float* __restrict__ d
 bool search_small_applies(const t2l_ctx* ctx, int Q, int K) {
   const int64_t n = ctx->db_rows;
   return ctx->search_small && Q >= 1 && Q <= kSmallMaxQ && K >= 1 && K <= T2L_MAX_TOPK && n > 0 && n <= (int64_t)kSmallMaxG * kSmallMaxR &&
-         ctx->search_mode == 0 && ctx->nsplit_override == 0;
+         ctx->knobs.search_mode == 0 && ctx->knobs.nsplit_override == 0;
 }
 
 int search_small_impl(t2l_ctx* ctx, const float* q, int Q, int K, int32_t* out_idx, double* out_score, hipStream_t s) {

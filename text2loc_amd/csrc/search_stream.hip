@@ -320,7 +320,7 @@ __global__ __launch_bounds__(256) void exact_only_kernel(const float* __restrict
     if (!flags[qid]) continue;
     __syncthreads();
     qs[threadIdx.x] = (double)q[(size_t)qid * kD + threadIdx.x];
-    if (threadIdx.x == 0) atomicAdd(&fb_count[0], 1);
+    if (threadIdx.x == 0) atomicAdd(&fb_count[kCntExactScan], 1);
     __syncthreads();
     exact_scan<32>(db, n_rows, qs, K, row_offset, out_idx + (size_t)qid * K,
                    out_score ? out_score + (size_t)qid * K : nullptr, red_s, red_i, red_t);
@@ -359,10 +359,10 @@ static int stream_launch(t2l_ctx* ctx, const float* q, int Q, int K, int32_t* ou
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr_done.mark(ctx->device);
   }
-  const float eps_rel = (float)(ctx->eps_scale * ((kD + 8) * 5.9604644775390625e-08 + 9.85e-4));  // f16 operands (search.hip)
-  // all 16 counters of the bank, not only the two this path counts in: the bank still holds the last batched call's [2..15], and
+  const float eps_rel = (float)(ctx->knobs.eps_scale * ((kD + 8) * 5.9604644775390625e-08 + 9.85e-4));  // f16 operands (search.hip)
+  // all kCntCleared (16) counters of the bank, not only the two this path counts in: the bank still holds the last batched call's [2..15], and
   // t2l_search_counters / t2l_search_fallbacks answer for THIS call (a cleared bank is what a first call finds, search.hip: reset_counts)
-  T2L_HIP(ctx, hipMemsetAsync(ctx->fb_count, 0, 16 * sizeof(int32_t), s));
+  T2L_HIP(ctx, hipMemsetAsync(ctx->fb_count, 0, kCntCleared * sizeof(int32_t), s));
   for (int q0 = 0; q0 < Q; q0 += kStreamQ) {
     const int nq = min(kStreamQ, Q - q0);
     event_begin(ctx, "search_scan", s);

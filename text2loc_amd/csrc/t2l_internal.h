@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "t2l.h"
+#include "search_plan.h"
 
 namespace t2l {
 
@@ -19,16 +20,36 @@ constexpr int kS = T2L_OBJECT_SIZE; // 28 object slots per cell
 constexpr int kSP = 32;             // slots padded to one 32-row MFMA tile
 
 // ---- search geometry -------------------------------------------------------------------------
-constexpr int kTileRows = 32;                      // DB rows per LDS tile (one 32x32 MFMA row block)
-constexpr int kRowStrideF = kD + 4;                // LDS row stride in floats (1040 B): ds_read_b128 conflict-free
-constexpr int kTileFloats = kTileRows * kRowStrideF;
+// (kTileRows, kRowStrideF, kTileFloats, kMaxParts, kMaxPerTiles, kSegmentRows: search_plan.h, which the host-only tests share)
+static_assert(kScanDim == kD, "search_plan.h plans for rows of kD floats");
 constexpr int kQPerWave = 32;
 constexpr int kScanWaves = 4;
 constexpr int kQPerBlock = kQPerWave * kScanWaves; // 128 queries per workgroup
 constexpr int kStageCap = 32;                      // staged (score,row) slots per lane between compactions
-constexpr int kMaxParts = 64;                      // per-query candidate partitions (= 2 * nsplit) the re-rank merges
-constexpr int kMaxPerTiles = 512;                  // tiles per split of one scan launch (13 key code bits)
-constexpr int kSegmentRows = (kMaxParts / 2) * kMaxPerTiles * 32;  // rows one scan launch covers (524,288); also the unit inside which the f16 plane deals rows to tiles strided
+
+// ---- search counters ---------------------------------------------------------------------------
+// A counter bank (dev i32[kBankInts]), per t2l_search call. Two banks in one allocation: a call counts in `fb_count`, which the
+// call before it left zeroed; `fb_prev` is that earlier call's bank. The first scan launch of a call (reset_counts, search.hip)
+// parks the finished call's [0..15] at fb_count[kReportBase ..] — rerank_kernel publishes that copy to the host's report card
+// (search_plan.h: ReportField) — and clears fb_prev for the call after this one. The host swaps the two per call. No workgroup
+// of a call ever waits for this reset (a launch may count from its first finished query block on, whatever workgroup 0 is doing).
+// t2l_search_counters hands out slots 0..7 (engine.py: search_counters names them).
+enum CounterSlot {
+  kCntExactScan = 0,      // queries that ended in an exact float64 VALU scan
+  kCntRescored = 1,       // queries whose first certificate failed (settled in the wave or not), or re-scored beyond the first L candidates
+  kCntUnsettled = 2,      // queries the first certificate + in-wave re-score left unsettled
+  kCntProbe = 3,          // f16-probe count (auto mode: what the f16 band would flag while the split-bf16 scan stands in)
+  kCntDeferred = 4,       // queries deferred to the float64 MFMA stage (heavy mode); the length of its list
+  kCntWideRepair = 5,     // queries a WIDE in-wave repair settled
+  kCntExactUncert = 6,    // queries the MFMA stage could not certify; the length of exact_list_kernel's list
+  kCntExactServed = 7,    // queries the MFMA stage served
+  kCntQ = 9,              // Q of the call (rerank_kernel)
+  kCntStatMode = 10,      // stat mode of the call: 0 not an f16-certificate count, 1 f16 scan, 2 split-bf16 stand-in probing for it
+  kCntDeferredSegs = 12,  // kCntDeferred of the earlier segments of a multi-segment shard (the deferred lists are per segment)
+  kCntCleared = 16,       // slots parked and cleared per call ([16..63]: phase stamps of dev builds, T2L_STAMPS)
+  kReportBase = 64,       // the previous call's [0..15], parked
+  kBankInts = 128,
+};
 
 // Per-kernel timing: a ring of hipEvent pairs recorded on the caller's stream (no sync when recording);
 // t2l_kernel_stats() reads them back after the caller's own synchronisation point.
@@ -70,8 +91,8 @@ struct t2l_ctx {
   // search workspace
   float* cand_score = nullptr;   // candidate keys [Q][2*nsplit][L]
   int32_t* flags = nullptr;      // dev i32[Q]: 1 = first-stage certificate failed -> fallback kernel
-  int32_t* fb_count = nullptr;   // dev i32[128] (2 used): [0] exact-scan fallbacks, [1] stage-2 re-scores of the last search
-  int32_t* fb_prev = nullptr;    // the other bank of the same allocation (search.hip: reset_counts); the host swaps the two per call
+  int32_t* fb_count = nullptr;   // dev i32[kBankInts]: this call's counter bank (CounterSlot above)
+  int32_t* fb_prev = nullptr;    // the other bank of the same allocation; the host swaps the two per call
   int32_t* seg_idx = nullptr;    // per-segment results when the shard exceeds one scan launch
   double* seg_score = nullptr;
   size_t cand_cap = 0, flag_cap = 0, seg_idx_cap = 0, seg_score_cap = 0;  // bytes
@@ -99,19 +120,10 @@ struct t2l_ctx {
   int text_head_rows = 0;        // token rows per pass of the text head (0 = default 16,384)
   int pn_self_loops = 1;         // PyG PointConv add_self_loops quirk on the bipartite batch (oracle/t2l_oracle_pointnet.py)
   // options
-  double eps_scale = 1.0;
-  int nsplit_override = 0;
-  int search_mode = 0;   // 0 = f16 MFMA scan (default), 1 = exact-f32 MFMA scan, 2 = split-bf16 MFMA scan
-  // mode 0 watches how many queries of a batch its certificate sends to the second stage (the fallback kernel writes the
-  // count to mapped host memory; no stream operation, no synchronisation) and, when that is more than one in eight —
-  // scores packed tighter than the f16 error band — searches with the split-bf16 scan (50x tighter bound) until fewer than
-  // one in sixteen would be flagged again
+  t2l::SearchKnobs knobs;  // what the launch plan reads (search_plan.h)
   int encoder_f32 = 0;   // 1: the all-f32-MFMA encoder kernel even when the split-f16 one is safe (encode_shaped.hip)
   int encoder_f16 = 0;   // 1: plain-f16 products (one MFMA per operand pair) instead of split-f16: ~1e-4 instead of 2e-7, 28 % faster
   int search_auto = 1;
-  int pair_ll = 6;       // per-lane list length of the paired scan (5 or 6)
-  int search_epilogue = 1;  // paired scan: 1 = the short epilogue + records laid out by XCD (scanp_kernel<..., SEL = 1>, record_slot), 0 = round 6's (SEL = 2)
-  int search_tile_sel = 1;  // paired scan with the tile-local top-3 selection (scanp_kernel<..., SEL = 1>; merged records only)
   int search_small = 1;      // batches of <= 16 queries against <= 65,536 rows: the one-launch exact float64 search (search_small.hip)
   int search_small_wgs = 0;  // ... its workgroups per 4-query slice (0 = by query count: 128 for Q <= 2 or Q > 8, else 192)
   bool last_search_small = false;  // the last search ran the one-launch path: t2l_search_fallbacks answers 0 (it leaves the counters alone)
@@ -119,28 +131,16 @@ struct t2l_ctx {
   unsigned small_ticket_base[4] = {0, 0, 0, 0};
   void* small_part = nullptr;             // published per-workgroup top-K lists {f64 score | i32 row}
   size_t small_part_cap = 0;
-  int wide_repair = 512;  // rows a re-rank wave may re-score in a wide repair before the query goes to an exact scan (0: never)
   int encoder_two_cells = 1;  // encode_cells: two cells per eight-wave workgroup on LDS planes (encode.hip: encode_cells2_kernel); 0: the one-cell kernel (encode_shaped.hip)
-  int search_merge = 2;    // the paired scan merges a workgroup's four lists per query into one 32-byte record (search.hip: MERGE / MG):
-                           // 0 never, 1 always, 2 while the f16 report cards show next to no failed first certificates (a repair behind
-                           // a merged record re-scores 4x the rows of a plain list's)
-  bool merge_live = true;  // (search_merge == 2) what the report cards say right now
-  int xcd_qgroups = 4;   // paired scan: query-block groups per XCD rectangle (1 = every XCD sees all queries and 1/8 of the splits;
-                         // 4 = a quarter of the queries and half of the splits: -1.3 us of scan span at Q = 4096 x N = 11,259, measured)
   int train_bf16 = 0;       // 1: the training step's GEMMs round their operands to bf16 (one bf16 MFMA per 16-step); 2: split-bf16 (three)
   int text_train_bf16 = 2;  // the same for the TEXT head's training GEMMs (d_model 1024: 466 GFLOP per step at B = 64): default split-bf16 —
                             // f32-class products (<= 2^-16 + 2^-18 relative, f32 accumulation, f32 exponent range) at 1.8x the f32 MFMA path's speed
   int train_gemm_block = 0;   // output block of the training step's tile GEMMs: 64 (2 x 2 tiles per wave: half the operand traffic), 32, or
                               // 0 = by measurement: 64 with bf16 / split-bf16 operands (0.555 -> 0.533 ms per step), 32 in f32 (0.640 vs 0.660)
   int train_keep_adam = 0;  // 1: t2l_train_bind keeps Adam moments + step when the parameter list is unchanged (a re-bind)
-  int eff_mode = 0;           // the scan the current t2l_search call runs
-  bool heavy = false;         // the database defeats the certificates: flagged queries go to the float64 MFMA stage
-  bool all_exact = false;     // ... and nearly all of them: EVERY query goes there, no candidate scan (search_impl)
-  unsigned all_exact_calls = 0;
-  bool escalated = false;     // the split-bf16 scan is standing in (it counts what the f16 band would still flag)
-  int32_t* host_stat = nullptr;      // mapped pinned host int32[8]: {sequence number of the last finished call, flagged, Q, previous exact-stage count, f16 stat, first-certificate failures}
+  t2l::SearchPolicy policy;          // what the report cards say about the next call (search_plan.h)
+  int32_t* host_stat = nullptr;      // mapped pinned host int32[kStatInts]: the report card (search_plan.h: ReportField)
   int32_t* host_stat_dev = nullptr;  // its device address
-  int stat_seq = 0, stat_seen = 0;
   // Pipelined searches (option "search_lanes" = n > 1): consecutive t2l_search calls are independent jobs, so call i runs its
   // scan -> re-rank chain on internal stream i % n with that lane's own scratch set; the chains overlap on the GPU (the next
   // scan's workgroups start while the previous call re-ranks; no kernel-boundary bubble between calls). Results are ordered
@@ -163,7 +163,6 @@ struct t2l_ctx {
   unsigned long long* scan_span = nullptr;  // dev u64[kSpanRing][kSpanWgs][2]: per workgroup {seq << 40 | start tick, seq << 40 | end tick}
   unsigned* span_grid = nullptr;            // host u32[kSpanRing]: grid of the launch in each ring entry (0: not stamped)
   unsigned span_seq = 0, span_read = 0, busy_read = 0;
-  int profile_rerank = 1;  // 0: sampled launches bracket the scan only (an event pair costs the stream ~6 us per kernel)
   int profile_events = 0;  // 0 off, n >= 1: record every n-th launch of each kernel
   std::unordered_map<std::string, t2l::EventRing> events;
 };
