@@ -280,24 +280,33 @@ int t2l_contrastive_loss(t2l_ctx* ctx, const float* anchor, const float* positiv
  * linear1.{weight [4096,1024],bias}, linear2.{weight [1024,4096],bias}, norm1.*, norm2.*}, inter_mlp.0.{0.weight [D,1024], 0.bias,
  * 1.weight, 1.bias, 1.running_mean, 1.running_var}, D <= 256; intra_module_num_layers must be 1 (the reference's default,
  * training/args.py:71). Synchronous; the library keeps packed copies.
+ * t2l_text_head_load_weights_heads: the same with the head count of the inter-sentence layer (inter_module_num_heads,
+ * training/args.py:70; a state dict does not carry it). `inter_module.0.*`, when present, is packed for t2l_text_inter when its
+ * width is D (that of inter_mlp) in {128, 256}, D / inter_num_heads is 32 or 64 (2 or 4 heads at 128, 4 or 8 at 256), its
+ * dim_feedforward is 4 D and there is no inter_module.1; any other width or head count, a second layer or mis-sized tensors do not
+ * fail the load: t2l_text_head works and t2l_text_inter answers T2L_ESTATE. t2l_text_head_load_weights is this call with 4 heads.
  * t2l_text_head: hidden = dev f32[n_sentences, n_tokens, 1024] (T5's last_hidden_state, sentence-major as the reference's
  * tokenizer call produces it), 1 <= n_tokens <= 32; out = dev f32[n_sentences, D]. Arithmetic: split-f16 MFMA products with f32
  * accumulation (~5e-7 relative; option "encoder_f16" = 1: one f16 product per operand pair, ~1e-4). *overflow (dev int32, may be
  * NULL) is set to 1 when a value entering a product left the f16 range (|v| >= 3e4 or non-finite): `out` is then not to be
  * trusted and the caller runs that batch on its f32 path. Option "text_head_rows" (default 16,384): token rows per pass. */
 int t2l_text_head_load_weights(t2l_ctx* ctx, const t2l_weight_desc* w, int32_t n, const char* prefix);
+int t2l_text_head_load_weights_heads(t2l_ctx* ctx, const t2l_weight_desc* w, int32_t n, const char* prefix, int32_t inter_num_heads);
 int t2l_text_head(t2l_ctx* ctx, const float* hidden, int32_t n_sentences, int32_t n_tokens, float* out, int32_t* overflow,
                   void* stream);
 /* t2l_text_inter — the other half of the head, eval mode. Replaces: LanguageEncoder.forward from
  * `description_encodings.view(batch_size, num_sentence, -1)` to its return value (models/language_encoder.py:137-147):
- * x = sent.view(n_descriptions, n_sentences_per, 256); x += TransformerEncoderLayer(d_model 256, 4 heads, dim_feedforward 1024,
+ * x = sent.view(n_descriptions, n_sentences_per, D); x += TransformerEncoderLayer(d_model D, heads, dim_feedforward 4 D,
  * post-norm, ReLU)(x) over the sentences of every description (the residual AROUND the layer is the reference's `+=`); max over
- * the sentences. sent = dev f32[n_descriptions * n_sentences_per, 256], description-major (exactly what t2l_text_head returns for
- * the reference's sentence order); out = dev f32[n_descriptions, 256] (NOT normalised: CellRetrievalNetwork.encode_text does that,
- * models/cell_retrieval.py:57-63). 1 <= n_sentences_per <= 32. Needs `inter_module.0.*` (in_proj [768,256], out_proj [256,256],
- * linear1 [1024,256], linear2 [256,1024], norm1, norm2) among the tensors handed to t2l_text_head_load_weights and
- * inter_module_num_layers = 1 (training/args.py:72's default); T2L_ESTATE otherwise (the fine model has no such layer). Same
- * arithmetic, overflow flag and kernels (with d_model 256) as t2l_text_head. */
+ * the sentences. D and heads are those of the loaded head (t2l_text_head_load_weights_heads): D = the width of inter_mlp, 128 or
+ * 256, with heads of 32 or 64 features: (256, 4) — the published model —, (256, 8), (128, 4) — --coarse_embed_dim 128 — and (128, 2).
+ * sent = dev f32[n_descriptions * n_sentences_per, D], description-major (exactly what t2l_text_head returns for
+ * the reference's sentence order); out = dev f32[n_descriptions, D] (NOT normalised: CellRetrievalNetwork.encode_text does that,
+ * models/cell_retrieval.py:57-63). 1 <= n_sentences_per <= 32. Needs `inter_module.0.*` (in_proj [3 D, D], out_proj [D, D],
+ * linear1 [4 D, D], linear2 [D, 4 D], norm1, norm2) among the tensors handed to the loader and
+ * inter_module_num_layers = 1 (training/args.py:69's default); T2L_ESTATE, with the compiled set in the message, otherwise (the fine
+ * model has no such layer). One launch; split-f16 MFMA products with f32 accumulation, plain f16 under option "encoder_f16", and the
+ * overflow flag of t2l_text_head. */
 int t2l_text_inter(t2l_ctx* ctx, const float* sent, int32_t n_descriptions, int32_t n_sentences_per, float* out, int32_t* overflow,
                    void* stream);
 

@@ -221,8 +221,14 @@ class LanguageEncoder(nn.Module):
                 and self._layer_is_stock(self.intra_module[0], 1024, 4096, 4) and isinstance(bn, nn.BatchNorm1d) and abs(bn.eps - 1e-5) < 1e-12)
 
     def _inter_gate(self, n_sent_per: int) -> bool:
-        return (not self.is_fine and len(self.inter_module) == 1 and self.inter_mlp[0][0].out_features == 256 and 1 <= n_sent_per <= 32
-                and self._layer_is_stock(self.inter_module[0], 256, 1024, 4))
+        """True exactly for what t2l_text_inter is compiled for: the coarse model, one stock inter layer of width D in {128, 256} with
+        heads of 32 or 64 features and a 4 D feed-forward, 1..32 sentences per description."""
+        if self.is_fine or len(self.inter_module) != 1 or not 1 <= n_sent_per <= 32:
+            return False
+        D, layer = self.inter_mlp[0][0].out_features, self.inter_module[0]
+        heads = layer.self_attn.num_heads
+        return (D in (128, 256) and heads > 0 and D % heads == 0 and D // heads in (32, 64)
+                and self._layer_is_stock(layer, D, 4 * D, heads))
 
     def _head_params(self):
         ps = getattr(self, "_th_params", None)
@@ -240,7 +246,8 @@ class LanguageEncoder(nn.Module):
                 self._th_engine = Engine(idx)
             sd = {"language_encoder." + n: t for n, t in self.state_dict().items()
                   if n.startswith(("intra_module.", "inter_mlp.", "inter_module."))}
-            self._th_engine.text_head_load_weights(sd)
+            inter = getattr(self, "inter_module", None)  # (the fine head has none; the loader's default then)
+            self._th_engine.text_head_load_weights(sd, inter_num_heads=inter[0].self_attn.num_heads if inter is not None and len(inter) else 4)
             self._th_params = None  # (load_state_dict may have swapped tensors: re-collect)
             version = (idx, self._head_generation) + tuple((t.data_ptr(), t._version) for t in self._head_params())
             self._th_version = version
@@ -408,7 +415,7 @@ class LanguageEncoder(nn.Module):
         n_per = x.shape[0] // batch_size
         if self.is_fine:
             return x.view(batch_size, n_per, -1)
-        if engine_ok and self._inter_gate(n_per):  # the 256-wide half in the engine too (t2l_text_inter)
+        if engine_ok and self._inter_gate(n_per):  # the inter-sentence half in the engine too (t2l_text_inter)
             out, flag = self._head_engine(x.device).text_inter(x.contiguous(), batch_size, check=False)
             out, overflowed = self._settle(out, flag)
             if not overflowed:

@@ -402,10 +402,14 @@ int t2l_contrastive_loss(t2l_ctx* ctx, const float* anchor, const float* positiv
 }
 
 int t2l_text_head_load_weights(t2l_ctx* ctx, const t2l_weight_desc* w, int32_t n, const char* prefix) {
+  return t2l_text_head_load_weights_heads(ctx, w, n, prefix, 4);
+}
+
+int t2l_text_head_load_weights_heads(t2l_ctx* ctx, const t2l_weight_desc* w, int32_t n, const char* prefix, int32_t inter_num_heads) {
   if (!ctx) return T2L_EINVAL;
   if (!w || n <= 0) return fail(ctx, T2L_EINVAL, "t2l_text_head_load_weights: null/empty arguments");
   T2L_HIP(ctx, hipSetDevice(ctx->device));
-  return text_head_load_impl(ctx, w, n, prefix);
+  return text_head_load_impl(ctx, w, n, prefix, inter_num_heads);
 }
 
 int t2l_text_head(t2l_ctx* ctx, const float* hidden, int32_t n_sentences, int32_t n_tokens, float* out, int32_t* overflow, void* stream) {

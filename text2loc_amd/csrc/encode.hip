@@ -1,5 +1,5 @@
-// The cell encoder at the published shape (256, 4 heads, 28 slots) in its default form, the fused t2l_text_inter layer, and the
-// weight loader of every encoder kernel.
+// The cell encoder at the published shape (256, 4 heads, 28 slots) in its default form, the fused t2l_text_inter layer at every compiled
+// (width, heads), and the weight loader of every encoder kernel.
 //
 // encode_cells2_kernel: ObjectEncoder.forward (models/object_encoder.py:66-153, eval mode) +
 // CellRetrievalNetwork.encode_objects (models/cell_retrieval.py:65-110) as ONE kernel, two cells per eight-wave workgroup, every
@@ -142,29 +142,31 @@ __device__ __forceinline__ void small_mlp(const SmallMlp& m, const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------
-// t2l_text_inter as ONE launch (models/language_encoder.py:137-147): x = sent.view(B, S, 256); x += TransformerEncoderLayer(256, 4 heads,
-// ff 1024, post-norm, ReLU)(x) over the S sentences of a description; max over the sentences. The layer is the cell encoder's
+// t2l_text_inter as ONE launch (models/language_encoder.py:137-147): x = sent.view(B, S, D); x += TransformerEncoderLayer(D, heads,
+// ff 4 D, post-norm, ReLU)(x) over the S sentences of a description; max over the sentences. Compiled for D in {128, 256} with heads of
+// 32 or 64 features; (256, 4 heads) is the published model. The layer is the cell encoder's
 // (encode_shaped.hip) with three differences: a 32-row tile holds floor(32 / S) whole DESCRIPTIONS and a query attends to the keys of its own
 // description only (block-diagonal mask; rows past the tile's last description are zero rows that form groups of their own: every
-// softmax has its own row as a key, nothing is NaN); the feed-forward hidden layer is 1,024 wide = four passes through `buf`
-// (pass c = hidden units [128c, 128c+128) and [512+128c, 512+128c+128): what k-steps [16c, 16c+16) of W2's half-split packing at
-// K = 1,024 cover); and the inputs are not bounded by the weights (they come out of inter_mlp), so every value that enters a
+// softmax has its own row as a key, nothing is NaN); the feed-forward hidden layer is 4 D wide = four passes through the B planes
+// (pass c = hidden units [c D/2, (c + 1) D/2) and 2 D + [c D/2, (c + 1) D/2): what k-steps [c D/16, (c + 1) D/16) of W2's half-split
+// packing at K = 4 D cover); and the inputs are not bounded by the weights (they come out of inter_mlp), so every value that enters a
 // split-f16 product is watched against the f16 range at run time: a tile that leaves it raises *flag and the caller redoes the batch
 // on the PyTorch modules (the protocol of t2l_text_head).
-// (The kernel: text_inter_fused2_kernel below — two tiles per eight-wave workgroup on LDS planes. The one-tile form on f32 tiles that
+// (The kernel: text_inter_fused2_kernel below — two tiles per workgroup of D / 32 waves on LDS planes. The one-tile form on f32 tiles that
 // this comment used to head was removed in round 5: 0.208 vs 0.179 ms for 4,096 descriptions x 6 sentences.)
 
 // ------------------------------------------------------------------------------------------------
 // The launch — the testbed for the lever the encoder family is left with (the packed-weight
-// stream out of the L2 is worth 23-32 % of these kernels, the per-MFMA VALU work another third): TWO row tiles per workgroup of EIGHT
-// waves, every activation resident in LDS as split-f16 PLANES (hi | lo, rows of 264 halves), so that
+// stream out of the L2 is worth 23-32 % of these kernels, the per-MFMA VALU work another third): TWO row tiles per workgroup of D / 32
+// waves (EIGHT at the published width), every activation resident in LDS as split-f16 PLANES (hi | lo, rows of D + 8 halves), so that
 //  * out_proj, linear1 and linear2 (3/4 of the FLOPs) load each weight fragment ONCE for both tiles — wave w owns one 32-wide tile of
 //    output features and multiplies it into both token tiles (products computed transposed: A = weight fragment, B = token fragment);
 //  * no operand is split in a GEMM loop: a token fragment is two ds_read_b128; the splitting happens once per produced element in the
 //    epilogues, which hold 4 consecutive features per register quad (transposed C layout) and store 8-byte plane pieces;
-//  * the attention runs as in the one-cell encoder, one wave per (tile, head), q/k/v projected per tile (their fragments are not shared), with
-//    O^T = V^T P^T so that its output has the same store-friendly layout.
-// 135 KB of LDS: one workgroup (two waves per SIMD) per CU. The residual is rebuilt from hi + lo (22 significand bits).
+//  * the attention runs as in the one-cell encoder, 64 / head_dim (tile, head) pairs per wave, q/k/v projected per tile (their fragments are
+//    not shared), with O^T = V^T P^T so that its output has the same store-friendly layout.
+// 135 KB of LDS at D = 256: one workgroup (two waves per SIMD) per CU; 70 KB at D = 128: two workgroups of four waves, the same two waves
+// per SIMD, and the second workgroup covers the first one's barriers. The residual is rebuilt from hi + lo (22 significand bits).
 #ifndef T2L_RING_DEPTH
 #define T2L_RING_DEPTH 3
 #endif
@@ -173,8 +175,16 @@ __device__ __forceinline__ void small_mlp(const SmallMlp& m, const float* __rest
 #endif
 constexpr int kQkRing = T2L_QK_RING;  // the same for the q / k projection (four weight tiles = 32 VGPRs per step; v: twice as deep)
 constexpr int kRingDepth = T2L_RING_DEPTH;  // k-steps of weight fragments in flight per wave in the row-wise products (8 VGPRs per step)
-constexpr int kLdP = 264;                 // halves per plane row (528 B: rows 4 banks apart, as the f32 tiles)
-constexpr int kPlane = kSP * kLdP;        // halves per plane
+// plane geometry at width D: rows of D + 8 halves (528 B at 256, 272 B at 128: rows 4 banks apart, as the f32 tiles of D + 4 floats)
+template <int D>
+struct PlaneGeo {
+  static constexpr int kLd = D + 8;          // halves per plane row
+  static constexpr int kSize = kSP * kLd;    // halves per plane
+  static constexpr int kLdF = D + 4;         // floats per row of the f32 tile the last LayerNorm may leave in a tile's B planes
+  static constexpr int kWaves = D / 32;      // waves of the workgroup: one per 32-wide tile of output features
+};
+constexpr int kLdP = PlaneGeo<kD>::kLd;   // the published width (the two-cell cell encoder below)
+constexpr int kPlane = PlaneGeo<kD>::kSize;
 typedef _Float16 ti_f16x4 __attribute__((ext_vector_type(4)));
 typedef float ti_f32x4 __attribute__((ext_vector_type(4)));
 
@@ -220,100 +230,130 @@ __device__ __forceinline__ void stream_weights(const uint4* __restrict__ wp, F&&
   }
 }
 
-__device__ __forceinline__ _Float16* pl_xh(_Float16* base, int t) { return base + (size_t)(4 * t + 0) * kPlane; }
-__device__ __forceinline__ _Float16* pl_xl(_Float16* base, int t) { return base + (size_t)(4 * t + 1) * kPlane; }
-__device__ __forceinline__ _Float16* pl_bh(_Float16* base, int t) { return base + (size_t)(4 * t + 2) * kPlane; }
-__device__ __forceinline__ _Float16* pl_bl(_Float16* base, int t) { return base + (size_t)(4 * t + 3) * kPlane; }
+template <int D = kD>
+__device__ __forceinline__ _Float16* pl_xh(_Float16* base, int t) { return base + (size_t)(4 * t + 0) * PlaneGeo<D>::kSize; }
+template <int D = kD>
+__device__ __forceinline__ _Float16* pl_xl(_Float16* base, int t) { return base + (size_t)(4 * t + 1) * PlaneGeo<D>::kSize; }
+template <int D = kD>
+__device__ __forceinline__ _Float16* pl_bh(_Float16* base, int t) { return base + (size_t)(4 * t + 2) * PlaneGeo<D>::kSize; }
+template <int D = kD>
+__device__ __forceinline__ _Float16* pl_bl(_Float16* base, int t) { return base + (size_t)(4 * t + 3) * PlaneGeo<D>::kSize; }
 
-// One post-norm TransformerEncoderLayer (d_model 256, 4 heads, ReLU, feed-forward of 256 FFP units) over the TWO 32-row token tiles of an
-// eight-wave workgroup, in place on the tiles' X planes (B planes: scratch). mask(i, j): may query row i see key row j (tile-local)?
-// WATCH: run-time f16-range watch on everything that enters a split product (`bad`). last_to_f32: the final LayerNorm leaves f32
-// [32][260] tiles in the B-plane regions instead of planes (for an epilogue that needs full precision). Ends behind a barrier.
-// lnred: 1,024 floats of LDS scratch (the row sums of the fused residual + LayerNorm epilogues).
-template <bool SG, int FFP, bool WATCH, typename Mask>
+// One post-norm TransformerEncoderLayer (d_model D, heads of HD features, ReLU, feed-forward of D * FFP units) over the TWO 32-row token
+// tiles of a workgroup of D / 32 waves, in place on the tiles' X planes (B planes: scratch). mask(i, j): may query row i see key row j
+// (tile-local)? WATCH: run-time f16-range watch on everything that enters a split product (`bad`). last_to_f32: the final LayerNorm
+// leaves f32 [32][D + 4] tiles in the B-plane regions instead of planes (for an epilogue that needs full precision). Ends behind a
+// barrier. lnred: 4 * (D / 32) * 32 floats of LDS scratch (the row sums of the fused residual + LayerNorm epilogues).
+// Compiled for D in {128, 256} and HD in {32, 64}; <256, 64> is the published shape: every constant below is then what the 256-only
+// form of this function spelled out, and its users return the same bits at the same speed.
+//   * the 2 D / HD (tile, head) pairs go 64 / HD to a wave (pair p = tile p / NH, head p % NH): a 64-wide head is two 32-row tiles of
+//     q^T, k^T and v, a 32-wide head is one (the score contraction is then two k-steps instead of four);
+//   * wave w owns output-feature tile w of out_proj, linear1 and linear2 for both token tiles;
+//   * pass c of the feed-forward covers k-steps [c D/16, (c + 1) D/16) of linear2's half-split packing at K = FFP D (mfma_h3.h:
+//     lane half kh of step s holds k = kh K/2 + 8 s ..), i.e. hidden units [c D/2, (c + 1) D/2) in columns [0, D/2) of the B planes and
+//     units K/2 + [c D/2, (c + 1) D/2) in columns [D/2, D): waves below D / 64 compute the former's tiles, the others the latter's.
+template <bool SG, int D, int HD, int FFP, bool WATCH, typename Mask>
 __device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& W, Mask mask, bool& bad, bool last_to_f32, float* lnred) {
+  static_assert(D == 128 || D == 256, "one wave per 32-wide feature tile, four or eight waves");
+  static_assert(HD == 32 || HD == 64, "a head is one or two 32-row tiles of q^T / k^T / v");
+  constexpr int LDP = PlaneGeo<D>::kLd, LDX = PlaneGeo<D>::kLdF, NW = PlaneGeo<D>::kWaves;
+  constexpr int KH = D / 2;       // k-values per lane half of a K = D product
+  constexpr int HS = D / 16;      // k-steps of a K = D product
+  constexpr int DT = D / 32;      // 32-row weight tiles per q / k / v block of in_proj
+  constexpr int NH = D / HD;      // heads
+  constexpr int LNH = NH == 2 ? 1 : NH == 4 ? 2 : 3;  // log2(NH)
+  constexpr int TPH = HD / 32;    // weight tiles per head
+  constexpr int PPW = 64 / HD;    // (tile, head) pairs per wave
+  constexpr float kScale = HD == 64 ? 0.125f : 0.17677669529663687f;  // 1 / sqrt(head_dim)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int col = lane & 31, half = lane >> 5;
   auto watch = [&](float v) { bad = bad || !(fabsf(v) < kSplitF16Safe); };
   auto watch4 = [&](ti_f32x4 v) { watch(v[0]); watch(v[1]); watch(v[2]); watch(v[3]); };
   (void)watch4;
-  {  // ---- self-attention: wave -> (tile t, head h); q^T, k^T, v from the tile's planes, scores / softmax / O^T from registers
-    const int t = wave >> 2, h = wave & 3;
-    constexpr int HS = kD / 16;
+#pragma unroll
+  for (int pp = 0; pp < PPW; ++pp) {  // ---- self-attention: wave -> (tile t, head h); q^T, k^T, v from the tile's planes, scores / softmax / O^T from registers
+    const int t = (wave * PPW + pp) >> LNH, h = (wave * PPW + pp) & (NH - 1);
     const float* ib = W.in_b;
-    const _Float16 *xh = pl_xh(base, t) + col * kLdP + half * 128, *xl = pl_xl(base, t) + col * kLdP + half * 128;
+    const _Float16 *xh = pl_xh<D>(base, t) + col * LDP + half * KH, *xl = pl_xl<D>(base, t) + col * LDP + half * KH;
     f32x16 st;
     float inv;
     {
-      f32x16 qT0, qT1, kT0, kT1;
+      f32x16 qT[TPH], kT[TPH];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) qT0[r] = qT1[r] = kT0[r] = kT1[r] = 0.f;
-      const uint4* hq0 = W.in_hp + ((size_t)(2 * h) * HS * 64 + lane) * 2;
-      const uint4* hq1 = W.in_hp + ((size_t)(2 * h + 1) * HS * 64 + lane) * 2;
-      const uint4* hk0 = W.in_hp + ((size_t)(8 + 2 * h) * HS * 64 + lane) * 2;
-      const uint4* hk1 = W.in_hp + ((size_t)(9 + 2 * h) * HS * 64 + lane) * 2;
-      {  // four weight tiles per step through a ring kQkRing steps deep (32 VGPRs per step)
-        constexpr int D = kQkRing;
-        HFrag ring[D][4];
-        auto load4 = [&](int s, HFrag (&f)[4]) {
-          f[0] = load_h1<SG>(hq0 + T2L_WSTEP(s) * 128);
-          f[1] = load_h1<SG>(hq1 + T2L_WSTEP(s) * 128);
-          f[2] = load_h1<SG>(hk0 + T2L_WSTEP(s) * 128);
-          f[3] = load_h1<SG>(hk1 + T2L_WSTEP(s) * 128);
+      for (int j = 0; j < TPH; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) qT[j][r] = kT[j][r] = 0.f;
+      const uint4* hqk[2 * TPH];  // the head's q tiles, then its k tiles
+#pragma unroll
+      for (int j = 0; j < TPH; ++j) {
+        hqk[j] = W.in_hp + ((size_t)(TPH * h + j) * HS * 64 + lane) * 2;
+        hqk[TPH + j] = W.in_hp + ((size_t)(DT + TPH * h + j) * HS * 64 + lane) * 2;
+      }
+      {  // 2 TPH weight tiles per step through a ring kQkRing steps deep (8 VGPRs per tile and step)
+        constexpr int RD = kQkRing;
+        HFrag ring[RD][2 * TPH];
+        auto loadqk = [&](int s, HFrag (&f)[2 * TPH]) {
+#pragma unroll
+          for (int e = 0; e < 2 * TPH; ++e) f[e] = load_h1<SG>(hqk[e] + T2L_WSTEP(s) * 128);
         };
 #pragma unroll
-        for (int i = 0; i < D; ++i) load4(i, ring[i]);
+        for (int i = 0; i < RD; ++i) loadqk(i, ring[i]);
 #pragma unroll
         for (int s = 0; s < HS; ++s) {
-          HFrag f[4];
+          HFrag f[2 * TPH];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) f[e] = ring[s % D][e];
-          if (s + D < HS) load4(s + D, ring[s % D]);
+          for (int e = 0; e < 2 * TPH; ++e) f[e] = ring[s % RD][e];
+          if (s + RD < HS) loadqk(s + RD, ring[s % RD]);
           __builtin_amdgcn_sched_barrier(0);
           const HFrag xf = plane_frag<SG>(xh, xl, 8 * s);
-          mfma_h3<SG>(qT0, f[0], xf);
-          mfma_h3<SG>(qT1, f[1], xf);
-          mfma_h3<SG>(kT0, f[2], xf);
-          mfma_h3<SG>(kT1, f[3], xf);
+#pragma unroll
+          for (int j = 0; j < TPH; ++j) mfma_h3<SG>(qT[j], f[j], xf);
+#pragma unroll
+          for (int j = 0; j < TPH; ++j) mfma_h3<SG>(kT[j], f[TPH + j], xf);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int f = (r & 3) + 8 * (r >> 2) + 4 * half;
-        qT0[r] += ib[h * 64 + f];
-        qT1[r] += ib[h * 64 + 32 + f];
-        kT0[r] += ib[kD + h * 64 + f];
-        kT1[r] += ib[kD + h * 64 + 32 + f];
+#pragma unroll
+        for (int j = 0; j < TPH; ++j) qT[j][r] += ib[h * HD + 32 * j + f];
+#pragma unroll
+        for (int j = 0; j < TPH; ++j) kT[j][r] += ib[D + h * HD + 32 * j + f];
       }
       // S^T = K Q^T (and O^T = V^T P^T below) as split-f16 products on the accumulator registers: kT / qT (v / P) sit in the same
       // MFMA output layout, so registers 0..7 and 8..15 of the two are matching k-halves of A and B — 12 MFMAs of 32 cycles here
-      // instead of 32 f32 MFMAs of 64 (the attention core was a third of a wave's matrix-pipe time in this layer). Always the
-      // three-product form (the logits carry the softmax); q, k, v are inside the load-time bound of the in_proj output (cell
-      // encoder) or watched here (WATCH).
+      // (64-wide heads) instead of 32 f32 MFMAs of 64 (the attention core was a third of a wave's matrix-pipe time in this layer).
+      // Always the three-product form (the logits carry the softmax); q, k, v are inside the load-time bound of the in_proj output
+      // (cell encoder) or watched here (WATCH).
       if constexpr (WATCH) {
         float wm = 0.f;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) wm = fmaxf(wm, fmaxf(fmaxf(fabsf(qT0[r]), fabsf(qT1[r])), fmaxf(fabsf(kT0[r]), fabsf(kT1[r]))));
+        for (int r = 0; r < 16; ++r) {
+          float wq = fabsf(qT[0][r]), wk = fabsf(kT[0][r]);
+#pragma unroll
+          for (int j = 1; j < TPH; ++j) {
+            wq = fmaxf(wq, fabsf(qT[j][r]));
+            wk = fmaxf(wk, fabsf(kT[j][r]));
+          }
+          wm = fmaxf(wm, fmaxf(wq, wk));
+        }
         watch(wm);
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) st[r] = 0.f;
 #pragma unroll
-      for (int m2 = 0; m2 < 2; ++m2) {  // (fenced: the compiler otherwise splits all eight fragments first — 64 registers of temporaries)
-        mfma_h3<false>(st, split_acc8<false>(kT0, m2), split_acc8<false>(qT0, m2));
-        __builtin_amdgcn_sched_barrier(0);
-      }
+      for (int j = 0; j < TPH; ++j)
 #pragma unroll
-      for (int m2 = 0; m2 < 2; ++m2) {
-        mfma_h3<false>(st, split_acc8<false>(kT1, m2), split_acc8<false>(qT1, m2));
-        __builtin_amdgcn_sched_barrier(0);
-      }
+        for (int m2 = 0; m2 < 2; ++m2) {  // (fenced: the compiler otherwise splits all the fragments first — 64 registers of temporaries)
+          mfma_h3<false>(st, split_acc8<false>(kT[j], m2), split_acc8<false>(qT[j], m2));
+          __builtin_amdgcn_sched_barrier(0);
+        }
       float m = -__builtin_inff();
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int j = (r & 3) + 8 * (r >> 2) + 4 * half;
-        st[r] = mask(col, j) ? st[r] * 0.125f : -__builtin_inff();
+        st[r] = mask(col, j) ? st[r] * kScale : -__builtin_inff();
         m = fmaxf(m, st[r]);
       }
       m = fmaxf(m, __shfl_xor(m, 32));
@@ -327,74 +367,91 @@ __device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& 
       inv = 1.f / sum;
     }
     {
-      f32x16 v0, v1;  // v straight: lane = feature column, register = token row
+      f32x16 v[TPH];  // v straight: lane = feature column, register = token row
 #pragma unroll
-      for (int r = 0; r < 16; ++r) v0[r] = v1[r] = 0.f;
-      const uint4* hv0 = W.in_hp + ((size_t)(16 + 2 * h) * HS * 64 + lane) * 2;
-      const uint4* hv1 = W.in_hp + ((size_t)(17 + 2 * h) * HS * 64 + lane) * 2;
+      for (int j = 0; j < TPH; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) v[j][r] = 0.f;
+      const uint4* hv[TPH];
+#pragma unroll
+      for (int j = 0; j < TPH; ++j) hv[j] = W.in_hp + ((size_t)(2 * DT + TPH * h + j) * HS * 64 + lane) * 2;
       {
-        constexpr int D = 2 * kQkRing;
-        HFrag ring[D][2];
+        constexpr int RD = 2 * kQkRing;
+        HFrag ring[RD][TPH];
 #pragma unroll
-        for (int i = 0; i < D; ++i) {
-          ring[i][0] = load_h1<SG>(hv0 + T2L_WSTEP(i) * 128);
-          ring[i][1] = load_h1<SG>(hv1 + T2L_WSTEP(i) * 128);
-        }
+        for (int i = 0; i < RD; ++i)
+#pragma unroll
+          for (int j = 0; j < TPH; ++j) ring[i][j] = load_h1<SG>(hv[j] + T2L_WSTEP(i) * 128);
 #pragma unroll
         for (int s = 0; s < HS; ++s) {
-          const HFrag f0 = ring[s % D][0], f1 = ring[s % D][1];
-          if (s + D < HS) {
-            ring[s % D][0] = load_h1<SG>(hv0 + T2L_WSTEP(s + D) * 128);
-            ring[s % D][1] = load_h1<SG>(hv1 + T2L_WSTEP(s + D) * 128);
+          HFrag f[TPH];
+#pragma unroll
+          for (int j = 0; j < TPH; ++j) f[j] = ring[s % RD][j];
+          if (s + RD < HS) {
+#pragma unroll
+            for (int j = 0; j < TPH; ++j) ring[s % RD][j] = load_h1<SG>(hv[j] + T2L_WSTEP(s + RD) * 128);
           }
           __builtin_amdgcn_sched_barrier(0);
           const HFrag xf = plane_frag<SG>(xh, xl, 8 * s);
-          mfma_h3<SG>(v0, xf, f0);
-          mfma_h3<SG>(v1, xf, f1);
+#pragma unroll
+          for (int j = 0; j < TPH; ++j) mfma_h3<SG>(v[j], xf, f[j]);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-      const float bv0 = ib[2 * kD + h * 64 + col], bv1 = ib[2 * kD + h * 64 + 32 + col];
+      float bv[TPH];
+#pragma unroll
+      for (int j = 0; j < TPH; ++j) bv[j] = ib[2 * D + h * HD + 32 * j + col];
       // O^T[f][i] = sum_j v[j][f] P[i][j]: A = v registers (lane = feature, lane half = the key of register r), B = P registers (lane =
       // query i, lane half = the same key) -> lane = query (token row), register quad = 4 consecutive features
-      f32x16 o0, o1;
+      f32x16 o[TPH];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) o0[r] = o1[r] = 0.f;
+      for (int j = 0; j < TPH; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[j][r] = 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         st[r] *= inv;
-        v0[r] += bv0;
-        v1[r] += bv1;
+#pragma unroll
+        for (int j = 0; j < TPH; ++j) v[j][r] += bv[j];
       }
       if constexpr (WATCH) {
         float wm = 0.f;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) wm = fmaxf(wm, fmaxf(fabsf(v0[r]), fabsf(v1[r])));
+        for (int r = 0; r < 16; ++r) {
+          float wv = fabsf(v[0][r]);
+#pragma unroll
+          for (int j = 1; j < TPH; ++j) wv = fmaxf(wv, fabsf(v[j][r]));
+          wm = fmaxf(wm, wv);
+        }
         watch(wm);
       }
 #pragma unroll
       for (int m2 = 0; m2 < 2; ++m2) {
         const HFrag pf = split_acc8<false>(st, m2);
-        mfma_h3<false>(o0, split_acc8<false>(v0, m2), pf);
-        mfma_h3<false>(o1, split_acc8<false>(v1, m2), pf);
+#pragma unroll
+        for (int j = 0; j < TPH; ++j) mfma_h3<false>(o[j], split_acc8<false>(v[j], m2), pf);
         __builtin_amdgcn_sched_barrier(0);
       }
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const ti_f32x4 a = {o0[4 * q], o0[4 * q + 1], o0[4 * q + 2], o0[4 * q + 3]};
-        const ti_f32x4 b = {o1[4 * q], o1[4 * q + 1], o1[4 * q + 2], o1[4 * q + 3]};
-        if constexpr (WATCH) watch4(a);
-        if constexpr (WATCH) watch4(b);
-        plane_put4<SG>(pl_bh(base, t), pl_bl(base, t), col * kLdP + h * 64 + 8 * q + 4 * half, a);
-        plane_put4<SG>(pl_bh(base, t), pl_bl(base, t), col * kLdP + h * 64 + 32 + 8 * q + 4 * half, b);
+        ti_f32x4 ov[TPH];
+#pragma unroll
+        for (int j = 0; j < TPH; ++j) ov[j] = ti_f32x4{o[j][4 * q], o[j][4 * q + 1], o[j][4 * q + 2], o[j][4 * q + 3]};
+        if constexpr (WATCH) {
+#pragma unroll
+          for (int j = 0; j < TPH; ++j) watch4(ov[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < TPH; ++j)
+          plane_put4<SG>(pl_bh<D>(base, t), pl_bl<D>(base, t), col * LDP + h * HD + 32 * j + 8 * q + 4 * half, ov[j]);
       }
     }
   }
   __syncthreads();
   // operand fragments of the row-wise products: token fragment of tile t at k-step s (this lane's row `col`, k half `half`)
-  const int frow = col * kLdP + half * 128;
+  const int frow = col * LDP + half * KH;
   // x = LayerNorm(x + acc^T + bias) * g + be for both tiles — the residual epilogue and the LayerNorm behind it in one go (round 5; proven
-  // on fine.hip first). A lane holds 16 of a token's 256 features per tile (its partner lane ^ 32 another 16, the other seven waves 32
+  // on fine.hip first). A lane holds 16 of a token's D features per tile (its partner lane ^ 32 another 16, the other waves 32
   // each): the row sums meet in `lnred` behind two light barriers (mean, then centred squares: the two-pass form), the values stay in
   // registers in between and the normalised rows are written once. As a separate pass (8 rows per wave, two full-wave reductions per
   // row) the two LayerNorms of a layer were ~700 VALU instructions per wave and a plane round trip each.
@@ -408,12 +465,12 @@ __device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& 
       for (int q = 0; q < 4; ++q) {
         const int f0 = 32 * wave + 8 * q + 4 * half;
         const float4 bb = *reinterpret_cast<const float4*>(bias + f0);
-        v[t][q] = plane_get4<SG>(pl_xh(base, t), pl_xl(base, t), col * kLdP + f0) +
+        v[t][q] = plane_get4<SG>(pl_xh<D>(base, t), pl_xl<D>(base, t), col * LDP + f0) +
                   ti_f32x4{acc[t][4 * q] + bb.x, acc[t][4 * q + 1] + bb.y, acc[t][4 * q + 2] + bb.z, acc[t][4 * q + 3] + bb.w};
         sm += (v[t][q][0] + v[t][q][1]) + (v[t][q][2] + v[t][q][3]);
       }
       sm += __shfl_xor(sm, 32);
-      if (half == 0) lnred[(t * 8 + wave) * 32 + col] = sm;
+      if (half == 0) lnred[(t * NW + wave) * 32 + col] = sm;
     }
     __syncthreads();
     float mean[2];
@@ -421,8 +478,8 @@ __device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& 
     for (int t = 0; t < 2; ++t) {
       float m = 0.f;
 #pragma unroll
-      for (int w = 0; w < 8; ++w) m += lnred[(t * 8 + w) * 32 + col];
-      mean[t] = m * (1.f / kD);
+      for (int w = 0; w < NW; ++w) m += lnred[(t * NW + w) * 32 + col];
+      mean[t] = m * (1.f / D);
       float qs = 0.f;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -430,26 +487,26 @@ __device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& 
         qs += (v[t][q][0] * v[t][q][0] + v[t][q][1] * v[t][q][1]) + (v[t][q][2] * v[t][q][2] + v[t][q][3] * v[t][q][3]);
       }
       qs += __shfl_xor(qs, 32);
-      if (half == 0) lnred[512 + (t * 8 + wave) * 32 + col] = qs;
+      if (half == 0) lnred[2 * NW * 32 + (t * NW + wave) * 32 + col] = qs;
     }
     __syncthreads();
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       float var = 0.f;
 #pragma unroll
-      for (int w = 0; w < 8; ++w) var += lnred[512 + (t * 8 + w) * 32 + col];
-      const float inv = 1.f / sqrtf(var * (1.f / kD) + 1e-5f);
+      for (int w = 0; w < NW; ++w) var += lnred[2 * NW * 32 + (t * NW + w) * 32 + col];
+      const float inv = 1.f / sqrtf(var * (1.f / D) + 1e-5f);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int f0 = 32 * wave + 8 * q + 4 * half;
         const float4 gg = *reinterpret_cast<const float4*>(g + f0), bb = *reinterpret_cast<const float4*>(be + f0);
         const ti_f32x4 o = {v[t][q][0] * inv * gg.x + bb.x, v[t][q][1] * inv * gg.y + bb.y, v[t][q][2] * inv * gg.z + bb.z,
                             v[t][q][3] * inv * gg.w + bb.w};
-        if (to_f32) {  // (the last LayerNorm: the tile's B planes become one f32 [32][260] tile for the epilogue)
-          *reinterpret_cast<ti_f32x4*>(reinterpret_cast<float*>(pl_bh(base, t)) + col * kLdX + f0) = o;
+        if (to_f32) {  // (the last LayerNorm: the tile's B planes become one f32 [32][D + 4] tile for the epilogue)
+          *reinterpret_cast<ti_f32x4*>(reinterpret_cast<float*>(pl_bh<D>(base, t)) + col * LDX + f0) = o;
         } else {
           if constexpr (WATCH) watch4(o);
-          plane_put4<SG>(pl_xh(base, t), pl_xl(base, t), col * kLdP + f0, o);
+          plane_put4<SG>(pl_xh<D>(base, t), pl_xl<D>(base, t), col * LDP + f0, o);
         }
       }
     }
@@ -460,34 +517,35 @@ __device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& 
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-    const uint4* wp = W.out_hp + ((size_t)wave * (kD / 16) * 64 + lane) * 2;
-    stream_weights<SG, kD / 16, kRingDepth>(wp, [&](int s, const HFrag& wf) {
+    const uint4* wp = W.out_hp + ((size_t)wave * HS * 64 + lane) * 2;
+    stream_weights<SG, HS, kRingDepth>(wp, [&](int s, const HFrag& wf) {
 #pragma unroll
-      for (int t = 0; t < 2; ++t) mfma_h3<SG>(acc[t], wf, plane_frag<SG>(pl_bh(base, t) + frow, pl_bl(base, t) + frow, 8 * s));
+      for (int t = 0; t < 2; ++t) mfma_h3<SG>(acc[t], wf, plane_frag<SG>(pl_bh<D>(base, t) + frow, pl_bl<D>(base, t) + frow, 8 * s));
     });
     resid_ln(acc, W.out_b, W.ln1_w, W.ln1_b, false);
   }
   __syncthreads();
-  {  // ---- feed-forward, four passes of 256 hidden units; wave w: one hidden tile per pass and one output tile, both token tiles
+  {  // ---- feed-forward, FFP passes of D hidden units; wave w: one hidden tile per pass and one output tile, both token tiles
     f32x16 acc[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
     const float* b1 = W.ff1_b;
-    constexpr int FS = FFP * kD / 16;  // k-steps of one W2 tile
-    const int cbase = wave < 4 ? 32 * wave : 128 + 32 * (wave - 4);  // where this wave's hidden tile lives in the B planes
+    constexpr int FS = FFP * HS;   // k-steps of one W2 tile (K = FFP D)
+    constexpr int LOW = NW / 2;    // waves whose hidden tile lies in the lower k half of W2, = 32-unit tiles per pass and k half
+    const int cbase = wave < LOW ? 32 * wave : KH + 32 * (wave - LOW);  // where this wave's hidden tile lives in the B planes
     for (int c = 0; c < FFP; ++c) {
-      const int tf = wave < 4 ? 4 * c + wave : 4 * FFP + 4 * c + (wave - 4);
+      const int tf = wave < LOW ? LOW * c + wave : LOW * FFP + LOW * c + (wave - LOW);
       f32x16 hT[2];
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) hT[t][r] = 0.f;
-      const uint4* w1 = W.ff1_hp + ((size_t)tf * (kD / 16) * 64 + lane) * 2;
-      stream_weights<SG, kD / 16, kRingDepth>(w1, [&](int s, const HFrag& wf) {
+      const uint4* w1 = W.ff1_hp + ((size_t)tf * HS * 64 + lane) * 2;
+      stream_weights<SG, HS, kRingDepth>(w1, [&](int s, const HFrag& wf) {
 #pragma unroll
-        for (int t = 0; t < 2; ++t) mfma_h3<SG>(hT[t], wf, plane_frag<SG>(pl_xh(base, t) + frow, pl_xl(base, t) + frow, 8 * s));
+        for (int t = 0; t < 2; ++t) mfma_h3<SG>(hT[t], wf, plane_frag<SG>(pl_xh<D>(base, t) + frow, pl_xl<D>(base, t) + frow, 8 * s));
       });
       if (c) __syncthreads();  // every wave has consumed the previous pass from the B planes
 #pragma unroll
@@ -499,13 +557,13 @@ __device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& 
           const ti_f32x4 v = {fmaxf(hT[t][4 * q] + bb.x, 0.f), fmaxf(hT[t][4 * q + 1] + bb.y, 0.f), fmaxf(hT[t][4 * q + 2] + bb.z, 0.f),
                               fmaxf(hT[t][4 * q + 3] + bb.w, 0.f)};
           if constexpr (WATCH) watch4(v);
-          plane_put4<SG>(pl_bh(base, t), pl_bl(base, t), col * kLdP + cbase + u0, v);
+          plane_put4<SG>(pl_bh<D>(base, t), pl_bl<D>(base, t), col * LDP + cbase + u0, v);
         }
       __syncthreads();
-      const uint4* w2 = W.ff2_hp + (((size_t)wave * FS + 16 * c) * 64 + lane) * 2;
-      stream_weights<SG, kD / 16, kRingDepth>(w2, [&](int s, const HFrag& wf) {
+      const uint4* w2 = W.ff2_hp + (((size_t)wave * FS + HS * c) * 64 + lane) * 2;
+      stream_weights<SG, HS, kRingDepth>(w2, [&](int s, const HFrag& wf) {
 #pragma unroll
-        for (int t = 0; t < 2; ++t) mfma_h3<SG>(acc[t], wf, plane_frag<SG>(pl_bh(base, t) + frow, pl_bl(base, t) + frow, 8 * s));
+        for (int t = 0; t < 2; ++t) mfma_h3<SG>(acc[t], wf, plane_frag<SG>(pl_bh<D>(base, t) + frow, pl_bl<D>(base, t) + frow, 8 * s));
       });
     }
     resid_ln(acc, W.ff2_b, W.ln2_w, W.ln2_b, last_to_f32);  // (every wave is past its reads of the B planes and of x at the first barrier inside)
@@ -513,20 +571,21 @@ __device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& 
   __syncthreads();
 }
 
-template <int H>
-__global__ __launch_bounds__(512, 1) void text_inter_fused2_kernel(InterFusedW W, const float* __restrict__ sent, int n_desc, int S, int dpt,
+template <int D, int HD, int H>
+__global__ __launch_bounds__(2 * D, D == 256 ? 1 : 2) void text_inter_fused2_kernel(InterFusedW W, const float* __restrict__ sent, int n_desc, int S, int dpt,
                                                                    float* __restrict__ out, int* __restrict__ flag) {
   static_assert(H == 1 || H == 2, "split-f16 or plain f16");
   constexpr bool SG = H == 2;
+  constexpr int LDP = PlaneGeo<D>::kLd, LDX = PlaneGeo<D>::kLdF, PLANE = PlaneGeo<D>::kSize;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   _Float16* base = reinterpret_cast<_Float16*>(smem);
-  // per tile t: X planes (token tile), B planes (attention output -> hidden pass; at the very end an f32 [32][260] tile)
-  auto XH = [&](int t) { return base + (size_t)(4 * t + 0) * kPlane; };
-  auto XL = [&](int t) { return base + (size_t)(4 * t + 1) * kPlane; };
-  auto BH = [&](int t) { return base + (size_t)(4 * t + 2) * kPlane; };
-  auto BL = [&](int t) { return base + (size_t)(4 * t + 3) * kPlane; };
-  int* grp = reinterpret_cast<int*>(base + (size_t)8 * kPlane);  // [32]: description of a tile-local row
-  float* lnred = reinterpret_cast<float*>(grp + kSP);              // [1024]: row sums of the fused residual + LayerNorm epilogues
+  // per tile t: X planes (token tile), B planes (attention output -> hidden pass; at the very end an f32 [32][D + 4] tile)
+  auto XH = [&](int t) { return base + (size_t)(4 * t + 0) * PLANE; };
+  auto XL = [&](int t) { return base + (size_t)(4 * t + 1) * PLANE; };
+  auto BH = [&](int t) { return base + (size_t)(4 * t + 2) * PLANE; };
+  auto BL = [&](int t) { return base + (size_t)(4 * t + 3) * PLANE; };
+  int* grp = reinterpret_cast<int*>(base + (size_t)8 * PLANE);  // [32]: description of a tile-local row
+  float* lnred = reinterpret_cast<float*>(grp + kSP);              // [4 NW 32]: row sums of the fused residual + LayerNorm epilogues
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int col = lane & 31, half = lane >> 5;
   const int d0 = blockIdx.x * 2 * dpt;
@@ -538,33 +597,34 @@ __global__ __launch_bounds__(512, 1) void text_inter_fused2_kernel(InterFusedW W
   nd[1] = max(0, min(dpt, n_desc - d0 - dpt));
   rows[0] = nd[0] * S;
   rows[1] = nd[1] * S;
-  // ---- the 64 rows -> planes (8 rows per wave, 4 columns per lane)
+  // ---- the 64 rows -> planes (64 / NW rows per wave, 4 columns per lane: a wave takes 256 / D rows per step)
+  constexpr int RPI = 256 / D, LPR = D / 4, LLPR = D == 256 ? 6 : 5;  // rows per step, lanes per row and their log2
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
-    const int r = wave * 8 + i, t = r >> 5, lr = r & 31;
+    const int r = (wave * 8 + i) * RPI + (lane >> LLPR), t = r >> 5, lr = r & 31, cl = lane & (LPR - 1);
     ti_f32x4 v = {0.f, 0.f, 0.f, 0.f};
     if (lr < rows[t]) {
-      const float4 g = reinterpret_cast<const float4*>(sent + ((size_t)(d0 + t * dpt) * S + lr) * kD)[lane];
+      const float4 g = reinterpret_cast<const float4*>(sent + ((size_t)(d0 + t * dpt) * S + lr) * D)[cl];
       v = ti_f32x4{g.x, g.y, g.z, g.w};
     }
     watch4(v);
-    plane_put4<SG>(XH(t), XL(t), lr * kLdP + 4 * lane, v);
+    plane_put4<SG>(XH(t), XL(t), lr * LDP + 4 * cl, v);
   }
   if (tid < kSP) grp[tid] = tid / S;
   __syncthreads();
 
-  planes_layer<SG, 4, true>(base, W, [&](int i, int j) { return grp[i] == grp[j]; }, bad, true, lnred);
+  planes_layer<SG, D, HD, 4, true>(base, W, [&](int i, int j) { return grp[i] == grp[j]; }, bad, true, lnred);
   {  // x_in + layer(x_in), max over the description's S sentences: thread = (tile, column)
-    const int t = tid >> 8, c = tid & 255;
+    const int t = tid >> (D == 256 ? 8 : 7), c = tid & (D - 1);
     const float* y = reinterpret_cast<const float*>(BH(t));
-    const float* src = sent + (size_t)(d0 + t * dpt) * S * kD;
+    const float* src = sent + (size_t)(d0 + t * dpt) * S * D;
     for (int d = 0; d < nd[t]; ++d) {
       float m = -__builtin_inff();
       for (int s_ = 0; s_ < S; ++s_) {
         const int r = d * S + s_;
-        m = fmaxf(m, y[r * kLdX + c] + src[(size_t)r * kD + c]);
+        m = fmaxf(m, y[r * LDX + c] + src[(size_t)r * D + c]);
       }
-      out[(size_t)(d0 + t * dpt + d) * kD + c] = m;
+      out[(size_t)(d0 + t * dpt + d) * D + c] = m;
     }
   }
   if (__syncthreads_or(bad ? 1 : 0) && tid == 0) atomicOr(flag, 1);
@@ -707,7 +767,7 @@ __global__ __launch_bounds__(512, 1) void encode_cells2_kernel(EncParams P, t2l_
     W.in_b = L.in_b; W.out_b = L.out_b; W.ff1_b = L.ff1_b; W.ff2_b = L.ff2_b;
     W.ln1_w = L.ln1_w; W.ln1_b = L.ln1_b; W.ln2_w = L.ln2_w; W.ln2_b = L.ln2_b;
     // no padding mask: the 28 slots, zero pads included, attend and are attended to; the 4 dead rows of the tile are no keys
-    planes_layer<SG, 2, false>(base, W, [](int, int j) { return j < kS; }, bad, l == P.num_layers - 1, hb_all);  // (hb_all: dead behind the feature MLPs)
+    planes_layer<SG, kD, 64, 2, false>(base, W, [](int, int j) { return j < kS; }, bad, l == P.num_layers - 1, hb_all);  // (hb_all: dead behind the feature MLPs)
   }
   {  // max over ALL 28 slots, then normalize: thread = (cell, column)
     const int t = tid >> 8, c = tid & 255;
@@ -722,24 +782,35 @@ __global__ __launch_bounds__(512, 1) void encode_cells2_kernel(EncParams P, t2l_
   }
 }
 
-int text_inter_fused_launch(t2l_ctx* ctx, const InterFusedW& W, bool single, const float* sent, int n_desc, int S, float* out, int* flag,
-                            hipStream_t s) {
-  {
-    const int dpt = kSP / S, tiles = (n_desc + 2 * dpt - 1) / (2 * dpt);
-    const size_t lds = (size_t)8 * kPlane * sizeof(_Float16) + kSP * sizeof(int) + 1024 * sizeof(float);
-    static PerDeviceOnce once2;
-    if (once2.need(ctx->device)) {
-      T2L_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&text_inter_fused2_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      T2L_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&text_inter_fused2_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      once2.mark(ctx->device);
-    }
-    if (single)
-      hipLaunchKernelGGL(text_inter_fused2_kernel<2>, dim3(tiles), dim3(512), lds, s, W, sent, n_desc, S, dpt, out, flag);
-    else
-      hipLaunchKernelGGL(text_inter_fused2_kernel<1>, dim3(tiles), dim3(512), lds, s, W, sent, n_desc, S, dpt, out, flag);
-    T2L_HIP(ctx, hipGetLastError());
-    return T2L_OK;
+template <int D, int HD>
+static int text_inter_launch_shape(t2l_ctx* ctx, const InterFusedW& W, bool single, const float* sent, int n_desc, int S, float* out, int* flag,
+                                   hipStream_t s) {
+  const TextInterPlan plan = text_inter_plan(D, n_desc, S);
+  static PerDeviceOnce once2;  // (one per instantiation)
+  if (once2.need(ctx->device)) {
+    T2L_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&text_inter_fused2_kernel<D, HD, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes));
+    T2L_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&text_inter_fused2_kernel<D, HD, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes));
+    once2.mark(ctx->device);
   }
+  if (single)
+    hipLaunchKernelGGL((text_inter_fused2_kernel<D, HD, 2>), dim3(plan.grid), dim3(plan.threads), plan.lds_bytes, s, W, sent, n_desc, S, plan.dpt, out, flag);
+  else
+    hipLaunchKernelGGL((text_inter_fused2_kernel<D, HD, 1>), dim3(plan.grid), dim3(plan.threads), plan.lds_bytes, s, W, sent, n_desc, S, plan.dpt, out, flag);
+  T2L_HIP(ctx, hipGetLastError());
+  return T2L_OK;
+}
+
+int text_inter_fused_launch(t2l_ctx* ctx, const InterFusedW& W, int D, int heads, bool single, const float* sent, int n_desc, int S, float* out,
+                            int* flag, hipStream_t s) {
+  const int hd = heads > 0 ? D / heads : 0;
+#define T2L_INTER_SHAPE(DD, HH) \
+  if (D == DD && hd == HH) return text_inter_launch_shape<DD, HH>(ctx, W, single, sent, n_desc, S, out, flag, s);
+  T2L_INTER_SHAPE(256, 64)
+  T2L_INTER_SHAPE(128, 32)
+  T2L_INTER_SHAPE(128, 64)
+  T2L_INTER_SHAPE(256, 32)
+#undef T2L_INTER_SHAPE
+  return fail(ctx, T2L_ESTATE, std::string("t2l_text_inter: no kernel for the loaded inter layer (") + text_inter_shapes_text() + ")");
 }
 
 // ---- host side: BN folding, fragment packing, upload -------------------------------------------

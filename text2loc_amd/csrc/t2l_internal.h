@@ -12,6 +12,7 @@
 
 #include "t2l.h"
 #include "search_plan.h"
+#include "text_inter_plan.h"
 
 namespace t2l {
 
@@ -223,15 +224,16 @@ int search_join_impl(t2l_ctx* ctx, hipStream_t s);
 void free_lanes(t2l_ctx* ctx);
 int adam_state_impl(t2l_ctx* ctx, int set, float* m, float* v, int64_t* step, int64_t* numel, hipStream_t s);
 void free_train(t2l_ctx* ctx);
-// t2l_text_inter as ONE launch (encode.hip: text_inter_fused_kernel — the cell encoder's per-tile transformer layer at S sentences per
+// t2l_text_inter as ONE launch (encode.hip: text_inter_fused2_kernel — the cell encoder's per-tile transformer layer at S sentences per
 // description): the inter layer's matrices in the encoder's split-f16 fragment packing (mfma_h3.h: pack_split_f16) + its f32 vectors
 struct InterFusedW {
   const uint4 *in_hp = nullptr, *out_hp = nullptr, *ff1_hp = nullptr, *ff2_hp = nullptr;
   const float *in_b = nullptr, *out_b = nullptr, *ff1_b = nullptr, *ff2_b = nullptr, *ln1_w = nullptr, *ln1_b = nullptr, *ln2_w = nullptr,
               *ln2_b = nullptr;
 };
-int text_inter_fused_launch(t2l_ctx* ctx, const InterFusedW& W, bool single, const float* sent, int n_desc, int S, float* out, int* flag,
-                            hipStream_t s);
+// D, heads: the inter layer's width and head count, one of the compiled set (text_inter_plan.h); anything else is T2L_ESTATE
+int text_inter_fused_launch(t2l_ctx* ctx, const InterFusedW& W, int D, int heads, bool single, const float* sent, int n_desc, int S, float* out,
+                            int* flag, hipStream_t s);
 void free_text_train(t2l_ctx* ctx);
 int text_adam_step_impl(t2l_ctx* ctx, float lr, float b1, float b2, float eps, hipStream_t s);
 int text_zero_grad_impl(t2l_ctx* ctx, hipStream_t s);
@@ -264,7 +266,7 @@ int fine_train_forward_points_impl(t2l_ctx* ctx, const t2l_packed_cells* in, con
 int fine_train_backward_impl(t2l_ctx* ctx, const float* grad_offsets, float* grad_hint, float* grad_pn, hipStream_t s);
 void free_fine_train(t2l_ctx* ctx);
 // text_head.hip
-int text_head_load_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const char* prefix);
+int text_head_load_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const char* prefix, int inter_num_heads);
 int text_head_impl(t2l_ctx* ctx, const float* hidden, int n_sentences, int n_tokens, float* out, int32_t* overflow, hipStream_t s);
 int fast_gemm(t2l_ctx* ctx, const float* A, bool a_trans, const float* B, bool b_trans, const float* bias, float* out, int Mo, int No, int Kc,
               int relu, int accumulate, bool single, hipStream_t s, float* a_colsum = nullptr);  // text_head.hip: the tiled bf16-plane GEMM for training

@@ -688,8 +688,10 @@ struct Weights {
   float *qkv_b = nullptr, *out_b = nullptr, *ff1_b = nullptr, *ff2_b = nullptr, *mlp_b = nullptr, *ln1_g = nullptr, *ln1_b = nullptr,
         *ln2_g = nullptr, *ln2_b = nullptr;
   int out_dim = 0;  // D of inter_mlp (256 coarse, 128 fine)
-  // the inter-sentence layer (inter_module.0: d_model 256, 4 heads, dim_feedforward 1024) — coarse model only
+  // the inter-sentence layer (inter_module.0: d_model D = out_dim, dim_feedforward 4 D, one of the compiled (D, heads) pairs of
+  // text_inter_plan.h) — coarse model only
   bool has_inter = false;
+  int inter_dim = 0, inter_heads = 0;  // what has_inter was recorded for
   InterFusedW fused;  // the inter layer in the encoder's fragment packing (text_inter_fused2_kernel, encode.hip)
   float *i_qkv_b = nullptr, *i_out_b = nullptr, *i_ff1_b = nullptr, *i_ff2_b = nullptr, *i_ln1_g = nullptr, *i_ln1_b = nullptr, *i_ln2_g = nullptr,
         *i_ln2_b = nullptr;
@@ -736,7 +738,7 @@ void free_text_head(t2l_ctx* ctx) {
   ctx->text_head = nullptr;
 }
 
-int text_head_load_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const char* prefix) {
+int text_head_load_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const char* prefix, int inter_num_heads) {
   using namespace th;
   const std::string P = prefix ? prefix : "language_encoder.";
   const std::string L0 = P + "intra_module.0.";
@@ -803,14 +805,17 @@ int text_head_load_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const cha
     }
     if ((rc = planes(wf.data(), D, kDM, &W->mlp_h, &W->mlp_l)) || (rc = upload(bf.data(), sizeof(float) * kTile, (void**)&W->mlp_b))) return rc;
   }
-  {  // inter_module.0 (language_encoder.py:101,143-144), when present and of the published shape: D = 256, 4 heads, ff 1024
-    constexpr int ID = 256, IF = 1024;
+  // inter_module.0 (language_encoder.py:101,143-144), when present and of a compiled shape: width D = that of inter_mlp in {128, 256},
+  // inter_num_heads heads of 32 or 64 features (the state dict does not carry the head count), ff 4 D, no second layer. Any other
+  // width or head count, a second layer, mis-sized tensors: has_inter stays false (t2l_text_inter then answers T2L_ESTATE).
+  if (text_inter_shape_is_compiled(D, inter_num_heads)) {
+    const int ID = D, IF = 4 * D;
     const std::string I0 = P + "inter_module.0.";
     const Req ireq[] = {{"self_attn.in_proj_weight", 3ll * ID * ID}, {"self_attn.in_proj_bias", 3 * ID}, {"self_attn.out_proj.weight", (int64_t)ID * ID},
                         {"self_attn.out_proj.bias", ID}, {"linear1.weight", (int64_t)IF * ID}, {"linear1.bias", IF}, {"linear2.weight", (int64_t)ID * IF},
                         {"linear2.bias", ID}, {"norm1.weight", ID}, {"norm1.bias", ID}, {"norm2.weight", ID}, {"norm2.bias", ID}};
     const t2l_weight_desc* it[12];
-    bool all = D == ID && !th_find(w, n, P + "inter_module.1.linear1.weight", (int64_t)IF * ID);
+    bool all = !th_find(w, n, P + "inter_module.1.linear1.weight", (int64_t)IF * ID);
     for (int i = 0; i < 12 && all; ++i) all = (it[i] = th_find(w, n, I0 + ireq[i].key, ireq[i].numel)) != nullptr;
     if (all) {
       if ((rc = vec(it[1]->data, 3 * ID, 3 * ID, &W->i_qkv_b)) || (rc = vec(it[3]->data, ID, ID, &W->i_out_b)) ||
@@ -818,7 +823,7 @@ int text_head_load_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const cha
           (rc = vec(it[8]->data, ID, ID, &W->i_ln1_g)) || (rc = vec(it[9]->data, ID, ID, &W->i_ln1_b)) ||
           (rc = vec(it[10]->data, ID, ID, &W->i_ln2_g)) || (rc = vec(it[11]->data, ID, ID, &W->i_ln2_b)))
         return rc;
-      {  // the four matrices as split-f16 MFMA fragments (mfma_h3.h packing; 1.5 MB)
+      {  // the four matrices as split-f16 MFMA fragments (mfma_h3.h packing; 1.5 MB at 256, 0.4 MB at 128)
         auto frag = [&](const float* Wm, int rows, int cols, const uint4** dst) -> int {
           const std::vector<float> pk = pack_split_f16(Wm, nullptr, rows, cols, cols);
           void* d = nullptr;
@@ -833,6 +838,8 @@ int text_head_load_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const cha
         W->fused.ln1_w = W->i_ln1_g; W->fused.ln1_b = W->i_ln1_b; W->fused.ln2_w = W->i_ln2_g; W->fused.ln2_b = W->i_ln2_b;
       }
       W->has_inter = true;
+      W->inter_dim = ID;
+      W->inter_heads = inter_num_heads;
     }
   }
   T2L_HIP(ctx, hipMalloc(&W->flag, sizeof(int)));
@@ -954,27 +961,26 @@ int text_head_impl(t2l_ctx* ctx, const float* hidden, int n_sent, int L, float* 
   return T2L_OK;
 }
 
-// The inter-sentence half of the head (models/language_encoder.py:137-147): sent [n_desc * S][256] row-major (what t2l_text_head
-// returns, description-major) -> view [n_desc, S, 256] -> x += TransformerEncoderLayer(256, 4 heads, ff 1024)(x) over the S
-// sentences of every description -> max over the S sentences -> out [n_desc][256]. The same kernels as the token layer with
-// d_model 256: rows = sentences, "tokens per sentence" = S.
+// The inter-sentence half of the head (models/language_encoder.py:137-147): sent [n_desc * S][D] row-major (what t2l_text_head
+// returns, description-major) -> view [n_desc, S, D] -> x += TransformerEncoderLayer(D, heads, ff 4 D)(x) over the S sentences of
+// every description -> max over the S sentences -> out [n_desc][D]. D and heads are those of the loaded inter layer.
 int text_inter_impl(t2l_ctx* ctx, const float* sent, int n_desc, int S, float* out, int32_t* overflow, hipStream_t s) {
   using namespace th;
-  constexpr int ID = 256, IF = 1024;
   Weights* W = (Weights*)ctx->text_head;
   if (!W) return fail(ctx, T2L_ESTATE, "t2l_text_inter: call t2l_text_head_load_weights first");
-  if (!W->has_inter) return fail(ctx, T2L_ESTATE, "t2l_text_inter: the loaded head has no inter_module.0 of the published shape (256 / 4 heads / 1024)");
+  if (!W->has_inter)
+    return fail(ctx, T2L_ESTATE, std::string("t2l_text_inter: the loaded head has no inter_module.0 of a compiled shape (") + text_inter_shapes_text() + ")");
   if (!sent || !out) return fail(ctx, T2L_EINVAL, "t2l_text_inter: null buffer");
   if (n_desc <= 0) return n_desc == 0 ? T2L_OK : fail(ctx, T2L_EINVAL, "t2l_text_inter: n_descriptions < 0");
   if (S < 1 || S > kMaxL) return fail(ctx, T2L_EINVAL, "t2l_text_inter: need 1 <= sentences per description <= 32");
   const bool single = ctx->encoder_f16 != 0;
-  // ONE launch: two tiles of floor(32 / S) descriptions per eight-wave workgroup, everything in LDS (encode.hip:
+  // ONE launch: two tiles of floor(32 / S) descriptions per workgroup of D / 32 waves, everything in LDS (encode.hip:
   // text_inter_fused2_kernel). Rounds 3-4 also shipped a chain of tiled GEMM / attention / LayerNorm launches (0.208 ms for 4,096
   // descriptions x 6 sentences) and a one-tile form of this launch; both measured slower than this one (0.179 ms) and were removed
   // in round 5.
   T2L_HIP(ctx, hipMemsetAsync(W->flag, 0, sizeof(int), s));
   event_begin(ctx, "text_inter", s);
-  const int rc_ = text_inter_fused_launch(ctx, W->fused, single, sent, n_desc, S, out, W->flag, s);
+  const int rc_ = text_inter_fused_launch(ctx, W->fused, W->inter_dim, W->inter_heads, single, sent, n_desc, S, out, W->flag, s);
   event_end(ctx, "text_inter", s);
   if (rc_ != T2L_OK) return rc_;
   if (overflow) T2L_HIP(ctx, hipMemcpyAsync(overflow, W->flag, sizeof(int), hipMemcpyDeviceToDevice, s));

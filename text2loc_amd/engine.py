@@ -106,6 +106,7 @@ EXPORTS = {
     "t2l_contrastive_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "t2l_text_head_load_weights": (C.c_int, [C.c_void_p, C.POINTER(_WeightDesc), C.c_int32, C.c_char_p]),
+    "t2l_text_head_load_weights_heads": (C.c_int, [C.c_void_p, C.POINTER(_WeightDesc), C.c_int32, C.c_char_p, C.c_int32]),
     "t2l_text_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "t2l_text_inter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "t2l_fine_load_weights": (C.c_int, [C.c_void_p, C.POINTER(_WeightDesc), C.c_int32, C.POINTER(_ModelConfig)]),
@@ -324,8 +325,10 @@ class Engine:
         return out
 
     # ------------------------------------------------------------------ text head after T5 (f-4a)
-    def text_head_load_weights(self, state_dict: Dict[str, object], prefix: str = "language_encoder."):
-        """state_dict: name -> tensor / ndarray holding ``<prefix>intra_module.0.*`` and ``<prefix>inter_mlp.0.*`` (fp32)."""
+    def text_head_load_weights(self, state_dict: Dict[str, object], prefix: str = "language_encoder.", inter_num_heads: int = 4):
+        """state_dict: name -> tensor / ndarray holding ``<prefix>intra_module.0.*`` and ``<prefix>inter_mlp.0.*`` (fp32), and for the
+        coarse model ``<prefix>inter_module.0.*``; ``inter_num_heads``: that layer's head count (inter_module_num_heads — a state dict
+        does not carry it). ``text_inter`` serves the layer when (inter_mlp width, heads) is (128, 2 | 4) or (256, 4 | 8)."""
         keep, descs = [], []
         for name, v in state_dict.items():
             if not name.startswith((prefix + "intra_module.", prefix + "inter_mlp.", prefix + "inter_module.")) or name.endswith("num_batches_tracked"):
@@ -337,8 +340,9 @@ class Engine:
         if not descs:
             raise T2LError(f"text_head_load_weights: no tensors under {prefix}intra_module / {prefix}inter_mlp")
         arr = (_WeightDesc * len(descs))(*descs)
-        self._check(self.lib.t2l_text_head_load_weights(self._h, arr, len(descs), prefix.encode()))
-        self._text_head_dim = int(state_dict[prefix + "inter_mlp.0.0.weight"].shape[0])
+        self._text_head_dim = None
+        self._check(self.lib.t2l_text_head_load_weights_heads(self._h, arr, len(descs), prefix.encode(), int(inter_num_heads)))
+        self._text_head_dim = int(state_dict[prefix + "inter_mlp.0.0.weight"].shape[0])  # also the inter layer's width
 
     def text_head(self, hidden: torch.Tensor, check: bool = True):
         """hidden f32[n_sentences, n_tokens, 1024] (T5 last_hidden_state) on the GPU -> f32[n_sentences, D] = inter_mlp(max over
@@ -356,13 +360,17 @@ class Engine:
         return (out, bool(flag.item())) if check else (out, flag)
 
     def text_inter(self, sent: torch.Tensor, n_descriptions: int, check: bool = True):
-        """sent f32[n_descriptions * S, 256] (t2l_text_head's output, description-major) -> f32[n_descriptions, 256] =
-        max over the S sentences of x + inter_module[0](x) (models/language_encoder.py:137-147). Returns (out, overflowed) like
-        ``text_head``."""
-        if sent.dim() != 2 or sent.shape[1] != 256 or n_descriptions <= 0 or sent.shape[0] % n_descriptions:
-            raise T2LError(f"text_inter: expected [n_descriptions * S, 256], got {tuple(sent.shape)} for {n_descriptions} descriptions")
+        """sent f32[n_descriptions * S, D] (t2l_text_head's output, description-major; D = the loaded head's width) ->
+        f32[n_descriptions, D] = max over the S sentences of x + inter_module[0](x) (models/language_encoder.py:137-147). Returns
+        (out, overflowed) like ``text_head``."""
+        D = getattr(self, "_text_head_dim", None)
+        if D is None:
+            raise T2LError("text_inter: call text_head_load_weights first")
+        if sent.dim() != 2 or sent.shape[1] != D or n_descriptions <= 0 or sent.shape[0] % n_descriptions:
+            raise T2LError(f"text_inter: expected [n_descriptions * S, {D}] (the loaded head is {D} wide), got {tuple(sent.shape)} "
+                           f"for {n_descriptions} descriptions")
         S = int(sent.shape[0]) // n_descriptions
-        out = torch.empty((n_descriptions, 256), dtype=torch.float32, device=sent.device)
+        out = torch.empty((n_descriptions, D), dtype=torch.float32, device=sent.device)
         flag = torch.zeros((1,), dtype=torch.int32, device=sent.device)
         self._check(self.lib.t2l_text_inter(self._h, self._ptr(sent, torch.float32, "sent"), n_descriptions, S, out.data_ptr(), flag.data_ptr(),
                                             _stream_ptr(self.device)))

@@ -14,7 +14,7 @@ A batch whose longest sentence has L tokens uses positions [0, L) of each of its
 tokenizer call + T5 produce for that batch (up to the rounding of differently-shaped rocBLAS calls). T5 itself is untouched and
 remains the path of a batch holding a sentence the cache cannot take (longer than Lmax); unseen sentences are encoded once and
 added. In eval mode the head's per-sentence half (intra_module + max + inter_mlp: a function of the sentence and L alone) is
-memoised too (``sentence_vectors``), keyed on L and the head's weight version: encode_text is then a gather of [256]-vectors and
+memoised too (``sentence_vectors``), keyed on L and the head's weight version: encode_text is then a gather of [D]-vectors and
 the inter-sentence layer.
 """
 from __future__ import annotations
