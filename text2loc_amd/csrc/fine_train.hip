@@ -19,6 +19,7 @@
 #include <string.h>
 
 #include "t2l_internal.h"
+#include "train_common.h"
 
 namespace t2l {
 namespace ft {
@@ -27,21 +28,10 @@ constexpr int kW = 128, kObj = 16, kHintMax = 8, kHeads = 4, kHd = 32, kFF = 512
 constexpr float kLnEps = 1e-5f, kBnEps = 1e-5f, kBnMom = 0.1f, kNormEps = 1e-12f;
 constexpr float kNumMean = 1826.6844940968194f, kNumStd = 2516.8905096993817f;  // models/object_encoder.py:43-44
 
-struct Drop {
-  uint32_t key = 0, thr = 0;  // thr == 0: identity
-  float scale = 1.f;
-};
-
-// the a9 mask rule (train_kernels.h: keep_bit, which is defined per translation unit of train.hip and cannot be shared)
-__device__ __forceinline__ bool keep_bit(uint32_t key, uint32_t idx, uint32_t thr) {
-  uint32_t x = idx * 0x9E3779B1u + key;
-  x ^= x >> 16;
-  x *= 0x7FEB352Du;
-  x ^= x >> 15;
-  x *= 0x846CA68Bu;
-  x ^= x >> 16;
-  return (x >> 8) >= thr;
-}
+// the a9 dropout rule, shared with the coarse step (train_common.h): Drop, keep_bit, make_drop(seed, site, p)
+using train::Drop;
+using train::keep_bit;
+using train::make_drop;
 
 __device__ __forceinline__ float dmask(const Drop& d, uint32_t idx) {
   return d.thr ? (keep_bit(d.key, idx, d.thr) ? d.scale : 0.f) : 1.f;
@@ -512,16 +502,6 @@ static void free_ft(FineTrain* st) {
   delete st;
 }
 
-static Drop make_drop(float p, uint32_t seed, int site) {
-  Drop d;
-  if (p > 0.f) {
-    d.thr = (uint32_t)(p * 16777216.f);
-    d.key = seed ^ ((uint32_t)site * 0x85EBCA77u);
-    d.scale = 1.f / (1.f - p);
-  }
-  return d;
-}
-
 static inline unsigned nblk(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 static void gemm(hipStream_t s, const float* A, int64_t sam, int64_t sak, const float* B, int64_t sbk, int64_t sbn, float* C, int64_t ldc,
@@ -647,23 +627,23 @@ static void dec_fwd(FineTrain* st, DecLayer& L, float p, uint32_t seed, float* t
   // self-attention block + dropout1 + norm1
   lin_fwd(s, L.x, kW, M, kW, L.in_w.d, kW, L.in_b.d, 3 * kW, L.qkv, 3 * kW);
   hipLaunchKernelGGL(k_attn_fwd, dim3(P * kHeads), dim3(256), 0, s, L.qkv, (int64_t)3 * kW, L.qkv + kW, (int64_t)3 * kW, L.qkv + 2 * kW,
-                     (int64_t)3 * kW, L.Tq, L.Tq, L.Ps, L.os, (int64_t)kW, make_drop(p, seed, L.site + 0));
+                     (int64_t)3 * kW, L.Tq, L.Tq, L.Ps, L.os, (int64_t)kW, make_drop(seed, L.site + 0, p));
   lin_fwd(s, L.os, kW, M, kW, L.out_w.d, kW, L.out_b.d, kW, tmp, kW);
-  add_ln(s, L.x, tmp, M, L.n1_w, L.n1_b, make_drop(p, seed, L.site + 1), L.xh1, L.r1, L.x1);
+  add_ln(s, L.x, tmp, M, L.n1_w, L.n1_b, make_drop(seed, L.site + 1, p), L.xh1, L.r1, L.x1);
   // cross-attention block + dropout2 + norm2
   lin_fwd(s, L.x1, kW, M, kW, L.cin_w.d, kW, L.cin_b.d, kW, L.q2, kW);
   lin_fwd(s, L.mem, kW, Mm, kW, L.cin_w.d + kW * kW, kW, L.cin_b.d + kW, 2 * kW, L.kv2, 2 * kW);
   hipLaunchKernelGGL(k_attn_fwd, dim3(P * kHeads), dim3(256), 0, s, L.q2, (int64_t)kW, L.kv2, (int64_t)2 * kW, L.kv2 + kW, (int64_t)2 * kW,
-                     L.Tq, L.Tk, L.Pc, L.oc, (int64_t)kW, make_drop(p, seed, L.site + 2));
+                     L.Tq, L.Tk, L.Pc, L.oc, (int64_t)kW, make_drop(seed, L.site + 2, p));
   lin_fwd(s, L.oc, kW, M, kW, L.cout_w.d, kW, L.cout_b.d, kW, tmp, kW);
-  add_ln(s, L.x1, tmp, M, L.n2_w, L.n2_b, make_drop(p, seed, L.site + 3), L.xh2, L.r2, L.x2);
+  add_ln(s, L.x1, tmp, M, L.n2_w, L.n2_b, make_drop(seed, L.site + 3, p), L.xh2, L.r2, L.x2);
   // feed-forward block + dropout3 + norm3
   lin_fwd(s, L.x2, kW, M, kW, L.l1_w.d, kW, L.l1_b.d, kFF, L.h1, kFF, 1);
   if (L.h1d != L.h1)
-    hipLaunchKernelGGL(k_dropout, dim3(nblk((int64_t)M * kFF, 256)), dim3(256), 0, s, L.h1, (int64_t)M * kFF, make_drop(p, seed, L.site + 4),
+    hipLaunchKernelGGL(k_dropout, dim3(nblk((int64_t)M * kFF, 256)), dim3(256), 0, s, L.h1, (int64_t)M * kFF, make_drop(seed, L.site + 4, p),
                        L.h1d);
   lin_fwd(s, L.h1d, kFF, M, kFF, L.l2_w.d, kFF, L.l2_b.d, kW, tmp, kW);
-  add_ln(s, L.x2, tmp, M, L.n3_w, L.n3_b, make_drop(p, seed, L.site + 5), L.xh3, L.r3, L.out);
+  add_ln(s, L.x2, tmp, M, L.n3_w, L.n3_b, make_drop(seed, L.site + 5, p), L.xh3, L.r3, L.out);
 }
 
 // backward of dec_fwd: dout -> dx (written), d mem ADDED to dmem
@@ -671,34 +651,34 @@ static void dec_bwd(FineTrain* st, DecLayer& L, float p, uint32_t seed, const fl
   const int P = st->P, M = P * L.Tq, Mm = P * L.Tk;
   float *dx2 = st->t_dx2, *dx1 = st->t_dx1, *ds = st->t_ds, *dob = st->t_do, *dq = st->t_dq, *dkv = st->t_dkv, *dh = st->t_dh;
   // norm3 / dropout3 / feed-forward
-  hipLaunchKernelGGL(k_ln_bwd, dim3(nblk(M, 32)), dim3(256), 0, s, dout, L.xh3, L.r3, L.n3_w.d, M, make_drop(p, seed, L.site + 5), dx2, ds,
+  hipLaunchKernelGGL(k_ln_bwd, dim3(nblk(M, 32)), dim3(256), 0, s, dout, L.xh3, L.r3, L.n3_w.d, M, make_drop(seed, L.site + 5, p), dx2, ds,
                      L.n3_w.g, L.n3_b.g);
   lin_dw(s, ds, kW, L.h1d, kFF, M, kW, kFF, L.l2_w.g, kFF, L.l2_b.g);
   lin_dx(s, ds, kW, M, kW, L.l2_w.d, kFF, kFF, dh, kFF, 0);
   hipLaunchKernelGGL(k_drop_relu_bwd, dim3(nblk((int64_t)M * kFF, 256)), dim3(256), 0, s, dh, L.h1, (int64_t)M * kFF,
-                     make_drop(p, seed, L.site + 4));
+                     make_drop(seed, L.site + 4, p));
   lin_dw(s, dh, kFF, L.x2, kW, M, kFF, kW, L.l1_w.g, kW, L.l1_b.g);
   lin_dx(s, dh, kFF, M, kFF, L.l1_w.d, kW, kW, dx2, kW, 1);
   // norm2 / dropout2 / cross-attention
-  hipLaunchKernelGGL(k_ln_bwd, dim3(nblk(M, 32)), dim3(256), 0, s, dx2, L.xh2, L.r2, L.n2_w.d, M, make_drop(p, seed, L.site + 3), dx1, ds,
+  hipLaunchKernelGGL(k_ln_bwd, dim3(nblk(M, 32)), dim3(256), 0, s, dx2, L.xh2, L.r2, L.n2_w.d, M, make_drop(seed, L.site + 3, p), dx1, ds,
                      L.n2_w.g, L.n2_b.g);
   lin_dw(s, ds, kW, L.oc, kW, M, kW, kW, L.cout_w.g, kW, L.cout_b.g);
   lin_dx(s, ds, kW, M, kW, L.cout_w.d, kW, kW, dob, kW, 0);
   hipLaunchKernelGGL(k_attn_bwd, dim3(P * kHeads), dim3(256), 0, s, L.q2, (int64_t)kW, L.kv2, (int64_t)2 * kW, L.kv2 + kW, (int64_t)2 * kW,
                      L.Pc, dob, (int64_t)kW, dq, (int64_t)kW, dkv, (int64_t)2 * kW, dkv + kW, (int64_t)2 * kW, L.Tq, L.Tk,
-                     make_drop(p, seed, L.site + 2));
+                     make_drop(seed, L.site + 2, p));
   lin_dw(s, dq, kW, L.x1, kW, M, kW, kW, L.cin_w.g, kW, L.cin_b.g);
   lin_dx(s, dq, kW, M, kW, L.cin_w.d, kW, kW, dx1, kW, 1);
   lin_dw(s, dkv, 2 * kW, L.mem, kW, Mm, 2 * kW, kW, L.cin_w.g ? L.cin_w.g + kW * kW : nullptr, kW, L.cin_b.g ? L.cin_b.g + kW : nullptr);
   lin_dx(s, dkv, 2 * kW, Mm, 2 * kW, L.cin_w.d + kW * kW, kW, kW, dmem, kW, 1);
   // norm1 / dropout1 / self-attention
-  hipLaunchKernelGGL(k_ln_bwd, dim3(nblk(M, 32)), dim3(256), 0, s, dx1, L.xh1, L.r1, L.n1_w.d, M, make_drop(p, seed, L.site + 1), dx, ds,
+  hipLaunchKernelGGL(k_ln_bwd, dim3(nblk(M, 32)), dim3(256), 0, s, dx1, L.xh1, L.r1, L.n1_w.d, M, make_drop(seed, L.site + 1, p), dx, ds,
                      L.n1_w.g, L.n1_b.g);
   lin_dw(s, ds, kW, L.os, kW, M, kW, kW, L.out_w.g, kW, L.out_b.g);
   lin_dx(s, ds, kW, M, kW, L.out_w.d, kW, kW, dob, kW, 0);
   hipLaunchKernelGGL(k_attn_bwd, dim3(P * kHeads), dim3(256), 0, s, L.qkv, (int64_t)3 * kW, L.qkv + kW, (int64_t)3 * kW, L.qkv + 2 * kW,
                      (int64_t)3 * kW, L.Ps, dob, (int64_t)kW, dq, (int64_t)3 * kW, dq + kW, (int64_t)3 * kW, dq + 2 * kW, (int64_t)3 * kW,
-                     L.Tq, L.Tq, make_drop(p, seed, L.site + 0));
+                     L.Tq, L.Tq, make_drop(seed, L.site + 0, p));
   lin_dw(s, dq, 3 * kW, L.x, kW, M, 3 * kW, kW, L.in_w.g, kW, L.in_b.g);
   lin_dx(s, dq, 3 * kW, M, 3 * kW, L.in_w.d, kW, kW, dx, kW, 1);
 }

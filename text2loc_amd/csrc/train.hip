@@ -37,8 +37,12 @@ struct Branch {
   std::vector<MlpLayer> layers;
   float* save_n = nullptr;
 };
-struct LayerSave {
-  std::string prefix;
+// One nn.TransformerEncoderLayer (4 heads, post-norm, ReLU) with its saved activations: obj_inter_module.l of the object branch, and
+// intra_module.0 / inter_module.0 of the text head (enc_layer_alloc / enc_layer_fwd / enc_layer_bwd below)
+struct EncLayer {
+  std::string prefix;  // of its tensors' names in the state's map
+  int T = 0, B = 0, S = 0;    // T = B * S rows: B groups (cells / sentences / descriptions) of S rows that attend to each other
+  int FF = 0, site0 = 0;      // feed-forward width; the first of its four dropout sites
   const float* x_in = nullptr;
   float *qkv = nullptr, *P = nullptr, *O = nullptr, *xhat1 = nullptr, *rstd1 = nullptr, *x1 = nullptr, *h = nullptr,
         *hd = nullptr, *xhat2 = nullptr, *rstd2 = nullptr, *x2 = nullptr;
@@ -64,9 +68,7 @@ struct TrainState {
   int64_t step = 0;          // Adam step of the object branch
   int64_t step_pn = 0;       // ... of the backbone: it only steps when its backward ran since the last zero_grad (torch.optim.Adam
   bool pn_touched = false;   // skips parameters whose .grad is None and keeps a step count per parameter)
-  // workspace (bump-allocated per forward)
-  char* ws = nullptr;
-  size_t ws_cap = 0, ws_off = 0;
+  Arena ws;  // workspace (bump-allocated per forward)
   // the last forward
   bool have_forward = false;
   int M = 0, B = 0, T = 0, n_feat = 0;
@@ -75,7 +77,7 @@ struct TrainState {
   MlpLayer merge;
   float *cat = nullptr, *X0 = nullptr, *save_nf = nullptr, *out = nullptr, *pool_n = nullptr;
   int32_t* pool_arg = nullptr;
-  std::vector<LayerSave> layers;
+  std::vector<EncLayer> layers;
   uint32_t seed = 0;
   float p = 0.f;
   void* pn = nullptr;  // PnTrain (pointnet_train.h): the PointNet++ backbone's training state, when its tensors are bound
@@ -102,27 +104,11 @@ static void sync_slots(t2l_ctx* ctx, double* first, int slots, hipStream_t s) {
 void free_train(t2l_ctx* ctx) {
   TrainState* st = state(ctx);
   if (!st) return;
-  for (void* p : {(void*)st->d_tensors, (void*)st->d_chunks, (void*)st->mv, (void*)st->ws, (void*)st->bn_acc})
+  for (void* p : {(void*)st->d_tensors, (void*)st->d_chunks, (void*)st->mv, (void*)st->ws.base, (void*)st->bn_acc})
     if (p) (void)hipFree(p);
   pn_train_free(st->pn);
   delete st;
   ctx->train = nullptr;
-}
-
-static Drop make_drop(uint32_t seed, int site, float p) {
-  Drop d;
-  d.key = seed ^ (uint32_t)((uint64_t)site * 0x85EBCA77ull);
-  d.thr = p > 0.f ? (uint32_t)((double)p * 16777216.0) : 0u;
-  d.scale = d.thr ? 1.0f / (1.0f - p) : 1.0f;
-  return d;
-}
-
-template <typename T>
-static T* bump(TrainState* st, size_t count) {
-  size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
-  T* p = reinterpret_cast<T*>(st->ws + st->ws_off);
-  st->ws_off += bytes;
-  return p;
 }
 
 // ---- GEMM launchers -----------------------------------------------------------------------------------------
@@ -193,6 +179,159 @@ static void gemm_tn_nn(const float* dY, const float* X, float* dW, float* db, co
   else
     hipLaunchKernelGGL(gemm_pair_kernel, dim3(p.tn_blocks + nn_blocks), dim3(256), 0, s, p);
 }
+// ---- one TransformerEncoderLayer, for the object branch and the text head alike -----------------------------------------------
+// What differs between the two states' Linear products. The text head's run on the tiled LDS-ring GEMM of text_head.hip (fast_gemm:
+// 256 x 256 tiles, bf16 planes, split-bf16 by default — 466 GFLOP per step at B = 64 are GEMM-shaped work that the object branch's
+// tile-per-workgroup products, built for 1,792-row operands, serve at a third of its rate); shapes it does not take (fewer than 64
+// rows, a width that is no multiple of 256) and every product of the object branch keep the products of gemm_f32.h with the same
+// operand arithmetic. (An f32-MFMA operand option existed until round 5: 7.6 ms per step against PyTorch's 5.6; removed.)
+struct Products {
+  t2l_ctx* ctx;
+  bool tiled;  // may use fast_gemm
+};
+static bool t_fast(const Products& pr, int M, int N, int K) { return pr.tiled && N % 256 == 0 && K % 32 == 0 && K % 4 == 0 && M >= 64; }
+static void t_gemm_nt(const Products& pr, const float* X, const float* W, const float* b, float* Y, int M, int N, int K, int relu, hipStream_t s) {
+  if (t_fast(pr, M, N, K)) (void)fast_gemm(pr.ctx, X, false, W, false, b, Y, M, N, K, relu, 0, pr.ctx->text_train_bf16 == 1, s);
+  else gemm_nt(X, W, b, Y, M, N, K, relu, s);
+}
+// dW[N,Kp] += dY^T X, db[N] += column sums of dY, and (dX != nullptr) dX[M,Kp] (+)= dY W, through the ReLU + dropout backward of the
+// layer that produced X's pre-image when mask_src is given
+static void t_gemm_tn_nn(const Products& pr, const float* dY, const float* X, float* dW, float* db, const float* W, float* dX, int M, int N, int Kp,
+                         int accumulate, const float* mask_src, const Drop* drop, hipStream_t s) {
+  if (t_fast(pr, N, Kp, M) && (!dX || t_fast(pr, M, Kp, N)) && N % 4 == 0) {
+    const bool single = pr.ctx->text_train_bf16 == 1;
+    (void)fast_gemm(pr.ctx, dY, true, X, true, nullptr, dW, N, Kp, M, 0, 1, single, s, db);  // (db: column sums of dY, in its split pass)
+    if (dX) {
+      (void)fast_gemm(pr.ctx, dY, false, W, true, nullptr, dX, M, Kp, N, 0, accumulate, single, s);
+      if (mask_src) {
+        const size_t n = (size_t)M * Kp;
+        hipLaunchKernelGGL(relu_drop_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dX, mask_src, n, *drop);
+      }
+    }
+    return;
+  }
+  if (dX) gemm_tn_nn(dY, X, dW, db, W, dX, M, N, Kp, accumulate, mask_src, drop, s);
+  else gemm_tn(dY, X, dW, db, M, N, Kp, s);
+}
+
+static size_t attn_lds(int S, int HD, bool bwd) { return sizeof(float) * ((size_t)(bwd ? 4 : 3) * S * (HD + 1) + (size_t)(bwd ? 3 : 1) * S * (S + 1)); }
+// the attention kernels of a layer: the instance with S at compile time where there is one (the object branch's shape), else S at run time
+template <int HD, typename... A>
+static void attn_fwd_launch(int B, int S, hipStream_t s, A... a) {
+  if (HD == kTHd && S == kTS) hipLaunchKernelGGL((attn_fwd_kernel<kTHd, kTS>), dim3(B * 4), dim3(256), attn_lds(S, HD, false), s, a...);
+  else hipLaunchKernelGGL((attn_fwd_kernel<HD, 0>), dim3(B * 4), dim3(256), attn_lds(S, HD, false), s, a...);
+}
+template <int HD, typename... A>
+static void attn_bwd_launch(int B, int S, hipStream_t s, A... a) {
+  if (HD == kTHd && S == kTS) hipLaunchKernelGGL((attn_bwd_kernel<kTHd, kTS>), dim3(B * 4), dim3(256), attn_lds(S, HD, true), s, a...);
+  else hipLaunchKernelGGL((attn_bwd_kernel<HD, 0>), dim3(B * 4), dim3(256), attn_lds(S, HD, true), s, a...);
+}
+
+using TensorMap = std::unordered_map<std::string, TTensor>;
+
+// the saved activations of L (T, B, S, FF set by the caller)
+template <int D>
+static void enc_layer_alloc(Arena& ws, EncLayer& L, float p) {
+  const size_t T = (size_t)L.T;
+  L.qkv = ws.take<float>(T * 3 * D);
+  L.P = ws.take<float>((size_t)L.B * 4 * L.S * L.S);
+  L.O = ws.take<float>(T * D);
+  L.xhat1 = ws.take<float>(T * D);
+  L.rstd1 = ws.take<float>(T);
+  L.x1 = ws.take<float>(T * D);
+  L.h = ws.take<float>(T * L.FF);
+  L.hd = p > 0.f ? ws.take<float>(T * L.FF) : L.h;
+  L.xhat2 = ws.take<float>(T * D);
+  L.rstd2 = ws.take<float>(T);
+  L.x2 = ws.take<float>(T * D);
+}
+// tmp: [T][D] scratch. 7 launches on the products of gemm_f32.h.
+template <int D>
+static void enc_layer_fwd(const Products& pr, const TensorMap& t, EncLayer& L, uint32_t seed, float p, float* tmp, hipStream_t s) {
+  constexpr int HD = D / 4;
+  const int T = L.T, FF = L.FF;
+  auto W = [&](const char* n) -> const TTensor& { return t.at(L.prefix + n); };
+  t_gemm_nt(pr, L.x_in, W(".self_attn.in_proj_weight").data, W(".self_attn.in_proj_bias").data, L.qkv, T, 3 * D, D, 0, s);
+  attn_fwd_launch<HD>(L.B, L.S, s, (const float*)L.qkv, L.P, L.O, L.S, make_drop(seed, L.site0 + 0, p));
+  t_gemm_nt(pr, L.O, W(".self_attn.out_proj.weight").data, W(".self_attn.out_proj.bias").data, tmp, T, D, D, 0, s);
+  hipLaunchKernelGGL((ln_fwd_kernel<D>), dim3((T + 3) / 4), dim3(256), 0, s, L.x_in, (const float*)tmp, T, W(".norm1.weight").data,
+                     W(".norm1.bias").data, make_drop(seed, L.site0 + 1, p), L.x1, L.xhat1, L.rstd1);
+  if (t_fast(pr, T, FF, D)) {  // linear1 + ReLU in the GEMM's epilogue (h is kept for backward); the dropout behind it as one pass
+    (void)fast_gemm(pr.ctx, L.x1, false, W(".linear1.weight").data, false, W(".linear1.bias").data, L.h, T, FF, D, 1, 0, pr.ctx->text_train_bf16 == 1, s);
+    if (p > 0.f) {
+      const size_t n = (size_t)T * FF;
+      hipLaunchKernelGGL(drop_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)L.h, n, make_drop(seed, L.site0 + 2, p), L.hd);
+    }
+  } else {  // ... and the dropout too in the same epilogue (hd feeds linear2)
+    GemmArgs g{L.x1, W(".linear1.weight").data, L.h, W(".linear1.bias").data, T, FF, D, D, D, FF, 1, 0, D, nullptr, tl_gemm_bf16};
+    if (p > 0.f) {
+      const Drop dr = make_drop(seed, L.site0 + 2, p);
+      g.epi = 1;
+      g.C2 = L.hd;
+      g.drop_key = dr.key;
+      g.drop_thr = dr.thr;
+      g.drop_scale = dr.scale;
+    }
+    gemm_nt_args(g, s);
+  }
+  t_gemm_nt(pr, L.hd, W(".linear2.weight").data, W(".linear2.bias").data, tmp, T, D, FF, 0, s);
+  hipLaunchKernelGGL((ln_fwd_kernel<D>), dim3((T + 3) / 4), dim3(256), 0, s, (const float*)L.x1, (const float*)tmp, T, W(".norm2.weight").data,
+                     W(".norm2.bias").data, make_drop(seed, L.site0 + 3, p), L.x2, L.xhat2, L.rstd2);
+}
+// The backward's scratch: taken by the CALLER, who knows whether its layers can share one (the object branch's do: same shape).
+struct EncScratch {
+  float *dA, *dB, *dC, *dB2, *dO, *dH, *dqkv;
+};
+template <int D>
+static EncScratch enc_scratch_take(Arena& ws, int T, int FF) {
+  const size_t n = (size_t)T * D;
+  EncScratch sc;
+  sc.dA = ws.take<float>(n);
+  sc.dB = ws.take<float>(n);
+  sc.dC = ws.take<float>(n);
+  sc.dB2 = ws.take<float>(n);
+  sc.dO = ws.take<float>(n);
+  sc.dH = ws.take<float>((size_t)T * FF);
+  sc.dqkv = ws.take<float>(n * 3);
+  return sc;
+}
+// dcur: gradient w.r.t. the layer's output x2 (read). Returns the gradient w.r.t. the layer's input, which lives in sc.dC (nullptr when
+// need_dx is false). 7 launches on the products of gemm_f32.h.
+// LN_WAVES: waves per workgroup of the LayerNorm backward, the caller's measured choice for its shape (train_kernels.h: ln_bwd_kernel):
+// 16 for the object branch's 1,792 rows of 256, in at most 32 workgroups; 4 for the text head, in at most 64 (at D = 1024 the
+// partials of 16 waves would not fit the LDS).
+template <int D, int LN_WAVES>
+static float* enc_layer_bwd(const Products& pr, const TensorMap& t, const EncLayer& L, uint32_t seed, float p, const EncScratch& sc,
+                            const float* dcur, bool need_dx, hipStream_t s) {
+  constexpr int HD = D / 4;
+  const int T = L.T, FF = L.FF;
+  auto W = [&](const char* nme) -> const TTensor& { return t.at(L.prefix + nme); };
+  const int ln_grid = std::min(LN_WAVES == 16 ? 32 : 64, (T + 15) / 16);
+  auto ln_bwd = [&](const float* dout, const float* xhat, const float* rstd, const TTensor& gamma, const TTensor& beta, int site, float* d_res,
+                    float* d_y) {
+    hipLaunchKernelGGL((ln_bwd_kernel<D, LN_WAVES>), dim3(ln_grid), dim3(LN_WAVES * 64), 0, s, dout, xhat, rstd, T, (const float*)gamma.data,
+                       make_drop(seed, site, p), d_res, d_y, gamma.grad, beta.grad);
+  };
+  // norm2 + dropout2
+  ln_bwd(dcur, L.xhat2, L.rstd2, W(".norm2.weight"), W(".norm2.bias"), L.site0 + 3, sc.dA, sc.dB);
+  {  // linear2: dW2 += dB^T hd, and dH = (dB W2) through the ReLU + dropout backward
+    const Drop dr = make_drop(seed, L.site0 + 2, p);
+    t_gemm_tn_nn(pr, sc.dB, L.hd, W(".linear2.weight").grad, W(".linear2.bias").grad, W(".linear2.weight").data, sc.dH, T, D, FF, 0, L.h, &dr, s);
+  }
+  // linear1; dA (= dz2, the residual path) += dH W1
+  t_gemm_tn_nn(pr, sc.dH, L.x1, W(".linear1.weight").grad, W(".linear1.bias").grad, W(".linear1.weight").data, sc.dA, T, FF, D, 1, nullptr, nullptr, s);
+  // norm1 + dropout1
+  ln_bwd(sc.dA, L.xhat1, L.rstd1, W(".norm1.weight"), W(".norm1.bias"), L.site0 + 1, sc.dC, sc.dB2);
+  // out_proj
+  t_gemm_tn_nn(pr, sc.dB2, L.O, W(".self_attn.out_proj.weight").grad, W(".self_attn.out_proj.bias").grad, W(".self_attn.out_proj.weight").data, sc.dO,
+               T, D, D, 0, nullptr, nullptr, s);
+  attn_bwd_launch<HD>(L.B, L.S, s, (const float*)L.qkv, (const float*)L.P, (const float*)sc.dO, sc.dqkv, L.S, make_drop(seed, L.site0 + 0, p));
+  // in_proj; dC (= dz1, the residual path) += dqkv Win
+  t_gemm_tn_nn(pr, sc.dqkv, L.x_in, W(".self_attn.in_proj_weight").grad, W(".self_attn.in_proj_bias").grad,
+               need_dx ? W(".self_attn.in_proj_weight").data : nullptr, need_dx ? sc.dC : nullptr, T, 3 * D, D, need_dx ? 1 : 0, nullptr, nullptr, s);
+  return need_dx ? sc.dC : nullptr;
+}
+
 static int need(t2l_ctx* ctx, TrainState* st, const std::string& name, int64_t numel, bool with_grad, TTensor** out) {
   auto it = st->t.find(name);
   if (it == st->t.end()) return fail(ctx, T2L_EINVAL, "t2l_train_bind: missing tensor '" + name + "'");
@@ -359,10 +498,10 @@ static MlpLayer make_layer(TrainState* st, const std::string& prefix, int cin, i
   L.prefix = prefix;
   L.cin = cin;
   L.cout = cout;
-  L.y = bump<float>(st, (size_t)M * cout);
-  L.a = bump<float>(st, (size_t)M * cout);
-  L.mean = bump<float>(st, cout);
-  L.rstd = bump<float>(st, cout);
+  L.y = st->ws.take<float>((size_t)M * cout);
+  L.a = st->ws.take<float>((size_t)M * cout);
+  L.mean = st->ws.take<float>(cout);
+  L.rstd = st->ws.take<float>(cout);
   return L;
 }
 
@@ -506,16 +645,16 @@ int train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, float p, uint32
       sizeof(float) * ((size_t)M * (2 * Kc + 30 * kTD) + (size_t)T * kTD * 18 +
                        (size_t)c.num_layers * ((size_t)T * (13 * kTD + 8) + (size_t)B * kTH * kTS * kTS) + (size_t)B * kTD * 4) +
       (1 << 20);
-  if (need_bytes > st->ws_cap) {
-    if (st->ws) (void)hipFree(st->ws);
-    st->ws = nullptr;
-    st->ws_cap = 0;
-    T2L_HIP(ctx, hipMalloc(&st->ws, need_bytes));
-    st->ws_cap = need_bytes;
+  if (need_bytes > st->ws.cap) {
+    if (st->ws.base) (void)hipFree(st->ws.base);
+    st->ws.base = nullptr;
+    st->ws.cap = 0;
+    T2L_HIP(ctx, hipMalloc(&st->ws.base, need_bytes));
+    st->ws.cap = need_bytes;
   }
   tl_gemm_bf16 = ctx->train_bf16;
   tl_gemm_block64 = ctx->train_gemm_block == 64 || (ctx->train_gemm_block == 0 && ctx->train_bf16 != 0);
-  st->ws_off = 0;
+  st->ws.off = 0;
   st->have_forward = false;
   st->M = M; st->B = B; st->T = T;
   st->offsets = in->offsets;
@@ -531,7 +670,7 @@ int train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, float p, uint32
   if (!st->fwd_acc_clean) T2L_HIP(ctx, hipMemsetAsync(acc_base(ctx, st), 0, sizeof(double) * kBnStride * kBnSlots, s));
   st->fwd_acc_clean = false;
 
-  st->cat = bump<float>(st, (size_t)M * Kc);
+  st->cat = st->ws.take<float>((size_t)M * Kc);
   const std::string oe = "object_encoder.";
   int slot = 0;
   std::vector<int> smalls;  // indices of the small branches: launched together below, one launch per stage
@@ -540,7 +679,7 @@ int train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, float p, uint32
     br.kind = 1; br.slot = slot++; br.x = x; br.k_in = k; br.standardize = standardize;
     br.layers.push_back(make_layer(st, oe + name + ".0", k, 64, M));
     br.layers.push_back(make_layer(st, oe + name + ".1", 64, kTD, M));
-    br.save_n = bump<float>(st, M);
+    br.save_n = st->ws.take<float>(M);
     smalls.push_back((int)st->branches.size());
     st->branches.push_back(br);
   };
@@ -548,7 +687,7 @@ int train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, float p, uint32
   auto embed_branch = [&](const std::string& table, const int32_t* idx) {
     Branch br;
     br.kind = 0; br.slot = slot++; br.table = oe + table; br.idx = idx;
-    br.save_n = bump<float>(st, M);
+    br.save_n = st->ws.take<float>(M);
     embeds.push_back((int)st->branches.size());
     st->branches.push_back(br);
   };
@@ -559,7 +698,7 @@ int train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, float p, uint32
       Branch br;
       br.kind = 2; br.slot = slot++; br.x = in->pn_feat; br.k_in = 256;
       br.layers.push_back(make_layer(st, oe + "mlp_pointnet.0", 256, kTD, M));
-      br.save_n = bump<float>(st, M);
+      br.save_n = st->ws.take<float>(M);
       mlp_layer_fwd(st, br.layers[0], in->pn_feat, M, 0, 0, s);
       hipLaunchKernelGGL(rownorm_fwd_kernel, dim3((M + 3) / 4), dim3(256), 0, s, br.layers[0].a, (const int32_t*)nullptr, M,
                          st->cat + br.slot * kTD, Kc, br.save_n);
@@ -586,61 +725,32 @@ int train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, float p, uint32
 
   st->merge = make_layer(st, oe + "mlp_merge.0", Kc, kTD, M);
   mlp_layer_fwd(st, st->merge, st->cat, M, 0, 0, s);
-  st->X0 = bump<float>(st, (size_t)T * kTD);
-  st->save_nf = bump<float>(st, M);
+  st->X0 = st->ws.take<float>((size_t)T * kTD);
+  st->save_nf = st->ws.take<float>(M);
   hipLaunchKernelGGL(scatter_norm_fwd_kernel, dim3((T + 3) / 4), dim3(256), 0, s, st->merge.a, in->offsets, B, st->X0, st->save_nf);
 
-  float* tmp = bump<float>(st, (size_t)T * kTD);
+  float* tmp = st->ws.take<float>((size_t)T * kTD);
   const float* x = st->X0;
+  const Products pr{ctx, false};  // the object branch's products are the tile-per-workgroup ones of gemm_f32.h
   for (int l = 0; l < c.num_layers; ++l) {
-    LayerSave L;
+    EncLayer L;
     L.prefix = "obj_inter_module." + std::to_string(l);
-    L.x_in = x;
-    L.qkv = bump<float>(st, (size_t)T * 3 * kTD);
-    L.P = bump<float>(st, (size_t)B * kTH * kTS * kTS);
-    L.O = bump<float>(st, (size_t)T * kTD);
-    L.xhat1 = bump<float>(st, (size_t)T * kTD);
-    L.rstd1 = bump<float>(st, T);
-    L.x1 = bump<float>(st, (size_t)T * kTD);
-    L.h = bump<float>(st, (size_t)T * 2 * kTD);
-    L.hd = p > 0.f ? bump<float>(st, (size_t)T * 2 * kTD) : L.h;
-    L.xhat2 = bump<float>(st, (size_t)T * kTD);
-    L.rstd2 = bump<float>(st, T);
-    L.x2 = bump<float>(st, (size_t)T * kTD);
-    gemm_nt(x, T_(st, L.prefix + ".self_attn.in_proj_weight").data, T_(st, L.prefix + ".self_attn.in_proj_bias").data, L.qkv, T, 3 * kTD, kTD, 0, s);
-    hipLaunchKernelGGL(attn_fwd_kernel, dim3(B * kTH), dim3(256), 0, s, L.qkv, L.P, L.O, make_drop(seed, l * 4 + 0, p));
-    gemm_nt(L.O, T_(st, L.prefix + ".self_attn.out_proj.weight").data, T_(st, L.prefix + ".self_attn.out_proj.bias").data, tmp, T, kTD, kTD, 0, s);
-    hipLaunchKernelGGL(ln_fwd_kernel, dim3((T + 3) / 4), dim3(256), 0, s, x, tmp, T, T_(st, L.prefix + ".norm1.weight").data,
-                       T_(st, L.prefix + ".norm1.bias").data, make_drop(seed, l * 4 + 1, p), L.x1, L.xhat1, L.rstd1);
-    {  // linear1 + ReLU, and the dropout behind it in the same epilogue (h is kept for backward, hd feeds linear2)
-      GemmArgs g{L.x1, T_(st, L.prefix + ".linear1.weight").data, L.h, T_(st, L.prefix + ".linear1.bias").data, T, 2 * kTD, kTD, kTD, kTD, 2 * kTD,
-                 1, 0, kTD, nullptr, tl_gemm_bf16};
-      if (p > 0.f) {
-        const Drop dr = make_drop(seed, l * 4 + 2, p);
-        g.epi = 1;
-        g.C2 = L.hd;
-        g.drop_key = dr.key;
-        g.drop_thr = dr.thr;
-        g.drop_scale = dr.scale;
-      }
-      gemm_nt_args(g, s);
-    }
-    gemm_nt(L.hd, T_(st, L.prefix + ".linear2.weight").data, T_(st, L.prefix + ".linear2.bias").data, tmp, T, kTD, 2 * kTD, 0, s);
-    hipLaunchKernelGGL(ln_fwd_kernel, dim3((T + 3) / 4), dim3(256), 0, s, L.x1, tmp, T, T_(st, L.prefix + ".norm2.weight").data,
-                       T_(st, L.prefix + ".norm2.bias").data, make_drop(seed, l * 4 + 3, p), L.x2, L.xhat2, L.rstd2);
+    L.T = T; L.B = B; L.S = kTS; L.FF = 2 * kTD; L.site0 = 4 * l; L.x_in = x;
+    enc_layer_alloc<kTD>(st->ws, L, p);
+    enc_layer_fwd<kTD>(pr, st->t, L, seed, p, tmp, s);
     x = L.x2;
     st->layers.push_back(L);
   }
-  st->out = bump<float>(st, (size_t)B * kTD);
-  st->pool_n = bump<float>(st, B);
-  st->pool_arg = bump<int32_t>(st, (size_t)B * kTD);
+  st->out = st->ws.take<float>((size_t)B * kTD);
+  st->pool_n = st->ws.take<float>(B);
+  st->pool_arg = st->ws.take<int32_t>((size_t)B * kTD);
   hipLaunchKernelGGL(pool_norm_fwd_kernel, dim3(B), dim3(256), 0, s, x, st->out, st->pool_arg, st->pool_n, out_emb, acc_base(ctx, st),
                      kBnStride * kBnSlots * 2);
   event_end(ctx, "train_forward", s);
   T2L_HIP(ctx, hipGetLastError());
   st->fwd_acc_clean = true;
   st->bwd_acc_clean = true;
-  if (st->ws_off > st->ws_cap) return fail(ctx, T2L_ENOMEM, "t2l_encode_cells_train: workspace bound exceeded (internal error)");
+  if (st->ws.off > st->ws.cap) return fail(ctx, T2L_ENOMEM, "t2l_encode_cells_train: workspace bound exceeded (internal error)");
   if (ctx->sync_failed) return fail(ctx, T2L_ESTATE, "t2l_encode_cells_train: the cross-rank sum callback (t2l_train_sync_bn) failed");
   st->have_forward = true;
   return T2L_OK;
@@ -679,57 +789,33 @@ int train_backward_impl(t2l_ctx* ctx, const float* grad_emb, float* grad_pn_feat
   const int M = st->M, B = st->B, T = st->T, Kc = st->n_feat * kTD;
   tl_gemm_bf16 = ctx->train_bf16;
   tl_gemm_block64 = ctx->train_gemm_block == 64 || (ctx->train_gemm_block == 0 && ctx->train_bf16 != 0);
-  const size_t mark = st->ws_off;
+  const size_t mark = st->ws.off;
   event_begin(ctx, "train_backward", s);
   st->bn_slot = kBnSlots;  // the backward's half of the accumulators: zeroed by the forward's memset, unless this is a second backward
   ctx->sync_failed = false;
   if (!st->bwd_acc_clean)
     T2L_HIP(ctx, hipMemsetAsync(acc_base(ctx, st) + (size_t)kBnSlots * kBnStride, 0, sizeof(double) * kBnStride * kBnSlots, s));
   st->bwd_acc_clean = false;
-  float* dcur = bump<float>(st, (size_t)T * kTD);
-  float* dA = bump<float>(st, (size_t)T * kTD);
-  float* dB = bump<float>(st, (size_t)T * kTD);
-  float* dC = bump<float>(st, (size_t)T * kTD);
-  float* dB2 = bump<float>(st, (size_t)T * kTD);
-  float* dO = bump<float>(st, (size_t)T * kTD);
-  float* dH = bump<float>(st, (size_t)T * 2 * kTD);
-  float* dqkv = bump<float>(st, (size_t)T * 3 * kTD);
-  float* dfeat = bump<float>(st, (size_t)M * kTD);
-  float* dcat = bump<float>(st, (size_t)M * Kc);
-  float* d2 = bump<float>(st, (size_t)kMaxJobs * M * kTD);  // scratch of the feature branches: one region per small branch (they run
-  float* d1 = bump<float>(st, (size_t)kMaxJobs * M * 64);   // together, stage by stage); the others use region 0 one after the other
-  if (st->ws_off > st->ws_cap) {
-    st->ws_off = mark;
+  float* dcur = st->ws.take<float>((size_t)T * kTD);
+  // the layers' scratch is taken ONCE and shared by all of them: taken per layer (as the text head does for its two layers of
+  // different shape) it would add 10 T kTD floats per layer, which the forward's workspace bound does not hold
+  EncScratch sc = enc_scratch_take<kTD>(st->ws, T, 2 * kTD);
+  float* dfeat = st->ws.take<float>((size_t)M * kTD);
+  float* dcat = st->ws.take<float>((size_t)M * Kc);
+  float* d2 = st->ws.take<float>((size_t)kMaxJobs * M * kTD);  // scratch of the feature branches: one region per small branch (they run
+  float* d1 = st->ws.take<float>((size_t)kMaxJobs * M * 64);   // together, stage by stage); the others use region 0 one after the other
+  if (st->ws.off > st->ws.cap) {
+    st->ws.off = mark;
     return fail(ctx, T2L_ENOMEM, "t2l_encode_cells_backward: workspace bound exceeded (internal error)");
   }
   const float* xl = st->layers.empty() ? st->X0 : st->layers.back().x2;
   (void)xl;
   hipLaunchKernelGGL(pool_norm_bwd_kernel, dim3(B), dim3(256), 0, s, grad_emb, st->out, st->pool_arg, st->pool_n, dcur);
-  const int ln_grid = std::min(32, (T + 15) / 16);  // few workgroups (each ends with 512 float atomics on the same addresses) of 16 waves
+  const Products pr{ctx, false};
   for (int l = (int)st->layers.size() - 1; l >= 0; --l) {
-    const LayerSave& L = st->layers[l];
-    auto W = [&](const char* n) -> const TTensor& { return T_(st, L.prefix + n); };
-    // norm2 + dropout2
-    hipLaunchKernelGGL(ln_bwd_kernel, dim3(ln_grid), dim3(1024), 0, s, dcur, L.xhat2, L.rstd2, T, W(".norm2.weight").data,
-                       make_drop(st->seed, l * 4 + 3, st->p), dA, dB, W(".norm2.weight").grad, W(".norm2.bias").grad);
-    // linear2
-    {  // dW2 += dB^T hd, and dH = (dB W2) through the ReLU + dropout backward — one launch
-      const Drop dr = make_drop(st->seed, l * 4 + 2, st->p);
-      gemm_tn_nn(dB, L.hd, W(".linear2.weight").grad, W(".linear2.bias").grad, W(".linear2.weight").data, dH, T, kTD, 2 * kTD, 0, L.h, &dr, s);
-    }
-    // linear1; dA (= dz2, the residual path) += dH W1
-    gemm_tn_nn(dH, L.x1, W(".linear1.weight").grad, W(".linear1.bias").grad, W(".linear1.weight").data, dA, T, 2 * kTD, kTD, 1, nullptr, nullptr, s);
-    // norm1 + dropout1
-    hipLaunchKernelGGL(ln_bwd_kernel, dim3(ln_grid), dim3(1024), 0, s, dA, L.xhat1, L.rstd1, T, W(".norm1.weight").data,
-                       make_drop(st->seed, l * 4 + 1, st->p), dC, dB2, W(".norm1.weight").grad, W(".norm1.bias").grad);
-    // out_proj
-    gemm_tn_nn(dB2, L.O, W(".self_attn.out_proj.weight").grad, W(".self_attn.out_proj.bias").grad, W(".self_attn.out_proj.weight").data, dO, T, kTD,
-               kTD, 0, nullptr, nullptr, s);
-    hipLaunchKernelGGL(attn_bwd_kernel, dim3(B * kTH), dim3(256), 0, s, L.qkv, L.P, dO, dqkv, make_drop(st->seed, l * 4 + 0, st->p));
-    // in_proj; dC (= dz1, the residual path) += dqkv Win
-    gemm_tn_nn(dqkv, L.x_in, W(".self_attn.in_proj_weight").grad, W(".self_attn.in_proj_bias").grad, W(".self_attn.in_proj_weight").data, dC, T,
-               3 * kTD, kTD, 1, nullptr, nullptr, s);
-    std::swap(dcur, dC);
+    float* dx = enc_layer_bwd<kTD, 16>(pr, st->t, st->layers[l], st->seed, st->p, sc, dcur, true, s);
+    sc.dC = dcur;  // (the layer's input gradient lives in the scratch's dC: the consumed dcur takes its place)
+    dcur = dx;
   }
   // tokens -> objects, merge MLP
   hipLaunchKernelGGL(scatter_norm_bwd_kernel, dim3((M + 3) / 4), dim3(256), 0, s, dcur, st->X0, st->save_nf, st->offsets, B, M, dfeat);
@@ -770,7 +856,7 @@ int train_backward_impl(t2l_ctx* ctx, const float* grad_emb, float* grad_pn_feat
     if (!smalls.empty()) small_branches_bwd(st, smalls, M, Kc, dcat, d2, d1, s);
   }
   event_end(ctx, "train_backward", s);
-  st->ws_off = mark;
+  st->ws.off = mark;
   T2L_HIP(ctx, hipGetLastError());
   if (ctx->sync_failed) return fail(ctx, T2L_ESTATE, "t2l_encode_cells_backward: the cross-rank sum callback (t2l_train_sync_bn) failed");
   return T2L_OK;
@@ -847,29 +933,21 @@ int zero_grad_impl(t2l_ctx* ctx, hipStream_t s) {
 // the BatchNorm at width 128: bound without inter_module tensors, out [n_sent, 128], the backward starts at the BatchNorm.
 // Forward keeps the activations; backward accumulates (+=) into the bound .grad buffers — the parameters stay torch's and are
 // stepped by t2l_text_adam_step (one launch over the 13.6 M head parameters; torch.optim.Adam when the caller prefers). The same
-// modular f32 kernels as the object branch (gemm_f32.h products, option train_bf16 for bf16 / split-bf16 operands), with the
-// attention / LayerNorm kernels in their generic forms (train_kernels.h).
+// modular f32 kernels as the object branch (gemm_f32.h products, option train_bf16 for bf16 / split-bf16 operands), and its
+// transformer layer (enc_layer_* above) with the products descriptor that lets a product run on the tiled GEMM.
 // =================================================================================================================
-struct TextLayer {
-  std::string prefix;
-  int T = 0, B = 0, S = 0, site0 = 0;
-  const float* x_in = nullptr;
-  float *qkv = nullptr, *P = nullptr, *O = nullptr, *xhat1 = nullptr, *rstd1 = nullptr, *x1 = nullptr, *h = nullptr, *hd = nullptr,
-        *xhat2 = nullptr, *rstd2 = nullptr, *x2 = nullptr;
-};
 struct TextTrain {
   t2l_ctx* ctx = nullptr;
   std::unordered_map<std::string, TTensor> t;
   std::string prefix;
-  char* ws = nullptr;
-  size_t ws_cap = 0, ws_off = 0;
+  Arena ws;
   bool have_forward = false;
   int n_sent = 0, L = 0, n_desc = 0, S = 0;
   int D = 256;        // width of inter_mlp: 256 (the coarse head) or 128 (the fine head)
   bool fine = false;  // the fine layout: no inter_module, the head ends behind inter_mlp's BatchNorm (out [n_sent, D])
   float p = 0.f;
   uint32_t seed = 0;
-  TextLayer intra, inter;
+  EncLayer intra, inter;
   float *pooled = nullptr, *mlp_y = nullptr, *mlp_out = nullptr, *bn_mean = nullptr, *bn_rstd = nullptr, *out = nullptr;
   int32_t *tok_arg = nullptr, *sent_arg = nullptr;
   // Adam over the head's parameters (t2l_text_adam_step): moments inside the library, one launch through the chunk table
@@ -885,17 +963,10 @@ static TextTrain* tstate(t2l_ctx* ctx) { return reinterpret_cast<TextTrain*>(ctx
 void free_text_train(t2l_ctx* ctx) {
   TextTrain* st = tstate(ctx);
   if (!st) return;
-  for (void* p : {(void*)st->ws, (void*)st->d_tensors, (void*)st->d_chunks, (void*)st->mv})
+  for (void* p : {(void*)st->ws.base, (void*)st->d_tensors, (void*)st->d_chunks, (void*)st->mv})
     if (p) (void)hipFree(p);
   delete st;
   ctx->text_train = nullptr;
-}
-template <typename T>
-static T* tbump(TextTrain* st, size_t count) {
-  const size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
-  T* p = reinterpret_cast<T*>(st->ws + st->ws_off);
-  st->ws_off += bytes;
-  return p;
 }
 static const TTensor& TT(TextTrain* st, const std::string& n) { return st->t.at(st->prefix + n); }
 
@@ -1003,8 +1074,8 @@ static int text_train_bind_body(t2l_ctx* ctx, const t2l_train_tensor* tensors, i
   }
   static PerDeviceOnce once;
   if (once.need(ctx->device)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_g_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_g_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<256, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<256, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     once.mark(ctx->device);
   }
   return T2L_OK;
@@ -1014,121 +1085,6 @@ int text_train_bind_impl(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n, c
   const int rc = text_train_bind_body(ctx, tensors, n, prefix);
   if (rc != T2L_OK) free_text_train(ctx);  // a refused bind leaves nothing half-bound behind: the next forward reports "bind first"
   return rc;
-}
-
-// The head's Linear products run on the tiled LDS-ring GEMM of text_head.hip (fast_gemm: 256 x 256 tiles, bf16 planes, split-bf16 by
-// default — 466 GFLOP per step at B = 64 are GEMM-shaped work that the object branch's tile-per-workgroup products, built for
-// 1,792-row operands, serve at a third of its rate); shapes it does not take (fewer than 64 rows) keep the products of gemm_f32.h
-// with the same operand arithmetic. (An f32-MFMA operand option existed until round 5: 7.6 ms per step against PyTorch's 5.6; removed.)
-static bool t_fast(TextTrain* st, int M, int N, int K) {
-  return N % 256 == 0 && K % 32 == 0 && K % 4 == 0 && M >= 64;
-}
-static void t_gemm_nt(TextTrain* st, const float* X, const float* W, const float* b, float* Y, int M, int N, int K, int relu, hipStream_t s) {
-  if (t_fast(st, M, N, K)) (void)fast_gemm(st->ctx, X, false, W, false, b, Y, M, N, K, relu, 0, st->ctx->text_train_bf16 == 1, s);
-  else gemm_nt(X, W, b, Y, M, N, K, relu, s);
-}
-// dW[N,Kp] += dY^T X, db[N] += column sums of dY, and (dX != nullptr) dX[M,Kp] (+)= dY W, through the ReLU + dropout backward of the
-// layer that produced X's pre-image when mask_src is given
-static void t_gemm_tn_nn(TextTrain* st, const float* dY, const float* X, float* dW, float* db, const float* W, float* dX, int M, int N, int Kp,
-                         int accumulate, const float* mask_src, const Drop* drop, hipStream_t s) {
-  if (t_fast(st, N, Kp, M) && (!dX || t_fast(st, M, Kp, N)) && N % 4 == 0) {
-    const bool single = st->ctx->text_train_bf16 == 1;
-    (void)fast_gemm(st->ctx, dY, true, X, true, nullptr, dW, N, Kp, M, 0, 1, single, s, db);  // (db: column sums of dY, in its split pass)
-    if (dX) {
-      (void)fast_gemm(st->ctx, dY, false, W, true, nullptr, dX, M, Kp, N, 0, accumulate, single, s);
-      if (mask_src) {
-        const size_t n = (size_t)M * Kp;
-        hipLaunchKernelGGL(relu_drop_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dX, mask_src, n, *drop);
-      }
-    }
-    return;
-  }
-  if (dX) gemm_tn_nn(dY, X, dW, db, W, dX, M, N, Kp, accumulate, mask_src, drop, s);
-  else gemm_tn(dY, X, dW, db, M, N, Kp, s);
-}
-
-static size_t attn_lds(int S, int HD, bool bwd) { return sizeof(float) * ((size_t)(bwd ? 4 : 3) * S * (HD + 1) + (size_t)(bwd ? 3 : 1) * S * (S + 1)); }
-
-template <int D>
-static void text_layer_alloc(TextTrain* st, TextLayer& L, float p) {
-  const size_t T = (size_t)L.T;
-  L.qkv = tbump<float>(st, T * 3 * D);
-  L.P = tbump<float>(st, (size_t)L.B * 4 * L.S * L.S);
-  L.O = tbump<float>(st, T * D);
-  L.xhat1 = tbump<float>(st, T * D);
-  L.rstd1 = tbump<float>(st, T);
-  L.x1 = tbump<float>(st, T * D);
-  L.h = tbump<float>(st, T * 4 * D);
-  L.hd = p > 0.f ? tbump<float>(st, T * 4 * D) : L.h;
-  L.xhat2 = tbump<float>(st, T * D);
-  L.rstd2 = tbump<float>(st, T);
-  L.x2 = tbump<float>(st, T * D);
-}
-template <int D>
-static void text_layer_fwd(TextTrain* st, TextLayer& L, float* tmp, hipStream_t s) {
-  constexpr int HD = D / 4, FF = 4 * D;
-  const int T = L.T;
-  auto W = [&](const char* n) -> const TTensor& { return TT(st, L.prefix + n); };
-  t_gemm_nt(st, L.x_in, W(".self_attn.in_proj_weight").data, W(".self_attn.in_proj_bias").data, L.qkv, T, 3 * D, D, 0, s);
-  hipLaunchKernelGGL((attn_fwd_g_kernel<HD>), dim3(L.B * 4), dim3(256), attn_lds(L.S, HD, false), s, L.qkv, L.P, L.O, L.S,
-                     make_drop(st->seed, L.site0 + 0, st->p));
-  t_gemm_nt(st, L.O, W(".self_attn.out_proj.weight").data, W(".self_attn.out_proj.bias").data, tmp, T, D, D, 0, s);
-  hipLaunchKernelGGL((ln_fwd_g_kernel<D>), dim3((T + 3) / 4), dim3(256), 0, s, L.x_in, (const float*)tmp, T, W(".norm1.weight").data,
-                     W(".norm1.bias").data, make_drop(st->seed, L.site0 + 1, st->p), L.x1, L.xhat1, L.rstd1);
-  if (t_fast(st, T, FF, D)) {  // linear1 + ReLU in the GEMM's epilogue (h is kept for backward); the dropout behind it as one pass
-    (void)fast_gemm(st->ctx, L.x1, false, W(".linear1.weight").data, false, W(".linear1.bias").data, L.h, T, FF, D, 1, 0, st->ctx->text_train_bf16 == 1, s);
-    if (st->p > 0.f) {
-      const size_t n = (size_t)T * FF;
-      hipLaunchKernelGGL(drop_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)L.h, n, make_drop(st->seed, L.site0 + 2, st->p), L.hd);
-    }
-  } else
-  {
-    GemmArgs g{L.x1, W(".linear1.weight").data, L.h, W(".linear1.bias").data, T, FF, D, D, D, FF, 1, 0, D, nullptr, tl_gemm_bf16};
-    if (st->p > 0.f) {
-      const Drop dr = make_drop(st->seed, L.site0 + 2, st->p);
-      g.epi = 1;
-      g.C2 = L.hd;
-      g.drop_key = dr.key;
-      g.drop_thr = dr.thr;
-      g.drop_scale = dr.scale;
-    }
-    gemm_nt_args(g, s);
-  }
-  t_gemm_nt(st, L.hd, W(".linear2.weight").data, W(".linear2.bias").data, tmp, T, D, FF, 0, s);
-  hipLaunchKernelGGL((ln_fwd_g_kernel<D>), dim3((T + 3) / 4), dim3(256), 0, s, (const float*)L.x1, (const float*)tmp, T, W(".norm2.weight").data,
-                     W(".norm2.bias").data, make_drop(st->seed, L.site0 + 3, st->p), L.x2, L.xhat2, L.rstd2);
-}
-// dcur: gradient w.r.t. the layer's output x2 (read). Returns the gradient w.r.t. the layer's input (nullptr when need_dx is false).
-template <int D>
-static float* text_layer_bwd(TextTrain* st, const TextLayer& L, const float* dcur, bool need_dx, hipStream_t s) {
-  constexpr int HD = D / 4, FF = 4 * D;
-  const int T = L.T;
-  const size_t n = (size_t)T * D;
-  float *dA = tbump<float>(st, n), *dB = tbump<float>(st, n), *dC = tbump<float>(st, n), *dB2 = tbump<float>(st, n), *dO = tbump<float>(st, n),
-        *dH = tbump<float>(st, n * 4), *dqkv = tbump<float>(st, n * 3);
-  auto W = [&](const char* nme) -> const TTensor& { return TT(st, L.prefix + nme); };
-  const int ln_grid = std::min(64, (T + 15) / 16);
-  hipLaunchKernelGGL((ln_bwd_g_kernel<D>), dim3(ln_grid), dim3(256), 0, s, dcur, (const float*)L.xhat2, (const float*)L.rstd2, T,
-                     W(".norm2.weight").data, make_drop(st->seed, L.site0 + 3, st->p), dA, dB, W(".norm2.weight").grad, W(".norm2.bias").grad);
-  {
-    const Drop dr = make_drop(st->seed, L.site0 + 2, st->p);
-    t_gemm_tn_nn(st, dB, L.hd, W(".linear2.weight").grad, W(".linear2.bias").grad, W(".linear2.weight").data, dH, T, D, FF, 0, L.h, &dr, s);
-  }
-  t_gemm_tn_nn(st, dH, L.x1, W(".linear1.weight").grad, W(".linear1.bias").grad, W(".linear1.weight").data, dA, T, FF, D, 1, nullptr, nullptr, s);
-  hipLaunchKernelGGL((ln_bwd_g_kernel<D>), dim3(ln_grid), dim3(256), 0, s, (const float*)dA, (const float*)L.xhat1, (const float*)L.rstd1, T,
-                     W(".norm1.weight").data, make_drop(st->seed, L.site0 + 1, st->p), dC, dB2, W(".norm1.weight").grad, W(".norm1.bias").grad);
-  t_gemm_tn_nn(st, dB2, L.O, W(".self_attn.out_proj.weight").grad, W(".self_attn.out_proj.bias").grad, W(".self_attn.out_proj.weight").data, dO, T, D,
-               D, 0, nullptr, nullptr, s);
-  hipLaunchKernelGGL((attn_bwd_g_kernel<HD>), dim3(L.B * 4), dim3(256), attn_lds(L.S, HD, true), s, (const float*)L.qkv, (const float*)L.P,
-                     (const float*)dO, dqkv, L.S, make_drop(st->seed, L.site0 + 0, st->p));
-  if (need_dx) {
-    t_gemm_tn_nn(st, dqkv, L.x_in, W(".self_attn.in_proj_weight").grad, W(".self_attn.in_proj_bias").grad, W(".self_attn.in_proj_weight").data, dC,
-                 T, 3 * D, D, 1, nullptr, nullptr, s);
-    return dC;
-  }
-  t_gemm_tn_nn(st, dqkv, L.x_in, W(".self_attn.in_proj_weight").grad, W(".self_attn.in_proj_bias").grad, nullptr, nullptr, T, 3 * D, D, 0, nullptr,
-               nullptr, s);
-  return nullptr;
 }
 
 int text_train_forward_impl(t2l_ctx* ctx, const float* hidden, int n_sent, int L, int n_desc, float p, uint32_t seed, float* out, hipStream_t s) {
@@ -1142,37 +1098,38 @@ int text_train_forward_impl(t2l_ctx* ctx, const float* hidden, int n_sent, int L
   tl_gemm_bf16 = ctx->text_train_bf16;
   tl_gemm_block64 = ctx->train_gemm_block == 64 || (ctx->train_gemm_block == 0 && ctx->text_train_bf16 != 0);
   const size_t T1 = (size_t)n_sent * L;
-  // saved activations + the backward's scratch: ~31 floats per (row, column) of each layer, see text_layer_alloc / text_layer_bwd
+  // saved activations + the backward's scratch: ~31 floats per (row, column) of each layer, see enc_layer_alloc / enc_scratch_take
   const size_t need = sizeof(float) * (32 * (T1 * 1024 + (size_t)n_sent * 256) + 2 * (size_t)n_sent * 4 * L * L + 2 * (size_t)n_desc * 4 * S * S +
                                        8 * (size_t)n_sent * 1024 + 16 * (size_t)n_desc * 256) + (1 << 20);
-  if (st->ws_cap < need) {
-    if (st->ws) T2L_HIP(ctx, hipFree(st->ws));
-    st->ws = nullptr;
-    st->ws_cap = 0;
-    T2L_HIP(ctx, hipMalloc(&st->ws, need));
-    st->ws_cap = need;
+  if (st->ws.cap < need) {
+    if (st->ws.base) T2L_HIP(ctx, hipFree(st->ws.base));
+    st->ws.base = nullptr;
+    st->ws.cap = 0;
+    T2L_HIP(ctx, hipMalloc(&st->ws.base, need));
+    st->ws.cap = need;
   }
-  st->ws_off = 0;
+  st->ws.off = 0;
   st->have_forward = false;
   st->n_sent = n_sent; st->L = L; st->n_desc = n_desc; st->S = S; st->p = p; st->seed = seed;
   event_begin(ctx, "text_train_forward", s);
-  float* tmp = tbump<float>(st, T1 * 1024);
-  TextLayer& A = st->intra;
-  A = TextLayer{};
-  A.prefix = "intra_module.0"; A.T = (int)T1; A.B = n_sent; A.S = L; A.site0 = 0; A.x_in = hidden;
-  text_layer_alloc<1024>(st, A, p);
-  text_layer_fwd<1024>(st, A, tmp, s);
-  st->pooled = tbump<float>(st, (size_t)n_sent * 1024);
-  st->tok_arg = tbump<int32_t>(st, (size_t)n_sent * 1024);
+  float* tmp = st->ws.take<float>(T1 * 1024);
+  const Products pr{ctx, true};
+  EncLayer& A = st->intra;
+  A = EncLayer{};
+  A.prefix = st->prefix + "intra_module.0"; A.T = (int)T1; A.B = n_sent; A.S = L; A.FF = 4096; A.site0 = 0; A.x_in = hidden;
+  enc_layer_alloc<1024>(st->ws, A, p);
+  enc_layer_fwd<1024>(pr, st->t, A, seed, p, tmp, s);
+  st->pooled = st->ws.take<float>((size_t)n_sent * 1024);
+  st->tok_arg = st->ws.take<int32_t>((size_t)n_sent * 1024);
   hipLaunchKernelGGL(seq_max_fwd_kernel, dim3((unsigned)(((size_t)n_sent * 1024 + 255) / 256)), dim3(256), 0, s, (const float*)A.x2, (const float*)nullptr,
                      n_sent, L, 1024, st->pooled, st->tok_arg);
   const int D = st->D;
-  st->mlp_y = tbump<float>(st, (size_t)n_sent * D);
-  st->mlp_out = tbump<float>(st, (size_t)n_sent * D);
-  st->bn_mean = tbump<float>(st, D);
-  st->bn_rstd = tbump<float>(st, D);
+  st->mlp_y = st->ws.take<float>((size_t)n_sent * D);
+  st->mlp_out = st->ws.take<float>((size_t)n_sent * D);
+  st->bn_mean = st->ws.take<float>(D);
+  st->bn_rstd = st->ws.take<float>(D);
   // (D = 128 is no multiple of the fast GEMM's 256-column tile: the fine head's Linear runs on the gemm_f32.h product, same operands)
-  t_gemm_nt(st, st->pooled, TT(st, "inter_mlp.0.0.weight").data, TT(st, "inter_mlp.0.0.bias").data, st->mlp_y, n_sent, D, 1024, 0, s);
+  t_gemm_nt(pr, st->pooled, TT(st, "inter_mlp.0.0.weight").data, TT(st, "inter_mlp.0.0.bias").data, st->mlp_y, n_sent, D, 1024, 0, s);
 #define T2L_TEXT_BN_FWD(PHASE, ACC)                                                                                                       \
   hipLaunchKernelGGL((bn_plain_fwd_kernel<PHASE>), dim3(D / 4), dim3(256), 0, s, (const float*)st->mlp_y, n_sent, D,                      \
                      TT(st, "inter_mlp.0.1.weight").data, TT(st, "inter_mlp.0.1.bias").data, TT(st, "inter_mlp.0.1.running_mean").data,   \
@@ -1191,24 +1148,24 @@ int text_train_forward_impl(t2l_ctx* ctx, const float* hidden, int n_sent, int L
     T2L_HIP(ctx, hipMemcpyAsync(out, st->mlp_out, sizeof(float) * (size_t)n_sent * D, hipMemcpyDeviceToDevice, s));
     event_end(ctx, "text_train_forward", s);
     T2L_HIP(ctx, hipGetLastError());
-    if (st->ws_off > st->ws_cap) return fail(ctx, T2L_ENOMEM, "t2l_text_head_train: workspace bound exceeded (internal error)");
+    if (st->ws.off > st->ws.cap) return fail(ctx, T2L_ENOMEM, "t2l_text_head_train: workspace bound exceeded (internal error)");
     if (ctx->sync_failed) return fail(ctx, T2L_ESTATE, "t2l_text_head_train: the cross-rank sum callback (t2l_train_sync_bn) failed");
     st->have_forward = true;
     return T2L_OK;
   }
-  TextLayer& I = st->inter;
-  I = TextLayer{};
-  I.prefix = "inter_module.0"; I.T = n_sent; I.B = n_desc; I.S = S; I.site0 = 4; I.x_in = st->mlp_out;
-  text_layer_alloc<256>(st, I, p);
-  text_layer_fwd<256>(st, I, tmp, s);
-  st->out = tbump<float>(st, (size_t)n_desc * 256);
-  st->sent_arg = tbump<int32_t>(st, (size_t)n_desc * 256);
+  EncLayer& I = st->inter;
+  I = EncLayer{};
+  I.prefix = st->prefix + "inter_module.0"; I.T = n_sent; I.B = n_desc; I.S = S; I.FF = 1024; I.site0 = 4; I.x_in = st->mlp_out;
+  enc_layer_alloc<256>(st->ws, I, p);
+  enc_layer_fwd<256>(pr, st->t, I, seed, p, tmp, s);
+  st->out = st->ws.take<float>((size_t)n_desc * 256);
+  st->sent_arg = st->ws.take<int32_t>((size_t)n_desc * 256);
   hipLaunchKernelGGL(seq_max_fwd_kernel, dim3((unsigned)(((size_t)n_desc * 256 + 255) / 256)), dim3(256), 0, s, (const float*)I.x2,
                      (const float*)st->mlp_out, n_desc, S, 256, st->out, st->sent_arg);
   T2L_HIP(ctx, hipMemcpyAsync(out, st->out, sizeof(float) * (size_t)n_desc * 256, hipMemcpyDeviceToDevice, s));
   event_end(ctx, "text_train_forward", s);
   T2L_HIP(ctx, hipGetLastError());
-  if (st->ws_off > st->ws_cap) return fail(ctx, T2L_ENOMEM, "t2l_text_head_train: workspace bound exceeded (internal error)");
+  if (st->ws.off > st->ws.cap) return fail(ctx, T2L_ENOMEM, "t2l_text_head_train: workspace bound exceeded (internal error)");
   if (ctx->sync_failed) return fail(ctx, T2L_ESTATE, "t2l_text_head_train: the cross-rank sum callback (t2l_train_sync_bn) failed");
   st->have_forward = true;
   return T2L_OK;
@@ -1220,20 +1177,21 @@ int text_train_backward_impl(t2l_ctx* ctx, const float* grad_out, hipStream_t s)
   if (!grad_out) return fail(ctx, T2L_EINVAL, "t2l_text_head_backward: null gradient");
   tl_gemm_bf16 = ctx->text_train_bf16;
   tl_gemm_block64 = ctx->train_gemm_block == 64 || (ctx->train_gemm_block == 0 && ctx->text_train_bf16 != 0);
-  const size_t mark = st->ws_off;
+  const size_t mark = st->ws.off;
+  const Products pr{ctx, true};
   const int n_sent = st->n_sent, n_desc = st->n_desc, S = st->S, L = st->L;
   const int D = st->D;
   event_begin(ctx, "text_train_backward", s);
   float* dX;
   if (st->fine) {  // grad_out IS the gradient behind the BatchNorm; its backward works in place, so on a copy
-    dX = tbump<float>(st, (size_t)n_sent * D);
+    dX = st->ws.take<float>((size_t)n_sent * D);
     T2L_HIP(ctx, hipMemcpyAsync(dX, grad_out, sizeof(float) * (size_t)n_sent * D, hipMemcpyDeviceToDevice, s));
   } else {
     // max over the sentences: the gradient goes to the arg-max row of (x + layer(x)) — to the layer's output AND to the residual x
-    float* dY2 = tbump<float>(st, (size_t)n_sent * 256);
+    float* dY2 = st->ws.take<float>((size_t)n_sent * 256);
     hipLaunchKernelGGL(seq_max_bwd_kernel, dim3((unsigned)(((size_t)n_sent * 256 + 255) / 256)), dim3(256), 0, s, grad_out, (const int32_t*)st->sent_arg,
                        n_desc, S, 256, dY2);
-    dX = text_layer_bwd<256>(st, st->inter, dY2, true, s);
+    dX = enc_layer_bwd<256, 4>(pr, st->t, st->inter, st->seed, st->p, enc_scratch_take<256>(st->ws, n_sent, 1024), dY2, true, s);
     hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)(((size_t)n_sent * 256 + 255) / 256)), dim3(256), 0, s, dX, (const float*)dY2, (size_t)n_sent * 256);
   }
   // inter_mlp: BatchNorm (batch statistics), Linear
@@ -1251,17 +1209,17 @@ int text_train_backward_impl(t2l_ctx* ctx, const float* grad_out, hipStream_t s)
     T2L_TEXT_BN_BWD(0, (double*)nullptr);
   }
 #undef T2L_TEXT_BN_BWD
-  float* dpool = tbump<float>(st, (size_t)n_sent * 1024);
-  t_gemm_tn_nn(st, dX, st->pooled, TT(st, "inter_mlp.0.0.weight").grad, TT(st, "inter_mlp.0.0.bias").grad, TT(st, "inter_mlp.0.0.weight").data, dpool,
+  float* dpool = st->ws.take<float>((size_t)n_sent * 1024);
+  t_gemm_tn_nn(pr, dX, st->pooled, TT(st, "inter_mlp.0.0.weight").grad, TT(st, "inter_mlp.0.0.bias").grad, TT(st, "inter_mlp.0.0.weight").data, dpool,
                n_sent, D, 1024, 0, nullptr, nullptr, s);
   // max over the tokens, then the d = 1024 layer (its input, T5's hidden states, is a constant: no dX)
-  float* dX2 = tbump<float>(st, (size_t)n_sent * L * 1024);
+  float* dX2 = st->ws.take<float>((size_t)n_sent * L * 1024);
   hipLaunchKernelGGL(seq_max_bwd_kernel, dim3((unsigned)(((size_t)n_sent * L * 1024 + 255) / 256)), dim3(256), 0, s, (const float*)dpool,
                      (const int32_t*)st->tok_arg, n_sent, L, 1024, dX2);
-  text_layer_bwd<1024>(st, st->intra, dX2, false, s);
+  enc_layer_bwd<1024, 4>(pr, st->t, st->intra, st->seed, st->p, enc_scratch_take<1024>(st->ws, n_sent * L, 4096), dX2, false, s);
   event_end(ctx, "text_train_backward", s);
-  const bool over = st->ws_off > st->ws_cap;
-  st->ws_off = mark;
+  const bool over = st->ws.off > st->ws.cap;
+  st->ws.off = mark;
   T2L_HIP(ctx, hipGetLastError());
   if (over) return fail(ctx, T2L_ENOMEM, "t2l_text_head_backward: workspace bound exceeded (internal error)");
   if (ctx->sync_failed) return fail(ctx, T2L_ESTATE, "t2l_text_head_backward: the cross-rank sum callback (t2l_train_sync_bn) failed");

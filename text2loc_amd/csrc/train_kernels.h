@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "gemm_f32.h"
+#include "train_common.h"
 
 namespace t2l {
 namespace train {
@@ -38,22 +39,6 @@ __device__ __forceinline__ float wsum(float v) {
   }
   return v;
 }
-
-// Counter-based dropout: keep element `idx` of site `site` iff the top 24 bits of lowbias32(idx*0x9E3779B1 + key) >= thr,
-// key = seed ^ site*0x85EBCA77, thr = p*2^24. oracle/t2l_oracle_train.py:dropout_keep is the same function.
-__device__ __forceinline__ bool keep_bit(uint32_t key, uint32_t idx, uint32_t thr) {
-  uint32_t x = idx * 0x9E3779B1u + key;
-  x ^= x >> 16;
-  x *= 0x7FEB352Du;
-  x ^= x >> 15;
-  x *= 0x846CA68Bu;
-  x ^= x >> 16;
-  return (x >> 8) >= thr;
-}
-struct Drop {
-  uint32_t key, thr;
-  float scale;  // 1/(1-p); thr == 0 -> identity
-};
 
 // ---------------------------------------------------------------------------------------------------------------
 // first Linear of the small branches (K = 1 or 3 inputs -> 64): y[m][c] = b[c] + sum_k x[m][k] w[c][k]
@@ -438,213 +423,273 @@ __global__ void scatter_norm_bwd_kernel(const float* __restrict__ dX0, const flo
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// self-attention over the 28 slots of one cell, one workgroup per (cell, head). No padding mask (cell_retrieval.py:102).
+// The kernels of one nn.TransformerEncoderLayer, for every caller (train.hip: enc_layer_fwd / enc_layer_bwd): the object branch's
+// obj_inter_module.* (D 256, 28 slots per cell) and the text head's intra_module.0 (D 1024 over L <= 32 tokens per sentence) and
+// inter_module.0 (D 256 over S <= 32 sentences per description; models/language_encoder.py:97-101,127-147).
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int kAS = kTHd + 1;  // LDS row stride of q/k/v tiles
-__global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ P,
-                                                       float* __restrict__ O, Drop dr) {
-  __shared__ float q[kTS * kAS], k[kTS * kAS], v[kTS * kAS], p[kTS * (kTS + 1)];
-  const int b = blockIdx.x >> 2, h = blockIdx.x & 3, tid = threadIdx.x;
-#pragma unroll  // (7 trips: every global load of the tile issued before the first LDS write waits for one)
-  for (int i = tid; i < kTS * kTHd; i += 256) {
-    const int s = i >> 6, d = i & 63;
-    const float* base = qkv + (size_t)(b * kTS + s) * (3 * kTD) + h * kTHd + d;
-    q[s * kAS + d] = base[0];
-    k[s * kAS + d] = base[kTD];
-    v[s * kAS + d] = base[2 * kTD];
+// self-attention over the S rows of one group (cell / sentence / description), one workgroup per (group, head); qkv [rows][3 D],
+// D = 4 HD. No padding mask (cell_retrieval.py:102). Dynamic LDS (train.hip: attn_lds): q, k, v tiles [S][HD + 1] + p [S][S + 1]
+// (forward), + go and two more [S][S + 1] (backward).
+// CS: S at compile time, 0 = the run-time argument. The object branch instantiates its 28 (every trip count known: its step is
+// latency-bound, and with S at run time its forward and backward measured 4-5 % slower, profiles/train_layer.md); same arithmetic.
+template <int HD, int CS>
+__global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ P, float* __restrict__ O,
+                                                       int S_rt, Drop dr) {
+  extern __shared__ float sm[];
+  constexpr int AS = HD + 1, D = 4 * HD;
+  // (S known: the tile's load loop unrolled whole, every global load issued before the first LDS write waits for one)
+  constexpr int kLoadTrips = CS ? (CS * HD + 255) / 256 : 1;
+  const int S = CS ? CS : S_rt;
+  float *q = sm, *k = q + S * AS, *v = k + S * AS, *p = v + S * AS;
+  const int b = blockIdx.x >> 2, h = blockIdx.x & 3, tid = threadIdx.x, SP = S + 1;
+  const float scale = 1.0f / sqrtf((float)HD);
+#pragma unroll kLoadTrips
+  for (int i = tid; i < S * HD; i += 256) {
+    const int s = i / HD, d = i - s * HD;
+    const float* base = qkv + (size_t)(b * S + s) * (3 * D) + h * HD + d;
+    q[s * AS + d] = base[0];
+    k[s * AS + d] = base[D];
+    v[s * AS + d] = base[2 * D];
   }
   __syncthreads();
-  for (int e = tid; e < kTS * kTS; e += 256) {
-    const int i = e / kTS, j = e - i * kTS;
+  for (int e = tid; e < S * S; e += 256) {
+    const int i = e / S, j = e - i * S;
     float s = 0.f;
 #pragma unroll 8
-    for (int d = 0; d < kTHd; ++d) s += q[i * kAS + d] * k[j * kAS + d];
-    p[i * (kTS + 1) + j] = s * 0.125f;
+    for (int d = 0; d < HD; ++d) s += q[i * AS + d] * k[j * AS + d];
+    p[i * SP + j] = s * scale;
   }
   __syncthreads();
-  if (tid < kTS) {
-    float* row = p + tid * (kTS + 1);
+  if (tid < S) {
+    float* row = p + tid * SP;
     float mx = row[0];
-    for (int j = 1; j < kTS; ++j) mx = fmaxf(mx, row[j]);
+    for (int j = 1; j < S; ++j) mx = fmaxf(mx, row[j]);
     float sum = 0.f;
-    for (int j = 0; j < kTS; ++j) {
+    for (int j = 0; j < S; ++j) {
       row[j] = expf(row[j] - mx);
       sum += row[j];
     }
-    for (int j = 0; j < kTS; ++j) row[j] /= sum;
+    for (int j = 0; j < S; ++j) row[j] /= sum;
   }
   __syncthreads();
-  const size_t pbase = (size_t)blockIdx.x * kTS * kTS;
-  for (int e = tid; e < kTS * kTS; e += 256) {
-    const int i = e / kTS, j = e - i * kTS;
-    float pv = p[i * (kTS + 1) + j];
+  const size_t pbase = (size_t)blockIdx.x * S * S;
+  for (int e = tid; e < S * S; e += 256) {
+    const int i = e / S, j = e - i * S;
+    float pv = p[i * SP + j];
     P[pbase + e] = pv;  // probabilities BEFORE dropout (softmax backward needs them)
     if (dr.thr) pv = keep_bit(dr.key, (uint32_t)(pbase + e), dr.thr) ? pv * dr.scale : 0.f;
-    p[i * (kTS + 1) + j] = pv;
+    p[i * SP + j] = pv;
   }
   __syncthreads();
-  for (int e = tid; e < kTS * kTHd; e += 256) {
-    const int i = e >> 6, d = e & 63;
+  for (int e = tid; e < S * HD; e += 256) {
+    const int i = e / HD, d = e - i * HD;
     float s = 0.f;
-    for (int j = 0; j < kTS; ++j) s += p[i * (kTS + 1) + j] * v[j * kAS + d];
-    O[(size_t)(b * kTS + i) * kTD + h * kTHd + d] = s;
+    for (int j = 0; j < S; ++j) s += p[i * SP + j] * v[j * AS + d];
+    O[(size_t)(b * S + i) * D + h * HD + d] = s;
   }
 }
+template <int HD, int CS>
 __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ P,
-                                                       const float* __restrict__ dO, float* __restrict__ dqkv, Drop dr) {
-  __shared__ float q[kTS * kAS], k[kTS * kAS], v[kTS * kAS], go[kTS * kAS];
-  __shared__ float p[kTS * (kTS + 1)], pd[kTS * (kTS + 1)], ds[kTS * (kTS + 1)];
+                                                       const float* __restrict__ dO, float* __restrict__ dqkv, int S_rt, Drop dr) {
+  extern __shared__ float sm[];
+  constexpr int AS = HD + 1, D = 4 * HD;
+  // (S known: the tile's load loop unrolled whole, every global load issued before the first LDS write waits for one)
+  constexpr int kLoadTrips = CS ? (CS * HD + 255) / 256 : 1;
+  const int S = CS ? CS : S_rt;
+  const int SP = S + 1;
+  float *q = sm, *k = q + S * AS, *v = k + S * AS, *go = v + S * AS, *p = go + S * AS, *pd = p + S * SP, *ds = pd + S * SP;
   const int b = blockIdx.x >> 2, h = blockIdx.x & 3, tid = threadIdx.x;
-#pragma unroll  // (7 trips: every global load of the tile issued before the first LDS write waits for one)
-  for (int i = tid; i < kTS * kTHd; i += 256) {
-    const int s = i >> 6, d = i & 63;
-    const float* base = qkv + (size_t)(b * kTS + s) * (3 * kTD) + h * kTHd + d;
-    q[s * kAS + d] = base[0];
-    k[s * kAS + d] = base[kTD];
-    v[s * kAS + d] = base[2 * kTD];
-    go[s * kAS + d] = dO[(size_t)(b * kTS + s) * kTD + h * kTHd + d];
+  const float scale = 1.0f / sqrtf((float)HD);
+#pragma unroll kLoadTrips
+  for (int i = tid; i < S * HD; i += 256) {
+    const int s = i / HD, d = i - s * HD;
+    const float* base = qkv + (size_t)(b * S + s) * (3 * D) + h * HD + d;
+    q[s * AS + d] = base[0];
+    k[s * AS + d] = base[D];
+    v[s * AS + d] = base[2 * D];
+    go[s * AS + d] = dO[(size_t)(b * S + s) * D + h * HD + d];
   }
-  const size_t pbase = (size_t)blockIdx.x * kTS * kTS;
-  for (int e = tid; e < kTS * kTS; e += 256) {
-    const int i = e / kTS, j = e - i * kTS;
+  const size_t pbase = (size_t)blockIdx.x * S * S;
+  for (int e = tid; e < S * S; e += 256) {
+    const int i = e / S, j = e - i * S;
     const float pv = P[pbase + e];
     const float m = dr.thr ? (keep_bit(dr.key, (uint32_t)(pbase + e), dr.thr) ? dr.scale : 0.f) : 1.f;
-    p[i * (kTS + 1) + j] = pv;
-    pd[i * (kTS + 1) + j] = pv * m;
-    ds[i * (kTS + 1) + j] = m;  // mask factor for now
+    p[i * SP + j] = pv;
+    pd[i * SP + j] = pv * m;
+    ds[i * SP + j] = m;  // mask factor for now
   }
   __syncthreads();
-  // dV[j][d] = sum_i Pd[i][j] dO[i][d]
-  for (int e = tid; e < kTS * kTHd; e += 256) {
-    const int j = e >> 6, d = e & 63;
+  for (int e = tid; e < S * HD; e += 256) {  // dV[j][d] = sum_i Pd[i][j] dO[i][d]
+    const int j = e / HD, d = e - j * HD;
     float s = 0.f;
-    for (int i = 0; i < kTS; ++i) s += pd[i * (kTS + 1) + j] * go[i * kAS + d];
-    dqkv[(size_t)(b * kTS + j) * (3 * kTD) + 2 * kTD + h * kTHd + d] = s;
+    for (int i = 0; i < S; ++i) s += pd[i * SP + j] * go[i * AS + d];
+    dqkv[(size_t)(b * S + j) * (3 * D) + 2 * D + h * HD + d] = s;
   }
-  // dP[i][j] = mask * sum_d dO[i][d] V[j][d]
-  for (int e = tid; e < kTS * kTS; e += 256) {
-    const int i = e / kTS, j = e - i * kTS;
+  for (int e = tid; e < S * S; e += 256) {  // dP[i][j] = mask * sum_d dO[i][d] V[j][d]
+    const int i = e / S, j = e - i * S;
     float s = 0.f;
 #pragma unroll 8
-    for (int d = 0; d < kTHd; ++d) s += go[i * kAS + d] * v[j * kAS + d];
-    ds[i * (kTS + 1) + j] *= s;
+    for (int d = 0; d < HD; ++d) s += go[i * AS + d] * v[j * AS + d];
+    ds[i * SP + j] *= s;
   }
   __syncthreads();
-  if (tid < kTS) {  // dS = P * (dP - sum_j dP*P) / sqrt(hd)
+  if (tid < S) {  // dS = P * (dP - sum_j dP*P) / sqrt(hd)
     float t = 0.f;
-    for (int j = 0; j < kTS; ++j) t += ds[tid * (kTS + 1) + j] * p[tid * (kTS + 1) + j];
-    for (int j = 0; j < kTS; ++j)
-      ds[tid * (kTS + 1) + j] = p[tid * (kTS + 1) + j] * (ds[tid * (kTS + 1) + j] - t) * 0.125f;
+    for (int j = 0; j < S; ++j) t += ds[tid * SP + j] * p[tid * SP + j];
+    for (int j = 0; j < S; ++j) ds[tid * SP + j] = p[tid * SP + j] * (ds[tid * SP + j] - t) * scale;
   }
   __syncthreads();
-  for (int e = tid; e < kTS * kTHd; e += 256) {
-    const int i = e >> 6, d = e & 63;
+  for (int e = tid; e < S * HD; e += 256) {
+    const int i = e / HD, d = e - i * HD;
     float sq = 0.f, sk = 0.f;
-    for (int j = 0; j < kTS; ++j) {
-      sq += ds[i * (kTS + 1) + j] * k[j * kAS + d];  // dQ[i] = sum_j dS[i][j] K[j]
-      sk += ds[j * (kTS + 1) + i] * q[j * kAS + d];  // dK[i] = sum_j dS[j][i] Q[j]
+    for (int j = 0; j < S; ++j) {
+      sq += ds[i * SP + j] * k[j * AS + d];
+      sk += ds[j * SP + i] * q[j * AS + d];
     }
-    float* base = dqkv + (size_t)(b * kTS + i) * (3 * kTD) + h * kTHd + d;
+    float* base = dqkv + (size_t)(b * S + i) * (3 * D) + h * HD + d;
     base[0] = sq;
-    base[kTD] = sk;
+    base[D] = sk;
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// out = LayerNorm(x + dropout(y)); one wave per token. Saves xhat and rstd.
-// ---------------------------------------------------------------------------------------------------------------
-__global__ void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y, int T,
-                              const float* __restrict__ gamma, const float* __restrict__ beta, Drop dr,
-                              float* __restrict__ out, float* __restrict__ xhat, float* __restrict__ save_rstd) {
+// out = LayerNorm(x + dropout(y)) over D columns, one wave per row (D / 256 float4 per lane, each wave-load 1 KiB contiguous).
+// Saves xhat and rstd.
+template <int D>
+__global__ void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y, int T, const float* __restrict__ gamma,
+                              const float* __restrict__ beta, Drop dr, float* __restrict__ out, float* __restrict__ xhat,
+                              float* __restrict__ save_rstd) {
+  constexpr int NV = D / 256;
   const int t = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
   if (t >= T) return;
-  const size_t o = (size_t)t * kTD + lane * 4;
-  float4 a = *reinterpret_cast<const float4*>(x + o);
-  float4 f = *reinterpret_cast<const float4*>(y + o);
-  if (dr.thr) {
-    f.x = keep_bit(dr.key, (uint32_t)o + 0, dr.thr) ? f.x * dr.scale : 0.f;
-    f.y = keep_bit(dr.key, (uint32_t)o + 1, dr.thr) ? f.y * dr.scale : 0.f;
-    f.z = keep_bit(dr.key, (uint32_t)o + 2, dr.thr) ? f.z * dr.scale : 0.f;
-    f.w = keep_bit(dr.key, (uint32_t)o + 3, dr.thr) ? f.w * dr.scale : 0.f;
+  float4 a[NV];
+  float s1 = 0.f;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const size_t o = (size_t)t * D + j * 256 + lane * 4;
+    a[j] = *reinterpret_cast<const float4*>(x + o);
+    float4 f = *reinterpret_cast<const float4*>(y + o);
+    if (dr.thr) {
+      f.x = keep_bit(dr.key, (uint32_t)o + 0, dr.thr) ? f.x * dr.scale : 0.f;
+      f.y = keep_bit(dr.key, (uint32_t)o + 1, dr.thr) ? f.y * dr.scale : 0.f;
+      f.z = keep_bit(dr.key, (uint32_t)o + 2, dr.thr) ? f.z * dr.scale : 0.f;
+      f.w = keep_bit(dr.key, (uint32_t)o + 3, dr.thr) ? f.w * dr.scale : 0.f;
+    }
+    a[j].x += f.x; a[j].y += f.y; a[j].z += f.z; a[j].w += f.w;
+    s1 += (a[j].x + a[j].y) + (a[j].z + a[j].w);
   }
-  a.x += f.x; a.y += f.y; a.z += f.z; a.w += f.w;
-  const float mu = wsum(a.x + a.y + a.z + a.w) * (1.f / kTD);
-  a.x -= mu; a.y -= mu; a.z -= mu; a.w -= mu;
-  const float var = wsum(a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w) * (1.f / kTD);
-  const float rstd = 1.0f / sqrtf(var + kLnEps);
-  const float4 h = make_float4(a.x * rstd, a.y * rstd, a.z * rstd, a.w * rstd);
-  const float4 g = *reinterpret_cast<const float4*>(gamma + lane * 4);
-  const float4 be = *reinterpret_cast<const float4*>(beta + lane * 4);
-  *reinterpret_cast<float4*>(xhat + o) = h;
-  *reinterpret_cast<float4*>(out + o) = make_float4(h.x * g.x + be.x, h.y * g.y + be.y, h.z * g.z + be.z, h.w * g.w + be.w);
+  const float mu = wsum(s1) * (1.f / D);
+  float s2 = 0.f;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    a[j].x -= mu; a[j].y -= mu; a[j].z -= mu; a[j].w -= mu;
+    s2 += (a[j].x * a[j].x + a[j].y * a[j].y) + (a[j].z * a[j].z + a[j].w * a[j].w);
+  }
+  const float rstd = 1.0f / sqrtf(wsum(s2) * (1.f / D) + kLnEps);
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const size_t o = (size_t)t * D + j * 256 + lane * 4;
+    const float4 h = make_float4(a[j].x * rstd, a[j].y * rstd, a[j].z * rstd, a[j].w * rstd);
+    const float4 g = *reinterpret_cast<const float4*>(gamma + j * 256 + lane * 4);
+    const float4 be = *reinterpret_cast<const float4*>(beta + j * 256 + lane * 4);
+    *reinterpret_cast<float4*>(xhat + o) = h;
+    *reinterpret_cast<float4*>(out + o) = make_float4(h.x * g.x + be.x, h.y * g.y + be.y, h.z * g.z + be.z, h.w * g.w + be.w);
+  }
   if (lane == 0) save_rstd[t] = rstd;
 }
 // dz = LN backward of dout; d_res = dz (gradient of the residual input), d_y = dz * dropout mask (gradient of y).
-// dgamma/dbeta: per-workgroup column partials, then atomics. grid = any; each workgroup strides over tokens.
-// Workgroups of 16 waves: the dgamma / dbeta atomics of a workgroup land on the same 512 addresses as everybody else's (~75 ns per
-// same-address atomic: 64 workgroups of 4 waves spent ~5 of their 10.7 us there, 128 workgroups took 15.5 us), so the rows are
-// spread over MORE WAVES per workgroup instead of more workgroups.
-__global__ __launch_bounds__(1024) void ln_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ xhat,
-                                                     const float* __restrict__ save_rstd, int T,
-                                                     const float* __restrict__ gamma, Drop dr, float* __restrict__ d_res,
-                                                     float* __restrict__ d_y, float* __restrict__ dgamma,
-                                                     float* __restrict__ dbeta) {
-  __shared__ float4 rg[1024], rb[1024];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
-  const float4 g = *reinterpret_cast<const float4*>(gamma + lane * 4);
-  float4 ag = make_float4(0.f, 0.f, 0.f, 0.f), ab = ag;
-  // a wave walks ~7 token rows: the next row's operands are loaded before the current row is reduced and stored (written as
-  // load -> reduce -> store per row, every row paid its own L2 round trip behind the previous row's stores: 11.4 us per launch)
-  const int stride = gridDim.x * nw;
-  int t = blockIdx.x * nw + w;
-  float4 d = make_float4(0.f, 0.f, 0.f, 0.f), h = d;
+// dgamma/dbeta: per-workgroup column partials, then atomics. grid = any; each of a workgroup's WAVES waves strides over rows.
+// The dgamma / dbeta atomics of a workgroup land on the same 2 D addresses as everybody else's (~75 ns per same-address atomic: at
+// D = 256, 64 workgroups of 4 waves spent ~5 of their 10.7 us there, 128 workgroups took 15.5 us), so the object branch spreads its
+// rows over MORE WAVES per workgroup (16) instead of more workgroups. The partials take WAVES * D * 8 bytes of LDS: 4 waves at D = 1024.
+template <int D, int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void ln_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ xhat,
+                                                            const float* __restrict__ save_rstd, int T, const float* __restrict__ gamma,
+                                                            Drop dr, float* __restrict__ d_res, float* __restrict__ d_y,
+                                                            float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  constexpr int NV = D / 256;
+  __shared__ float4 rg[WAVES * 64 * NV], rb[WAVES * 64 * NV];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  float4 g[NV], ag[NV], ab[NV], d[NV], h[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    g[j] = *reinterpret_cast<const float4*>(gamma + j * 256 + lane * 4);
+    ag[j] = ab[j] = d[j] = h[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  // a wave walks several rows: the next row's operands are loaded before the current row is reduced and stored (written as
+  // load -> reduce -> store per row, every row paid its own L2 round trip behind the previous row's stores: 11.4 us per launch
+  // at the object branch's shape)
+  const int stride = gridDim.x * WAVES;
+  int t = blockIdx.x * WAVES + w;
   float rstd = 0.f;
   if (t < T) {
-    const size_t o = (size_t)t * kTD + lane * 4;
-    d = *reinterpret_cast<const float4*>(dout + o);
-    h = *reinterpret_cast<const float4*>(xhat + o);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      const size_t o = (size_t)t * D + j * 256 + lane * 4;
+      d[j] = *reinterpret_cast<const float4*>(dout + o);
+      h[j] = *reinterpret_cast<const float4*>(xhat + o);
+    }
     rstd = save_rstd[t];
   }
   while (t < T) {
     const int tn = min(t + stride, T - 1);  // (clamped: the last prefetch re-reads a valid row and is dropped)
-    const size_t on = (size_t)tn * kTD + lane * 4;
-    const float4 nd = *reinterpret_cast<const float4*>(dout + on);
-    const float4 nh = *reinterpret_cast<const float4*>(xhat + on);
-    const float nrstd = save_rstd[tn];
-    const size_t o = (size_t)t * kTD + lane * 4;
-    ag.x += d.x * h.x; ag.y += d.y * h.y; ag.z += d.z * h.z; ag.w += d.w * h.w;
-    ab.x += d.x; ab.y += d.y; ab.z += d.z; ab.w += d.w;
-    const float4 dh = make_float4(d.x * g.x, d.y * g.y, d.z * g.z, d.w * g.w);
-    const float m1 = wsum(dh.x + dh.y + dh.z + dh.w) * (1.f / kTD);
-    const float m2 = wsum(dh.x * h.x + dh.y * h.y + dh.z * h.z + dh.w * h.w) * (1.f / kTD);
-    float4 dz = make_float4(rstd * (dh.x - m1 - h.x * m2), rstd * (dh.y - m1 - h.y * m2), rstd * (dh.z - m1 - h.z * m2),
-                            rstd * (dh.w - m1 - h.w * m2));
-    *reinterpret_cast<float4*>(d_res + o) = dz;
-    if (dr.thr) {
-      dz.x = keep_bit(dr.key, (uint32_t)o + 0, dr.thr) ? dz.x * dr.scale : 0.f;
-      dz.y = keep_bit(dr.key, (uint32_t)o + 1, dr.thr) ? dz.y * dr.scale : 0.f;
-      dz.z = keep_bit(dr.key, (uint32_t)o + 2, dr.thr) ? dz.z * dr.scale : 0.f;
-      dz.w = keep_bit(dr.key, (uint32_t)o + 3, dr.thr) ? dz.w * dr.scale : 0.f;
+    float4 nd[NV], nh[NV], dh[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      const size_t on = (size_t)tn * D + j * 256 + lane * 4;
+      nd[j] = *reinterpret_cast<const float4*>(dout + on);
+      nh[j] = *reinterpret_cast<const float4*>(xhat + on);
     }
-    *reinterpret_cast<float4*>(d_y + o) = dz;
-    d = nd;
-    h = nh;
+    const float nrstd = save_rstd[tn];
+    float m1 = 0.f, m2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      ag[j].x += d[j].x * h[j].x; ag[j].y += d[j].y * h[j].y; ag[j].z += d[j].z * h[j].z; ag[j].w += d[j].w * h[j].w;
+      ab[j].x += d[j].x; ab[j].y += d[j].y; ab[j].z += d[j].z; ab[j].w += d[j].w;
+      dh[j] = make_float4(d[j].x * g[j].x, d[j].y * g[j].y, d[j].z * g[j].z, d[j].w * g[j].w);
+      m1 += (dh[j].x + dh[j].y) + (dh[j].z + dh[j].w);
+      m2 += (dh[j].x * h[j].x + dh[j].y * h[j].y) + (dh[j].z * h[j].z + dh[j].w * h[j].w);
+    }
+    m1 = wsum(m1) * (1.f / D);
+    m2 = wsum(m2) * (1.f / D);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      const size_t o = (size_t)t * D + j * 256 + lane * 4;
+      float4 dz = make_float4(rstd * (dh[j].x - m1 - h[j].x * m2), rstd * (dh[j].y - m1 - h[j].y * m2),
+                              rstd * (dh[j].z - m1 - h[j].z * m2), rstd * (dh[j].w - m1 - h[j].w * m2));
+      *reinterpret_cast<float4*>(d_res + o) = dz;
+      if (dr.thr) {
+        dz.x = keep_bit(dr.key, (uint32_t)o + 0, dr.thr) ? dz.x * dr.scale : 0.f;
+        dz.y = keep_bit(dr.key, (uint32_t)o + 1, dr.thr) ? dz.y * dr.scale : 0.f;
+        dz.z = keep_bit(dr.key, (uint32_t)o + 2, dr.thr) ? dz.z * dr.scale : 0.f;
+        dz.w = keep_bit(dr.key, (uint32_t)o + 3, dr.thr) ? dz.w * dr.scale : 0.f;
+      }
+      *reinterpret_cast<float4*>(d_y + o) = dz;
+      d[j] = nd[j];
+      h[j] = nh[j];
+    }
     rstd = nrstd;
     t += stride;
   }
-  rg[threadIdx.x] = ag;
-  rb[threadIdx.x] = ab;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    rg[threadIdx.x * NV + j] = ag[j];
+    rb[threadIdx.x * NV + j] = ab[j];
+  }
   __syncthreads();
   if (w == 0) {
-    for (int i = 1; i < nw; ++i) {
-      const float4 a = rg[lane + 64 * i], c = rb[lane + 64 * i];
-      ag.x += a.x; ag.y += a.y; ag.z += a.z; ag.w += a.w;
-      ab.x += c.x; ab.y += c.y; ab.z += c.z; ab.w += c.w;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      float4 sg = ag[j], sb = ab[j];
+      for (int i = 1; i < WAVES; ++i) {
+        const float4 a = rg[(lane + 64 * i) * NV + j], c = rb[(lane + 64 * i) * NV + j];
+        sg.x += a.x; sg.y += a.y; sg.z += a.z; sg.w += a.w;
+        sb.x += c.x; sb.y += c.y; sb.z += c.z; sb.w += c.w;
+      }
+      float* pg = dgamma + j * 256 + lane * 4;
+      float* pb = dbeta + j * 256 + lane * 4;
+      unsafeAtomicAdd(pg + 0, sg.x); unsafeAtomicAdd(pg + 1, sg.y); unsafeAtomicAdd(pg + 2, sg.z); unsafeAtomicAdd(pg + 3, sg.w);
+      unsafeAtomicAdd(pb + 0, sb.x); unsafeAtomicAdd(pb + 1, sb.y); unsafeAtomicAdd(pb + 2, sb.z); unsafeAtomicAdd(pb + 3, sb.w);
     }
-    float* pg = dgamma + lane * 4;
-    float* pb = dbeta + lane * 4;
-    unsafeAtomicAdd(pg + 0, ag.x); unsafeAtomicAdd(pg + 1, ag.y); unsafeAtomicAdd(pg + 2, ag.z); unsafeAtomicAdd(pg + 3, ag.w);
-    unsafeAtomicAdd(pb + 0, ab.x); unsafeAtomicAdd(pb + 1, ab.y); unsafeAtomicAdd(pb + 2, ab.z); unsafeAtomicAdd(pb + 3, ab.w);
   }
 }
 
@@ -749,239 +794,9 @@ __global__ void zero_kernel(const AdamTensor* __restrict__ ts, const AdamChunk* 
   }
 }
 
-// ===============================================================================================================
-// Generic forms for the TEXT head's training step (train.hip: text_train_*): the same ops at the head's shapes —
-// d_model 1024 / head_dim 256 over L <= 32 tokens per sentence, and d_model 256 / head_dim 64 over S <= 32 sentences
-// per description (models/language_encoder.py:97-101,127-147).
-// ===============================================================================================================
-// self-attention over the S rows of one group (sentence / description), one workgroup per (group, head); qkv [rows][3 D],
-// D = 4 HD. Dynamic LDS: q, k, v tiles [S][HD + 1] + p [S][S + 1] (forward), + go and two more [S][S + 1] (backward).
-template <int HD>
-__global__ __launch_bounds__(256) void attn_fwd_g_kernel(const float* __restrict__ qkv, float* __restrict__ P, float* __restrict__ O,
-                                                         int S, Drop dr) {
-  extern __shared__ float sm[];
-  constexpr int AS = HD + 1, D = 4 * HD;
-  float *q = sm, *k = q + S * AS, *v = k + S * AS, *p = v + S * AS;
-  const int b = blockIdx.x >> 2, h = blockIdx.x & 3, tid = threadIdx.x, SP = S + 1;
-  const float scale = 1.0f / sqrtf((float)HD);
-  for (int i = tid; i < S * HD; i += 256) {
-    const int s = i / HD, d = i - s * HD;
-    const float* base = qkv + (size_t)(b * S + s) * (3 * D) + h * HD + d;
-    q[s * AS + d] = base[0];
-    k[s * AS + d] = base[D];
-    v[s * AS + d] = base[2 * D];
-  }
-  __syncthreads();
-  for (int e = tid; e < S * S; e += 256) {
-    const int i = e / S, j = e - i * S;
-    float s = 0.f;
-#pragma unroll 8
-    for (int d = 0; d < HD; ++d) s += q[i * AS + d] * k[j * AS + d];
-    p[i * SP + j] = s * scale;
-  }
-  __syncthreads();
-  if (tid < S) {
-    float* row = p + tid * SP;
-    float mx = row[0];
-    for (int j = 1; j < S; ++j) mx = fmaxf(mx, row[j]);
-    float sum = 0.f;
-    for (int j = 0; j < S; ++j) {
-      row[j] = expf(row[j] - mx);
-      sum += row[j];
-    }
-    for (int j = 0; j < S; ++j) row[j] /= sum;
-  }
-  __syncthreads();
-  const size_t pbase = (size_t)blockIdx.x * S * S;
-  for (int e = tid; e < S * S; e += 256) {
-    const int i = e / S, j = e - i * S;
-    float pv = p[i * SP + j];
-    P[pbase + e] = pv;  // probabilities BEFORE dropout (softmax backward needs them)
-    if (dr.thr) pv = keep_bit(dr.key, (uint32_t)(pbase + e), dr.thr) ? pv * dr.scale : 0.f;
-    p[i * SP + j] = pv;
-  }
-  __syncthreads();
-  for (int e = tid; e < S * HD; e += 256) {
-    const int i = e / HD, d = e - i * HD;
-    float s = 0.f;
-    for (int j = 0; j < S; ++j) s += p[i * SP + j] * v[j * AS + d];
-    O[(size_t)(b * S + i) * D + h * HD + d] = s;
-  }
-}
-template <int HD>
-__global__ __launch_bounds__(256) void attn_bwd_g_kernel(const float* __restrict__ qkv, const float* __restrict__ P,
-                                                         const float* __restrict__ dO, float* __restrict__ dqkv, int S, Drop dr) {
-  extern __shared__ float sm[];
-  constexpr int AS = HD + 1, D = 4 * HD;
-  const int SP = S + 1;
-  float *q = sm, *k = q + S * AS, *v = k + S * AS, *go = v + S * AS, *p = go + S * AS, *pd = p + S * SP, *ds = pd + S * SP;
-  const int b = blockIdx.x >> 2, h = blockIdx.x & 3, tid = threadIdx.x;
-  const float scale = 1.0f / sqrtf((float)HD);
-  for (int i = tid; i < S * HD; i += 256) {
-    const int s = i / HD, d = i - s * HD;
-    const float* base = qkv + (size_t)(b * S + s) * (3 * D) + h * HD + d;
-    q[s * AS + d] = base[0];
-    k[s * AS + d] = base[D];
-    v[s * AS + d] = base[2 * D];
-    go[s * AS + d] = dO[(size_t)(b * S + s) * D + h * HD + d];
-  }
-  const size_t pbase = (size_t)blockIdx.x * S * S;
-  for (int e = tid; e < S * S; e += 256) {
-    const int i = e / S, j = e - i * S;
-    const float pv = P[pbase + e];
-    const float m = dr.thr ? (keep_bit(dr.key, (uint32_t)(pbase + e), dr.thr) ? dr.scale : 0.f) : 1.f;
-    p[i * SP + j] = pv;
-    pd[i * SP + j] = pv * m;
-    ds[i * SP + j] = m;  // mask factor for now
-  }
-  __syncthreads();
-  for (int e = tid; e < S * HD; e += 256) {  // dV[j][d] = sum_i Pd[i][j] dO[i][d]
-    const int j = e / HD, d = e - j * HD;
-    float s = 0.f;
-    for (int i = 0; i < S; ++i) s += pd[i * SP + j] * go[i * AS + d];
-    dqkv[(size_t)(b * S + j) * (3 * D) + 2 * D + h * HD + d] = s;
-  }
-  for (int e = tid; e < S * S; e += 256) {  // dP[i][j] = mask * sum_d dO[i][d] V[j][d]
-    const int i = e / S, j = e - i * S;
-    float s = 0.f;
-#pragma unroll 8
-    for (int d = 0; d < HD; ++d) s += go[i * AS + d] * v[j * AS + d];
-    ds[i * SP + j] *= s;
-  }
-  __syncthreads();
-  if (tid < S) {  // dS = P * (dP - sum_j dP*P) / sqrt(hd)
-    float t = 0.f;
-    for (int j = 0; j < S; ++j) t += ds[tid * SP + j] * p[tid * SP + j];
-    for (int j = 0; j < S; ++j) ds[tid * SP + j] = p[tid * SP + j] * (ds[tid * SP + j] - t) * scale;
-  }
-  __syncthreads();
-  for (int e = tid; e < S * HD; e += 256) {
-    const int i = e / HD, d = e - i * HD;
-    float sq = 0.f, sk = 0.f;
-    for (int j = 0; j < S; ++j) {
-      sq += ds[i * SP + j] * k[j * AS + d];
-      sk += ds[j * SP + i] * q[j * AS + d];
-    }
-    float* base = dqkv + (size_t)(b * S + i) * (3 * D) + h * HD + d;
-    base[0] = sq;
-    base[D] = sk;
-  }
-}
-
-// out = LayerNorm(x + dropout(y)) over D columns, one wave per row (D / 256 float4 per lane, each wave-load 1 KiB contiguous).
-template <int D>
-__global__ void ln_fwd_g_kernel(const float* __restrict__ x, const float* __restrict__ y, int T, const float* __restrict__ gamma,
-                                const float* __restrict__ beta, Drop dr, float* __restrict__ out, float* __restrict__ xhat,
-                                float* __restrict__ save_rstd) {
-  constexpr int NV = D / 256;
-  const int t = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-  if (t >= T) return;
-  float4 a[NV];
-  float s1 = 0.f;
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const size_t o = (size_t)t * D + j * 256 + lane * 4;
-    a[j] = *reinterpret_cast<const float4*>(x + o);
-    float4 f = *reinterpret_cast<const float4*>(y + o);
-    if (dr.thr) {
-      f.x = keep_bit(dr.key, (uint32_t)o + 0, dr.thr) ? f.x * dr.scale : 0.f;
-      f.y = keep_bit(dr.key, (uint32_t)o + 1, dr.thr) ? f.y * dr.scale : 0.f;
-      f.z = keep_bit(dr.key, (uint32_t)o + 2, dr.thr) ? f.z * dr.scale : 0.f;
-      f.w = keep_bit(dr.key, (uint32_t)o + 3, dr.thr) ? f.w * dr.scale : 0.f;
-    }
-    a[j].x += f.x; a[j].y += f.y; a[j].z += f.z; a[j].w += f.w;
-    s1 += (a[j].x + a[j].y) + (a[j].z + a[j].w);
-  }
-  const float mu = wsum(s1) * (1.f / D);
-  float s2 = 0.f;
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    a[j].x -= mu; a[j].y -= mu; a[j].z -= mu; a[j].w -= mu;
-    s2 += (a[j].x * a[j].x + a[j].y * a[j].y) + (a[j].z * a[j].z + a[j].w * a[j].w);
-  }
-  const float rstd = 1.0f / sqrtf(wsum(s2) * (1.f / D) + kLnEps);
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const size_t o = (size_t)t * D + j * 256 + lane * 4;
-    const float4 h = make_float4(a[j].x * rstd, a[j].y * rstd, a[j].z * rstd, a[j].w * rstd);
-    const float4 g = *reinterpret_cast<const float4*>(gamma + j * 256 + lane * 4);
-    const float4 be = *reinterpret_cast<const float4*>(beta + j * 256 + lane * 4);
-    *reinterpret_cast<float4*>(xhat + o) = h;
-    *reinterpret_cast<float4*>(out + o) = make_float4(h.x * g.x + be.x, h.y * g.y + be.y, h.z * g.z + be.z, h.w * g.w + be.w);
-  }
-  if (lane == 0) save_rstd[t] = rstd;
-}
-// LN backward (see ln_bwd_kernel): d_res = dz, d_y = dz * dropout mask; dgamma / dbeta by per-workgroup partials + atomics.
-// 256-thread workgroups (4 waves), each wave strides over rows.
-template <int D>
-__global__ __launch_bounds__(256) void ln_bwd_g_kernel(const float* __restrict__ dout, const float* __restrict__ xhat,
-                                                       const float* __restrict__ save_rstd, int T, const float* __restrict__ gamma,
-                                                       Drop dr, float* __restrict__ d_res, float* __restrict__ d_y,
-                                                       float* __restrict__ dgamma, float* __restrict__ dbeta) {
-  constexpr int NV = D / 256;
-  __shared__ float4 rg[256 * NV], rb[256 * NV];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  float4 g[NV], ag[NV], ab[NV];
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    g[j] = *reinterpret_cast<const float4*>(gamma + j * 256 + lane * 4);
-    ag[j] = ab[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  for (int t = blockIdx.x * 4 + w; t < T; t += gridDim.x * 4) {
-    const float rstd = save_rstd[t];
-    float4 d[NV], h[NV], dh[NV];
-    float m1 = 0.f, m2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-      const size_t o = (size_t)t * D + j * 256 + lane * 4;
-      d[j] = *reinterpret_cast<const float4*>(dout + o);
-      h[j] = *reinterpret_cast<const float4*>(xhat + o);
-      ag[j].x += d[j].x * h[j].x; ag[j].y += d[j].y * h[j].y; ag[j].z += d[j].z * h[j].z; ag[j].w += d[j].w * h[j].w;
-      ab[j].x += d[j].x; ab[j].y += d[j].y; ab[j].z += d[j].z; ab[j].w += d[j].w;
-      dh[j] = make_float4(d[j].x * g[j].x, d[j].y * g[j].y, d[j].z * g[j].z, d[j].w * g[j].w);
-      m1 += (dh[j].x + dh[j].y) + (dh[j].z + dh[j].w);
-      m2 += (dh[j].x * h[j].x + dh[j].y * h[j].y) + (dh[j].z * h[j].z + dh[j].w * h[j].w);
-    }
-    m1 = wsum(m1) * (1.f / D);
-    m2 = wsum(m2) * (1.f / D);
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-      const size_t o = (size_t)t * D + j * 256 + lane * 4;
-      float4 dz = make_float4(rstd * (dh[j].x - m1 - h[j].x * m2), rstd * (dh[j].y - m1 - h[j].y * m2),
-                              rstd * (dh[j].z - m1 - h[j].z * m2), rstd * (dh[j].w - m1 - h[j].w * m2));
-      *reinterpret_cast<float4*>(d_res + o) = dz;
-      if (dr.thr) {
-        dz.x = keep_bit(dr.key, (uint32_t)o + 0, dr.thr) ? dz.x * dr.scale : 0.f;
-        dz.y = keep_bit(dr.key, (uint32_t)o + 1, dr.thr) ? dz.y * dr.scale : 0.f;
-        dz.z = keep_bit(dr.key, (uint32_t)o + 2, dr.thr) ? dz.z * dr.scale : 0.f;
-        dz.w = keep_bit(dr.key, (uint32_t)o + 3, dr.thr) ? dz.w * dr.scale : 0.f;
-      }
-      *reinterpret_cast<float4*>(d_y + o) = dz;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    rg[threadIdx.x * NV + j] = ag[j];
-    rb[threadIdx.x * NV + j] = ab[j];
-  }
-  __syncthreads();
-  if (w == 0) {
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-      float4 sg = ag[j], sb = ab[j];
-      for (int i = 1; i < 4; ++i) {
-        const float4 a = rg[(lane + 64 * i) * NV + j], c = rb[(lane + 64 * i) * NV + j];
-        sg.x += a.x; sg.y += a.y; sg.z += a.z; sg.w += a.w;
-        sb.x += c.x; sb.y += c.y; sb.z += c.z; sb.w += c.w;
-      }
-      float* pg = dgamma + j * 256 + lane * 4;
-      float* pb = dbeta + j * 256 + lane * 4;
-      unsafeAtomicAdd(pg + 0, sg.x); unsafeAtomicAdd(pg + 1, sg.y); unsafeAtomicAdd(pg + 2, sg.z); unsafeAtomicAdd(pg + 3, sg.w);
-      unsafeAtomicAdd(pb + 0, sb.x); unsafeAtomicAdd(pb + 1, sb.y); unsafeAtomicAdd(pb + 2, sb.z); unsafeAtomicAdd(pb + 3, sb.w);
-    }
-  }
-}
-
+// ---------------------------------------------------------------------------------------------------------------
+// The text head's own ops (train.hip: text_train_*)
+// ---------------------------------------------------------------------------------------------------------------
 // out[b][c] = max over the S rows of group b of (X + R) (R optional: the residual AROUND the inter-sentence layer); first maximal
 // row wins, as torch.max does. arg keeps the row for the backward scatter.
 __global__ __launch_bounds__(256) void seq_max_fwd_kernel(const float* __restrict__ X, const float* __restrict__ R, int B, int S, int D,
