@@ -17,30 +17,34 @@ pytestmark = pytest.mark.gpu
 GPU_MARGIN_SCALE = 10.0
 
 
-def used_names(sd, embed):
+def used_names(sd, embed, color_embed=None):
+    """embed: class_embed, and color_embed too unless that is given apart"""
+    color_embed = embed if color_embed is None else color_embed
     out = {}
     for k, v in sd.items():
         if k.endswith("num_batches_tracked") or k.startswith("object_encoder.pointnet."):
             continue
-        if embed and (".color_encoder." in k or ".mlp_pointnet." in k):
+        if (color_embed and ".color_encoder." in k) or (embed and ".mlp_pointnet." in k):
             continue
-        if not embed and k.endswith("_embedding.weight"):
+        if (not embed and k.endswith("class_embedding.weight")) or (not color_embed and k.endswith("color_embedding.weight")):
             continue
         out[k] = v
     return out
 
 
-def bind(eng, sd, embed):
+def bind(eng, sd, embed, color_embed=None):
     """name -> (param tensor, grad tensor | None) on the GPU, bound to the engine."""
+    color_embed = embed if color_embed is None else color_embed
     tensors = {}
-    for k, v in used_names(sd, embed).items():
+    for k, v in used_names(sd, embed, color_embed).items():
         t = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).cuda()
         tensors[k] = (t, None if "running_" in k else torch.zeros_like(t))
-    eng.train_bind(tensors, class_embed=embed, color_embed=embed)
+    eng.train_bind(tensors, class_embed=embed, color_embed=color_embed)
     return tensors
 
 
 def to_dev(cells, embed):
+    """embed: class_embed (without it the class branch reads pn_feat)"""
     keys = ["offsets", "class_idx", "color_idx", "rgb", "center", "n_pts"] + ([] if embed else ["pn_feat"])
     return {k: torch.from_numpy(np.ascontiguousarray(cells[k])).cuda() for k in keys}
 
@@ -83,9 +87,22 @@ def eng():
 @pytest.mark.parametrize("p_drop", [0.0, 0.1])
 @pytest.mark.parametrize("n_cells,min_obj,max_obj", [(5, 3, 33), (64, 6, 35)])
 def test_forward_backward_match_the_float64_oracle(eng, embed, p_drop, n_cells, min_obj, max_obj):
+    forward_backward_case(eng, embed, embed, p_drop, n_cells, min_obj, max_obj)
+
+
+@pytest.mark.parametrize("embed,color_embed", [(True, False), (False, True)], ids=["class", "color"])
+@pytest.mark.parametrize("p_drop", [0.0, 0.1])
+def test_forward_backward_match_the_float64_oracle_in_the_mixed_configurations(eng, embed, color_embed, p_drop):
+    """The same check, same bars, with the two flags apart, at the small shape (5 cells of 3 to 33 objects: across the 28-slot cut):
+    class_embed only — one embedding job beside three small branches — and color_embed only — the PointNet-feature block, one
+    embedding job and two small branches."""
+    forward_backward_case(eng, embed, color_embed, p_drop, 5, 3, 33)
+
+
+def forward_backward_case(eng, embed, color_embed, p_drop, n_cells, min_obj, max_obj):  # embed: class_embed
     cells = synth.make_cells(n_cells, seed=21 + n_cells, with_pn_feat=True, min_obj=min_obj, max_obj=max_obj)
     sd = synth.make_object_branch_weights(3)
-    tensors = bind(eng, sd, embed)
+    tensors = bind(eng, sd, embed, color_embed)
     dcells = to_dev(cells, embed)
     seed = 0xC0FFEE + n_cells
     p32 = float(np.float32(p_drop))
@@ -95,7 +112,7 @@ def test_forward_backward_match_the_float64_oracle(eng, embed, p_drop, n_cells, 
     gpn = None if embed else torch.zeros((int(cells["offsets"][-1]), 256), device="cuda")
     eng.encode_cells_backward(torch.from_numpy(gout).cuda(), gpn)
     torch.cuda.synchronize()
-    ref_out, info = OT.encode_cells_train(cells, sd, embed, embed, grad_out=gout, p_drop=p32, seed=seed)
+    ref_out, info = OT.encode_cells_train(cells, sd, embed, color_embed, grad_out=gout, p_drop=p32, seed=seed)
     assert np.abs(out.cpu().numpy() - ref_out).max() < 2e-5
     assert_grads(tensors, info["grads"])
     if not embed:
@@ -111,7 +128,7 @@ def test_forward_backward_match_the_float64_oracle(eng, embed, p_drop, n_cells, 
             continue
         assert np.allclose(tensors[k][0].cpu().numpy(), v, rtol=2e-4, atol=2e-5), k
         checked += 1
-    assert checked >= (10 if embed else 14)
+    assert checked >= {(True, True): 10, (False, False): 14, (True, False): 14, (False, True): 12}[(embed, color_embed)]  # (mixed: 10 + 4 / 10 + 2)
 
 
 def test_gradients_accumulate_and_zero_grad(eng):

@@ -26,9 +26,8 @@ namespace ft {
 
 constexpr int kW = 128, kObj = 16, kHintMax = 8, kHeads = 4, kHd = 32, kFF = 512;
 constexpr float kLnEps = 1e-5f, kBnEps = 1e-5f, kBnMom = 0.1f, kNormEps = 1e-12f;
-constexpr float kNumMean = 1826.6844940968194f, kNumStd = 2516.8905096993817f;  // models/object_encoder.py:43-44
 
-// the a9 dropout rule, shared with the coarse step (train_common.h): Drop, keep_bit, make_drop(seed, site, p)
+// shared with the coarse step (train_common.h): the a9 dropout rule — Drop, keep_bit, make_drop(seed, site, p) — and num_encoder's constants
 using train::Drop;
 using train::keep_bit;
 using train::make_drop;
@@ -242,7 +241,7 @@ __global__ void k_scatter_add(const float* dY, int rows, const int32_t* idx, int
 
 __global__ void k_num_in(const float* n_pts, int M, float* out) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < M) out[i] = (n_pts[i] - kNumMean) / kNumStd;
+  if (i < M) out[i] = (n_pts[i] - train::kNumPtsMean) / train::kNumPtsStd;
 }
 
 // attention of one (pair, head): probabilities (before dropout) to P[pair, head, query, key], output to O[:, head*32 : +32]

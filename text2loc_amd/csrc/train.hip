@@ -8,6 +8,7 @@
 #include <math.h>
 #include <string.h>
 
+#include "adam_plan.h"
 #include "t2l_internal.h"
 #include "train_kernels.h"
 
@@ -19,6 +20,89 @@ struct TTensor {
   float* data = nullptr;
   float* grad = nullptr;
   int64_t numel = 0;
+};
+using TensorMap = std::unordered_map<std::string, TTensor>;
+
+// ---- one optimizer state (torch.optim.Adam's moments, inside the library) for the object branch and the text head alike; the layout
+// and the keep decision are adam_plan.h's, the step counts the owner's
+struct AdamSet {
+  std::vector<std::string> names;  // the trained tensors, in step order
+  std::vector<int64_t> numel;
+  AdamPlan plan;        // offsets, chunks, total
+  float* mv = nullptr;  // [2][plan.total]: first moments of all tensors (names order), then second moments
+  AdamTensor* d_tensors = nullptr;
+  AdamChunk* d_chunks = nullptr;
+
+  // What a re-bind detaches from the binding it is about to free: a re-bind of the SAME model (model.to(), an externally assigned
+  // .grad, ...) only moves POINTERS, so build() adopts these moments when adam_keep says so; on every other path (a refused bind
+  // included) they are freed here
+  struct Old {
+    std::vector<std::string> names;
+    std::vector<int64_t> numel;
+    float* mv = nullptr;
+    ~Old() { if (mv) (void)hipFree(mv); }
+  };
+  void detach(Old& o) {
+    o.names = names, o.numel = numel, o.mv = mv;
+    mv = nullptr;  // (release() must not free it)
+  }
+  void release() {
+    for (void* p : {(void*)d_tensors, (void*)d_chunks, (void*)mv})
+      if (p) (void)hipFree(p);
+    d_tensors = nullptr; d_chunks = nullptr; mv = nullptr;
+  }
+  // build-or-adopt: the tables over `names` (set by the owner; every one is in t). *kept: old's moments were adopted — the owner then
+  // keeps its step counts too; otherwise the moments are zero
+  int build(t2l_ctx* ctx, const TensorMap& t, Old& old, bool* kept) {
+    for (auto& nme : names) numel.push_back(t.at(nme).numel);
+    plan = adam_plan(numel);
+    const int64_t total = plan.total;
+    *kept = adam_keep(ctx->train_keep_adam != 0, old.mv != nullptr, old.names, old.numel, names, numel);
+    if (*kept) {
+      std::swap(mv, old.mv);
+    } else {
+      if (old.mv) (void)hipFree(old.mv);  // (before its successor is allocated)
+      old.mv = nullptr;
+      T2L_HIP(ctx, hipMalloc(&mv, sizeof(float) * 2 * (size_t)total));
+      T2L_HIP(ctx, hipMemset(mv, 0, sizeof(float) * 2 * (size_t)total));
+    }
+    std::vector<AdamTensor> ts;
+    std::vector<AdamChunk> cs;
+    for (size_t i = 0; i < names.size(); ++i) {
+      const TTensor& x = t.at(names[i]);
+      ts.push_back(AdamTensor{x.data, x.grad, mv + plan.offset[i], mv + total + plan.offset[i], x.numel});
+    }
+    for (int c = 0; c < plan.n_chunks(); ++c) cs.push_back(AdamChunk{plan.chunk_tensor[c], plan.chunk_first[c]});
+    T2L_HIP(ctx, hipMalloc(&d_tensors, sizeof(AdamTensor) * ts.size()));
+    T2L_HIP(ctx, hipMalloc(&d_chunks, sizeof(AdamChunk) * cs.size()));
+    T2L_HIP(ctx, hipMemcpy(d_tensors, ts.data(), sizeof(AdamTensor) * ts.size(), hipMemcpyHostToDevice));
+    T2L_HIP(ctx, hipMemcpy(d_chunks, cs.data(), sizeof(AdamChunk) * cs.size(), hipMemcpyHostToDevice));
+    return T2L_OK;
+  }
+  // one step of the tensors behind chunks [c0, c1), which have taken `step` steps with this one
+  void launch(int c0, int c1, int64_t step, float lr, float b1, float b2, float eps, hipStream_t s) const {
+    if (c1 <= c0) return;
+    const float bc1 = (float)(1.0 - pow((double)b1, (double)step));
+    const float bc2s = (float)sqrt(1.0 - pow((double)b2, (double)step));
+    hipLaunchKernelGGL(adam_kernel, dim3(c1 - c0), dim3(256), 0, s, d_tensors, d_chunks + c0, lr, b1, b2, eps, bc1, bc2s);
+  }
+  void zero(hipStream_t s) const { hipLaunchKernelGGL(zero_kernel, dim3(plan.n_chunks()), dim3(256), 0, s, d_tensors, d_chunks); }
+  // t2l_adam_state / t2l_text_adam_state (`api`): the size and, when asked, the step (m == v == NULL), or the moments copied in (set) or
+  // out with the step. `packed`: the owner's step count(s) as the call reports them; after a set with moments the owner takes *step.
+  int state(t2l_ctx* ctx, const char* api, int set, float* m, float* v, int64_t* step, int64_t* n, int64_t packed, hipStream_t s) {
+    const int64_t total = plan.total;
+    if (n) *n = total;
+    if (!m && !v) {
+      if (step && !set) *step = packed;
+      return T2L_OK;
+    }
+    if (!m || !v || !step) return fail(ctx, T2L_EINVAL, std::string(api) + ": pass m, v and step together");
+    const size_t bytes = sizeof(float) * (size_t)total;
+    T2L_HIP(ctx, hipMemcpyAsync(set ? mv : m, set ? m : mv, bytes, hipMemcpyDeviceToDevice, s));
+    T2L_HIP(ctx, hipMemcpyAsync(set ? mv + total : v, set ? v : mv + total, bytes, hipMemcpyDeviceToDevice, s));
+    if (!set) *step = packed;
+    return T2L_OK;
+  }
 };
 
 // One [Linear, BatchNorm1d, ReLU] block of get_mlp (models/language_encoder.py:16-41) with its saved activations.
@@ -52,19 +136,14 @@ constexpr int kBnSlots = 8;  // BatchNorm layers per pass: <= 2*3 small branches
 
 struct TrainState {
   t2l_ctx* ctx = nullptr;
-  std::unordered_map<std::string, TTensor> t;
+  TensorMap t;
   t2l_model_config cfg{};
-  std::vector<std::string> adam_names;
-  AdamTensor* d_tensors = nullptr;
-  AdamChunk* d_chunks = nullptr;
-  float* mv = nullptr;       // [2][mv_total]: first moments of all Adam tensors (adam_names order), then second moments
-  int64_t mv_total = 0;
+  AdamSet adam;
   double* bn_acc = nullptr;  // [2][kBnSlots][kBnStride] float64 partial sums of the BatchNorm stages (one slot per BN pass; forward | backward)
   int bn_slot = 0;
   bool fwd_acc_clean = false;  // the previous forward's last launch zeroed all accumulators (no memset launch in a step)
   bool bwd_acc_clean = false;  // the forward zeroed the backward half too; false after a backward used it (a second backward memsets)
-  int n_chunks = 0;
-  int pn_chunk0 = 0;         // chunks [pn_chunk0, n_chunks) belong to the PointNet++ backbone (bound last)
+  int pn_chunk0 = 0;         // chunks [pn_chunk0, adam.plan.n_chunks()) belong to the PointNet++ backbone (bound last)
   int64_t step = 0;          // Adam step of the object branch
   int64_t step_pn = 0;       // ... of the backbone: it only steps when its backward ran since the last zero_grad (torch.optim.Adam
   bool pn_touched = false;   // skips parameters whose .grad is None and keeps a step count per parameter)
@@ -104,7 +183,8 @@ static void sync_slots(t2l_ctx* ctx, double* first, int slots, hipStream_t s) {
 void free_train(t2l_ctx* ctx) {
   TrainState* st = state(ctx);
   if (!st) return;
-  for (void* p : {(void*)st->d_tensors, (void*)st->d_chunks, (void*)st->mv, (void*)st->ws.base, (void*)st->bn_acc})
+  st->adam.release();
+  for (void* p : {(void*)st->ws.base, (void*)st->bn_acc})
     if (p) (void)hipFree(p);
   pn_train_free(st->pn);
   delete st;
@@ -226,8 +306,6 @@ static void attn_bwd_launch(int B, int S, hipStream_t s, A... a) {
   if (HD == kTHd && S == kTS) hipLaunchKernelGGL((attn_bwd_kernel<kTHd, kTS>), dim3(B * 4), dim3(256), attn_lds(S, HD, true), s, a...);
   else hipLaunchKernelGGL((attn_bwd_kernel<HD, 0>), dim3(B * 4), dim3(256), attn_lds(S, HD, true), s, a...);
 }
-
-using TensorMap = std::unordered_map<std::string, TTensor>;
 
 // the saved activations of L (T, B, S, FF set by the caller)
 template <int D>
@@ -363,26 +441,15 @@ int train_bind_impl(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n, const 
   if (cfg->num_heads != kTH) return fail(ctx, T2L_EINVAL, "t2l_train_bind: the training step is built for the published shape only (embed dim 256, 4 attention heads, object_size 28)");
   const int n_feat = (cfg->use_class != 0) + (cfg->use_color != 0) + (cfg->use_position != 0) + (cfg->use_num != 0);
   if (n_feat < 2) return fail(ctx, T2L_EINVAL, "t2l_train_bind: training needs at least two of the class/color/position/num features");
-  // a re-bind of the SAME model (model.to(), an externally assigned .grad, ...) only moves POINTERS: with option
-  // "train_keep_adam_state" set (the Python seam sets it for exactly that case) the Adam moments and the bias-correction
-  // step of the previous binding carry over when the parameter list (names and sizes) is unchanged
-  TrainState* old = state(ctx);
-  std::vector<std::string> old_names;
-  std::vector<int64_t> old_numel;
-  float* old_mv = nullptr;
+  // with option "train_keep_adam_state" set (the Python seam sets it for exactly a re-bind of the same model) the Adam moments and
+  // the bias-correction steps of the previous binding carry over when the parameter list (names and sizes) is unchanged
+  AdamSet::Old old;
   int64_t old_step = 0, old_step_pn = 0;
-  if (old && ctx->train_keep_adam) {
-    old_names = old->adam_names;
-    for (auto& nme : old_names) old_numel.push_back(old->t[nme].numel);
-    old_mv = old->mv;
-    old->mv = nullptr;  // survives free_train below
-    old_step = old->step;
-    old_step_pn = old->step_pn;
+  if (TrainState* o = state(ctx)) {
+    o->adam.detach(old);
+    old_step = o->step;
+    old_step_pn = o->step_pn;
   }
-  struct MvGuard {
-    float* p;
-    ~MvGuard() { if (p) (void)hipFree(p); }
-  } guard{old_mv};
   free_train(ctx);
   TrainState* st = new TrainState();
   ctx->train = st;
@@ -392,7 +459,7 @@ int train_bind_impl(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n, const 
     if (!tensors[i].name || !tensors[i].data) return fail(ctx, T2L_EINVAL, "t2l_train_bind: null name/data");
     st->t[tensors[i].name] = TTensor{tensors[i].data, tensors[i].grad, tensors[i].numel};
   }
-  std::vector<std::string>& P = st->adam_names;
+  std::vector<std::string>& P = st->adam.names;
   const std::string oe = "object_encoder.";
   int rc;
   if (cfg->use_class) {
@@ -437,60 +504,16 @@ int train_bind_impl(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n, const 
   }
   const size_t n_obj_tensors = P.size();
   if ((rc = pn_train_bind(ctx, st, P))) return rc;  // the PointNet++ backbone, when bound with gradients
-  // Adam tables: moments zero-initialised, one chunk per 1,024 elements
-  std::vector<AdamTensor> ts;
-  std::vector<AdamChunk> cs;
-  int64_t total = 0;
-  for (auto& nme : P) total += st->t[nme].numel;
   T2L_HIP(ctx, hipMalloc(&st->bn_acc, sizeof(double) * kBnStride * kBnSlots * 2));  // slots of the forward, then of the backward
   st->ctx = ctx;
-  T2L_HIP(ctx, hipMalloc(&st->mv, sizeof(float) * 2 * (size_t)total));
-  T2L_HIP(ctx, hipMemset(st->mv, 0, sizeof(float) * 2 * (size_t)total));
-  st->mv_total = total;
-  {
-    bool same = old_mv != nullptr && old_names == P;
-    for (size_t i = 0; same && i < P.size(); ++i) same = st->t[P[i]].numel == old_numel[i];
-    if (same) {
-      T2L_HIP(ctx, hipMemcpy(st->mv, old_mv, sizeof(float) * 2 * (size_t)total, hipMemcpyDeviceToDevice));
-      st->step = old_step;
-      st->step_pn = old_step_pn;
-    }
+  bool kept;
+  if ((rc = st->adam.build(ctx, st->t, old, &kept))) return rc;
+  if (kept) {
+    st->step = old_step;
+    st->step_pn = old_step_pn;
   }
-  int64_t off = 0;
-  st->pn_chunk0 = -1;
-  for (auto& nme : P) {
-    const TTensor& t = st->t[nme];
-    if (ts.size() == n_obj_tensors) st->pn_chunk0 = (int)cs.size();
-    ts.push_back(AdamTensor{t.data, t.grad, st->mv + off, st->mv + total + off, t.numel});
-    for (int64_t c = 0; c * 1024 < t.numel; ++c) cs.push_back(AdamChunk{(int32_t)ts.size() - 1, (int32_t)c});
-    off += t.numel;
-  }
-  st->n_chunks = (int)cs.size();
-  if (st->pn_chunk0 < 0) st->pn_chunk0 = st->n_chunks;
-  T2L_HIP(ctx, hipMalloc(&st->d_tensors, sizeof(AdamTensor) * ts.size()));
-  T2L_HIP(ctx, hipMalloc(&st->d_chunks, sizeof(AdamChunk) * cs.size()));
-  T2L_HIP(ctx, hipMemcpy(st->d_tensors, ts.data(), sizeof(AdamTensor) * ts.size(), hipMemcpyHostToDevice));
-  T2L_HIP(ctx, hipMemcpy(st->d_chunks, cs.data(), sizeof(AdamChunk) * cs.size(), hipMemcpyHostToDevice));
+  st->pn_chunk0 = st->adam.plan.first_chunk(n_obj_tensors);
   return T2L_OK;
-}
-
-// ---- forward ---------------------------------------------------------------------------------------------------
-static void mlp_layer_fwd(TrainState* st, MlpLayer& L, const float* x, int M, int small_k, int standardize, hipStream_t s) {
-  const TTensor& W = T_(st, L.prefix + ".0.weight");
-  const TTensor& b = T_(st, L.prefix + ".0.bias");
-  if (small_k)
-    hipLaunchKernelGGL(smallk_fwd_kernel, dim3((M * 64 + 255) / 256), dim3(256), 0, s, x, M, small_k, W.data, b.data, standardize,
-                       1826.6844940968194f, 2516.8905096993817f, L.y);
-  else
-    gemm_nt(x, W.data, b.data, L.y, M, L.cout, L.cin, 0, s);
-  const int sync = st->ctx->sync_fn ? 1 : 0;
-  double* acc = acc_base(st->ctx, st) + (size_t)(st->bn_slot++ % (2 * kBnSlots)) * kBnStride;
-  hipLaunchKernelGGL((bn_stats_kernel<0>), dim3(L.cout / 64, (M + kBnRows - 1) / kBnRows), dim3(256), 0, s, L.y, (const float*)nullptr,
-                     (const float*)nullptr, M, L.cout, (const float*)nullptr, (const float*)nullptr, acc, sync, (float*)nullptr, (float*)nullptr);
-  sync_slots(st->ctx, acc, 1, s);
-  hipLaunchKernelGGL(bn_apply_fwd_kernel, dim3((unsigned)(((size_t)M * L.cout + 255) / 256)), dim3(256), 0, s, L.y, M, L.cout, acc,
-                     T_(st, L.prefix + ".1.weight").data, T_(st, L.prefix + ".1.bias").data, T_(st, L.prefix + ".1.running_mean").data,
-                     T_(st, L.prefix + ".1.running_var").data, 0.1f, L.a, L.mean, L.rstd, sync);
 }
 
 static MlpLayer make_layer(TrainState* st, const std::string& prefix, int cin, int cout, int M) {
@@ -505,9 +528,8 @@ static MlpLayer make_layer(TrainState* st, const std::string& prefix, int cin, i
   return L;
 }
 
-// ---- the small feature branches (position, point count, colour: [K -> 64 -> 256] + normalize, identical shapes) stage by stage,
-// every stage ONE launch over all of them (kMaxJobs = 3): 7 launches instead of 7 per branch, forward and backward
-// slot: the launch's jobs take CONSECUTIVE accumulator slots (one cross-rank sum covers them)
+// ---- the [BatchNorm1d, ReLU] stage of n <= kMaxJobs blocks of one shape, ONE launch per step of it (train_kernels.h): the layers that
+// are alone (mlp_merge, mlp_pointnet) with n = 1, the small branches with n = 2 or 3
 static BnJob bn_job(TrainState* st, const MlpLayer& L, float* d, int slot) {
   BnJob j{};
   j.y = L.y;
@@ -524,108 +546,126 @@ static BnJob bn_job(TrainState* st, const MlpLayer& L, float* d, int slot) {
   j.dbeta = T_(st, L.prefix + ".1.bias").grad;
   return j;
 }
-static void small_branches_fwd(TrainState* st, const std::vector<int>& which, int M, int Kc, hipStream_t s) {
-  const int n = (int)which.size();
-  SmallkMulti sk{};
-  sk.M = M;
-  sk.mean = 1826.6844940968194f;
-  sk.stdv = 2516.8905096993817f;
-  BnMulti b0{}, b1{};
-  b0.M = b1.M = M;
-  b0.C = 64;
-  b1.C = kTD;
-  b0.momentum = b1.momentum = 0.1f;
-  b0.sync = b1.sync = st->ctx->sync_fn ? 1 : 0;
-  const int slot0 = st->bn_slot, slot1 = st->bn_slot + n;
-  st->bn_slot += 2 * n;
-  GemmMulti gm{};
+// the jobs of blocks L[0..n) (backward: d[q] = the gradient w.r.t. L[q]'s ReLU output, overwritten) on the next n accumulator slots:
+// CONSECUTIVE ones, so that one cross-rank sum covers the launch
+static BnMulti bn_jobs(TrainState* st, int n, const MlpLayer* const* L, float* const* d, int M) {
+  BnMulti b{};
+  b.M = M;
+  b.C = L[0]->cout;
+  b.momentum = 0.1f;
+  b.sync = st->ctx->sync_fn ? 1 : 0;
+  for (int q = 0; q < n; ++q) b.j[q] = bn_job(st, *L[q], d ? d[q] : nullptr, st->bn_slot++);
+  return b;
+}
+static void bn_relu_fwd(TrainState* st, const BnMulti& b, int n, hipStream_t s) {
+  hipLaunchKernelGGL((bn_stats_kernel<0>), dim3(b.C / 64, (b.M + kBnRows - 1) / kBnRows, n), dim3(256), 0, s, b);
+  sync_slots(st->ctx, b.j[0].acc, n, s);
+  hipLaunchKernelGGL(bn_apply_fwd_kernel, dim3((unsigned)(((size_t)b.M * b.C + 255) / 256), n), dim3(256), 0, s, b);
+}
+static void bn_relu_bwd(TrainState* st, const BnMulti& b, int n, hipStream_t s) {
+  hipLaunchKernelGGL((bn_stats_kernel<1>), dim3(b.C / 64, (b.M + kBnRows - 1) / kBnRows, n), dim3(256), 0, s, b);
+  sync_slots(st->ctx, b.j[0].acc, n, s);
+  hipLaunchKernelGGL(bn_apply_bwd_kernel, dim3((unsigned)(((size_t)b.M * b.C + 255) / 256), n), dim3(256), 0, s, b);
+}
+// F.normalize of n jobs' 256-wide rows into (forward) / out of (backward) their slots of the concatenated feature row
+static void rownorm_launch(bool fwd, const RownormJob* j, int n, int M, int Kc, hipStream_t s) {
   RownormMulti rn{};
   rn.M = M;
   rn.ld = Kc;
+  for (int q = 0; q < n; ++q) rn.j[q] = j[q];
+  if (fwd) hipLaunchKernelGGL(rownorm_fwd_kernel, dim3((M + 3) / 4, n), dim3(256), 0, s, rn);
+  else hipLaunchKernelGGL(rownorm_bwd_kernel, dim3((M + 3) / 4, n), dim3(256), 0, s, rn);
+}
+
+// ---- forward ---------------------------------------------------------------------------------------------------
+// one [Linear, BatchNorm1d, ReLU] block that is alone
+static void mlp_layer_fwd(TrainState* st, MlpLayer& L, const float* x, int M, hipStream_t s) {
+  gemm_nt(x, T_(st, L.prefix + ".0.weight").data, T_(st, L.prefix + ".0.bias").data, L.y, M, L.cout, L.cin, 0, s);
+  const MlpLayer* Lp = &L;
+  bn_relu_fwd(st, bn_jobs(st, 1, &Lp, nullptr, M), 1, s);
+}
+
+// ---- the small feature branches (position, point count, colour: [K -> 64 -> 256] + normalize, identical shapes) stage by stage,
+// every stage ONE launch over all of them (kMaxJobs = 3): 7 launches instead of 7 per branch, forward and backward
+static SmallkMulti smallk_jobs(int M) {
+  SmallkMulti sk{};
+  sk.M = M;
+  sk.mean = kNumPtsMean;
+  sk.stdv = kNumPtsStd;
+  sk.rows_per_block = 32;  // (backward; 64 rows per workgroup halve the end-of-workgroup atomics but double the serial row loop: 7.8 -> 10.4 us)
+  return sk;
+}
+static void small_branches_fwd(TrainState* st, const std::vector<int>& which, int M, int Kc, hipStream_t s) {
+  const int n = (int)which.size();
+  SmallkMulti sk = smallk_jobs(M);
+  GemmMulti gm{};
+  RownormJob rn[kMaxJobs];
+  const MlpLayer *L0[kMaxJobs], *L1[kMaxJobs];
   for (int q = 0; q < n; ++q) {
     Branch& br = st->branches[which[q]];
-    const MlpLayer &L0 = br.layers[0], &L1 = br.layers[1];
+    L0[q] = &br.layers[0];
+    L1[q] = &br.layers[1];
     sk.j[q].x = br.x;
     sk.j[q].K = br.k_in;
     sk.j[q].standardize = br.standardize;
-    sk.j[q].w = T_(st, L0.prefix + ".0.weight").data;
-    sk.j[q].b = T_(st, L0.prefix + ".0.bias").data;
-    sk.j[q].y = L0.y;
-    b0.j[q] = bn_job(st, L0, nullptr, slot0 + q);
-    gm.j[q] = GemmArgs{L0.a, T_(st, L1.prefix + ".0.weight").data, L1.y, T_(st, L1.prefix + ".0.bias").data, M, kTD, 64, 64, 64, kTD, 0, 0, 64,
-                       nullptr, tl_gemm_bf16};
-    b1.j[q] = bn_job(st, L1, nullptr, slot1 + q);
-    rn.j[q] = RownormJob{L1.a, nullptr, st->cat + br.slot * kTD, nullptr, br.save_n};
+    sk.j[q].w = T_(st, L0[q]->prefix + ".0.weight").data;
+    sk.j[q].b = T_(st, L0[q]->prefix + ".0.bias").data;
+    sk.j[q].y = L0[q]->y;
+    gm.j[q] = GemmArgs{L0[q]->a, T_(st, L1[q]->prefix + ".0.weight").data, L1[q]->y, T_(st, L1[q]->prefix + ".0.bias").data, M, kTD, 64, 64, 64, kTD, 0, 0,
+                       64, nullptr, tl_gemm_bf16};
+    rn[q] = RownormJob{L1[q]->a, nullptr, st->cat + br.slot * kTD, nullptr, br.save_n};
   }
-  hipLaunchKernelGGL(smallk_fwd_multi_kernel, dim3((M * 64 + 255) / 256, n), dim3(256), 0, s, sk);
-  hipLaunchKernelGGL((bn_stats_multi_kernel<0>), dim3(1, (M + kBnRows - 1) / kBnRows, n), dim3(256), 0, s, b0);
-  sync_slots(st->ctx, b0.j[0].acc, n, s);
-  hipLaunchKernelGGL(bn_apply_fwd_multi_kernel, dim3((unsigned)(((size_t)M * 64 + 255) / 256), n), dim3(256), 0, s, b0);
+  const BnMulti b0 = bn_jobs(st, n, L0, nullptr, M);  // (slot order: the first stage's n, then the second's)
+  const BnMulti b1 = bn_jobs(st, n, L1, nullptr, M);
+  hipLaunchKernelGGL(smallk_fwd_kernel, dim3((M * 64 + 255) / 256, n), dim3(256), 0, s, sk);
+  bn_relu_fwd(st, b0, n, s);
   hipLaunchKernelGGL((gemm_multi_kernel<true, true>), dim3(kTD / 32, (M + 31) / 32, n), dim3(256), 0, s, gm);
-  hipLaunchKernelGGL((bn_stats_multi_kernel<0>), dim3(kTD / 64, (M + kBnRows - 1) / kBnRows, n), dim3(256), 0, s, b1);
-  sync_slots(st->ctx, b1.j[0].acc, n, s);
-  hipLaunchKernelGGL(bn_apply_fwd_multi_kernel, dim3((unsigned)(((size_t)M * kTD + 255) / 256), n), dim3(256), 0, s, b1);
-  hipLaunchKernelGGL(rownorm_fwd_multi_kernel, dim3((M + 3) / 4, n), dim3(256), 0, s, rn);
+  bn_relu_fwd(st, b1, n, s);
+  rownorm_launch(true, rn, n, M, Kc, s);
 }
-// d2 / d1: [n][M][256] / [n][M][64] scratch (every branch needs its own now)
+// d2 / d1: [n][M][256] / [n][M][64] scratch (every branch needs its own)
 static void small_branches_bwd(TrainState* st, const std::vector<int>& which, int M, int Kc, const float* dcat, float* d2, float* d1,
                                hipStream_t s) {
   const int n = (int)which.size();
-  RownormMulti rn{};
-  rn.M = M;
-  rn.ld = Kc;
-  BnMulti b1{}, b0{};
-  b0.M = b1.M = M;
-  b0.C = 64;
-  b1.C = kTD;
-  b0.sync = b1.sync = st->ctx->sync_fn ? 1 : 0;
-  const int slot1 = st->bn_slot, slot0 = st->bn_slot + n;
-  st->bn_slot += 2 * n;
+  SmallkMulti sk = smallk_jobs(M);
   GemmPairMulti gp{};
-  SmallkMulti sk{};
-  sk.M = M;
-  sk.mean = 1826.6844940968194f;
-  sk.stdv = 2516.8905096993817f;
-  sk.rows_per_block = 32;  // (64 rows per workgroup halve the end-of-workgroup atomics but double the serial row loop: 7.8 -> 10.4 us)
+  RownormJob rn[kMaxJobs];
+  const MlpLayer *L0[kMaxJobs], *L1[kMaxJobs];
+  float *dq2[kMaxJobs], *dq1[kMaxJobs];
   const int N = kTD, Kp = 64;
-  const int tiles = (N / 32) * (Kp / 32);
-  int ksplit = std::max(1, std::min((M + 255) / 256, (1024 + tiles - 1) / tiles));
-  const int kchunk = (((M + ksplit - 1) / ksplit) + 63) & ~63;
-  ksplit = (M + kchunk - 1) / kchunk;
+  int ksplit, kchunk;
+  tn_split(M, N, Kp, 32, ksplit, kchunk);
   int pair_blocks = 0;
   for (int q = 0; q < n; ++q) {
     const Branch& br = st->branches[which[q]];
-    const MlpLayer &L0 = br.layers[0], &L1 = br.layers[1];
-    float* dq2 = d2 + (size_t)q * M * kTD;
-    float* dq1 = d1 + (size_t)q * M * 64;
-    rn.j[q] = RownormJob{dcat + br.slot * kTD, nullptr, dq2, st->cat + br.slot * kTD, br.save_n};
-    b1.j[q] = bn_job(st, L1, dq2, slot1 + q);
+    L0[q] = &br.layers[0];
+    L1[q] = &br.layers[1];
+    dq2[q] = d2 + (size_t)q * M * kTD;
+    dq1[q] = d1 + (size_t)q * M * 64;
+    rn[q] = RownormJob{dcat + br.slot * kTD, nullptr, dq2[q], st->cat + br.slot * kTD, br.save_n};
     GemmPair& p = gp.p[q];
-    p.tn = GemmArgs{dq2, L0.a, T_(st, L1.prefix + ".0.weight").grad, nullptr, N, Kp, M, N, Kp, Kp, 0, 1, kchunk,
-                    T_(st, L1.prefix + ".0.bias").grad, tl_gemm_bf16};
-    p.nn = GemmArgs{dq2, T_(st, L1.prefix + ".0.weight").data, dq1, nullptr, M, Kp, N, N, Kp, Kp, 0, 0, N, nullptr, tl_gemm_bf16};
+    p.tn = GemmArgs{dq2[q], L0[q]->a, T_(st, L1[q]->prefix + ".0.weight").grad, nullptr, N, Kp, M, N, Kp, Kp, 0, 1, kchunk,
+                    T_(st, L1[q]->prefix + ".0.bias").grad, tl_gemm_bf16};
+    p.nn = GemmArgs{dq2[q], T_(st, L1[q]->prefix + ".0.weight").data, dq1[q], nullptr, M, Kp, N, N, Kp, Kp, 0, 0, N, nullptr, tl_gemm_bf16};
     p.tn_gx = Kp / 32;
     p.tn_gy = N / 32;
     p.tn_blocks = p.tn_gx * p.tn_gy * ksplit;
     p.nn_gx = Kp / 32;
     pair_blocks = p.tn_blocks + p.nn_gx * ((M + 31) / 32);
-    b0.j[q] = bn_job(st, L0, dq1, slot0 + q);
     sk.j[q].x = br.x;
     sk.j[q].K = br.k_in;
     sk.j[q].standardize = br.standardize;
-    sk.j[q].dy = dq1;
-    sk.j[q].dW = T_(st, L0.prefix + ".0.weight").grad;
-    sk.j[q].db = T_(st, L0.prefix + ".0.bias").grad;
+    sk.j[q].dy = dq1[q];
+    sk.j[q].dW = T_(st, L0[q]->prefix + ".0.weight").grad;
+    sk.j[q].db = T_(st, L0[q]->prefix + ".0.bias").grad;
   }
-  hipLaunchKernelGGL(rownorm_bwd_multi_kernel, dim3((M + 3) / 4, n), dim3(256), 0, s, rn);
-  hipLaunchKernelGGL((bn_stats_multi_kernel<1>), dim3(kTD / 64, (M + kBnRows - 1) / kBnRows, n), dim3(256), 0, s, b1);
-  sync_slots(st->ctx, b1.j[0].acc, n, s);
-  hipLaunchKernelGGL(bn_apply_bwd_multi_kernel, dim3((unsigned)(((size_t)M * kTD + 255) / 256), n), dim3(256), 0, s, b1);
+  const BnMulti b1 = bn_jobs(st, n, L1, dq2, M);  // (slot order: the second stage's n, then the first's)
+  const BnMulti b0 = bn_jobs(st, n, L0, dq1, M);
+  rownorm_launch(false, rn, n, M, Kc, s);
+  bn_relu_bwd(st, b1, n, s);
   hipLaunchKernelGGL(gemm_pair_multi_kernel, dim3(pair_blocks, n), dim3(256), 0, s, gp);
-  hipLaunchKernelGGL((bn_stats_multi_kernel<1>), dim3(1, (M + kBnRows - 1) / kBnRows, n), dim3(256), 0, s, b0);
-  sync_slots(st->ctx, b0.j[0].acc, n, s);
-  hipLaunchKernelGGL(bn_apply_bwd_multi_kernel, dim3((unsigned)(((size_t)M * 64 + 255) / 256), n), dim3(256), 0, s, b0);
-  hipLaunchKernelGGL(smallk_bwd_multi_kernel, dim3((M + 31) / 32, n), dim3(256), 0, s, sk);
+  bn_relu_bwd(st, b0, n, s);
+  hipLaunchKernelGGL(smallk_bwd_kernel, dim3((M + 31) / 32, n), dim3(256), 0, s, sk);
 }
 
 int train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, float p, uint32_t seed, float* out_emb, hipStream_t s) {
@@ -699,9 +739,9 @@ int train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, float p, uint32
       br.kind = 2; br.slot = slot++; br.x = in->pn_feat; br.k_in = 256;
       br.layers.push_back(make_layer(st, oe + "mlp_pointnet.0", 256, kTD, M));
       br.save_n = st->ws.take<float>(M);
-      mlp_layer_fwd(st, br.layers[0], in->pn_feat, M, 0, 0, s);
-      hipLaunchKernelGGL(rownorm_fwd_kernel, dim3((M + 3) / 4), dim3(256), 0, s, br.layers[0].a, (const int32_t*)nullptr, M,
-                         st->cat + br.slot * kTD, Kc, br.save_n);
+      mlp_layer_fwd(st, br.layers[0], in->pn_feat, M, s);
+      const RownormJob rn{br.layers[0].a, nullptr, st->cat + br.slot * kTD, nullptr, br.save_n};
+      rownorm_launch(true, &rn, 1, M, Kc, s);
       st->branches.push_back(br);
     }
   }
@@ -712,19 +752,17 @@ int train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, float p, uint32
   if (c.use_position) small_branch("pos_encoder", in->center, 3, 0);
   if (c.use_num) small_branch("num_encoder", in->n_pts, 1, 1);
   if (!embeds.empty()) {
-    RownormMulti rn{};
-    rn.M = M;
-    rn.ld = Kc;
+    RownormJob rn[kMaxJobs];
     for (size_t q = 0; q < embeds.size(); ++q) {
       const Branch& br = st->branches[embeds[q]];
-      rn.j[q] = RownormJob{T_(st, br.table).data, br.idx, st->cat + br.slot * kTD, nullptr, br.save_n};
+      rn[q] = RownormJob{T_(st, br.table).data, br.idx, st->cat + br.slot * kTD, nullptr, br.save_n};
     }
-    hipLaunchKernelGGL(rownorm_fwd_multi_kernel, dim3((M + 3) / 4, (unsigned)embeds.size()), dim3(256), 0, s, rn);
+    rownorm_launch(true, rn, (int)embeds.size(), M, Kc, s);
   }
   if (!smalls.empty()) small_branches_fwd(st, smalls, M, Kc, s);
 
   st->merge = make_layer(st, oe + "mlp_merge.0", Kc, kTD, M);
-  mlp_layer_fwd(st, st->merge, st->cat, M, 0, 0, s);
+  mlp_layer_fwd(st, st->merge, st->cat, M, s);
   st->X0 = st->ws.take<float>((size_t)T * kTD);
   st->save_nf = st->ws.take<float>(M);
   hipLaunchKernelGGL(scatter_norm_fwd_kernel, dim3((T + 3) / 4), dim3(256), 0, s, st->merge.a, in->offsets, B, st->X0, st->save_nf);
@@ -758,28 +796,12 @@ int train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, float p, uint32
 
 // ---- backward --------------------------------------------------------------------------------------------------
 // d: gradient w.r.t. the block's ReLU output [M,cout] (overwritten); x: the block's input; dx (optional) receives d W.
-static void mlp_layer_bwd(TrainState* st, const MlpLayer& L, float* d, const float* x, int M, int small_k, int standardize, float* dx,
-                          hipStream_t s) {
-  const int sync = st->ctx->sync_fn ? 1 : 0;
-  double* acc = acc_base(st->ctx, st) + (size_t)(st->bn_slot++ % (2 * kBnSlots)) * kBnStride;
-  hipLaunchKernelGGL((bn_stats_kernel<1>), dim3(L.cout / 64, (M + kBnRows - 1) / kBnRows), dim3(256), 0, s, L.y, (const float*)d, (const float*)L.a,
-                     M, L.cout, (const float*)L.mean, (const float*)L.rstd, acc, sync, T_(st, L.prefix + ".1.weight").grad,
-                     T_(st, L.prefix + ".1.bias").grad);
-  sync_slots(st->ctx, acc, 1, s);
-  hipLaunchKernelGGL(bn_apply_bwd_kernel, dim3((unsigned)(((size_t)M * L.cout + 255) / 256)), dim3(256), 0, s, d, L.a, L.y, M, L.cout, acc,
-                     T_(st, L.prefix + ".1.weight").data, L.mean, L.rstd, T_(st, L.prefix + ".1.weight").grad, T_(st, L.prefix + ".1.bias").grad,
-                     sync);
-  if (small_k) {
-    const int rows = 32;
-    hipLaunchKernelGGL(smallk_bwd_kernel, dim3((M + rows - 1) / rows), dim3(256), 0, s, x, M, small_k, d, standardize, 1826.6844940968194f,
-                       2516.8905096993817f, rows, T_(st, L.prefix + ".0.weight").grad, T_(st, L.prefix + ".0.bias").grad);
-  } else {
-    if (dx)
-      gemm_tn_nn(d, x, T_(st, L.prefix + ".0.weight").grad, T_(st, L.prefix + ".0.bias").grad, T_(st, L.prefix + ".0.weight").data, dx, M, L.cout,
-                 L.cin, 0, nullptr, nullptr, s);
-    else
-      gemm_tn(d, x, T_(st, L.prefix + ".0.weight").grad, T_(st, L.prefix + ".0.bias").grad, M, L.cout, L.cin, s);
-  }
+static void mlp_layer_bwd(TrainState* st, const MlpLayer& L, float* d, const float* x, int M, float* dx, hipStream_t s) {
+  const MlpLayer* Lp = &L;
+  bn_relu_bwd(st, bn_jobs(st, 1, &Lp, &d, M), 1, s);
+  const TTensor &W = T_(st, L.prefix + ".0.weight"), &b = T_(st, L.prefix + ".0.bias");
+  if (dx) gemm_tn_nn(d, x, W.grad, b.grad, W.data, dx, M, L.cout, L.cin, 0, nullptr, nullptr, s);
+  else gemm_tn(d, x, W.grad, b.grad, M, L.cout, L.cin, s);
 }
 
 int train_backward_impl(t2l_ctx* ctx, const float* grad_emb, float* grad_pn_feat, hipStream_t s) {
@@ -808,8 +830,6 @@ int train_backward_impl(t2l_ctx* ctx, const float* grad_emb, float* grad_pn_feat
     st->ws.off = mark;
     return fail(ctx, T2L_ENOMEM, "t2l_encode_cells_backward: workspace bound exceeded (internal error)");
   }
-  const float* xl = st->layers.empty() ? st->X0 : st->layers.back().x2;
-  (void)xl;
   hipLaunchKernelGGL(pool_norm_bwd_kernel, dim3(B), dim3(256), 0, s, grad_emb, st->out, st->pool_arg, st->pool_n, dcur);
   const Products pr{ctx, false};
   for (int l = (int)st->layers.size() - 1; l >= 0; --l) {
@@ -819,18 +839,16 @@ int train_backward_impl(t2l_ctx* ctx, const float* grad_emb, float* grad_pn_feat
   }
   // tokens -> objects, merge MLP
   hipLaunchKernelGGL(scatter_norm_bwd_kernel, dim3((M + 3) / 4), dim3(256), 0, s, dcur, st->X0, st->save_nf, st->offsets, B, M, dfeat);
-  mlp_layer_bwd(st, st->merge, dfeat, st->cat, M, 0, 0, dcat, s);
+  mlp_layer_bwd(st, st->merge, dfeat, st->cat, M, dcat, s);
   {  // embedding tables: normalize-backward of both slots in one launch, then the per-row sums of both tables in one
-    RownormMulti rn{};
-    rn.M = M;
-    rn.ld = Kc;
+    RownormJob rn[kMaxJobs];
     EmbedSumMulti es{};
     es.M = M;
     int ne = 0, max_rows = 0;
     for (const Branch& br : st->branches) {
       if (br.kind != 0) continue;
       float* dq = d2 + (size_t)ne * M * kTD;
-      rn.j[ne] = RownormJob{dcat + br.slot * kTD, nullptr, dq, st->cat + br.slot * kTD, br.save_n};
+      rn[ne] = RownormJob{dcat + br.slot * kTD, nullptr, dq, st->cat + br.slot * kTD, br.save_n};
       es.g[ne] = dq;
       es.idx[ne] = br.idx;
       es.dtable[ne] = T_(st, br.table).grad;
@@ -839,15 +857,15 @@ int train_backward_impl(t2l_ctx* ctx, const float* grad_emb, float* grad_pn_feat
       ++ne;
     }
     if (ne) {
-      hipLaunchKernelGGL(rownorm_bwd_multi_kernel, dim3((M + 3) / 4, ne), dim3(256), 0, s, rn);
-      if (max_rows > 1) hipLaunchKernelGGL(embed_sum_multi_kernel, dim3(max_rows - 1, kEmbSplit, ne), dim3(256), 0, s, es);
+      rownorm_launch(false, rn, ne, M, Kc, s);
+      if (max_rows > 1) hipLaunchKernelGGL(embed_sum_kernel, dim3(max_rows - 1, kEmbSplit, ne), dim3(256), 0, s, es);
     }
   }
   for (const Branch& br : st->branches) {
     if (br.kind != 2) continue;  // the PointNet++-feature branch: one [256 -> 256] block
-    hipLaunchKernelGGL(rownorm_bwd_kernel, dim3((M + 3) / 4), dim3(256), 0, s, dcat + br.slot * kTD, st->cat + br.slot * kTD, Kc, br.save_n, M,
-                       d2);
-    mlp_layer_bwd(st, br.layers[0], d2, br.x, M, 0, 0, grad_pn_feat, s);
+    const RownormJob rn{dcat + br.slot * kTD, nullptr, d2, st->cat + br.slot * kTD, br.save_n};
+    rownorm_launch(false, &rn, 1, M, Kc, s);
+    mlp_layer_bwd(st, br.layers[0], d2, br.x, M, grad_pn_feat, s);
   }
   {
     std::vector<int> smalls;
@@ -862,27 +880,21 @@ int train_backward_impl(t2l_ctx* ctx, const float* grad_emb, float* grad_pn_feat
   return T2L_OK;
 }
 
-static void adam_launch(TrainState* st, int chunk0, int chunk1, int64_t step, float lr, float b1, float b2, float eps, hipStream_t s) {
-  if (chunk1 <= chunk0) return;
-  const float bc1 = (float)(1.0 - pow((double)b1, (double)step));
-  const float bc2s = (float)sqrt(1.0 - pow((double)b2, (double)step));
-  hipLaunchKernelGGL(adam_kernel, dim3(chunk1 - chunk0), dim3(256), 0, s, st->d_tensors, st->d_chunks + chunk0, lr, b1, b2, eps, bc1, bc2s);
-}
-
 int adam_step_impl(t2l_ctx* ctx, float lr, float b1, float b2, float eps, hipStream_t s) {
   TrainState* st = state(ctx);
   if (!st) return fail(ctx, T2L_ESTATE, "t2l_adam_step: call t2l_train_bind first");
   st->step += 1;
   // the backbone's tensors step only when its backward added into their gradients since the last zero_grad (a batch that
   // passed precomputed features2 leaves them untouched: torch.optim.Adam would skip .grad = None parameters, not decay them)
-  const bool pn = st->pn_chunk0 < st->n_chunks && st->pn_touched;
+  const int n_chunks = st->adam.plan.n_chunks();
+  const bool pn = st->pn_chunk0 < n_chunks && st->pn_touched;
   if (pn) st->step_pn += 1;
   event_begin(ctx, "adam_step", s);
   if (pn && st->step_pn == st->step) {
-    adam_launch(st, 0, st->n_chunks, st->step, lr, b1, b2, eps, s);
+    st->adam.launch(0, n_chunks, st->step, lr, b1, b2, eps, s);
   } else {
-    adam_launch(st, 0, st->pn_chunk0, st->step, lr, b1, b2, eps, s);
-    if (pn) adam_launch(st, st->pn_chunk0, st->n_chunks, st->step_pn, lr, b1, b2, eps, s);
+    st->adam.launch(0, st->pn_chunk0, st->step, lr, b1, b2, eps, s);
+    if (pn) st->adam.launch(st->pn_chunk0, n_chunks, st->step_pn, lr, b1, b2, eps, s);
   }
   event_end(ctx, "adam_step", s);
   T2L_HIP(ctx, hipGetLastError());
@@ -892,30 +904,18 @@ int adam_step_impl(t2l_ctx* ctx, float lr, float b1, float b2, float eps, hipStr
 int adam_state_impl(t2l_ctx* ctx, int set, float* m, float* v, int64_t* step, int64_t* numel, hipStream_t s) {
   TrainState* st = state(ctx);
   if (!st) return fail(ctx, T2L_ESTATE, "t2l_adam_state: call t2l_train_bind first");
-  if (numel) *numel = st->mv_total;
-  if (!m && !v) {  // size / step query
-    if (step && !set) *step = st->step | (st->step_pn << 32);
-    return T2L_OK;
-  }
-  if (!m || !v || !step) return fail(ctx, T2L_EINVAL, "t2l_adam_state: pass m, v and step together");
-  const size_t bytes = sizeof(float) * (size_t)st->mv_total;
-  if (set) {
-    T2L_HIP(ctx, hipMemcpyAsync(st->mv, m, bytes, hipMemcpyDeviceToDevice, s));
-    T2L_HIP(ctx, hipMemcpyAsync(st->mv + st->mv_total, v, bytes, hipMemcpyDeviceToDevice, s));
+  const int rc = st->adam.state(ctx, "t2l_adam_state", set, m, v, step, numel, st->step | (st->step_pn << 32), s);
+  if (rc == T2L_OK && set && m) {
     st->step = *step & 0xFFFFFFFFll;
-    st->step_pn = st->pn_chunk0 < st->n_chunks ? (*step >> 32) : 0;
-  } else {
-    T2L_HIP(ctx, hipMemcpyAsync(m, st->mv, bytes, hipMemcpyDeviceToDevice, s));
-    T2L_HIP(ctx, hipMemcpyAsync(v, st->mv + st->mv_total, bytes, hipMemcpyDeviceToDevice, s));
-    *step = st->step | (st->step_pn << 32);
+    st->step_pn = st->pn_chunk0 < st->adam.plan.n_chunks() ? (*step >> 32) : 0;
   }
-  return T2L_OK;
+  return rc;
 }
 
 int zero_grad_impl(t2l_ctx* ctx, hipStream_t s) {
   TrainState* st = state(ctx);
   if (!st) return fail(ctx, T2L_ESTATE, "t2l_zero_grad: call t2l_train_bind first");
-  hipLaunchKernelGGL(zero_kernel, dim3(st->n_chunks), dim3(256), 0, s, st->d_tensors, st->d_chunks);
+  st->adam.zero(s);
   st->pn_touched = false;
   T2L_HIP(ctx, hipGetLastError());
   return T2L_OK;
@@ -938,7 +938,7 @@ int zero_grad_impl(t2l_ctx* ctx, hipStream_t s) {
 // =================================================================================================================
 struct TextTrain {
   t2l_ctx* ctx = nullptr;
-  std::unordered_map<std::string, TTensor> t;
+  TensorMap t;
   std::string prefix;
   Arena ws;
   bool have_forward = false;
@@ -950,21 +950,15 @@ struct TextTrain {
   EncLayer intra, inter;
   float *pooled = nullptr, *mlp_y = nullptr, *mlp_out = nullptr, *bn_mean = nullptr, *bn_rstd = nullptr, *out = nullptr;
   int32_t *tok_arg = nullptr, *sent_arg = nullptr;
-  // Adam over the head's parameters (t2l_text_adam_step): moments inside the library, one launch through the chunk table
-  std::vector<std::string> adam_names;  // bind order
-  std::vector<int64_t> adam_numel;
-  AdamTensor* d_tensors = nullptr;
-  AdamChunk* d_chunks = nullptr;
-  float* mv = nullptr;  // [2][mv_total]
-  int64_t mv_total = 0, step = 0;
-  int n_chunks = 0;
+  AdamSet adam;  // over the head's parameters, in bind order (t2l_text_adam_step)
+  int64_t step = 0;
 };
 static TextTrain* tstate(t2l_ctx* ctx) { return reinterpret_cast<TextTrain*>(ctx->text_train); }
 void free_text_train(t2l_ctx* ctx) {
   TextTrain* st = tstate(ctx);
   if (!st) return;
-  for (void* p : {(void*)st->ws.base, (void*)st->d_tensors, (void*)st->d_chunks, (void*)st->mv})
-    if (p) (void)hipFree(p);
+  st->adam.release();
+  if (st->ws.base) (void)hipFree(st->ws.base);
   delete st;
   ctx->text_train = nullptr;
 }
@@ -975,27 +969,28 @@ __global__ void add_inplace_kernel(float* __restrict__ a, const float* __restric
   if (i < n) a[i] += b[i];
 }
 
+// inter_mlp's BatchNorm (no ReLU behind it) over the n_sent rows of mlp_y; PHASE, acc: bn_plain_fwd_kernel
+template <int PHASE>
+static void text_bn_fwd(TextTrain* st, double* acc, hipStream_t s) {
+  hipLaunchKernelGGL((bn_plain_fwd_kernel<PHASE>), dim3(st->D / 4), dim3(256), 0, s, (const float*)st->mlp_y, st->n_sent, st->D,
+                     TT(st, "inter_mlp.0.1.weight").data, TT(st, "inter_mlp.0.1.bias").data, TT(st, "inter_mlp.0.1.running_mean").data,
+                     TT(st, "inter_mlp.0.1.running_var").data, 0.1f, st->mlp_out, st->bn_mean, st->bn_rstd, acc);
+}
+template <int PHASE>
+static void text_bn_bwd(TextTrain* st, float* dX, double* acc, hipStream_t s) {
+  hipLaunchKernelGGL((bn_plain_bwd_kernel<PHASE>), dim3(st->D / 4), dim3(256), 0, s, dX, (const float*)st->mlp_y, st->n_sent, st->D,
+                     TT(st, "inter_mlp.0.1.weight").data, (const float*)st->bn_mean, (const float*)st->bn_rstd,
+                     TT(st, "inter_mlp.0.1.weight").grad, TT(st, "inter_mlp.0.1.bias").grad, acc);
+}
+
 static int text_train_bind_body(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n, const char* prefix) {
   if (!tensors || n <= 0) return fail(ctx, T2L_EINVAL, "t2l_text_train_bind: null argument");
   // a re-bind of the same parameter list (moved storage: model.to(), re-assigned .grad) keeps the optimizer state, as t2l_train_bind does
-  std::vector<std::string> old_names;
-  std::vector<int64_t> old_numel;
-  float* old_mv = nullptr;
-  int64_t old_total = 0, old_step = 0;
-  struct MvGuard {  // the detached moments are freed on every path that does not adopt them (a refused re-bind included)
-    float* p = nullptr;
-    ~MvGuard() { if (p) (void)hipFree(p); }
-  } old_guard;
+  AdamSet::Old old;
+  int64_t old_step = 0;
   if (TextTrain* o = tstate(ctx)) {
-    if (ctx->train_keep_adam && o->mv) {
-      old_names = o->adam_names;
-      old_numel = o->adam_numel;
-      old_mv = o->mv;
-      old_total = o->mv_total;
-      old_step = o->step;
-      o->mv = nullptr;  // (free_text_train below must not free it)
-      old_guard.p = old_mv;
-    }
+    o->adam.detach(old);
+    old_step = o->step;
   }
   free_text_train(ctx);
   TextTrain* st = new TextTrain();
@@ -1039,39 +1034,11 @@ static int text_train_bind_body(t2l_ctx* ctx, const t2l_train_tensor* tensors, i
       (rc = need_t("inter_mlp.0.1.weight", D, true)) || (rc = need_t("inter_mlp.0.1.bias", D, true)) ||
       (rc = need_t("inter_mlp.0.1.running_mean", D, false)) || (rc = need_t("inter_mlp.0.1.running_var", D, false)))
     return rc;
-  {  // Adam tables over every bound tensor that has a gradient buffer, in bind order; moments zero-initialised
-    std::vector<AdamTensor> ts;
-    std::vector<AdamChunk> cs;
-    for (int i = 0; i < n; ++i)
-      if (tensors[i].grad && st->t.count(tensors[i].name)) {
-        st->adam_names.push_back(tensors[i].name);
-        st->adam_numel.push_back(tensors[i].numel);
-        st->mv_total += tensors[i].numel;
-      }
-    const bool same = old_mv && old_names == st->adam_names && old_numel == st->adam_numel && old_total == st->mv_total;
-    if (same) {
-      st->mv = old_mv;
-      st->step = old_step;
-      old_guard.p = nullptr;
-    } else {
-      if (old_mv) (void)hipFree(old_mv);
-      old_guard.p = nullptr;
-      T2L_HIP(ctx, hipMalloc(&st->mv, sizeof(float) * 2 * (size_t)st->mv_total));
-      T2L_HIP(ctx, hipMemset(st->mv, 0, sizeof(float) * 2 * (size_t)st->mv_total));
-    }
-    int64_t off = 0;
-    for (size_t i = 0; i < st->adam_names.size(); ++i) {
-      const TTensor& t = st->t[st->adam_names[i]];
-      ts.push_back(AdamTensor{t.data, t.grad, st->mv + off, st->mv + st->mv_total + off, t.numel});
-      for (int64_t c = 0; c * 1024 < t.numel; ++c) cs.push_back(AdamChunk{(int32_t)i, (int32_t)c});
-      off += t.numel;
-    }
-    st->n_chunks = (int)cs.size();
-    T2L_HIP(ctx, hipMalloc(&st->d_tensors, sizeof(AdamTensor) * ts.size()));
-    T2L_HIP(ctx, hipMalloc(&st->d_chunks, sizeof(AdamChunk) * cs.size()));
-    T2L_HIP(ctx, hipMemcpy(st->d_tensors, ts.data(), sizeof(AdamTensor) * ts.size(), hipMemcpyHostToDevice));
-    T2L_HIP(ctx, hipMemcpy(st->d_chunks, cs.data(), sizeof(AdamChunk) * cs.size(), hipMemcpyHostToDevice));
-  }
+  for (int i = 0; i < n; ++i)  // Adam over every bound tensor that has a gradient buffer, in bind order (each is in st->t: inserted above)
+    if (tensors[i].grad) st->adam.names.push_back(tensors[i].name);
+  bool kept;
+  if ((rc = st->adam.build(ctx, st->t, old, &kept))) return rc;
+  if (kept) st->step = old_step;
   static PerDeviceOnce once;
   if (once.need(ctx->device)) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<256, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
@@ -1130,20 +1097,15 @@ int text_train_forward_impl(t2l_ctx* ctx, const float* hidden, int n_sent, int L
   st->bn_rstd = st->ws.take<float>(D);
   // (D = 128 is no multiple of the fast GEMM's 256-column tile: the fine head's Linear runs on the gemm_f32.h product, same operands)
   t_gemm_nt(pr, st->pooled, TT(st, "inter_mlp.0.0.weight").data, TT(st, "inter_mlp.0.0.bias").data, st->mlp_y, n_sent, D, 1024, 0, s);
-#define T2L_TEXT_BN_FWD(PHASE, ACC)                                                                                                       \
-  hipLaunchKernelGGL((bn_plain_fwd_kernel<PHASE>), dim3(D / 4), dim3(256), 0, s, (const float*)st->mlp_y, n_sent, D,                      \
-                     TT(st, "inter_mlp.0.1.weight").data, TT(st, "inter_mlp.0.1.bias").data, TT(st, "inter_mlp.0.1.running_mean").data,   \
-                     TT(st, "inter_mlp.0.1.running_var").data, 0.1f, st->mlp_out, st->bn_mean, st->bn_rstd, ACC)
   if (ctx->sync_fn) {  // statistics | sum over the ranks | apply (t2l_train_sync_bn)
     double* acc = ctx->sync_buf + (size_t)(2 * kBnSlots) * kBnStride;
     ctx->sync_failed = false;
-    T2L_TEXT_BN_FWD(1, acc);
+    text_bn_fwd<1>(st, acc, s);
     sync_slots(ctx, acc, 1, s);
-    T2L_TEXT_BN_FWD(2, acc);
+    text_bn_fwd<2>(st, acc, s);
   } else {
-    T2L_TEXT_BN_FWD(0, (double*)nullptr);
+    text_bn_fwd<0>(st, nullptr, s);
   }
-#undef T2L_TEXT_BN_FWD
   if (st->fine) {  // the fine head ends here: one vector per hint, viewed [n_desc, S, D] by the caller (language_encoder.py:137-141)
     T2L_HIP(ctx, hipMemcpyAsync(out, st->mlp_out, sizeof(float) * (size_t)n_sent * D, hipMemcpyDeviceToDevice, s));
     event_end(ctx, "text_train_forward", s);
@@ -1195,20 +1157,15 @@ int text_train_backward_impl(t2l_ctx* ctx, const float* grad_out, hipStream_t s)
     hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)(((size_t)n_sent * 256 + 255) / 256)), dim3(256), 0, s, dX, (const float*)dY2, (size_t)n_sent * 256);
   }
   // inter_mlp: BatchNorm (batch statistics), Linear
-#define T2L_TEXT_BN_BWD(PHASE, ACC)                                                                                                    \
-  hipLaunchKernelGGL((bn_plain_bwd_kernel<PHASE>), dim3(D / 4), dim3(256), 0, s, dX, (const float*)st->mlp_y, n_sent, D,                \
-                     TT(st, "inter_mlp.0.1.weight").data, (const float*)st->bn_mean, (const float*)st->bn_rstd,                         \
-                     TT(st, "inter_mlp.0.1.weight").grad, TT(st, "inter_mlp.0.1.bias").grad, ACC)
   if (ctx->sync_fn) {
     double* acc = ctx->sync_buf + (size_t)(2 * kBnSlots + 1) * kBnStride;
     ctx->sync_failed = false;
-    T2L_TEXT_BN_BWD(1, acc);
+    text_bn_bwd<1>(st, dX, acc, s);
     sync_slots(ctx, acc, 1, s);
-    T2L_TEXT_BN_BWD(2, acc);
+    text_bn_bwd<2>(st, dX, acc, s);
   } else {
-    T2L_TEXT_BN_BWD(0, (double*)nullptr);
+    text_bn_bwd<0>(st, dX, nullptr, s);
   }
-#undef T2L_TEXT_BN_BWD
   float* dpool = st->ws.take<float>((size_t)n_sent * 1024);
   t_gemm_tn_nn(pr, dX, st->pooled, TT(st, "inter_mlp.0.0.weight").grad, TT(st, "inter_mlp.0.0.bias").grad, TT(st, "inter_mlp.0.0.weight").data, dpool,
                n_sent, D, 1024, 0, nullptr, nullptr, s);
@@ -1231,10 +1188,8 @@ int text_adam_step_impl(t2l_ctx* ctx, float lr, float b1, float b2, float eps, h
   TextTrain* st = tstate(ctx);
   if (!st) return fail(ctx, T2L_ESTATE, "t2l_text_adam_step: call t2l_text_train_bind first");
   st->step += 1;
-  const float bc1 = (float)(1.0 - pow((double)b1, (double)st->step));
-  const float bc2s = (float)sqrt(1.0 - pow((double)b2, (double)st->step));
   event_begin(ctx, "text_adam_step", s);
-  hipLaunchKernelGGL(adam_kernel, dim3(st->n_chunks), dim3(256), 0, s, st->d_tensors, st->d_chunks, lr, b1, b2, eps, bc1, bc2s);
+  st->adam.launch(0, st->adam.plan.n_chunks(), st->step, lr, b1, b2, eps, s);
   event_end(ctx, "text_adam_step", s);
   T2L_HIP(ctx, hipGetLastError());
   return T2L_OK;
@@ -1243,7 +1198,7 @@ int text_adam_step_impl(t2l_ctx* ctx, float lr, float b1, float b2, float eps, h
 int text_zero_grad_impl(t2l_ctx* ctx, hipStream_t s) {
   TextTrain* st = tstate(ctx);
   if (!st) return fail(ctx, T2L_ESTATE, "t2l_text_zero_grad: call t2l_text_train_bind first");
-  hipLaunchKernelGGL(zero_kernel, dim3(st->n_chunks), dim3(256), 0, s, st->d_tensors, st->d_chunks);
+  st->adam.zero(s);
   T2L_HIP(ctx, hipGetLastError());
   return T2L_OK;
 }
@@ -1251,23 +1206,9 @@ int text_zero_grad_impl(t2l_ctx* ctx, hipStream_t s) {
 int text_adam_state_impl(t2l_ctx* ctx, int set, float* m, float* v, int64_t* step, int64_t* numel, hipStream_t s) {
   TextTrain* st = tstate(ctx);
   if (!st) return fail(ctx, T2L_ESTATE, "t2l_text_adam_state: call t2l_text_train_bind first");
-  if (numel) *numel = st->mv_total;
-  if (!m && !v) {
-    if (step && !set) *step = st->step;
-    return T2L_OK;
-  }
-  if (!m || !v || !step) return fail(ctx, T2L_EINVAL, "t2l_text_adam_state: pass m, v and step together");
-  const size_t bytes = sizeof(float) * (size_t)st->mv_total;
-  if (set) {
-    T2L_HIP(ctx, hipMemcpyAsync(st->mv, m, bytes, hipMemcpyDeviceToDevice, s));
-    T2L_HIP(ctx, hipMemcpyAsync(st->mv + st->mv_total, v, bytes, hipMemcpyDeviceToDevice, s));
-    st->step = *step;
-  } else {
-    T2L_HIP(ctx, hipMemcpyAsync(m, st->mv, bytes, hipMemcpyDeviceToDevice, s));
-    T2L_HIP(ctx, hipMemcpyAsync(v, st->mv + st->mv_total, bytes, hipMemcpyDeviceToDevice, s));
-    *step = st->step;
-  }
-  return T2L_OK;
+  const int rc = st->adam.state(ctx, "t2l_text_adam_state", set, m, v, step, numel, st->step, s);
+  if (rc == T2L_OK && set && m) st->step = *step;
+  return rc;
 }
 
 }  // namespace t2l

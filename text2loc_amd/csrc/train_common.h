@@ -1,5 +1,5 @@
 // What the training translation units share (train.hip through train_kernels.h, fine_train.hip): the counter-based dropout rule and
-// the bump arena of a step's activations. No __global__ definitions here, so any number of translation units may include it.
+// the bump arena of a step's activations, the point-count standardization. No __global__ definitions here, so any number of translation units may include it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -7,6 +7,9 @@
 
 namespace t2l {
 namespace train {
+
+// num_encoder's input is (n_pts - mean) / std with these (models/object_encoder.py:43-44, 141-144)
+constexpr float kNumPtsMean = 1826.6844940968194f, kNumPtsStd = 2516.8905096993817f;
 
 // Counter-based dropout: keep element `idx` of site `site` iff the top 24 bits of lowbias32(idx*0x9E3779B1 + key) >= thr,
 // key = seed ^ site*0x85EBCA77, thr = p*2^24. oracle/t2l_oracle_train.py:dropout_keep is the same function.

@@ -49,9 +49,9 @@ __device__ __forceinline__ float small_in(const float* x, int m, int K, int k, i
   float v = x[(size_t)m * K + k];
   return standardize ? (v - mean) / stdv : v;
 }
-// (every kernel of the feature branches exists as a body + a plain launch + a MULTI launch: the two or three small branches —
-//  position, point count, colour — are independent chains of identical shape, so each stage of all of them is ONE launch with the
-//  branch in an extra grid dimension: a dependent launch costs ~5 us whatever it does, and the branches ran one after the other)
+// Every op of the feature branches is ONE kernel over a job list (<= kMaxJobs jobs, the job in an extra grid dimension): the two or three
+// small branches — position, point count, colour — are independent chains of identical shape, so each stage of all of them is one
+// launch (a dependent launch costs ~5 us whatever it does); a layer that is alone (mlp_merge, mlp_pointnet) is a list of one.
 constexpr int kMaxJobs = 3;
 __device__ __forceinline__ void smallk_fwd_body(const float* __restrict__ x, int M, int K, const float* __restrict__ w,
                                                 const float* __restrict__ b, int standardize, float mean, float stdv,
@@ -62,11 +62,6 @@ __device__ __forceinline__ void smallk_fwd_body(const float* __restrict__ x, int
   float s = b[c];
   for (int k = 0; k < K; ++k) s += small_in(x, m, K, k, standardize, mean, stdv) * w[c * K + k];
   y[i] = s;
-}
-__global__ void smallk_fwd_kernel(const float* __restrict__ x, int M, int K, const float* __restrict__ w,
-                                  const float* __restrict__ b, int standardize, float mean, float stdv,
-                                  float* __restrict__ y) {
-  smallk_fwd_body(x, M, K, w, b, standardize, mean, stdv, y, blockIdx.x);
 }
 struct SmallkJob {
   const float* x;
@@ -81,7 +76,7 @@ struct SmallkMulti {
   int M, rows_per_block;
   float mean, stdv;
 };
-__global__ void smallk_fwd_multi_kernel(SmallkMulti m) {
+__global__ void smallk_fwd_kernel(SmallkMulti m) {
   const SmallkJob& j = m.j[blockIdx.y];
   smallk_fwd_body(j.x, m.M, j.K, j.w, j.b, j.standardize, m.mean, m.stdv, j.y, blockIdx.x);
 }
@@ -107,13 +102,7 @@ __device__ __forceinline__ void smallk_bwd_body(const float* __restrict__ x, int
     unsafeAtomicAdd(db + c, red[3][c] + red[3][c + 64] + red[3][c + 128] + red[3][c + 192]);
   }
 }
-__global__ __launch_bounds__(256) void smallk_bwd_kernel(const float* __restrict__ x, int M, int K,
-                                                         const float* __restrict__ dy, int standardize, float mean,
-                                                         float stdv, int rows_per_block, float* __restrict__ dW,
-                                                         float* __restrict__ db) {
-  smallk_bwd_body(x, M, K, dy, standardize, mean, stdv, rows_per_block, dW, db, blockIdx.x);
-}
-__global__ __launch_bounds__(256) void smallk_bwd_multi_kernel(SmallkMulti m) {
+__global__ __launch_bounds__(256) void smallk_bwd_kernel(SmallkMulti m) {
   const SmallkJob& j = m.j[blockIdx.y];
   smallk_bwd_body(j.x, m.M, j.K, j.dy, j.standardize, m.mean, m.stdv, m.rows_per_block, j.dW, j.db, blockIdx.x);
 }
@@ -133,8 +122,8 @@ constexpr int kBnStride = 2056;
 template <int MODE>
 __device__ __forceinline__ void bn_stats_body(const float* __restrict__ y, const float* __restrict__ d, const float* __restrict__ out, int M,
                                               int C, const float* __restrict__ save_mean, const float* __restrict__ save_rstd,
-                                              double* __restrict__ acc, unsigned bx, unsigned by, int sync = 0,
-                                              float* __restrict__ dgamma = nullptr, float* __restrict__ dbeta = nullptr) {
+                                              double* __restrict__ acc, unsigned bx, unsigned by, int sync,
+                                              float* __restrict__ dgamma, float* __restrict__ dbeta) {
   __shared__ float r1[256], r2[256];
   const int c = bx * 64 + (threadIdx.x & 63), g = threadIdx.x >> 6;
   const int lo = by * kBnRows, hi = min(M, lo + kBnRows);
@@ -177,14 +166,6 @@ __device__ __forceinline__ void bn_stats_body(const float* __restrict__ y, const
     }
   }
 }
-template <int MODE>
-__global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ y, const float* __restrict__ d,
-                                                       const float* __restrict__ out, int M, int C,
-                                                       const float* __restrict__ save_mean,
-                                                       const float* __restrict__ save_rstd, double* __restrict__ acc, int sync,
-                                                       float* __restrict__ dgamma, float* __restrict__ dbeta) {
-  bn_stats_body<MODE>(y, d, out, M, C, save_mean, save_rstd, acc, blockIdx.x, blockIdx.y, sync, dgamma, dbeta);
-}
 // one BatchNorm layer of one branch: everything the statistics / apply kernels of either direction need
 struct BnJob {
   const float* y;       // pre-BatchNorm Linear output
@@ -201,7 +182,7 @@ struct BnMulti {
   int sync;
 };
 template <int MODE>
-__global__ __launch_bounds__(256) void bn_stats_multi_kernel(BnMulti m) {
+__global__ __launch_bounds__(256) void bn_stats_kernel(BnMulti m) {
   const BnJob& j = m.j[blockIdx.z];
   bn_stats_body<MODE>(j.y, j.d, j.out, m.M, m.C, j.save_mean, j.save_rstd, j.acc, blockIdx.x, blockIdx.y, m.sync, j.dgamma, j.dbeta);
 }
@@ -209,7 +190,7 @@ __device__ __forceinline__ void bn_apply_fwd_body(const float* __restrict__ y, i
                                                   const float* __restrict__ gamma, const float* __restrict__ beta,
                                                   float* __restrict__ run_mean, float* __restrict__ run_var, float momentum,
                                                   float* __restrict__ out, float* __restrict__ save_mean, float* __restrict__ save_rstd,
-                                                  unsigned bx, int sync = 0) {
+                                                  unsigned bx, int sync) {
   const size_t i = (size_t)bx * 256 + threadIdx.x;
   const double Mg = sync ? acc[kBnCount] : (double)M;  // rows behind the sums: this rank's, or every rank's
   if (i < (size_t)M * C) {
@@ -229,15 +210,7 @@ __device__ __forceinline__ void bn_apply_fwd_body(const float* __restrict__ y, i
       run_var[c] = (1.f - momentum) * run_var[c] + momentum * (float)(var * (Mg / fmax(Mg - 1.0, 1.0)));
     }
 }
-__global__ __launch_bounds__(256) void bn_apply_fwd_kernel(const float* __restrict__ y, int M, int C,
-                                                           const double* __restrict__ acc,
-                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                           float* __restrict__ run_mean, float* __restrict__ run_var,
-                                                           float momentum, float* __restrict__ out,
-                                                           float* __restrict__ save_mean, float* __restrict__ save_rstd, int sync) {
-  bn_apply_fwd_body(y, M, C, acc, gamma, beta, run_mean, run_var, momentum, out, save_mean, save_rstd, blockIdx.x, sync);
-}
-__global__ __launch_bounds__(256) void bn_apply_fwd_multi_kernel(BnMulti m) {
+__global__ __launch_bounds__(256) void bn_apply_fwd_kernel(BnMulti m) {
   const BnJob& j = m.j[blockIdx.y];
   bn_apply_fwd_body(j.y, m.M, m.C, j.acc, j.gamma, j.beta, j.run_mean, j.run_var, m.momentum, j.out, j.save_mean, j.save_rstd, blockIdx.x, m.sync);
 }
@@ -245,7 +218,7 @@ __global__ __launch_bounds__(256) void bn_apply_fwd_multi_kernel(BnMulti m) {
 __device__ __forceinline__ void bn_apply_bwd_body(float* __restrict__ d, const float* __restrict__ out, const float* __restrict__ y, int M,
                                                   int C, const double* __restrict__ acc, const float* __restrict__ gamma,
                                                   const float* __restrict__ save_mean, const float* __restrict__ save_rstd,
-                                                  float* __restrict__ dgamma, float* __restrict__ dbeta, unsigned bx, int sync = 0) {
+                                                  float* __restrict__ dgamma, float* __restrict__ dbeta, unsigned bx, int sync) {
   const size_t i = (size_t)bx * 256 + threadIdx.x;
   if (i < (size_t)M * C) {
     const int c = (int)(i % C);
@@ -260,15 +233,7 @@ __device__ __forceinline__ void bn_apply_bwd_body(float* __restrict__ d, const f
       unsafeAtomicAdd(dbeta + c, (float)acc[c]);
     }
 }
-__global__ __launch_bounds__(256) void bn_apply_bwd_kernel(float* __restrict__ d, const float* __restrict__ out,
-                                                           const float* __restrict__ y, int M, int C,
-                                                           const double* __restrict__ acc, const float* __restrict__ gamma,
-                                                           const float* __restrict__ save_mean,
-                                                           const float* __restrict__ save_rstd, float* __restrict__ dgamma,
-                                                           float* __restrict__ dbeta, int sync) {
-  bn_apply_bwd_body(d, out, y, M, C, acc, gamma, save_mean, save_rstd, dgamma, dbeta, blockIdx.x, sync);
-}
-__global__ __launch_bounds__(256) void bn_apply_bwd_multi_kernel(BnMulti m) {
+__global__ __launch_bounds__(256) void bn_apply_bwd_kernel(BnMulti m) {
   const BnJob& j = m.j[blockIdx.y];
   bn_apply_bwd_body(j.d, j.out, j.y, m.M, m.C, j.acc, j.gamma, j.save_mean, j.save_rstd, j.dgamma, j.dbeta, blockIdx.x, m.sync);
 }
@@ -297,10 +262,6 @@ __device__ __forceinline__ void rownorm_fwd_body(const float* __restrict__ src, 
   *reinterpret_cast<float4*>(dst + (size_t)m * ldd + lane * 4) = y;
   if (lane == 0) save_n[m] = n;
 }
-__global__ void rownorm_fwd_kernel(const float* __restrict__ src, const int32_t* __restrict__ idx, int M,
-                                   float* __restrict__ dst, int ldd, float* __restrict__ save_n) {
-  rownorm_fwd_body(src, idx, M, dst, ldd, save_n, blockIdx.x);
-}
 struct RownormJob {
   const float* src;      // forward: rows to normalise (or the embedding table); backward: dy (a slot of dcat)
   const int32_t* idx;    // forward: embedding lookup or nullptr
@@ -312,7 +273,7 @@ struct RownormMulti {
   RownormJob j[kMaxJobs];
   int M, ld;
 };
-__global__ void rownorm_fwd_multi_kernel(RownormMulti m) {
+__global__ void rownorm_fwd_kernel(RownormMulti m) {
   const RownormJob& j = m.j[blockIdx.y];
   rownorm_fwd_body(j.src, j.idx, m.M, j.dst, m.ld, j.save_n, blockIdx.x);
 }
@@ -325,11 +286,7 @@ __device__ __forceinline__ void rownorm_bwd_body(const float* __restrict__ dy, c
   const float4 yy = *reinterpret_cast<const float4*>(y + (size_t)m * ld + lane * 4);
   *reinterpret_cast<float4*>(dx + (size_t)m * kTD + lane * 4) = norm_bwd(d, yy, save_n[m]);
 }
-__global__ void rownorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y, int ld,
-                                   const float* __restrict__ save_n, int M, float* __restrict__ dx) {
-  rownorm_bwd_body(dy, y, ld, save_n, M, dx, blockIdx.x);
-}
-__global__ void rownorm_bwd_multi_kernel(RownormMulti m) {
+__global__ void rownorm_bwd_kernel(RownormMulti m) {
   const RownormJob& j = m.j[blockIdx.y];
   rownorm_bwd_body(j.src, j.y, m.ld, j.save_n, m.M, j.dst, blockIdx.x);
 }
@@ -370,10 +327,6 @@ __device__ __forceinline__ void embed_sum_body(const float* __restrict__ g, cons
     unsafeAtomicAdd(t + 0, a.x); unsafeAtomicAdd(t + 1, a.y); unsafeAtomicAdd(t + 2, a.z); unsafeAtomicAdd(t + 3, a.w);
   }
 }
-__global__ __launch_bounds__(256) void embed_sum_kernel(const float* __restrict__ g, const int32_t* __restrict__ idx, int M,
-                                                        float* __restrict__ dtable) {
-  embed_sum_body(g, idx, M, dtable, blockIdx.x, blockIdx.y);
-}
 struct EmbedSumMulti {
   const float* g[kMaxJobs];
   const int32_t* idx[kMaxJobs];
@@ -381,7 +334,7 @@ struct EmbedSumMulti {
   int rows[kMaxJobs];  // table rows (row 0 = padding_idx receives nothing); grid.x = max(rows) - 1
   int M;
 };
-__global__ __launch_bounds__(256) void embed_sum_multi_kernel(EmbedSumMulti m) {
+__global__ __launch_bounds__(256) void embed_sum_kernel(EmbedSumMulti m) {
   const int j = blockIdx.z;
   if ((int)blockIdx.x + 1 >= m.rows[j]) return;  // (workgroup-uniform: the barriers inside are not reached by anyone)
   embed_sum_body(m.g[j], m.idx[j], m.M, m.dtable[j], blockIdx.x, blockIdx.y);
