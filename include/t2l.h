@@ -588,6 +588,11 @@ int t2l_adam_state(t2l_ctx* ctx, int32_t set, float* m, float* v, int64_t* step,
  *                     one XCD owns (search_xcd_qgroups) are contiguous, so every 128-byte line of the record buffer is written by one
  *                     XCD's L2. 0 = round 6's epilogue and record order (A/B; both arms run in one process). Applies to merged records
  *                     (the layout) with search_tile_sel = 1 (the epilogue). Ids and float64 scores are bit-identical either way.
+ * "search_rerank_form" (default 1): the re-rank of merged records of the tile-local selection. 1 = the merge of a query's (at most 16)
+ *                     records reduces over the one 16-lane row that holds them and pops only the six key slots, and the twelve rows of
+ *                     the early certificate are fetched in one round trip. 0 = round 7's form (whole-wave merge; A/B, both arms run in
+ *                     one process). Other candidate forms (plain lists, records of search_tile_sel = 0) always take form 0. Ids, float64
+ *                     scores, flags and counters are bit-identical either way.
  * "search_pair_ll"    (default 6): per-lane list length of the paired scan (5: experiment, halves the certificate's margin).
  * "profile_events"    (default 0): n >= 1 records hipEvents around every n-th launch of each kernel (t2l_kernel_stats);
  *                     two records cost ~6 us of queue time per bracketed kernel, which matters beside a 30 us kernel.

@@ -626,6 +626,15 @@ int t2l_set_option(t2l_ctx* ctx, const char* name, double value) {
   } else if (!strcmp(name, "search_epilogue")) {
     if (value != 0 && value != 1) return fail(ctx, T2L_EINVAL, "search_epilogue: 0 (round 6's epilogue and record layout) or 1 (default)");
     ctx->knobs.search_epilogue = (int)value;
+  } else if (!strcmp(name, "search_rerank_form")) {
+#ifdef T2L_RERANK_PARTS  // dev build: 2 = the row-local merge alone, 3 = the one round trip alone
+    if (value == 2 || value == 3) {
+      ctx->knobs.rerank_form = (int)value;
+      return T2L_OK;
+    }
+#endif
+    if (value != 0 && value != 1) return fail(ctx, T2L_EINVAL, "search_rerank_form: 0 (round 7's re-rank of merged records) or 1 (default: row-local merge, one gather round trip)");
+    ctx->knobs.rerank_form = (int)value;
   } else if (!strcmp(name, "search_pair_ll")) {
     if (value != 5 && value != 6) return fail(ctx, T2L_EINVAL, "search_pair_ll must be 5 or 6");
     ctx->knobs.pair_ll = (int)value;

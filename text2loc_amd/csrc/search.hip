@@ -31,6 +31,7 @@
 #include <limits.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "t2l_internal.h"
 #include "search_dev.h"
@@ -368,6 +369,12 @@ __global__ __launch_bounds__(256, 1) void scanh_kernel(const uint4* __restrict__
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float v) {
   return __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), CTRL, 0xF, 0xF, true));
+}
+
+// f(B), f(B + 1), ... with the index as a compile-time constant
+template <int B, class F, int... I>
+__device__ __forceinline__ void const_for(F&& f, std::integer_sequence<int, I...>) {
+  (f(std::integral_constant<int, B + I>{}), ...);
 }
 
 // The arguments of the re-rank's per-query routine (rerank_query), as one struct.
@@ -962,13 +969,49 @@ __device__ __forceinline__ void publish_report(int32_t* fb_count, int32_t* host_
   }
 }
 
+// dev builds (make stamps, tools/rerank_stamps.py): every query wave of the re-rank leaves the 100 MHz clock at seven points of its
+// path and where it ran — [0] wave start, [1] records in registers, [2] up-front merge done, [3] first early row arrived, [4] last
+// early row arrived, [5] early result stored (0: the query took the long path), [6] wave end, [7] HW_ID | XCC_ID << 32 (which SIMD of
+// which CU: the four waves of a SIMD come from four workgroups). `dep` ties a stamp to the value whose arrival it marks (the compiler
+// places the wait for it in front); the scheduling fences keep each phase's instructions on its own side of the stamp.
+#ifdef T2L_STAMPS
+constexpr int kRrStampWaves = 4096, kRrStampSlots = 8;
+__device__ long long g_rr_stamps[kRrStampWaves * kRrStampSlots];
+#define T2L_RR_STAMP(k, dep)                                                                \
+  {                                                                                         \
+    __builtin_amdgcn_sched_barrier(0);                                                      \
+    asm volatile("" ::"v"(dep));                                                            \
+    const long long t_ = __builtin_amdgcn_s_memrealtime();                                  \
+    if (lane == 0 && qid < kRrStampWaves) g_rr_stamps[qid * kRrStampSlots + (k)] = t_;      \
+    __builtin_amdgcn_sched_barrier(0);                                                      \
+  }
+#else
+#define T2L_RR_STAMP(k, dep)
+#endif
+
 // One query, one wave. `my_wg_flag`: this wave's slot of the workgroup's "rank exactly" flags; `wr_buf`: kWideCap ints of LDS.
 // MG: the lists are the MERGED records of scanp_kernel<..., MERGE> — `parts` = physical splits, one record of kMergedLL floats per
 // (query, split): 7 keys whose low bits are code << 2 | source list, then the bound on every key the record does not list (what
 // `lane_floor` is for a plain list: the floor of a full list).
-template <int LL, int L, bool MG = false>
+// FORM = 1 (option "search_rerank_form", the default; six-key records of the tile-local selection only — a.rec6): the records sit in
+// lanes 0..15, ONE DPP row, and every other lane holds a list of -inf, so
+//   - the merge's arg-max, `floor_max` and the B1 maximum reduce over that row (four DPP steps + a v_readfirstlane) instead of the whole
+//     wave (+ two permlane swaps with their copies and hazard nops), the round's (key, part) go to lane r by v_writelane, and the
+//     winner pops the six slots that can hold keys. Lanes 16..63 compare equal to the maximum only when it is -inf, and lane 0 does
+//     then too: "lowest part among equal keys" is still the ballot's lowest set bit, exactly as in FORM = 0;
+//   - the loads of all twelve early rows are issued together, right behind the merge and before the first wait on any of them (48
+//     landing registers beside the float64 query: it fits the 128 once the certificate's scale is scalar).
+// Nothing else differs: `lst`, keys, rows, sums, flags and counters come out bit for bit as under FORM = 0, which stays compiled for
+// the A/B and serves every other candidate form.
+template <int LL, int L, bool MG = false, int FORM = 0>
 __device__ __forceinline__ void rerank_query(const RerankArgs& a, const int qid, const int lane, int* my_wg_flag, int* wr_buf) {
   static_assert(!MG || LL == kMergedLL, "merged records are 8 floats");
+  static_assert(FORM == 0 || (MG && L == 16), "the row-local form is written for merged records, 16 candidates");
+  // (dev builds with -DT2L_RERANK_PARTS also compile FORM = 2, the row-local merge alone, and FORM = 3, the one round trip alone, and
+  // the option accepts them: each part measured by itself against FORM = 0, tools/rerank_form_probe.py --parts)
+  constexpr bool RLM = FORM == 1 || FORM == 2;  // the row-local merge
+  constexpr bool RLG = FORM == 1 || FORM == 3;  // the twelve early loads in one round trip (+ the scalar certificate scale that makes room)
+  constexpr int kKeys = RLM ? LL - 2 : LL;  // list slots that can hold keys (FORM = 1: B1 and B2 are taken out below)
   const float* __restrict__ db = a.db;
   const float* __restrict__ q = a.q;
   const int Q = a.Q, K = a.K, parts = a.parts, code_bits = a.code_bits, row_offset = a.row_offset, half_mode = a.half_mode;
@@ -1025,13 +1068,19 @@ __device__ __forceinline__ void rerank_query(const RerankArgs& a, const int qid,
   // (8 rows) of the record's four lanes — everything those lanes dropped past their lists lies at or below it, and all of it except
   // the other 5 rows of B1's own group at or below the record's bound B2 (slot 7, `lane_floor`)
   float b1 = T2L_NEG_INF;
-  if constexpr (MG) {
+  if constexpr (RLM) {  // (the host picks this form for rec6 records only)
+    b1 = lst[LL - 2];
+    lst[LL - 2] = T2L_NEG_INF;
+  } else if constexpr (MG) {
     if (a.rec6) {
       b1 = lst[LL - 2];
       lst[LL - 2] = T2L_NEG_INF;
     }
   }
-  const float floor_max = wave_max_f32(fmaxf(lane_floor, b1), pinf);
+  float floor_max;
+  T2L_RR_STAMP(1, lst[0]);
+  if constexpr (RLM) floor_max = row0_max_f32(fmaxf(lane_floor, b1));
+  else floor_max = wave_max_f32(fmaxf(lane_floor, b1), pinf);
   // the query as float64, 16 elements per lane (dims 64 i + 4 seg + e: each load instruction reads 256 contiguous bytes
   // per 16-lane row); the lanes of one row cover the 256 dims, the 4 rows hold copies
   const int seg = lane & 15;
@@ -1057,51 +1106,31 @@ __device__ __forceinline__ void rerank_query(const RerankArgs& a, const int qid,
   // the last four rounds run only on the way into the full path, in front of the four rows they select.
   float my_key = T2L_NEG_INF;
   int my_part = 0;
-  auto merge_round = [&](int r) {
-    const float bk = wave_max_f32(lst[0], pinf);
+  auto merge_round = [&](auto r_tag) {
+    constexpr int r = decltype(r_tag)::value;
+    float bk;
+    if constexpr (RLM) bk = row0_max_f32(lst[0]);  // (scalar: rows 1..3 hold -inf only)
+    else bk = wave_max_f32(lst[0], pinf);
     const unsigned long long who = __ballot(lst[0] == bk);
-    const int bl = __ffsll((long long)who) - 1;  // equal keys: lowest part first
-    if (lane == r) {
+    // equal keys: lowest part first (FORM = 1: never empty — some lane of row 0 holds the row's maximum, and keys are never NaN: the
+    // scan builds them from finite-or-inf scores with the code in the low mantissa bits, so a head always equals its own maximum)
+    const int bl = RLM ? __builtin_ctzll(who) : __ffsll((long long)who) - 1;
+    if constexpr (RLM) {  // (both values are scalars; a scalar that is the DATA of a v_writelane needs no wait states)
+      asm("v_writelane_b32 %0, %1, %2" : "+v"(my_key) : "s"(bk), "n"(r));
+      asm("v_writelane_b32 %0, %1, %2" : "+v"(my_part) : "s"(bl), "n"(r));
+    } else if (lane == r) {
       my_key = bk;
       my_part = bl;
     }
     const bool pop = lane == bl;  // the winner pops its head (register shift, no memory)
 #pragma unroll
-    for (int i = 0; i < LL - 1; ++i) lst[i] = pop ? lst[i + 1] : lst[i];
-    lst[LL - 1] = pop ? T2L_NEG_INF : lst[LL - 1];
+    for (int i = 0; i < kKeys - 1; ++i) lst[i] = pop ? lst[i + 1] : lst[i];
+    lst[kKeys - 1] = pop ? T2L_NEG_INF : lst[kKeys - 1];
   };
-#pragma unroll
-  for (int r = 0; r < L - 4; ++r) merge_round(r);
+  const_for<0>(merge_round, std::make_integer_sequence<int, L - 4>{});
   int my_row = (lane < L - 4 && my_key != T2L_NEG_INF) ? krow(my_key, my_part) : INT_MAX;
+  T2L_RR_STAMP(2, my_row);
 
-  // ---- certificate scale (keys of the f16 scan are true scores times 2^(shift_db + shift_q): undo that exactly)
-  double kscale = 1.0;
-  bool representable = true;
-  {
-    const float m = row16_max_f32(q_absmax);
-    int sq, sd;
-    representable = half_shift_of(m, sq);
-    representable = half_shift_of(db_norm_max[1], sd) && representable;
-    if (half_mode) {
-      kscale = ldexp(1.0, -(sq + sd));
-    } else {
-      // the f32 / split-bf16 scans multiply the raw values: their relative error bound needs every product that matters
-      // to stay a normal f32, which magnitudes within 2^-40 .. 2^40 guarantee with a wide margin
-      representable = representable && abs(sq - 14) <= 40 && abs(sd - 14) <= 40;
-    }
-  }
-
-  // ---- float64 re-score of the selected rows (products of f32 values are exact in f64). Four rows at a time, one per
-  // 16-lane row of the wave: a lane multiplies 16 elements and the row sum is 4 DPP steps (a whole-wave reduction per
-  // row costs 3x the VALU). The re-rank is bound by these gathers (16 KB per query from L2 / Infinity Cache: skipping four
-  // of the sixteen rows was measured at -1.3 us per step), so they come in two stages: the best L - 4 candidates first, and
-  // when the certificate already holds against the (L-4)-th merged key — 9 queries in 10 — the last four rows are never
-  // fetched: everything not re-scored, those four included, has a key at or below that bound.
-  double qn = 0.0;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) qn += qd[i] * qd[i];
-  qn = row16_sum_f64(qn);
-  const double eps32 = (double)eps_rel * sqrt(qn) * (double)(*db_norm_max);
   constexpr int LA = L - 4;
   float4 rows[L / 4][4];
   auto gather = [&](int p) {
@@ -1121,6 +1150,58 @@ __device__ __forceinline__ void rerank_query(const RerankArgs& a, const int qid,
 #pragma unroll
     for (int i = 0; i < 4; ++i) rows[p][i] = rp[16 * i];
   };
+  // FORM = 1: the twelve early rows leave NOW, all of them before anything waits for one (the fence keeps the scheduler from sinking a
+  // group's loads behind the scoring of the group before it, which it does to save landing registers); the certificate's scale and
+  // the query's norm below are computed while they travel
+  if constexpr (RLG) {
+#pragma unroll
+    for (int p = 0; p < L / 4 - 1; ++p) gather(p);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+
+  // ---- certificate scale (keys of the f16 scan are true scores times 2^(shift_db + shift_q): undo that exactly)
+  double kscale = 1.0;
+  int kexp = 0;  // FORM = 1: kscale = 2^kexp, kept as its (scalar) exponent and rebuilt at each use — a register pair the early path cannot spare
+  bool representable = true;
+  {
+    float m = row16_max_f32(q_absmax);
+    // (every 16-lane row holds a copy of the query: the maximum is wave-uniform, and as a scalar it takes the scale's arithmetic — and
+    // the register pair of kscale — off the vector side)
+    if constexpr (RLG) m = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(m)));
+    int sq, sd;
+    representable = half_shift_of(m, sq);
+    representable = half_shift_of(db_norm_max[1], sd) && representable;
+    if (half_mode) {
+      if constexpr (RLG) kexp = -(sq + sd);
+      else kscale = ldexp(1.0, -(sq + sd));
+    } else {
+      // the f32 / split-bf16 scans multiply the raw values: their relative error bound needs every product that matters
+      // to stay a normal f32, which magnitudes within 2^-40 .. 2^40 guarantee with a wide margin
+      representable = representable && abs(sq - 14) <= 40 && abs(sd - 14) <= 40;
+    }
+  }
+
+  auto kscale_of = [&]() {
+    if constexpr (RLG) {
+      int e = kexp;
+      asm volatile("" : "+s"(e));  // (opaque: one v_ldexp_f64 where it is used, not a value held from here on)
+      return ldexp(1.0, e);
+    } else {
+      return kscale;
+    }
+  };
+  // ---- float64 re-score of the selected rows (products of f32 values are exact in f64). Four rows at a time, one per
+  // 16-lane row of the wave: a lane multiplies 16 elements and the row sum is 4 DPP steps (a whole-wave reduction per
+  // row costs 3x the VALU). These gathers are the largest single part of the re-rank (16 KB per query from L2 / Infinity Cache:
+  // skipping four of the sixteen rows was measured at -1.3 us per step; the serial instruction chain in front of and behind them is the
+  // rest), so they come in two stages: the best L - 4 candidates first, and
+  // when the certificate already holds against the (L-4)-th merged key — 9 queries in 10 — the last four rows are never
+  // fetched: everything not re-scored, those four included, has a key at or below that bound.
+  double qn = 0.0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) qn += qd[i] * qd[i];
+  qn = row16_sum_f64(qn);
+  const double eps32 = (double)eps_rel * sqrt(qn) * (double)(*db_norm_max);
   double my_d = -__builtin_inf();
   auto score = [&](int p) {
     double d0 = 0.0, d1 = 0.0;
@@ -1159,10 +1240,16 @@ __device__ __forceinline__ void rerank_query(const RerankArgs& a, const int qid,
       if (out_score) out_score[(size_t)qid * K + r] = my_d;
     }
   };
+  if constexpr (!RLG) {
 #pragma unroll
-  for (int p = 0; p < L / 4 - 1; ++p) gather(p);
+    for (int p = 0; p < L / 4 - 1; ++p) gather(p);
+  }
+  T2L_RR_STAMP(3, rows[0][0].x);
 #pragma unroll
-  for (int p = 0; p < L / 4 - 1; ++p) score(p);
+  for (int p = 0; p < L / 4 - 1; ++p) {
+    if (p == L / 4 - 2) T2L_RR_STAMP(4, rows[L / 4 - 2][3].w);
+    score(p);
+  }
   bool early = false;
   if (K <= LA && representable && eps_rel_probe == 0.f) {  // (the stand-in probe counts against the full certificate below)
     const float gA = fmaxf(__uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_key), LA - 1)), floor_max);
@@ -1172,7 +1259,7 @@ __device__ __forceinline__ void rerank_query(const RerankArgs& a, const int qid,
       const unsigned long long kthA = __ballot(validA && rA == K - 1);
       if (kthA != 0ull) {
         const double dK = __shfl(my_d, __ffsll((long long)kthA) - 1);
-        if (dK > (double)gA * kscale + key_slack(gA, slack_bits, eps32, kscale)) {  // wave-uniform
+        if (dK > (double)gA * kscale_of() + key_slack(gA, slack_bits, eps32, kscale_of())) {  // wave-uniform
           emit(validA, rA);
           early = true;
         }
@@ -1181,9 +1268,9 @@ __device__ __forceinline__ void rerank_query(const RerankArgs& a, const int qid,
   }
   if (early) {
     if (lane == 0) flags[qid] = 0;
+    T2L_RR_STAMP(5, lane);
   } else {
-#pragma unroll
-  for (int r = L - 4; r < L; ++r) merge_round(r);
+  const_for<L - 4>(merge_round, std::make_integer_sequence<int, 4>{});
   if (lane >= L - 4 && lane < L && my_key != T2L_NEG_INF) my_row = krow(my_key, my_part);
   // every row that is NOT re-scored has key <= g: kept rows lie at or below the L-th merged key, rows dropped inside a
   // lane at or below that lane's floor (with LL == L a floor above the L-th key cannot happen; with LL < L it can)
@@ -1202,13 +1289,15 @@ __device__ __forceinline__ void rerank_query(const RerankArgs& a, const int qid,
   if constexpr (MG && L == 16) {
     int d_lane = -1;
     // (cheap gate first: a B1 can only be what stands in the way when it lies above every B2 and above the L-th merged key)
-    const float b1_max = a.rec6 ? wave_max_f32(b1, pinf) : T2L_NEG_INF;
+    float b1_max = T2L_NEG_INF;
+    if constexpr (RLM) b1_max = row0_max_f32(b1);
+    else if (a.rec6) b1_max = wave_max_f32(b1, pinf);
     if (b1_max != T2L_NEG_INF && b1_max > fmaxf(key_L, wave_max_f32(lane_floor, pinf)) && representable && K <= LA && eps_rel_probe == 0.f) {
       const int rA = rank_among(std::integral_constant<int, LA>{});
       const unsigned long long kthA = __ballot(lane < LA && my_row != INT_MAX && rA == K - 1);
       if (kthA != 0ull) {
         const double dKA = __shfl(my_d, __ffsll((long long)kthA) - 1);
-        const double tA = (dKA - 2.0 * (fabs(dKA) * ldexp(1.0, slack_bits - 22) + eps32)) / kscale;
+        const double tA = (dKA - 2.0 * (fabs(dKA) * ldexp(1.0, slack_bits - 22) + eps32)) / kscale_of();
         float thrA = (float)tA;
         if ((double)thrA > tA) thrA = __uint_as_float(__float_as_uint(thrA) + (thrA > 0.f ? -1 : 1));  // round down
         if (fabs(tA) < 3.0e38) {
@@ -1260,7 +1349,7 @@ __device__ __forceinline__ void rerank_query(const RerankArgs& a, const int qid,
       const float g2 = fmaxf(key_L, wave_max_f32(lane == d_lane ? lane_floor : fmaxf(lane_floor, b1), pinf));
       if (kth2 != 0ull) {
         const double dK2 = __shfl(my_d, __ffsll((long long)kth2) - 1);
-        if (dK2 > (double)g2 * kscale + key_slack(g2, slack_bits, eps32, kscale)) {
+        if (dK2 > (double)g2 * kscale_of() + key_slack(g2, slack_bits, eps32, kscale_of())) {
           emit(valid2, rank2);
           if (lane == 0) {
             flags[qid] = 0;
@@ -1291,16 +1380,16 @@ __device__ __forceinline__ void rerank_query(const RerankArgs& a, const int qid,
     const unsigned long long kth = __ballot(valid && rank == K - 1);
     if (K <= L && kth != 0ull) {
       const double dK = __shfl(my_d, __ffsll((long long)kth) - 1);
-      certified = dK > (double)g * kscale + key_slack(g, slack_bits, eps32, kscale);
+      certified = dK > (double)g * kscale_of() + key_slack(g, slack_bits, eps32, kscale_of());
       // while the split-bf16 scan stands in for the f16 scan on a DB that overwhelmed its certificate, count the queries
       // the f16 error band would still flag: the host goes back to the f16 scan when they become rare
       if (eps_rel_probe > 0.f && lane == 0 &&
-          !(dK > (double)g * kscale + key_slack(g, slack_bits, (double)eps_rel_probe * sqrt(qn) * (double)(*db_norm_max), kscale)))
+          !(dK > (double)g * kscale_of() + key_slack(g, slack_bits, (double)eps_rel_probe * sqrt(qn) * (double)(*db_norm_max), kscale_of())))
         atomicAdd(&fb_count[kCntProbe], 1);
       // a row with key k has score <= k*kscale + |k|*kscale*2^(cb-22) + eps32; with S = 2*(|dK|*2^(cb-22) + eps32) every
       // key below (dK - S)/kscale is therefore below the current K-th best score dK (and the final K-th is >= dK)
       const double S = 2.0 * (fabs(dK) * ldexp(1.0, slack_bits - 22) + eps32);
-      const double t = (dK - S) / kscale;
+      const double t = (dK - S) / kscale_of();
       thr = (float)t;
       if ((double)thr > t) thr = __uint_as_float(__float_as_uint(thr) + (thr > 0.f ? -1 : 1));  // round down
       if (!(fabs(t) < 3.0e38)) thr = T2L_NEG_INF;
@@ -1516,7 +1605,7 @@ __device__ __forceinline__ void rerank_query(const RerankArgs& a, const int qid,
 // rerank (stage 1): one wave per query, 4 queries per 256-thread block.
 // ------------------------------------------------------------------------------------------------
 // LL = length of the per-lane lists the scan wrote, L = rows re-scored per query (LL <= L).
-template <int LL, int L, bool MG = false>
+template <int LL, int L, bool MG = false, int FORM = 0>
 // (the merged-record form holds its group-repair path inside 128 VGPRs: four waves per SIMD = all 4,096 query waves of a batch resident at once;
 //  the other forms keep the occupancy the compiler finds — L = 32 takes 139 VGPRs and would spill under the bound)
 __global__ __launch_bounds__(256, (MG ? 4 : 1)) void rerank_kernel(const float* __restrict__ db, const float* __restrict__ q, int Q,
@@ -1541,7 +1630,17 @@ __global__ __launch_bounds__(256, (MG ? 4 : 1)) void rerank_kernel(const float* 
     fb_count[kCntStatMode] = stat_mode;  // 0: not an f16-certificate count, 1: f16 scan, 2: split-bf16 stand-in probing for it
   }
   __syncthreads();
-  if (qid < Q) rerank_query<LL, L, MG>(a, qid, lane, &wg_flag[threadIdx.x >> 6], wide_rows[threadIdx.x >> 6]);
+#ifdef T2L_STAMPS
+  if (qid < Q && qid < kRrStampWaves && lane == 0) {
+    long long* st = g_rr_stamps + qid * kRrStampSlots;
+    st[0] = __builtin_amdgcn_s_memrealtime();
+    st[5] = 0;
+    st[7] = (long long)(unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4) |          // HW_REG_HW_ID: wave, SIMD, CU, SH, SE
+            ((long long)(unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);  // HW_REG_XCC_ID
+  }
+#endif
+  if (qid < Q) rerank_query<LL, L, MG, FORM>(a, qid, lane, &wg_flag[threadIdx.x >> 6], wide_rows[threadIdx.x >> 6]);
+  T2L_RR_STAMP(6, lane);
   // ---- unsettled queries of this workgroup: the exact float64 ranking, all 4 waves on one query at a time
   __syncthreads();
 #pragma unroll 1
@@ -1733,7 +1832,14 @@ static int launch_search(t2l_ctx* ctx, const SegmentPlan& p, const float* db, co
     case RerankKernel::kLists8: rerank(&rerank_kernel<8, 16>); break;
     case RerankKernel::kLists16: rerank(&rerank_kernel<16, 16>); break;
     case RerankKernel::kLists32: rerank(&rerank_kernel<32, 32>); break;
-    case RerankKernel::kRecords: rerank(&rerank_kernel<kMergedLL, 16, true>); break;
+    case RerankKernel::kRecords:
+      if (p.rerank_form == 1) rerank(&rerank_kernel<kMergedLL, 16, true, 1>);
+#ifdef T2L_RERANK_PARTS
+      else if (p.rerank_form == 2) rerank(&rerank_kernel<kMergedLL, 16, true, 2>);
+      else if (p.rerank_form == 3) rerank(&rerank_kernel<kMergedLL, 16, true, 3>);
+#endif
+      else rerank(&rerank_kernel<kMergedLL, 16, true>);
+      break;
   }
   T2L_HIP(ctx, hipGetLastError());
   if (p.defer) return exact_stage_impl(ctx, db, n_rows, row_offset, q, Q, K, out_idx, out_score, s);
@@ -1908,3 +2014,14 @@ int search_lanes_impl(t2l_ctx* ctx, const float* q, int Q, int K, int32_t* out_i
 }
 
 }  // namespace t2l
+
+#ifdef T2L_STAMPS
+// dev builds only: the re-rank's per-wave stamps of the last call (synchronises); out: n_waves x 8 values
+extern "C" int t2l_debug_rerank_stamps(t2l_ctx* ctx, long long* out, int n_waves) {
+  if (!ctx || !out || n_waves < 0 || n_waves > t2l::kRrStampWaves) return T2L_EINVAL;
+  if (hipSetDevice(ctx->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return T2L_EHIP;
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(t2l::g_rr_stamps), (size_t)n_waves * t2l::kRrStampSlots * sizeof(long long)) == hipSuccess
+             ? T2L_OK
+             : T2L_EHIP;
+}
+#endif

@@ -517,6 +517,21 @@ __device__ __forceinline__ float row16_max_f32(float v) {
   return v;
 }
 
+// ... the row's maximum as four one-instruction DPP steps (wave_max_f32 without its two cross-row swaps)
+__device__ __forceinline__ float row16_max_dpp_f32(float x) {
+  float v;  // (the first step out of place: the caller's value stays where it is, no copy)
+  asm volatile("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "=v"(v) : "v"(x));
+  T2L_MAX_DPP(v, "quad_perm:[2,3,0,1]");
+  T2L_MAX_DPP(v, "row_half_mirror");
+  T2L_MAX_DPP(v, "row_mirror");
+  return v;
+}
+// The maximum over lanes 0..15 as a wave-uniform (scalar) value. For a wave whose lanes 16..63 hold nothing above that maximum
+// (the re-rank of merged records: at most 16 records, -inf lists elsewhere) this is wave_max_f32 at less than half its VALU.
+__device__ __forceinline__ float row0_max_f32(float v) {
+  return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(row16_max_dpp_f32(v))));
+}
+
 // The f16 plane deals rows to tiles STRIDED (round 6): inside a segment of the database (kSegmentRows rows; the whole shard when
 // it is smaller) with F = rows / 32 full tiles, slot j of tile t < F holds row j F + t; the partial last tile (rows % 32 of them)
 // stays blocked. Neighbouring rows — overlapping KITTI360Pose cells that share most of their objects, i.e. a query's best rows come

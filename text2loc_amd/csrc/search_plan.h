@@ -40,6 +40,8 @@ struct SearchKnobs {
   int xcd_qgroups = 4;      // [search_xcd_qgroups] paired scan: query-block groups per XCD rectangle (1 = every XCD sees all queries and 1/8 of the splits;
                             // 4 = a quarter of the queries and half of the splits: -1.3 us of scan span at Q = 4096 x N = 11,259, measured)
   int profile_rerank = 1;   // [profile_rerank] 0: sampled launches bracket the scan only (an event pair costs the stream ~6 us per kernel)
+  int rerank_form = 1;      // [search_rerank_form] re-rank of merged records of the tile-local selection: 1 = the merge reduces over the 16-lane row that holds
+                            // the records and all twelve early row fetches are issued before the first wait (rerank_kernel<..., FORM = 1>), 0 = round 7's form
 };
 
 // ---- the report card ---------------------------------------------------------------------------
@@ -184,6 +186,7 @@ struct SegmentPlan {
   RerankKernel rerank;
   int rerank_parts, rec6, rerank_slot_bits, wide_cap;
   bool time_rerank;   // sampled launches bracket the re-rank too
+  int rerank_form;    // kRecords: rerank_kernel<kMergedLL, 16, true, rerank_form> (1 needs the six-key records of the tile-local selection: rec6)
 };
 
 inline SegmentPlan plan_segment(const SearchKnobs& k, int eff_mode, bool merge_live, bool heavy, int Q, int K, int rows) {
@@ -283,6 +286,7 @@ inline SegmentPlan plan_segment(const SearchKnobs& k, int eff_mode, bool merge_l
     p.rerank_parts = nsplit / 2;
     p.rec6 = k.search_tile_sel ? 1 : 0;
     p.rerank_slot_bits = p.slot_bits;
+    p.rerank_form = p.rec6 ? k.rerank_form : 0;
   } else {
     p.rerank = LL == 5 ? RerankKernel::kLists5 : LL == 6 ? RerankKernel::kLists6 : LL == 8 ? RerankKernel::kLists8
              : LL == 16 ? RerankKernel::kLists16 : RerankKernel::kLists32;
