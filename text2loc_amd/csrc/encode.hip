@@ -31,19 +31,10 @@
 #include <string.h>
 
 #include "t2l_internal.h"
-#include "mfma_h3.h"
 #include "encode_shared.h"
 
 #ifndef T2L_ENC_UNROLL
 #define T2L_ENC_UNROLL 4
-#endif
-// dev experiment (make exp_enc EXPFLAG=-DT2L_EXP_HOTW, tools/hotw_probe.py; WRONG results, timing only): every weight fragment of a tile
-// comes from its first two k-steps — the packed-weight stream out of the L2 disappears, the instruction stream stays. How much of the
-// fused kernels' time is that stream?
-#ifdef T2L_EXP_HOTW
-#define T2L_WSTEP(s) ((s) & 1)
-#else
-#define T2L_WSTEP(s) (s)
 #endif
 
 namespace t2l {
@@ -86,14 +77,15 @@ __device__ __forceinline__ void gemm32(const float* __restrict__ A, int lda, int
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+      const int row = acc_row(r, half);
       epi(0, r, row, nt0 * 32 + col, acc0[r]);
       epi(1, r, row, nt1 * 32 + col, acc1[r]);
     }
   }
 }
 
-// F.normalize over 256 columns of `rows` rows starting at buf (row stride ld); rows >= nvalid are zeroed.
+// F.normalize over 256 columns of `rows` rows starting at buf (row stride ld); rows >= nvalid are zeroed. (One float4 per lane at the
+// published width; normalize_rows_d of encode_shaped.hip and f_normalize_rows of fine.hip differ in access width and in what they zero.)
 __device__ __forceinline__ void normalize_rows(float* buf, int ld, int nvalid, int wave, int lane) {
   for (int i = wave; i < kSP; i += 4) {
     float4* p = reinterpret_cast<float4*>(buf + i * ld) + lane;
@@ -185,50 +177,6 @@ struct PlaneGeo {
 };
 constexpr int kLdP = PlaneGeo<kD>::kLd;   // the published width (the two-cell cell encoder below)
 constexpr int kPlane = PlaneGeo<kD>::kSize;
-typedef _Float16 ti_f16x4 __attribute__((ext_vector_type(4)));
-typedef float ti_f32x4 __attribute__((ext_vector_type(4)));
-
-template <bool SG>
-__device__ __forceinline__ HFrag plane_frag(const _Float16* __restrict__ hi, const _Float16* __restrict__ lo, int off) {
-  HFrag f;
-  f.hi = *reinterpret_cast<const h3_f16x8*>(hi + off);
-  if constexpr (SG) f.lo = f.hi;
-  else f.lo = *reinterpret_cast<const h3_f16x8*>(lo + off);
-  return f;
-}
-template <bool SG>
-__device__ __forceinline__ void plane_put4(_Float16* __restrict__ hi, _Float16* __restrict__ lo, int off, ti_f32x4 v) {
-  h3_f16x4 h, l;
-  h3_split4(h3_f32x4{v[0], v[1], v[2], v[3]}, h, l);
-  *reinterpret_cast<h3_f16x4*>(hi + off) = h;
-  // (the plain-f16 option drops the low halves from the PRODUCTS only: the stored activations — the residual stream — keep both)
-  *reinterpret_cast<h3_f16x4*>(lo + off) = l;
-}
-template <bool SG>
-__device__ __forceinline__ ti_f32x4 plane_get4(const _Float16* __restrict__ hi, const _Float16* __restrict__ lo, int off) {
-  const h3_f32x4 v = h3_join4(*reinterpret_cast<const h3_f16x4*>(hi + off), *reinterpret_cast<const h3_f16x4*>(lo + off));
-  return ti_f32x4{v[0], v[1], v[2], v[3]};
-}
-
-// The weight fragments of one tile pass, STEPS k-steps, through a register ring D steps deep: the fragment of step s + D is requested
-// when step s is consumed, sched_barriers keep the requests where they are written (the compiler otherwise sinks every load to its use:
-// one L2 round trip of ~1 us in front of every 0.1 us of MFMAs). body(s, fragment). Measured on t2l_text_inter (4,096 x 6): no ring
-// 0.218 ms; D = 2 / 3 / 4 / 5 / 6 / 8 / 12 / 16: 0.169 / 0.168 / 0.169 / 0.170 / 0.173 / 0.174 / 0.181 / 0.186 ms — what matters is that the
-// next requests are out before the MFMAs start, not how many (deeper rings cost registers and scalar spills).
-template <bool SG, int STEPS, int D, typename F>
-__device__ __forceinline__ void stream_weights(const uint4* __restrict__ wp, F&& body) {
-  HFrag ring[D];
-#pragma unroll
-  for (int i = 0; i < D; ++i) ring[i] = load_h1<SG>(wp + T2L_WSTEP(i) * 128);
-#pragma unroll
-  for (int s = 0; s < STEPS; ++s) {
-    const HFrag wf = ring[s % D];
-    if (s + D < STEPS) ring[s % D] = load_h1<SG>(wp + T2L_WSTEP(s + D) * 128);
-    __builtin_amdgcn_sched_barrier(0);
-    body(s, wf);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
 
 template <int D = kD>
 __device__ __forceinline__ _Float16* pl_xh(_Float16* base, int t) { return base + (size_t)(4 * t + 0) * PlaneGeo<D>::kSize; }
@@ -268,7 +216,7 @@ __device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int col = lane & 31, half = lane >> 5;
   auto watch = [&](float v) { bad = bad || !(fabsf(v) < kSplitF16Safe); };
-  auto watch4 = [&](ti_f32x4 v) { watch(v[0]); watch(v[1]); watch(v[2]); watch(v[3]); };
+  auto watch4 = [&](h3_f32x4 v) { watch(v[0]); watch(v[1]); watch(v[2]); watch(v[3]); };
   (void)watch4;
 #pragma unroll
   for (int pp = 0; pp < PPW; ++pp) {  // ---- self-attention: wave -> (tile t, head h); q^T, k^T, v from the tile's planes, scores / softmax / O^T from registers
@@ -289,12 +237,14 @@ __device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& 
         hqk[j] = W.in_hp + ((size_t)(TPH * h + j) * HS * 64 + lane) * 2;
         hqk[TPH + j] = W.in_hp + ((size_t)(DT + TPH * h + j) * HS * 64 + lane) * 2;
       }
-      {  // 2 TPH weight tiles per step through a ring kQkRing steps deep (8 VGPRs per tile and step)
+      {  // 2 TPH weight tiles per step through a ring kQkRing steps deep (8 VGPRs per tile and step). This ring and v's below are not
+         // stream_weights (several tiles per step) and not fp_attention's ring (fine.hip: opaque pointer increments, depth T2L_ATT_RING):
+         // merging any two would change one kernel's schedule.
         constexpr int RD = kQkRing;
         HFrag ring[RD][2 * TPH];
         auto loadqk = [&](int s, HFrag (&f)[2 * TPH]) {
 #pragma unroll
-          for (int e = 0; e < 2 * TPH; ++e) f[e] = load_h1<SG>(hqk[e] + T2L_WSTEP(s) * 128);
+          for (int e = 0; e < 2 * TPH; ++e) f[e] = load_h1<SG>(hqk[e] + T2L_HOT(s) * 128);
         };
 #pragma unroll
         for (int i = 0; i < RD; ++i) loadqk(i, ring[i]);
@@ -315,7 +265,7 @@ __device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& 
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int f = (r & 3) + 8 * (r >> 2) + 4 * half;
+        const int f = acc_row(r, half);
 #pragma unroll
         for (int j = 0; j < TPH; ++j) qT[j][r] += ib[h * HD + 32 * j + f];
 #pragma unroll
@@ -352,7 +302,7 @@ __device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& 
       float m = -__builtin_inff();
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int j = (r & 3) + 8 * (r >> 2) + 4 * half;
+        const int j = acc_row(r, half);
         st[r] = mask(col, j) ? st[r] * kScale : -__builtin_inff();
         m = fmaxf(m, st[r]);
       }
@@ -381,7 +331,7 @@ __device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& 
 #pragma unroll
         for (int i = 0; i < RD; ++i)
 #pragma unroll
-          for (int j = 0; j < TPH; ++j) ring[i][j] = load_h1<SG>(hv[j] + T2L_WSTEP(i) * 128);
+          for (int j = 0; j < TPH; ++j) ring[i][j] = load_h1<SG>(hv[j] + T2L_HOT(i) * 128);
 #pragma unroll
         for (int s = 0; s < HS; ++s) {
           HFrag f[TPH];
@@ -389,7 +339,7 @@ __device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& 
           for (int j = 0; j < TPH; ++j) f[j] = ring[s % RD][j];
           if (s + RD < HS) {
 #pragma unroll
-            for (int j = 0; j < TPH; ++j) ring[s % RD][j] = load_h1<SG>(hv[j] + T2L_WSTEP(s + RD) * 128);
+            for (int j = 0; j < TPH; ++j) ring[s % RD][j] = load_h1<SG>(hv[j] + T2L_HOT(s + RD) * 128);
           }
           __builtin_amdgcn_sched_barrier(0);
           const HFrag xf = plane_frag<SG>(xh, xl, 8 * s);
@@ -434,16 +384,16 @@ __device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& 
       }
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        ti_f32x4 ov[TPH];
+        h3_f32x4 ov[TPH];
 #pragma unroll
-        for (int j = 0; j < TPH; ++j) ov[j] = ti_f32x4{o[j][4 * q], o[j][4 * q + 1], o[j][4 * q + 2], o[j][4 * q + 3]};
+        for (int j = 0; j < TPH; ++j) ov[j] = h3_f32x4{o[j][4 * q], o[j][4 * q + 1], o[j][4 * q + 2], o[j][4 * q + 3]};
         if constexpr (WATCH) {
 #pragma unroll
           for (int j = 0; j < TPH; ++j) watch4(ov[j]);
         }
 #pragma unroll
         for (int j = 0; j < TPH; ++j)
-          plane_put4<SG>(pl_bh<D>(base, t), pl_bl<D>(base, t), col * LDP + h * HD + 32 * j + 8 * q + 4 * half, ov[j]);
+          plane_put4(pl_bh<D>(base, t), pl_bl<D>(base, t), col * LDP + h * HD + 32 * j + 8 * q + 4 * half, ov[j]);
       }
     }
   }
@@ -455,9 +405,11 @@ __device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& 
   // each): the row sums meet in `lnred` behind two light barriers (mean, then centred squares: the two-pass form), the values stay in
   // registers in between and the normalised rows are written once. As a separate pass (8 rows per wave, two full-wave reductions per
   // row) the two LayerNorms of a layer were ~700 VALU instructions per wave and a plane round trip each.
+  // Stands beside fine.hip's fp_epilogue_ln, not merged with it: the waves' row sums are added one after the other here, pairwise
+  // there — another association, other bits.
   auto resid_ln = [&](const f32x16 (&acc)[2], const float* __restrict__ bias, const float* __restrict__ g, const float* __restrict__ be,
                       bool to_f32) {
-    ti_f32x4 v[2][4];
+    h3_f32x4 v[2][4];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       float sm = 0.f;
@@ -465,8 +417,8 @@ __device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& 
       for (int q = 0; q < 4; ++q) {
         const int f0 = 32 * wave + 8 * q + 4 * half;
         const float4 bb = *reinterpret_cast<const float4*>(bias + f0);
-        v[t][q] = plane_get4<SG>(pl_xh<D>(base, t), pl_xl<D>(base, t), col * LDP + f0) +
-                  ti_f32x4{acc[t][4 * q] + bb.x, acc[t][4 * q + 1] + bb.y, acc[t][4 * q + 2] + bb.z, acc[t][4 * q + 3] + bb.w};
+        v[t][q] = plane_get4(pl_xh<D>(base, t), pl_xl<D>(base, t), col * LDP + f0) +
+                  h3_f32x4{acc[t][4 * q] + bb.x, acc[t][4 * q + 1] + bb.y, acc[t][4 * q + 2] + bb.z, acc[t][4 * q + 3] + bb.w};
         sm += (v[t][q][0] + v[t][q][1]) + (v[t][q][2] + v[t][q][3]);
       }
       sm += __shfl_xor(sm, 32);
@@ -500,13 +452,13 @@ __device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& 
       for (int q = 0; q < 4; ++q) {
         const int f0 = 32 * wave + 8 * q + 4 * half;
         const float4 gg = *reinterpret_cast<const float4*>(g + f0), bb = *reinterpret_cast<const float4*>(be + f0);
-        const ti_f32x4 o = {v[t][q][0] * inv * gg.x + bb.x, v[t][q][1] * inv * gg.y + bb.y, v[t][q][2] * inv * gg.z + bb.z,
+        const h3_f32x4 o = {v[t][q][0] * inv * gg.x + bb.x, v[t][q][1] * inv * gg.y + bb.y, v[t][q][2] * inv * gg.z + bb.z,
                             v[t][q][3] * inv * gg.w + bb.w};
         if (to_f32) {  // (the last LayerNorm: the tile's B planes become one f32 [32][D + 4] tile for the epilogue)
-          *reinterpret_cast<ti_f32x4*>(reinterpret_cast<float*>(pl_bh<D>(base, t)) + col * LDX + f0) = o;
+          *reinterpret_cast<h3_f32x4*>(reinterpret_cast<float*>(pl_bh<D>(base, t)) + col * LDX + f0) = o;
         } else {
           if constexpr (WATCH) watch4(o);
-          plane_put4<SG>(pl_xh<D>(base, t), pl_xl<D>(base, t), col * LDP + f0, o);
+          plane_put4(pl_xh<D>(base, t), pl_xl<D>(base, t), col * LDP + f0, o);
         }
       }
     }
@@ -554,10 +506,10 @@ __device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& 
         for (int q = 0; q < 4; ++q) {
           const int u0 = 8 * q + 4 * half;
           const float4 bb = *reinterpret_cast<const float4*>(b1 + tf * 32 + u0);
-          const ti_f32x4 v = {fmaxf(hT[t][4 * q] + bb.x, 0.f), fmaxf(hT[t][4 * q + 1] + bb.y, 0.f), fmaxf(hT[t][4 * q + 2] + bb.z, 0.f),
+          const h3_f32x4 v = {fmaxf(hT[t][4 * q] + bb.x, 0.f), fmaxf(hT[t][4 * q + 1] + bb.y, 0.f), fmaxf(hT[t][4 * q + 2] + bb.z, 0.f),
                               fmaxf(hT[t][4 * q + 3] + bb.w, 0.f)};
           if constexpr (WATCH) watch4(v);
-          plane_put4<SG>(pl_bh<D>(base, t), pl_bl<D>(base, t), col * LDP + cbase + u0, v);
+          plane_put4(pl_bh<D>(base, t), pl_bl<D>(base, t), col * LDP + cbase + u0, v);
         }
       __syncthreads();
       const uint4* w2 = W.ff2_hp + (((size_t)wave * FS + HS * c) * 64 + lane) * 2;
@@ -591,7 +543,7 @@ __global__ __launch_bounds__(2 * D, D == 256 ? 1 : 2) void text_inter_fused2_ker
   const int d0 = blockIdx.x * 2 * dpt;
   bool bad = false;
   auto watch = [&](float v) { bad = bad || !(fabsf(v) < kSplitF16Safe); };
-  auto watch4 = [&](ti_f32x4 v) { watch(v[0]); watch(v[1]); watch(v[2]); watch(v[3]); };
+  auto watch4 = [&](h3_f32x4 v) { watch(v[0]); watch(v[1]); watch(v[2]); watch(v[3]); };
   int nd[2], rows[2];
   nd[0] = min(dpt, n_desc - d0);
   nd[1] = max(0, min(dpt, n_desc - d0 - dpt));
@@ -602,13 +554,13 @@ __global__ __launch_bounds__(2 * D, D == 256 ? 1 : 2) void text_inter_fused2_ker
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const int r = (wave * 8 + i) * RPI + (lane >> LLPR), t = r >> 5, lr = r & 31, cl = lane & (LPR - 1);
-    ti_f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    h3_f32x4 v = {0.f, 0.f, 0.f, 0.f};
     if (lr < rows[t]) {
       const float4 g = reinterpret_cast<const float4*>(sent + ((size_t)(d0 + t * dpt) * S + lr) * D)[cl];
-      v = ti_f32x4{g.x, g.y, g.z, g.w};
+      v = h3_f32x4{g.x, g.y, g.z, g.w};
     }
     watch4(v);
-    plane_put4<SG>(XH(t), XL(t), lr * LDP + 4 * cl, v);
+    plane_put4(XH(t), XL(t), lr * LDP + 4 * cl, v);
   }
   if (tid < kSP) grp[tid] = tid / S;
   __syncthreads();
@@ -670,18 +622,18 @@ __global__ __launch_bounds__(512, 1) void encode_cells2_kernel(EncParams P, t2l_
   auto tile_to_planes = [&]() {  // the group's normalised f32 slot (X region) -> its cell's B planes
     for (int i = lw; i < kSP; i += 4) {
       const float4 g = *(reinterpret_cast<const float4*>(xf32 + i * kLdX) + lane);
-      plane_put4<SG>(pl_bh(base, tc), pl_bl(base, tc), i * kLdP + 4 * lane, ti_f32x4{g.x, g.y, g.z, g.w});
+      plane_put4(pl_bh(base, tc), pl_bl(base, tc), i * kLdP + 4 * lane, h3_f32x4{g.x, g.y, g.z, g.w});
     }
   };
   auto table_to_planes = [&](const float* __restrict__ tab, const int32_t* __restrict__ idx, int n_tab) {
     for (int o = lw; o < kSP; o += 4) {
-      ti_f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      h3_f32x4 v = {0.f, 0.f, 0.f, 0.f};
       if (o < my_nobj) {
         const int ci = min(max(idx[my_obj0 + o], 0), n_tab - 1);
         const float4 g = reinterpret_cast<const float4*>(tab + (size_t)ci * kD)[lane];
-        v = ti_f32x4{g.x, g.y, g.z, g.w};
+        v = h3_f32x4{g.x, g.y, g.z, g.w};
       }
-      plane_put4<SG>(pl_bh(base, tc), pl_bl(base, tc), o * kLdP + 4 * lane, v);
+      plane_put4(pl_bh(base, tc), pl_bl(base, tc), o * kLdP + 4 * lane, v);
     }
   };
   auto merge_slot = [&]() {  // both cells' B planes hold slot `slot`: keep += Wmerge[:, 256 slot : 256 slot + 256] @ slot^T
@@ -743,20 +695,20 @@ __global__ __launch_bounds__(512, 1) void encode_cells2_kernel(EncParams P, t2l_
       for (int q = 0; q < 4; ++q) {
         const int f0 = 32 * wave + 8 * q + 4 * half;
         const float4 bb = *reinterpret_cast<const float4*>(mb + f0);
-        const ti_f32x4 v = {fmaxf(keep[t][4 * q] + bb.x, 0.f), fmaxf(keep[t][4 * q + 1] + bb.y, 0.f), fmaxf(keep[t][4 * q + 2] + bb.z, 0.f),
+        const h3_f32x4 v = {fmaxf(keep[t][4 * q] + bb.x, 0.f), fmaxf(keep[t][4 * q + 1] + bb.y, 0.f), fmaxf(keep[t][4 * q + 2] + bb.z, 0.f),
                             fmaxf(keep[t][4 * q + 3] + bb.w, 0.f)};
-        plane_put4<SG>(pl_xh(base, t), pl_xl(base, t), col * kLdP + f0, v);
+        plane_put4(pl_xh(base, t), pl_xl(base, t), col * kLdP + f0, v);
       }
   }
   __syncthreads();
 #pragma unroll
   for (int i = 0; i < 8; ++i) {  // F.normalize per object row; rows >= nobj are the zero pad slots (cell_retrieval.py:85,92)
     const int r = wave * 8 + i, t = r >> 5, lr = r & 31, off = lr * kLdP + 4 * lane;
-    ti_f32x4 v = plane_get4<SG>(pl_xh(base, t), pl_xl(base, t), off);
+    h3_f32x4 v = plane_get4(pl_xh(base, t), pl_xl(base, t), off);
     const float ss = wave_sum(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]);
     const float inv = lr < nobj[t] ? 1.f / fmaxf(sqrtf(ss), 1e-12f) : 0.f;
     v *= inv;
-    plane_put4<SG>(pl_xh(base, t), pl_xl(base, t), off, v);
+    plane_put4(pl_xh(base, t), pl_xl(base, t), off, v);
   }
   __syncthreads();
   bool bad = false;
@@ -855,27 +807,9 @@ bool fold(t2l_ctx* ctx, const WMap& m, const std::string& lin, const std::string
     const float* rm = need(ctx, m, bn + ".running_mean", out, rc);
     const float* rv = need(ctx, m, bn + ".running_var", out, rc);
     if (!g || !be || !rm || !rv) return false;
-    for (int o = 0; o < out; ++o) {
-      // float32 arithmetic in the order torch evaluates eval-mode BN: (x - mean) / sqrt(var + eps) * w + b
-      const float s = g[o] / sqrtf(rv[o] + 1e-5f);
-      for (int k = 0; k < in; ++k) (*W)[(size_t)o * in + k] *= s;
-      (*b)[o] = ((*b)[o] - rm[o]) * s + be[o];
-    }
+    fold_batchnorm(W->data(), b->data(), out, in, g, be, rm, rv);
   }
   return true;
-}
-
-// W [N][K] row-major -> [N/32][K/8][64 lanes][4]: lane (col, half) of step q holds W[nt*32+col][half*K/2 + 4q .. +3]
-std::vector<float> pack(const std::vector<float>& W, int N, int K) {
-  std::vector<float> p((size_t)N * K);
-  const int qn = K / 8;
-  for (int nt = 0; nt < N / 32; ++nt)
-    for (int q = 0; q < qn; ++q)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int e = 0; e < 4; ++e)
-          p[(((size_t)nt * qn + q) * 64 + lane) * 4 + e] =
-              W[(size_t)(nt * 32 + (lane & 31)) * K + (lane >> 5) * (K / 2) + 4 * q + e];
-  return p;
 }
 
 std::vector<float> pack_h(const std::vector<float>& W, int N, int K) { return pack_split_f16(W.data(), nullptr, N, K, K); }
@@ -903,7 +837,7 @@ bool add_small(t2l_ctx* ctx, const WMap& m, const std::string& pre, int in, int 
   if (!fold(ctx, m, pre + ".1.0", pre + ".1.1", D, 64, &W2, &b2, rc)) return false;
   off->w1 = blob->add(W1);
   off->b1 = blob->add(b1);
-  off->w2p = blob->add(pack(W2, D, 64));
+  off->w2p = blob->add(pack_half_split(W2, nullptr, D, 64, 64));
   off->b2 = blob->add(b2);
   return true;
 }
@@ -948,7 +882,7 @@ int load_weights_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const t2l_m
     } else {
       std::vector<float> W, b;
       if (!fold(ctx, m, oe + "mlp_pointnet.0.0", oe + "mlp_pointnet.0.1", D, 256, &W, &b, &rc)) return rc;  // features2 is 256 wide at every D
-      pn_wp = blob.add(pack(W, D, 256));
+      pn_wp = blob.add(pack_half_split(W, nullptr, D, 256, 256));
       pn_b = blob.add(b);
       w_absmax = fmaxf(w_absmax, max_abs(W.data(), W.size()));
     }
@@ -974,7 +908,7 @@ int load_weights_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const t2l_m
         std::vector<float> Ws((size_t)D * D);
         for (int n = 0; n < D; ++n)
           for (int k = 0; k < D; ++k) Ws[(size_t)n * D + k] = W[(size_t)n * nfeat * D + sl * D + k];
-        const std::vector<float> ps = pack(Ws, D, D);
+        const std::vector<float> ps = pack_half_split(Ws, nullptr, D, D, D);
         all.insert(all.end(), ps.begin(), ps.end());
         const std::vector<float> ph = pack_h(Ws, D, D);
         all_h.insert(all_h.end(), ph.begin(), ph.end());
@@ -997,7 +931,7 @@ int load_weights_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const t2l_m
       const float* b = need(ctx, m, p + bn, out, &rc);
       if (!W || !b) return false;
       const std::vector<float> Wv(W, W + (size_t)out * in);
-      *wp = blob.add(pack(Wv, out, in));
+      *wp = blob.add(pack_half_split(Wv, nullptr, out, in, in));
       *hp = blob.add(pack_h(Wv, out, in));
       *bo = blob.add(std::vector<float>(b, b + out));
       w_absmax = fmaxf(w_absmax, max_abs(W, Wv.size()));

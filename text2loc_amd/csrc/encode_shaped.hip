@@ -45,7 +45,6 @@
 #include <string>
 
 #include "t2l_internal.h"
-#include "mfma_h3.h"
 #include "encode_shared.h"
 
 #ifndef T2L_ENC_UNROLL
@@ -60,9 +59,10 @@ constexpr int kLdHid = 64 + 4;     // hidden layer of the small MLPs
 
 // acc[t] += X W_t^T (WA = false: this lane's LDS row half is the A operand) or W_t X^T (WA = true: the packed weight tile is the
 // A operand, the product comes out transposed), over `khalf` k-values per lane half starting at per-half offset `koff` of a
-// matrix packed for K = ktot. H = 0: f32 packing (pack) on v_mfma_f32_32x32x2_f32; 1: split-f16 fragments (pack_h), three
+// matrix packed for K = ktot. H = 0: f32 packing (pack_half_split) on v_mfma_f32_32x32x2_f32; 1: split-f16 fragments (pack_h), three
 // products; 2: plain f16, the high halves of the same fragments, one product. AHEAD (the f16 forms at D = 256, where a SIMD
-// holds two waves): the NT weight fragments of the next k-step are in flight behind the MFMAs of the current one.
+// holds two waves): the NT weight fragments of the next k-step are in flight behind the MFMAs of the current one. Not stream_weights
+// (tile_blocks.h): one step ahead for NT tiles at once, the activation split on the fly, a partly unrolled loop — another schedule.
 template <int H, bool WA, int NT, bool AHEAD = false>
 __device__ __forceinline__ void mm_tiles(const float* __restrict__ arow, int khalf, const float4* __restrict__ wp,
                                          const uint4* __restrict__ hp, int ktot, int koff, const int (&tile)[NT],
@@ -137,10 +137,8 @@ __device__ __forceinline__ void zero_tiles(f32x16 (&acc)[NT]) {
     for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 }
 
-// accumulator register r of lane half `half` holds row (r & 3) + 8 (r >> 2) + 4 half of a 32 x 32 tile (column = lane & 31)
-__device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
-// F.normalize over the D columns of the 32 rows at buf (row stride ld); rows >= nvalid are zeroed
+// F.normalize over the D columns of the 32 rows at buf (row stride ld); rows >= nvalid are zeroed. (D / 64 scalars per lane, the
+// zeroing folded into the store; encode.hip's normalize_rows reads float4 at 256 only, fine.hip's f_normalize_rows zeroes nothing.)
 template <int D>
 __device__ __forceinline__ void normalize_rows_d(float* buf, int ld, int nvalid, int wave, int lane) {
   constexpr int EL = D / 64;

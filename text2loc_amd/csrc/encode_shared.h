@@ -3,10 +3,9 @@
 // workgroup at every compiled shape).
 #pragma once
 #include "t2l_internal.h"
+#include "tile_blocks.h"
 
 namespace t2l {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr float kNumMean = 1826.6844940968194f;  // models/object_encoder.py:43
 constexpr float kNumStd = 2516.8905096993817f;   // models/object_encoder.py:44
@@ -49,29 +48,6 @@ struct EncoderWeights {
   int embed_dim = kD, object_size = kS, num_heads = 4;
   bool published() const { return embed_dim == kD && object_size == kS && num_heads == 4; }
 };
-
-// ---- device helpers ----------------------------------------------------------------------------
-// all-reduce sum over the 64 lanes on the VALU (DPP + v_permlane swaps): __shfl_xor lowers to ds_bpermute_b32 — six dependent
-// LDS round trips per sum
-template <int CTRL>
-__device__ __forceinline__ float wave_sum_dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float wave_sum(float v) {
-  v += wave_sum_dpp<0xB1>(v);   // quad_perm [1,0,3,2]
-  v += wave_sum_dpp<0x4E>(v);   // quad_perm [2,3,0,1]
-  v += wave_sum_dpp<0x141>(v);  // row_half_mirror
-  v += wave_sum_dpp<0x140>(v);  // row_mirror
-  {
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  }
-  {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  }
-  return v;
-}
 
 // the one-cell kernel (encode_shaped.hip): true when (embed_dim, num_heads, object_size) is a compiled shape
 bool shape_is_compiled(int embed_dim, int num_heads, int object_size);

@@ -15,8 +15,7 @@
 #include <string.h>
 
 #include "t2l_internal.h"
-#include "mfma32.h"
-#include "mfma_h3.h"
+#include "tile_blocks.h"
 
 namespace t2l {
 
@@ -81,7 +80,8 @@ static int fupload(t2l_ctx* ctx, FineWeights* W, const std::vector<float>& v, co
   *dst = d;
   return T2L_OK;
 }
-// Linear [N,K] (+ optional eval BatchNorm `bn` folded in) -> transposed [K][N] + bias
+// Linear [N,K] (+ optional eval BatchNorm `bn` folded in) -> transposed [K][N] + bias. Not fold_batchnorm (mfma32.h): the bias here is
+// b*s + (be - rm*s), there (b - rm)*s + be — the two differ in the last bit, and the loaded weights are part of what the goldens pin.
 static int flinear(t2l_ctx* ctx, FineWeights* W, const WMap& m, const std::string& lin, const std::string& bn, int K, int N, FLinear* out) {
   const float *w = fget(m, lin + ".weight", (int64_t)N * K), *b = fget(m, lin + ".bias", N);
   if (!w || !b) return fail(ctx, T2L_EINVAL, "t2l_fine_load_weights: missing or mis-shaped '" + lin + "'");
@@ -251,34 +251,14 @@ __device__ void f_linear(const float* __restrict__ x, int ldx, int T8, const FLi
   }
 }
 
-// all-reduce sum over the 64 lanes on the VALU (DPP + v_permlane swaps): __shfl_xor lowers to ds_bpermute_b32, six dependent
-// LDS round trips per sum, and LayerNorm needs two sums per token row
-template <int CTRL>
-__device__ __forceinline__ float f_dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float f_wsum(float v) {
-  v += f_dpp<0xB1>(v);   // quad_perm [1,0,3,2]
-  v += f_dpp<0x4E>(v);   // quad_perm [2,3,0,1]
-  v += f_dpp<0x141>(v);  // row_half_mirror
-  v += f_dpp<0x140>(v);  // row_mirror
-  {
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  }
-  {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  }
-  return v;
-}
-// rows t < T of x (128 wide): x = normalize(x) (F.normalize, eps 1e-12); one wave per row
+// rows t < T of x (128 wide): x = normalize(x) (F.normalize, eps 1e-12); one wave per row. (Not the cell encoder's normalize_rows /
+// normalize_rows_d: scalar accesses at a run-time width, a division per element, and no rows to zero.)
 __device__ void f_normalize_rows(float* x, int ld, int T, int width = kFD) {
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (int t = w; t < T; t += 4) {
     float s = 0.f;
     for (int c = lane; c < width; c += 64) s += x[t * ld + c] * x[t * ld + c];
-    const float n = fmaxf(sqrtf(f_wsum(s)), 1e-12f);
+    const float n = fmaxf(sqrtf(wave_sum(s)), 1e-12f);
     for (int c = lane; c < width; c += 64) x[t * ld + c] /= n;
   }
 }
@@ -289,9 +269,9 @@ __device__ void f_ln_rows(float* x, int ld, int T, const float* __restrict__ g, 
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (int t = w; t < T; t += 4) {
     const float v0 = x[t * ld + lane], v1 = x[t * ld + lane + 64];
-    const float mu = f_wsum(v0 + v1) * (1.f / kFD);
+    const float mu = wave_sum(v0 + v1) * (1.f / kFD);
     const float d0 = v0 - mu, d1 = v1 - mu;
-    const float rstd = 1.0f / sqrtf(f_wsum(d0 * d0 + d1 * d1) * (1.f / kFD) + 1e-5f);
+    const float rstd = 1.0f / sqrtf(wave_sum(d0 * d0 + d1 * d1) * (1.f / kFD) + 1e-5f);
     x[t * ld + lane] = d0 * rstd * g[lane] + b[lane];
     x[t * ld + lane + 64] = d1 * rstd * g[lane + 64] + b[lane + 64];
   }
@@ -303,6 +283,31 @@ struct TileGroups {
   int shift, count, rows, base;
 };
 
+// The group-masked softmax over a score tile S^T in accumulator layout (lane: query i = col, keys j = acc_row(r, half)): a query of
+// tile x sees the keys of its own pair's group in tile mem only. st: logits in, unnormalised probabilities out; returns 1 / their sum.
+// any = false (and zeros): a row that is nobody's query (tile padding), or whose pair sits in another mem tile, sees no key at all.
+__device__ __forceinline__ float f_group_softmax(f32x16& st, TileGroups gx, TileGroups gm, int col, int half, bool& any) {
+  const int gi = gx.base + (col >> gx.shift) - gm.base;  // the mem tile's group that holds this query's pair (may be out of the tile)
+  float m = -__builtin_inff();
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int j = acc_row(r, half);
+    const bool ok = (j >> gm.shift) == gi && (j & ((1 << gm.shift) - 1)) < gm.count && j < gm.rows;
+    st[r] = ok ? st[r] * 0.17677669529663687f : -__builtin_inff();  // 1/sqrt(32)
+    m = fmaxf(m, st[r]);
+  }
+  m = fmaxf(m, __shfl_xor(m, 32));
+  any = m > -__builtin_inff();
+  float sum = 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    st[r] = any ? __expf(st[r] - m) : 0.f;
+    sum += st[r];
+  }
+  sum += __shfl_xor(sum, 32);
+  return any ? 1.f / sum : 0.f;
+}
+
 // One attention block of nn.TransformerDecoderLayer for the kPairs pairs of the tile, head h = wave, REGISTERS ONLY:
 // q_h^T (from the x tile) and k_h^T (from the mem tile) are computed transposed (A = packed in_proj rows, B = token rows),
 // v_h straight (A = mem token rows, B = packed rows); in those MFMA output layouts k_h^T / q_h^T are the A / B operands of
@@ -310,7 +315,7 @@ struct TileGroups {
 // Writes o_h (32 rows x 32 columns) into obuf[:, 32 h ..]. x == mem for self-attention.
 // ACC: the output is ADDED to obuf (a query tile whose groups find their keys in different mem tiles attends each mem tile in turn;
 // a query row sees keys in exactly one of them and contributes zeros to the other pass).
-template <int H, bool ACC = false>
+template <bool ACC = false>
 __device__ __forceinline__ void f_attention_regs(const float* __restrict__ x, TileGroups gx, const float* __restrict__ mem, TileGroups gm,
                                                  const FPacked in_proj, float* __restrict__ obuf) {
   const int lane = threadIdx.x & 63, h = threadIdx.x >> 6, col = lane & 31, half = lane >> 5;
@@ -323,21 +328,6 @@ __device__ __forceinline__ void f_attention_regs(const float* __restrict__ x, Ti
   f32x16 qT, kT, v;
 #pragma unroll
   for (int r = 0; r < 16; ++r) qT[r] = kT[r] = v[r] = 0.f;
-  if constexpr (H != 0) {
-    constexpr int HS = kFD / 16;  // 8 steps of 16
-    const uint4* hq = in_proj.h + ((size_t)h * HS * 64 + lane) * 2;
-    const uint4* hk = in_proj.h + ((size_t)(4 + h) * HS * 64 + lane) * 2;
-    const uint4* hv = in_proj.h + ((size_t)(8 + h) * HS * 64 + lane) * 2;
-    // (a pinned ring for these three fragments — as in mm32_dot_h — was measured SLOWER here: 5.98 ms against 5.66 ms, the kernel
-    // runs three workgroups per CU at <= 168 VGPRs)
-#pragma unroll 4
-    for (int st = 0; st < HS; ++st) {
-      const HFrag xf = split_h<H == 2>(xr + 8 * st), mf = split_h<H == 2>(mr + 8 * st);
-      mfma_h3<H == 2>(qT, load_h1<H == 2>(hq + T2L_HOT(st) * 128), xf);
-      mfma_h3<H == 2>(kT, load_h1<H == 2>(hk + T2L_HOT(st) * 128), mf);
-      mfma_h3<H == 2>(v, mf, load_h1<H == 2>(hv + T2L_HOT(st) * 128));
-    }
-  } else {
 #pragma unroll 4
   for (int q = 0; q < QN; ++q) {
     const float4 xv = *reinterpret_cast<const float4*>(xr + 4 * q);
@@ -350,13 +340,12 @@ __device__ __forceinline__ void f_attention_regs(const float* __restrict__ x, Ti
     T2L_F_QKV(x) T2L_F_QKV(y) T2L_F_QKV(z) T2L_F_QKV(w)
 #undef T2L_F_QKV
   }
-  }
   {
     const float* ib = in_proj.b;
     const float bv = ib[2 * kFD + h * kFHd + col];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int f = (r & 3) + 8 * (r >> 2) + 4 * half;
+      const int f = acc_row(r, half);
       qT[r] += ib[h * kFHd + f];
       kT[r] += ib[kFD + h * kFHd + f];
       v[r] += bv;
@@ -367,26 +356,8 @@ __device__ __forceinline__ void f_attention_regs(const float* __restrict__ x, Ti
   for (int r = 0; r < 16; ++r) st[r] = 0.f;
 #pragma unroll
   for (int r = 0; r < 16; ++r) st = __builtin_amdgcn_mfma_f32_32x32x2f32(kT[r], qT[r], st, 0, 0, 0);
-  // lane: query i = col, keys j = (r&3) + 8*(r>>2) + 4*half
-  const int gi = gx.base + (col >> gx.shift) - gm.base;  // the mem tile's group that holds this query's pair (may be out of the tile)
-  float m = -__builtin_inff();
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int j = (r & 3) + 8 * (r >> 2) + 4 * half;
-    const bool ok = (j >> gm.shift) == gi && (j & ((1 << gm.shift) - 1)) < gm.count && j < gm.rows;
-    st[r] = ok ? st[r] * 0.17677669529663687f : -__builtin_inff();  // 1/sqrt(32)
-    m = fmaxf(m, st[r]);
-  }
-  m = fmaxf(m, __shfl_xor(m, 32));
-  const bool any = m > -__builtin_inff();  // rows that are nobody's query (tile padding) see no key at all
-  float sum = 0.f;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    st[r] = any ? __expf(st[r] - m) : 0.f;
-    sum += st[r];
-  }
-  sum += __shfl_xor(sum, 32);
-  const float inv = any ? 1.f / sum : 0.f;
+  bool any;
+  const float inv = f_group_softmax(st, gx, gm, col, half, any);
   f32x16 o;
 #pragma unroll
   for (int r = 0; r < 16; ++r) o[r] = 0.f;
@@ -394,42 +365,41 @@ __device__ __forceinline__ void f_attention_regs(const float* __restrict__ x, Ti
   for (int r = 0; r < 16; ++r) o = __builtin_amdgcn_mfma_f32_32x32x2f32(st[r] * inv, v[r], o, 0, 0, 0);
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    float* dst = obuf + ((r & 3) + 8 * (r >> 2) + 4 * half) * kFS + h * kFHd + col;
+    float* dst = obuf + acc_row(r, half) * kFS + h * kFHd + col;
     if constexpr (ACC) *dst += o[r]; else *dst = o[r];
   }
 }
 
 // x += A @ W^T + b for a 128 -> 128 Linear (out_proj): one 32-column tile per wave
-template <int H>
 __device__ __forceinline__ void f_proj_add(const float* __restrict__ A, const FPacked L, float* __restrict__ x) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, col = lane & 31, half = lane >> 5;
   f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  if constexpr (H != 0) mm32_dot_h<kFD / 16, H == 2>(A + col * kFS + half * (kFD / 2), L.h + ((size_t)w * (kFD / 16) * 64 + lane) * 2, acc);
-  else mm32_dot<kFD / 8>(A + col * kFS + half * (kFD / 2), L.w + (size_t)w * (kFD / 8) * 64 + lane, acc);
+  mm32_dot<kFD / 8>(A + col * kFS + half * (kFD / 2), L.w + (size_t)w * (kFD / 8) * 64 + lane, acc);
   const float bv = L.b[w * 32 + col];
 #pragma unroll
-  for (int r = 0; r < 16; ++r) x[((r & 3) + 8 * (r >> 2) + 4 * half) * kFS + w * 32 + col] += acc[r] + bv;
+  for (int r = 0; r < 16; ++r) x[acc_row(r, half) * kFS + w * 32 + col] += acc[r] + bv;
 }
 
 // nn.TransformerDecoderLayer (post-norm, ReLU, eval, no masks) for the kPairs pairs of a workgroup. x / mem: 32-row token
 // tiles (LDS, stride kFS); buf: one more 32 x 128 tile (attention output, then the feed-forward hidden in four quarters).
 // mem2 != nullptr: the memory is TWO tiles (the hint tile of four pairs attends the pairs' two object tiles).
-template <int H>
+// This f32 tile form (f32 MFMA on f32 token tiles) stands beside the plane form below because it is the fallback: the workgroups
+// the run-time guard turns away, weights that do not bound the activations, and option encoder_f32.
 __device__ void f_decoder(float* x, TileGroups gx, const float* mem, TileGroups gm, const FDecoder D, float* buf,
                           const float* mem2 = nullptr, TileGroups gm2 = TileGroups{0, 0, 0, 0}) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, col = lane & 31, half = lane >> 5;
-  f_attention_regs<H>(x, gx, x, gx, D.sa_in, buf);
+  f_attention_regs(x, gx, x, gx, D.sa_in, buf);
   __syncthreads();
-  f_proj_add<H>(buf, D.sa_out, x);
+  f_proj_add(buf, D.sa_out, x);
   __syncthreads();
   f_ln_rows(x, kFS, gx.rows, D.g1, D.b1);
   __syncthreads();
-  f_attention_regs<H>(x, gx, mem, gm, D.ca_in, buf);
-  if (mem2) f_attention_regs<H, true>(x, gx, mem2, gm2, D.ca_in, buf);  // (same wave, same obuf columns: ordered without a barrier)
+  f_attention_regs(x, gx, mem, gm, D.ca_in, buf);
+  if (mem2) f_attention_regs<true>(x, gx, mem2, gm2, D.ca_in, buf);  // (same wave, same obuf columns: ordered without a barrier)
   __syncthreads();
-  f_proj_add<H>(buf, D.ca_out, x);
+  f_proj_add(buf, D.ca_out, x);
   __syncthreads();
   f_ln_rows(x, kFS, gx.rows, D.g2, D.b2);
   __syncthreads();
@@ -444,21 +414,18 @@ __device__ void f_decoder(float* x, TileGroups gx, const float* mem, TileGroups 
       f32x16 hh;
 #pragma unroll
       for (int r = 0; r < 16; ++r) hh[r] = 0.f;
-      if constexpr (H != 0) mm32_dot_h<kFD / 16, H == 2>(x + col * kFS + half * (kFD / 2), D.l1.h + ((size_t)tile * (kFD / 16) * 64 + lane) * 2, hh);
-      else mm32_dot<kFD / 8>(x + col * kFS + half * (kFD / 2), D.l1.w + (size_t)tile * (kFD / 8) * 64 + lane, hh);
+      mm32_dot<kFD / 8>(x + col * kFS + half * (kFD / 2), D.l1.w + (size_t)tile * (kFD / 8) * 64 + lane, hh);
       if (qtr) __syncthreads();  // every wave has consumed the previous quarter
       const float bv = D.l1.b[tile * 32 + col];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) buf[((r & 3) + 8 * (r >> 2) + 4 * half) * kFS + w * 32 + col] = fmaxf(hh[r] + bv, 0.f);
+      for (int r = 0; r < 16; ++r) buf[acc_row(r, half) * kFS + w * 32 + col] = fmaxf(hh[r] + bv, 0.f);
       __syncthreads();
-      if constexpr (H != 0)  // K = 512: 32 steps per tile, quarter qtr = steps [8 qtr, 8 qtr + 8)
-        mm32_dot_h<kFD / 16, H == 2>(buf + col * kFS + half * (kFD / 2), D.l2.h + (((size_t)w * (4 * kFD / 16) + 8 * qtr) * 64 + lane) * 2, acc);
-      else
-        mm32_dot<kFD / 8>(buf + col * kFS + half * (kFD / 2), D.l2.w + ((size_t)w * (4 * kFD / 8) + 16 * qtr) * 64 + lane, acc);
+      // K = 512: 64 packed steps per tile, quarter qtr = steps [16 qtr, 16 qtr + 16)
+      mm32_dot<kFD / 8>(buf + col * kFS + half * (kFD / 2), D.l2.w + ((size_t)w * (4 * kFD / 8) + 16 * qtr) * 64 + lane, acc);
     }
     const float bv = D.l2.b[w * 32 + col];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) x[((r & 3) + 8 * (r >> 2) + 4 * half) * kFS + w * 32 + col] += acc[r] + bv;
+    for (int r = 0; r < 16; ++r) x[acc_row(r, half) * kFS + w * 32 + col] += acc[r] + bv;
   }
   __syncthreads();
   f_ln_rows(x, kFS, gx.rows, D.g3, D.b3);
@@ -466,10 +433,11 @@ __device__ void f_decoder(float* x, TileGroups gx, const float* mem, TileGroups 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// The same decoder layer on split-f16 PLANES (round 5; the recipe of encode.hip's second form). In the f32-tile form above every
-// product splits its activation operand into hi + lo f16 on the fly — 20 VALU per 3 MFMAs, repeated by each of the four waves
-// (they multiply the same token rows into different output columns) and again for every use of the same rows (q, k, v, four
-// feed-forward quarters): ~2,200 of the ~2,800 VALU instructions a wave issued per tile pass were operand conversions (PMC, round 4:
+// The same decoder layer on split-f16 PLANES (round 5; the recipe of encode.hip's second form). Split-f16 products on the f32 tiles
+// above (round 4; that arm is gone, the tile form is all-f32 now) split every activation operand into hi + lo f16 on the fly — 20
+// VALU per 3 MFMAs, repeated by each of the four waves (they multiply the same token rows into different output columns) and again
+// for every use of the same rows (q, k, v, four feed-forward quarters): ~2,200 of the ~2,800 VALU instructions a wave issued per
+// tile pass were operand conversions (PMC, round 4:
 // 11.4 VALU per MFMA, MFMA pipe busy 0.19 by instruction count). Here every token tile lives in LDS as two f16 planes (hi | lo,
 // rows of 136 halves = 272 B: the 32 lanes of a fragment read are conflict-free 16-byte reads) and
 //  * a product's activation operand is two ds_read_b128, no conversion;
@@ -481,10 +449,6 @@ __device__ void f_decoder(float* x, TileGroups gx, const float* mem, TileGroups 
 constexpr int kLdF = kFD + 8;                    // halves per plane row
 constexpr int kPlaneHalves = 32 * kLdF;          // one plane of a 32-row tile
 constexpr int kTileBytes = 2 * kPlaneHalves * 2; // hi + lo: 17,408 B (the f32 tile of the other form: 16,896 B)
-typedef _Float16 ff_f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 ff_f16x2 __attribute__((ext_vector_type(2)));
-typedef float ff_f32x4 __attribute__((ext_vector_type(4)));
-typedef float ff_f32x2 __attribute__((ext_vector_type(2)));
 struct FP {
   _Float16* hi;
   _Float16* lo;
@@ -495,54 +459,24 @@ __device__ __forceinline__ FP fp_at(void* base) {
   t.lo = t.hi + kPlaneHalves;
   return t;
 }
-template <bool SG>
-__device__ __forceinline__ HFrag fp_frag(const FP t, int off) {
-  HFrag f;
-  f.hi = *reinterpret_cast<const h3_f16x8*>(t.hi + off);
-  if constexpr (SG) f.lo = f.hi;
-  else f.lo = *reinterpret_cast<const h3_f16x8*>(t.lo + off);
-  return f;
-}
-__device__ __forceinline__ void fp_put4(const FP t, int off, ff_f32x4 v) {
-  h3_f16x4 h, l;
-  h3_split4(h3_f32x4{v[0], v[1], v[2], v[3]}, h, l);
-  *reinterpret_cast<h3_f16x4*>(t.hi + off) = h;
-  *reinterpret_cast<h3_f16x4*>(t.lo + off) = l;
-}
-__device__ __forceinline__ ff_f32x4 fp_get4(const FP t, int off) {
-  const h3_f32x4 v = h3_join4(*reinterpret_cast<const h3_f16x4*>(t.hi + off), *reinterpret_cast<const h3_f16x4*>(t.lo + off));
-  return ff_f32x4{v[0], v[1], v[2], v[3]};
-}
 // acc (D[feature][token]) += W tile (STEPS k-steps of packed fragments at wp) x tokens (plane rows, this lane's half row at aoff)
 template <int STEPS, bool SG>
 __device__ __forceinline__ void fp_dot(const FP a, int aoff, const uint4* __restrict__ wp, f32x16& acc) {
   // ring depth 3 (same-box A/B against 2 and 4, round 5: 4.35 / 4.28 / 4.31 ms, plain f16 3.44 / 3.31 / 3.36): the fragments' L2
   // latency is this kernel's largest single cost now
-  constexpr int kRing = 3, D = STEPS < kRing ? STEPS : kRing;
-  HFrag ring[D];
-#pragma unroll
-  for (int i = 0; i < D; ++i) ring[i] = load_h1<SG>(wp + T2L_HOT(i) * 128);
-#pragma unroll
-  for (int st = 0; st < STEPS; ++st) {
-    const HFrag wf = ring[st % D];
-    if (st + D < STEPS) ring[st % D] = load_h1<SG>(wp + T2L_HOT(st + D) * 128);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma_h3<SG>(acc, wf, fp_frag<SG>(a, aoff + 8 * st));
-    __builtin_amdgcn_sched_barrier(0);
-  }
+  stream_weights<SG, STEPS, 3>(wp, [&](int st, const HFrag& wf) { mfma_h3<SG>(acc, wf, plane_frag<SG>(a.hi, a.lo, aoff + 8 * st)); });
 }
-// x[t][32 w + f] (+)= acc[f][t] + bias[32 w + f] for the wave's feature tile; RELU: buf = relu(acc + bias) (no accumulation)
-template <bool ADD, bool RELU>
+// dst[t][dcol0 + f] = acc[f][t] + bias[f] for the wave's feature tile; RELU: relu of it
+template <bool RELU>
 __device__ __forceinline__ void fp_epilogue(const FP dst, int dcol0, const f32x16& acc, const float* __restrict__ bias) {
   const int lane = threadIdx.x & 63, col = lane & 31, half = lane >> 5;
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
     const int f = 8 * g + 4 * half, off = col * kLdF + dcol0 + f;
     const float4 b = *reinterpret_cast<const float4*>(bias + f);
-    ff_f32x4 v = {acc[4 * g] + b.x, acc[4 * g + 1] + b.y, acc[4 * g + 2] + b.z, acc[4 * g + 3] + b.w};
-    if constexpr (RELU) v = ff_f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
-    if constexpr (ADD) v += fp_get4(dst, off);
-    fp_put4(dst, off, v);
+    h3_f32x4 v = {acc[4 * g] + b.x, acc[4 * g + 1] + b.y, acc[4 * g + 2] + b.z, acc[4 * g + 3] + b.w};
+    if constexpr (RELU) v = h3_f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
+    plane_put4(dst.hi, dst.lo, off, v);
   }
 }
 // x[t][32 w + f] = LayerNorm_t(x[t] + acc[.][t] + bias) * g + b — the residual epilogue and the LayerNorm behind it in one go. A lane
@@ -550,16 +484,18 @@ __device__ __forceinline__ void fp_epilogue(const FP dst, int dcol0, const f32x1
 // 1 KB of LDS (two light barriers: mean, then the centred squares — the two-pass form, as nn.LayerNorm), the values stay in
 // registers in between, and the normalised row is written ONCE. (As a separate pass — one wave per row, two full-wave reductions per
 // row — the three LayerNorms were ~960 of a wave's VALU instructions per tile pass and a plane round trip each.)
+// Stands beside planes_layer's resid_ln (encode.hip), not merged with it: the four waves' row sums are added pairwise here, one after
+// the other there — another association, other bits.
 __device__ __forceinline__ void fp_epilogue_ln(const FP x, const f32x16& acc, const float* __restrict__ bias, const float* __restrict__ g,
                                                const float* __restrict__ b, float* __restrict__ red) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, col = lane & 31, half = lane >> 5;
-  ff_f32x4 v[4];
+  h3_f32x4 v[4];
   float s = 0.f;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int f = 32 * w + 8 * q + 4 * half;
     const float4 bb = *reinterpret_cast<const float4*>(bias + f);
-    v[q] = fp_get4(x, col * kLdF + f) + ff_f32x4{acc[4 * q] + bb.x, acc[4 * q + 1] + bb.y, acc[4 * q + 2] + bb.z, acc[4 * q + 3] + bb.w};
+    v[q] = plane_get4(x.hi, x.lo, col * kLdF + f) + h3_f32x4{acc[4 * q] + bb.x, acc[4 * q + 1] + bb.y, acc[4 * q + 2] + bb.z, acc[4 * q + 3] + bb.w};
     s += (v[q][0] + v[q][1]) + (v[q][2] + v[q][3]);
   }
   s += __shfl_xor(s, 32);
@@ -569,7 +505,7 @@ __device__ __forceinline__ void fp_epilogue_ln(const FP x, const f32x16& acc, co
   float qs = 0.f;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    v[q] -= ff_f32x4{mu, mu, mu, mu};
+    v[q] -= h3_f32x4{mu, mu, mu, mu};
     qs += (v[q][0] * v[q][0] + v[q][1] * v[q][1]) + (v[q][2] * v[q][2] + v[q][3] * v[q][3]);
   }
   qs += __shfl_xor(qs, 32);
@@ -580,25 +516,8 @@ __device__ __forceinline__ void fp_epilogue_ln(const FP x, const f32x16& acc, co
   for (int q = 0; q < 4; ++q) {
     const int f = 32 * w + 8 * q + 4 * half;
     const float4 gg = *reinterpret_cast<const float4*>(g + f), bb = *reinterpret_cast<const float4*>(b + f);
-    fp_put4(x, col * kLdF + f, ff_f32x4{v[q][0] * rstd * gg.x + bb.x, v[q][1] * rstd * gg.y + bb.y, v[q][2] * rstd * gg.z + bb.z,
+    plane_put4(x.hi, x.lo, col * kLdF + f, h3_f32x4{v[q][0] * rstd * gg.x + bb.x, v[q][1] * rstd * gg.y + bb.y, v[q][2] * rstd * gg.z + bb.z,
                                          v[q][3] * rstd * gg.w + bb.w});
-  }
-}
-// x[t] = LayerNorm(x[t]) * g + b for t < T (in place; one wave per row, two consecutive features per lane)
-__device__ void fp_ln_rows(const FP x, int T, const float* __restrict__ g, const float* __restrict__ b) {
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const float2 gv = *reinterpret_cast<const float2*>(g + 2 * lane), bv = *reinterpret_cast<const float2*>(b + 2 * lane);
-  for (int t = w; t < T; t += 4) {
-    const int off = t * kLdF + 2 * lane;
-    const h3_f32x2 v = h3_join2(*reinterpret_cast<const h3_f16x2*>(x.hi + off), *reinterpret_cast<const h3_f16x2*>(x.lo + off));
-    const float mu = f_wsum(v[0] + v[1]) * (1.f / kFD);
-    const float d0 = v[0] - mu, d1 = v[1] - mu;
-    const float rstd = 1.0f / sqrtf(f_wsum(d0 * d0 + d1 * d1) * (1.f / kFD) + 1e-5f);
-    const ff_f32x2 o = {d0 * rstd * gv.x + bv.x, d1 * rstd * gv.y + bv.y};
-    h3_f16x2 h, l;
-    h3_split2(h3_f32x2{o[0], o[1]}, h, l);
-    *reinterpret_cast<h3_f16x2*>(x.hi + off) = h;
-    *reinterpret_cast<h3_f16x2*>(x.lo + off) = l;
   }
 }
 // One attention block on planes, head h = wave (f_attention_regs with plane operands and the output transposed). SHARED: the query tile's
@@ -624,6 +543,8 @@ __device__ __forceinline__ void fp_attention(const FP x, TileGroups gx, const FP
      // load (24 of them: 120+ spilled registers); as a partly unrolled loop without a ring (rounds 4-5) every body of four steps
      // started with the L2 round trip of its twelve loads exposed. Same-box A/B: no ring 4.28 ms, D = 1 / 2 / 3: 3.75 / 3.83 / 4.04
      // (251 registers and no spill at D = 1; 20 / 44 spilled registers at 2 / 3); plain f16 3.45 -> 2.94.
+     // Not stream_weights and not planes_layer's q/k/v rings (encode.hip): those address `base + constant` and at other depths — one
+     // spelling for both would change this kernel's schedule or theirs.
 #ifndef T2L_ATT_RING
 #define T2L_ATT_RING 1
 #endif
@@ -649,8 +570,8 @@ __device__ __forceinline__ void fp_attention(const FP x, TileGroups gx, const FP
       for (int e = 0; e < 3; ++e) f[e] = ring[st % D][e];
       if (st + D < HS) load3(ring[st % D]);
       __builtin_amdgcn_sched_barrier(0);
-      const HFrag xf = fp_frag<SG>(x, aoff + 8 * st);
-      const HFrag mf = self ? xf : fp_frag<SG>(mem, aoff + 8 * st);
+      const HFrag xf = plane_frag<SG>(x.hi, x.lo, aoff + 8 * st);
+      const HFrag mf = self ? xf : plane_frag<SG>(mem.hi, mem.lo, aoff + 8 * st);
       mfma_h3<SG>(qT, f[0], xf);
       mfma_h3<SG>(kT, f[1], mf);
       mfma_h3<SG>(v, mf, f[2]);
@@ -662,7 +583,7 @@ __device__ __forceinline__ void fp_attention(const FP x, TileGroups gx, const FP
     const float bv = ib[2 * kFD + h * kFHd + col];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int f = (r & 3) + 8 * (r >> 2) + 4 * half;
+      const int f = acc_row(r, half);
       qT[r] += ib[h * kFHd + f];
       kT[r] += ib[kFD + h * kFHd + f];
       v[r] += bv;
@@ -677,26 +598,8 @@ __device__ __forceinline__ void fp_attention(const FP x, TileGroups gx, const FP
   for (int r = 0; r < 16; ++r) st[r] = 0.f;
 #pragma unroll
   for (int m2 = 0; m2 < 2; ++m2) mfma_h3<false>(st, split_acc8<false>(kT, m2), split_acc8<false>(qT, m2));
-  // lane: query i = col, keys j = (r&3) + 8*(r>>2) + 4*half
-  const int gi = gx.base + (col >> gx.shift) - gm.base;
-  float m = -__builtin_inff();
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int j = (r & 3) + 8 * (r >> 2) + 4 * half;
-    const bool ok = (j >> gm.shift) == gi && (j & ((1 << gm.shift) - 1)) < gm.count && j < gm.rows;
-    st[r] = ok ? st[r] * 0.17677669529663687f : -__builtin_inff();  // 1/sqrt(32)
-    m = fmaxf(m, st[r]);
-  }
-  m = fmaxf(m, __shfl_xor(m, 32));
-  const bool any = m > -__builtin_inff();
-  float sum = 0.f;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    st[r] = any ? __expf(st[r] - m) : 0.f;
-    sum += st[r];
-  }
-  sum += __shfl_xor(sum, 32);
-  const float inv = any ? 1.f / sum : 0.f;
+  bool any;
+  const float inv = f_group_softmax(st, gx, gm, col, half, any);
   // O^T = V^T P^T: A[feature c][key] = v (as it sits: lane (c, half) holds V[key(r, half)][c]), B[key][query] = P (lane (query, half))
   f32x16 oT;
 #pragma unroll
@@ -709,8 +612,8 @@ __device__ __forceinline__ void fp_attention(const FP x, TileGroups gx, const FP
 #pragma unroll
   for (int g = 0; g < 4; ++g) {  // lane (query = col, half): features 8 g + 4 half + 0..3 of head h
     const int off = col * kLdF + h * kFHd + 8 * g + 4 * half;
-    const ff_f32x4 o4 = {oT[4 * g], oT[4 * g + 1], oT[4 * g + 2], oT[4 * g + 3]};
-    if (!SHARED || any) fp_put4(obuf, off, o4);
+    const h3_f32x4 o4 = {oT[4 * g], oT[4 * g + 1], oT[4 * g + 2], oT[4 * g + 3]};
+    if (!SHARED || any) plane_put4(obuf.hi, obuf.lo, off, o4);
   }
 }
 template <int H>
@@ -750,7 +653,7 @@ __device__ void fp_decoder(const FP x, TileGroups gx, const FP mem, TileGroups g
       for (int r = 0; r < 16; ++r) hh[r] = 0.f;
       fp_dot<kFD / 16, SG>(x, aoff, D.l1.h + ((size_t)tile * (kFD / 16) * 64 + lane) * 2, hh);
       if (qtr) __syncthreads();  // every wave has consumed the previous quarter
-      fp_epilogue<false, true>(buf, w * 32, hh, D.l1.b + tile * 32);
+      fp_epilogue<true>(buf, w * 32, hh, D.l1.b + tile * 32);
       __syncthreads();
       fp_dot<kFD / 16, SG>(buf, aoff, D.l2.h + (((size_t)w * (4 * kFD / 16) + 8 * qtr) * 64 + lane) * 2, acc);
     }
@@ -857,7 +760,7 @@ __global__ __launch_bounds__(256, 2) void fine_match_kernel(FineParams P, const 
         }
       }
       const FP t = row < 32 ? pa : (row < 64 ? pb : ph);
-      fp_put4(t, (row & 31) * kLdF + c, ff_f32x4{v.x, v.y, v.z, v.w});
+      plane_put4(t.hi, t.lo, (row & 31) * kLdF + c, h3_f32x4{v.x, v.y, v.z, v.w});
       float ss = v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;  // the row's 32 quads sit in 32 consecutive lanes (half a wave)
 #pragma unroll
       for (int off = 16; off >= 1; off >>= 1) ss += __shfl_xor(ss, off);
@@ -902,11 +805,11 @@ __global__ __launch_bounds__(256, 2) void fine_match_kernel(FineParams P, const 
   float* d0b = d0 + 32 * kFS;
   const TileGroups gobjA{4, kFObj, 32, 0}, gobjB{4, kFObj, 32, 2}, ghint{3, n_hints, 32, 0};
   for (int l = 0; l < P.n_layers; ++l) {  // cross_matcher.py:114-118
-    f_decoder<H>(d0, gobjA, d1, ghint, P.obj[l], buf);
-    f_decoder<H>(d0b, gobjB, d1, ghint, P.obj[l], buf);
-    f_decoder<H>(d1, ghint, d0, gobjA, P.hint[l], buf, d0b, gobjB);
+    f_decoder(d0, gobjA, d1, ghint, P.obj[l], buf);
+    f_decoder(d0b, gobjB, d1, ghint, P.obj[l], buf);
+    f_decoder(d1, ghint, d0, gobjA, P.hint[l], buf, d0b, gobjB);
   }
-  if (P.n_layers == 0) f_decoder<H>(d1, ghint, d0, gobjA, P.hint[0], buf, d0b, gobjB);  // cross_matcher.py:119-120
+  if (P.n_layers == 0) f_decoder(d1, ghint, d0, gobjA, P.hint[0], buf, d0b, gobjB);  // cross_matcher.py:119-120
   for (int i = tid; i < kPairs * kFD; i += 256) {  // desc1.max(dim=0) over the hints (cross_matcher.py:128)
     const int p = i >> 7, c = i & 127;
     float m = d1[(8 * p) * kFS + c];

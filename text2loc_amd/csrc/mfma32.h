@@ -1,16 +1,16 @@
-// 32-row f32 MFMA building blocks shared by pointnet.hip and fine.hip (gfx950 only): the "half-split" weight packing and the
-// matching dot-product loop with an explicit 4-deep prefetch ring on the weight stream.
+// 32-row f32 MFMA building blocks shared by pointnet.hip, fine.hip and the cell encoder (gfx950 only): the "half-split" weight
+// packing (with the BatchNorm fold in front of it) and the matching dot-product loop with an explicit 4-deep prefetch ring on the
+// weight stream.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include <vector>
 
-#include "gemm_f32.h"
-
 namespace t2l {
 
-using train::f32x16;
+typedef float f32x16 __attribute__((ext_vector_type(16)));  // one 32 x 32 accumulator tile
 
 // [rows/32][kp/8][64 lanes] float4: lane (i, kh) holds Wf[tile*32+i][kh*kp/2 + 4*s4 + 0..3]; Wf = [W | bias column | 0] of width kp
 static inline std::vector<float> pack_half_split(const std::vector<float>& W, const std::vector<float>* bias, int rows, int cin, int kp) {
@@ -27,6 +27,16 @@ static inline std::vector<float> pack_half_split(const std::vector<float>& W, co
           out[(((size_t)t * (kp / 8) + s4) * 64 + lane) * 4 + c] = v;
         }
   return out;
+}
+
+// eval-mode BatchNorm1d folded into the Linear in front of it, in place: W [out][in], b [out]. float32 arithmetic in the order torch
+// evaluates the BatchNorm: (x - mean) / sqrt(var + eps) * weight + bias
+static inline void fold_batchnorm(float* W, float* b, int out, int in, const float* g, const float* be, const float* rm, const float* rv) {
+  for (int o = 0; o < out; ++o) {
+    const float s = g[o] / sqrtf(rv[o] + 1e-5f);
+    for (int k = 0; k < in; ++k) W[(size_t)o * in + k] *= s;
+    b[o] = (b[o] - rm[o]) * s + be[o];
+  }
 }
 
 // acc += A[32 x 8*S4] (this lane's row half, LDS, float4 per 4 k-steps) * B (packed weights, global: wp[s4*64], lane folded in),

@@ -9,7 +9,8 @@
 //
 // Weight packing: [n_tile(32 rows)][K/16 steps][64 lanes][hi 16 B | lo 16 B]; lane (i, kh) of step s holds
 // W[tile*32 + i][kh*K/2 + 8 s .. +7] (the "half-split" k order of the f32 packing, 8 values per step).
-// Activations: a lane's LDS row half, 8 consecutive floats per step, split on the fly (20 VALU).
+// Activations: a lane's LDS row half, 8 consecutive floats per step, split on the fly (split_h, 20 VALU), or two ds_read_b128 out of
+// LDS planes that hold them split already; the plane access and the pinned ring that streams the packed fragments are tile_blocks.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -102,14 +103,6 @@ __device__ __forceinline__ HFrag split_h(const float* __restrict__ p) {  // 8 co
   const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
   return split_v8<SINGLE>(h3_f32x8{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w});
 }
-__device__ __forceinline__ HFrag load_h(const uint4* __restrict__ wp) {
-  // packed weights live in global memory: say so (a pointer that went through an opaque asm would otherwise load as flat_*)
-  const __attribute__((address_space(1))) uint4* gp = (const __attribute__((address_space(1))) uint4*)wp;
-  HFrag f;
-  f.hi = __builtin_bit_cast(h3_f16x8, gp[0]);
-  f.lo = __builtin_bit_cast(h3_f16x8, gp[1]);
-  return f;
-}
 // acc += A * B with A, B split fragments (a = A operand, b = B operand of the MFMA)
 template <bool SINGLE = false>
 __device__ __forceinline__ void mfma_h3(h3_f32x16& acc, const HFrag& a, const HFrag& b) {
@@ -121,6 +114,7 @@ __device__ __forceinline__ void mfma_h3(h3_f32x16& acc, const HFrag& a, const HF
 }
 template <bool SINGLE = false>
 __device__ __forceinline__ HFrag load_h1(const uint4* __restrict__ wp) {  // SINGLE: the high half only (half the weight bytes)
+  // packed weights live in global memory: say so (a pointer that went through an opaque asm would otherwise load as flat_*)
   const __attribute__((address_space(1))) uint4* gp = (const __attribute__((address_space(1))) uint4*)wp;
   HFrag f;
   f.hi = __builtin_bit_cast(h3_f16x8, gp[0]);
@@ -128,38 +122,6 @@ __device__ __forceinline__ HFrag load_h1(const uint4* __restrict__ wp) {  // SIN
   else f.lo = __builtin_bit_cast(h3_f16x8, gp[1]);
   return f;
 }
-// acc += A[32 x 16*STEPS] (this lane's LDS row half) * W^T (one packed weight tile, offset to its first step and to this
-// lane: 2 uint4 per lane and step, 128 uint4 per step)
-// dev experiment (make exp_fine / exp_enc EXPFLAG=-DT2L_EXP_HOTW; WRONG results, timing only): every weight fragment of a tile pass comes
-// from the pass's first two k-steps — the instruction stream stays, the packed-weight stream out of the L2 disappears
-#ifdef T2L_EXP_HOTW
-#define T2L_HOT(s) ((s) & 1)
-#else
-#define T2L_HOT(s) (s)
-#endif
-#ifndef T2L_DOT_RING
-#define T2L_DOT_RING 2
-#endif
-constexpr int kDotRing = T2L_DOT_RING;
-template <int STEPS, bool SINGLE = false>
-__device__ __forceinline__ void mm32_dot_h(const float* __restrict__ arow, const uint4* __restrict__ wp, h3_f32x16& acc) {
-  // the weight fragments through a register ring kDotRing steps deep, each request issued before the MFMAs of the step that frees its
-  // slot and pinned there (the compiler otherwise sinks every load to its use; encode.hip: stream_weights). fine_match, 40,960 pairs:
-  // no ring 5.90 ms, depth 2 / 4 / 8: 5.66 / 5.70 / 5.84 ms. Same arithmetic in the same order: bit-identical results.
-  constexpr int D = STEPS < kDotRing ? STEPS : kDotRing;
-  HFrag ring[D];
-#pragma unroll
-  for (int i = 0; i < D; ++i) ring[i] = load_h1<SINGLE>(wp + T2L_HOT(i) * 128);
-#pragma unroll
-  for (int s = 0; s < STEPS; ++s) {
-    const HFrag wf = ring[s % D];
-    if (s + D < STEPS) ring[s % D] = load_h1<SINGLE>(wp + T2L_HOT(s + D) * 128);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma_h3<SINGLE>(acc, split_h<SINGLE>(arow + 8 * s), wf);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
 // W [rows][cin] row-major (optionally [W | bias column | 0] of width kp, as pack_half_split) -> split-f16 fragments; bit
 // patterns carried in a float vector (8 floats per lane and step)
 static inline std::vector<float> pack_split_f16(const float* W, const float* bias, int rows, int cin, int kp) {

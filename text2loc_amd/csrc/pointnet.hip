@@ -30,9 +30,6 @@
 
 namespace t2l {
 
-using train::f32x16;
-
-
 struct PointNetWeights {
   uint4 *w1h[3] = {}, *w2h[3] = {};  // split-f16 packings of the same matrices (level 1; the other levels read streams)
   uint4* gash = nullptr;  // the global MLP's stream (same form)
@@ -73,13 +70,9 @@ static bool fold_block(const WMap& m, const std::string& prefix, int i, int cin,
   const float *w = get(".0.weight", (int64_t)cin * cout), *bb = get(".0.bias", cout), *g = get(".1.weight", cout), *be = get(".1.bias", cout),
               *rm = get(".1.running_mean", cout), *rv = get(".1.running_var", cout);
   if (!w || !bb || !g || !be || !rm || !rv) return false;
-  W.assign((size_t)cin * cout, 0.f);
-  b.assign(cout, 0.f);
-  for (int o = 0; o < cout; ++o) {
-    const float s = g[o] / sqrtf(rv[o] + 1e-5f);
-    for (int k = 0; k < cin; ++k) W[(size_t)o * cin + k] = w[(size_t)o * cin + k] * s;
-    b[o] = (bb[o] - rm[o]) * s + be[o];
-  }
+  W.assign(w, w + (size_t)cin * cout);
+  b.assign(bb, bb + cout);
+  fold_batchnorm(W.data(), b.data(), cout, cin, g, be, rm, rv);
   return true;
 }
 
