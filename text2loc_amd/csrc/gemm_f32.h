@@ -17,8 +17,14 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // range four ways; every wave streams its operands straight from global memory into the MFMA operand registers — no
 // LDS staging, no barrier in the loop. The k index inside a 16-step is permuted (lane half kh owns k0+8*kh .. +7) so
 // that k-contiguous operands are two float4 loads per lane; any permutation is valid as long as A and B share it. The
-// four partial tiles meet in LDS once, at the end. M and the reduction range may be ragged; N must be a multiple of 32
-// (and M too when !A_KC).
+// four partial tiles meet in LDS once, at the end.
+// Shape contract (nothing in the kernel checks it; the launchers of train.hip do, host side):
+//   N is a multiple of 32 (64 for the 64 x 64 blocking), and so is M when !A_KC: those rows are loaded and, with colsum, added unguarded;
+//   M may be ragged when A_KC (row loads and stores are guarded);
+//   the reduction range [0, K) may be ragged ONLY when neither operand is k-contiguous (the dW product: its loads test k against the
+//   end of the wave's share). A k-contiguous operand (A_KC or B_KC) is loaded as two float4 per lane per 16-step with NO test against
+//   the end, so K and kchunk must be multiples of 16 — else the last step reads up to 15 floats past the row (the next row's, or past
+//   the buffer behind the last row) and multiplies them in.
 // ---------------------------------------------------------------------------------------------------------------
 struct GemmArgs {
   const float* A;

@@ -195,8 +195,17 @@ void free_train(t2l_ctx* ctx) {
 static thread_local int tl_gemm_bf16 = 0;  // set from the context option "train_bf16" at the top of every forward / backward
 static thread_local int tl_gemm_block64 = 0;  // option "train_gemm_block": 64 x 64 output blocks where the shape allows (default: with bf16 operands)
 static inline bool blk64(int rows_out_mult, int cols_out) { return tl_gemm_block64 && rows_out_mult % 64 == 0 && cols_out % 64 == 0; }
+// gemm_f32.h's contract for a k-contiguous operand: the reduction length is a whole number of 16-steps (gemm_load<true> reads two
+// float4 per lane without a test against the end of the range). Every product of the step has one; a launch that has not is refused
+// here, loudly, instead of reading past the operand's rows.
+static inline bool gemm_kc_ok(int K, const char* who) {
+  if (K > 0 && K % 16 == 0) return true;
+  fprintf(stderr, "t2l: %s: a k-contiguous operand needs a reduction length that is a multiple of 16, got %d (launch refused)\n", who, K);
+  return false;
+}
 // Y[M,N] = X[M,K] W[N,K]^T + b (relu)
 static void gemm_nt_args(GemmArgs g, hipStream_t s) {  // g.M rows (ragged allowed), g.N columns
+  if (!gemm_kc_ok(g.K, "gemm_nt")) return;
   if (blk64(64, g.N))
     hipLaunchKernelGGL((gemm4_kernel<true, true>), dim3(g.N / 64, (g.M + 63) / 64, 1), dim3(256), 0, s, g);
   else
@@ -208,6 +217,7 @@ static void gemm_nt(const float* X, const float* W, const float* b, float* Y, in
 // dX[M,Kp] (+)= dY[M,N] W[N,Kp]
 static void gemm_nn(const float* dY, const float* W, float* dX, int M, int N, int Kp, int accumulate, hipStream_t s) {
   GemmArgs g{dY, W, dX, nullptr, M, Kp, N, N, Kp, Kp, 0, accumulate, N, nullptr, tl_gemm_bf16};
+  if (!gemm_kc_ok(N, "gemm_nn")) return;
   if (blk64(64, Kp))
     hipLaunchKernelGGL((gemm4_kernel<true, false>), dim3(Kp / 64, (M + 63) / 64, 1), dim3(256), 0, s, g);
   else
@@ -235,6 +245,7 @@ static void gemm_tn(const float* dY, const float* X, float* dW, float* db, int M
 // of the layer that produced X's pre-image, applied in dX's epilogue (epi 2) instead of by a launch of its own
 static void gemm_tn_nn(const float* dY, const float* X, float* dW, float* db, const float* W, float* dX, int M, int N, int Kp, int accumulate,
                        const float* mask_src, const Drop* drop, hipStream_t s) {
+  if (!gemm_kc_ok(N, "gemm_tn_nn")) return;
   const bool b64 = blk64(N, Kp);
   const int blk = b64 ? 64 : 32;
   int ksplit, kchunk;
@@ -258,6 +269,35 @@ static void gemm_tn_nn(const float* dY, const float* X, float* dW, float* db, co
     hipLaunchKernelGGL(gemm4_pair_kernel, dim3(p.tn_blocks + nn_blocks), dim3(256), 0, s, p);
   else
     hipLaunchKernelGGL(gemm_pair_kernel, dim3(p.tn_blocks + nn_blocks), dim3(256), 0, s, p);
+}
+// Y_q[M,N] = X_q[M,K] W_q[N,K]^T + b_q for n <= 3 independent jobs of one shape, ONE launch (32 x 32 tiles; grid.z = job)
+static void gemm_nt_multi(int n, const float* const* X, const float* const* W, const float* const* b, float* const* Y, int M, int N, int K,
+                          hipStream_t s) {
+  if (!gemm_kc_ok(K, "gemm_nt_multi")) return;
+  GemmMulti gm{};
+  for (int q = 0; q < n; ++q) gm.j[q] = GemmArgs{X[q], W[q], Y[q], b[q], M, N, K, K, K, N, 0, 0, K, nullptr, tl_gemm_bf16};
+  hipLaunchKernelGGL((gemm_multi_kernel<true, true>), dim3(N / 32, (M + 31) / 32, n), dim3(256), 0, s, gm);
+}
+// dW_q[N,Kp] += dY_q^T X_q (+ db_q) and dX_q[M,Kp] = dY_q W_q for n <= 3 independent jobs of one shape, ONE launch (32 x 32 tiles;
+// grid.y = job, a job's blocks flattened in x as gemm_tn_nn's)
+static void gemm_tn_nn_multi(int n, const float* const* dY, const float* const* X, float* const* dW, float* const* db, const float* const* W,
+                             float* const* dX, int M, int N, int Kp, hipStream_t s) {
+  if (!gemm_kc_ok(N, "gemm_tn_nn_multi")) return;
+  int ksplit, kchunk;
+  tn_split(M, N, Kp, 32, ksplit, kchunk);
+  GemmPairMulti gp{};
+  int pair_blocks = 0;
+  for (int q = 0; q < n; ++q) {
+    GemmPair& p = gp.p[q];
+    p.tn = GemmArgs{dY[q], X[q], dW[q], nullptr, N, Kp, M, N, Kp, Kp, 0, 1, kchunk, db[q], tl_gemm_bf16};
+    p.nn = GemmArgs{dY[q], W[q], dX[q], nullptr, M, Kp, N, N, Kp, Kp, 0, 0, N, nullptr, tl_gemm_bf16};
+    p.tn_gx = Kp / 32;
+    p.tn_gy = N / 32;
+    p.tn_blocks = p.tn_gx * p.tn_gy * ksplit;
+    p.nn_gx = Kp / 32;
+    pair_blocks = p.tn_blocks + p.nn_gx * ((M + 31) / 32);
+  }
+  hipLaunchKernelGGL(gemm_pair_multi_kernel, dim3(pair_blocks, n), dim3(256), 0, s, gp);
 }
 // ---- one TransformerEncoderLayer, for the object branch and the text head alike -----------------------------------------------
 // What differs between the two states' Linear products. The text head's run on the tiled LDS-ring GEMM of text_head.hip (fast_gemm:
@@ -306,6 +346,47 @@ static void attn_bwd_launch(int B, int S, hipStream_t s, A... a) {
   if (HD == kTHd && S == kTS) hipLaunchKernelGGL((attn_bwd_kernel<kTHd, kTS>), dim3(B * 4), dim3(256), attn_lds(S, HD, true), s, a...);
   else hipLaunchKernelGGL((attn_bwd_kernel<HD, 0>), dim3(B * 4), dim3(256), attn_lds(S, HD, true), s, a...);
 }
+// the HD = 256 instances (the text head's d = 1024 layer) take more dynamic LDS than a kernel gets unasked: once per device
+static void attn256_allow_lds(int device) {
+  static PerDeviceOnce once;
+  if (once.need(device)) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<256, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<256, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    once.mark(device);
+  }
+}
+// out = LayerNorm(x + dropout(y)) over T rows of D: one wave per row, four rows per workgroup
+template <int D>
+static void ln_fwd_launch(const float* x, const float* y, int T, const float* gamma, const float* beta, const Drop& dr, float* out, float* xhat,
+                          float* rstd, hipStream_t s) {
+  hipLaunchKernelGGL((ln_fwd_kernel<D>), dim3((T + 3) / 4), dim3(256), 0, s, x, y, T, gamma, beta, dr, out, xhat, rstd);
+}
+// its backward; dgamma / dbeta are added to. LN_WAVES: waves per workgroup, the caller's measured choice for its shape (train_kernels.h:
+// ln_bwd_kernel): 16 for the object branch's 1,792 rows of 256, in at most 32 workgroups; 4 for the text head, in at most 64 (at
+// D = 1024 the partials of 16 waves would not fit the LDS).
+template <int D, int LN_WAVES>
+static void ln_bwd_launch(const float* dout, const float* xhat, const float* rstd, int T, const float* gamma, const Drop& dr, float* d_res,
+                          float* d_y, float* dgamma, float* dbeta, hipStream_t s) {
+  const int ln_grid = std::min(LN_WAVES == 16 ? 32 : 64, (T + 15) / 16);
+  hipLaunchKernelGGL((ln_bwd_kernel<D, LN_WAVES>), dim3(ln_grid), dim3(LN_WAVES * 64), 0, s, dout, xhat, rstd, T, gamma, dr, d_res, d_y, dgamma,
+                     dbeta);
+}
+// max over a cell's 28 slots + F.normalize (one workgroup per cell), and its backward. zero / zero_n: what the forward's last launch
+// clears for the step (pool_norm_fwd_kernel)
+static void pool_norm_fwd_launch(const float* x, float* out, int32_t* arg, float* save_n, float* out2, double* zero, int zero_n, int B,
+                                 hipStream_t s) {
+  hipLaunchKernelGGL(pool_norm_fwd_kernel, dim3(B), dim3(256), 0, s, x, out, arg, save_n, out2, zero, zero_n);
+}
+static void pool_norm_bwd_launch(const float* gout, const float* out, const int32_t* arg, const float* save_n, float* dX, int B, hipStream_t s) {
+  hipLaunchKernelGGL(pool_norm_bwd_kernel, dim3(B), dim3(256), 0, s, gout, out, arg, save_n, dX);
+}
+// out[b][c] = max over the S rows of group b of (X + R) (R optional) with its argument, and the scatter back (text head)
+static void seq_max_fwd_launch(const float* X, const float* R, int B, int S, int D, float* out, int32_t* arg, hipStream_t s) {
+  hipLaunchKernelGGL(seq_max_fwd_kernel, dim3((unsigned)(((size_t)B * D + 255) / 256)), dim3(256), 0, s, X, R, B, S, D, out, arg);
+}
+static void seq_max_bwd_launch(const float* g, const int32_t* arg, int B, int S, int D, float* dX, hipStream_t s) {
+  hipLaunchKernelGGL(seq_max_bwd_kernel, dim3((unsigned)(((size_t)B * S * D + 255) / 256)), dim3(256), 0, s, g, arg, B, S, D, dX);
+}
 
 // the saved activations of L (T, B, S, FF set by the caller)
 template <int D>
@@ -332,8 +413,7 @@ static void enc_layer_fwd(const Products& pr, const TensorMap& t, EncLayer& L, u
   t_gemm_nt(pr, L.x_in, W(".self_attn.in_proj_weight").data, W(".self_attn.in_proj_bias").data, L.qkv, T, 3 * D, D, 0, s);
   attn_fwd_launch<HD>(L.B, L.S, s, (const float*)L.qkv, L.P, L.O, L.S, make_drop(seed, L.site0 + 0, p));
   t_gemm_nt(pr, L.O, W(".self_attn.out_proj.weight").data, W(".self_attn.out_proj.bias").data, tmp, T, D, D, 0, s);
-  hipLaunchKernelGGL((ln_fwd_kernel<D>), dim3((T + 3) / 4), dim3(256), 0, s, L.x_in, (const float*)tmp, T, W(".norm1.weight").data,
-                     W(".norm1.bias").data, make_drop(seed, L.site0 + 1, p), L.x1, L.xhat1, L.rstd1);
+  ln_fwd_launch<D>(L.x_in, tmp, T, W(".norm1.weight").data, W(".norm1.bias").data, make_drop(seed, L.site0 + 1, p), L.x1, L.xhat1, L.rstd1, s);
   if (t_fast(pr, T, FF, D)) {  // linear1 + ReLU in the GEMM's epilogue (h is kept for backward); the dropout behind it as one pass
     (void)fast_gemm(pr.ctx, L.x1, false, W(".linear1.weight").data, false, W(".linear1.bias").data, L.h, T, FF, D, 1, 0, pr.ctx->text_train_bf16 == 1, s);
     if (p > 0.f) {
@@ -353,8 +433,7 @@ static void enc_layer_fwd(const Products& pr, const TensorMap& t, EncLayer& L, u
     gemm_nt_args(g, s);
   }
   t_gemm_nt(pr, L.hd, W(".linear2.weight").data, W(".linear2.bias").data, tmp, T, D, FF, 0, s);
-  hipLaunchKernelGGL((ln_fwd_kernel<D>), dim3((T + 3) / 4), dim3(256), 0, s, (const float*)L.x1, (const float*)tmp, T, W(".norm2.weight").data,
-                     W(".norm2.bias").data, make_drop(seed, L.site0 + 3, p), L.x2, L.xhat2, L.rstd2);
+  ln_fwd_launch<D>(L.x1, tmp, T, W(".norm2.weight").data, W(".norm2.bias").data, make_drop(seed, L.site0 + 3, p), L.x2, L.xhat2, L.rstd2, s);
 }
 // The backward's scratch: taken by the CALLER, who knows whether its layers can share one (the object branch's do: same shape).
 struct EncScratch {
@@ -375,20 +454,16 @@ static EncScratch enc_scratch_take(Arena& ws, int T, int FF) {
 }
 // dcur: gradient w.r.t. the layer's output x2 (read). Returns the gradient w.r.t. the layer's input, which lives in sc.dC (nullptr when
 // need_dx is false). 7 launches on the products of gemm_f32.h.
-// LN_WAVES: waves per workgroup of the LayerNorm backward, the caller's measured choice for its shape (train_kernels.h: ln_bwd_kernel):
-// 16 for the object branch's 1,792 rows of 256, in at most 32 workgroups; 4 for the text head, in at most 64 (at D = 1024 the
-// partials of 16 waves would not fit the LDS).
+// LN_WAVES: waves per workgroup of the LayerNorm backward (ln_bwd_launch).
 template <int D, int LN_WAVES>
 static float* enc_layer_bwd(const Products& pr, const TensorMap& t, const EncLayer& L, uint32_t seed, float p, const EncScratch& sc,
                             const float* dcur, bool need_dx, hipStream_t s) {
   constexpr int HD = D / 4;
   const int T = L.T, FF = L.FF;
   auto W = [&](const char* nme) -> const TTensor& { return t.at(L.prefix + nme); };
-  const int ln_grid = std::min(LN_WAVES == 16 ? 32 : 64, (T + 15) / 16);
   auto ln_bwd = [&](const float* dout, const float* xhat, const float* rstd, const TTensor& gamma, const TTensor& beta, int site, float* d_res,
                     float* d_y) {
-    hipLaunchKernelGGL((ln_bwd_kernel<D, LN_WAVES>), dim3(ln_grid), dim3(LN_WAVES * 64), 0, s, dout, xhat, rstd, T, (const float*)gamma.data,
-                       make_drop(seed, site, p), d_res, d_y, gamma.grad, beta.grad);
+    ln_bwd_launch<D, LN_WAVES>(dout, xhat, rstd, T, gamma.data, make_drop(seed, site, p), d_res, d_y, gamma.grad, beta.grad, s);
   };
   // norm2 + dropout2
   ln_bwd(dcur, L.xhat2, L.rstd2, W(".norm2.weight"), W(".norm2.bias"), L.site0 + 3, sc.dA, sc.dB);
@@ -598,7 +673,8 @@ static SmallkMulti smallk_jobs(int M) {
 static void small_branches_fwd(TrainState* st, const std::vector<int>& which, int M, int Kc, hipStream_t s) {
   const int n = (int)which.size();
   SmallkMulti sk = smallk_jobs(M);
-  GemmMulti gm{};
+  const float *gx[kMaxJobs], *gw[kMaxJobs], *gb[kMaxJobs];
+  float* gy[kMaxJobs];
   RownormJob rn[kMaxJobs];
   const MlpLayer *L0[kMaxJobs], *L1[kMaxJobs];
   for (int q = 0; q < n; ++q) {
@@ -611,15 +687,17 @@ static void small_branches_fwd(TrainState* st, const std::vector<int>& which, in
     sk.j[q].w = T_(st, L0[q]->prefix + ".0.weight").data;
     sk.j[q].b = T_(st, L0[q]->prefix + ".0.bias").data;
     sk.j[q].y = L0[q]->y;
-    gm.j[q] = GemmArgs{L0[q]->a, T_(st, L1[q]->prefix + ".0.weight").data, L1[q]->y, T_(st, L1[q]->prefix + ".0.bias").data, M, kTD, 64, 64, 64, kTD, 0, 0,
-                       64, nullptr, tl_gemm_bf16};
+    gx[q] = L0[q]->a;
+    gw[q] = T_(st, L1[q]->prefix + ".0.weight").data;
+    gb[q] = T_(st, L1[q]->prefix + ".0.bias").data;
+    gy[q] = L1[q]->y;
     rn[q] = RownormJob{L1[q]->a, nullptr, st->cat + br.slot * kTD, nullptr, br.save_n};
   }
   const BnMulti b0 = bn_jobs(st, n, L0, nullptr, M);  // (slot order: the first stage's n, then the second's)
   const BnMulti b1 = bn_jobs(st, n, L1, nullptr, M);
   hipLaunchKernelGGL(smallk_fwd_kernel, dim3((M * 64 + 255) / 256, n), dim3(256), 0, s, sk);
   bn_relu_fwd(st, b0, n, s);
-  hipLaunchKernelGGL((gemm_multi_kernel<true, true>), dim3(kTD / 32, (M + 31) / 32, n), dim3(256), 0, s, gm);
+  gemm_nt_multi(n, gx, gw, gb, gy, M, kTD, 64, s);
   bn_relu_fwd(st, b1, n, s);
   rownorm_launch(true, rn, n, M, Kc, s);
 }
@@ -628,14 +706,10 @@ static void small_branches_bwd(TrainState* st, const std::vector<int>& which, in
                                hipStream_t s) {
   const int n = (int)which.size();
   SmallkMulti sk = smallk_jobs(M);
-  GemmPairMulti gp{};
   RownormJob rn[kMaxJobs];
   const MlpLayer *L0[kMaxJobs], *L1[kMaxJobs];
-  float *dq2[kMaxJobs], *dq1[kMaxJobs];
-  const int N = kTD, Kp = 64;
-  int ksplit, kchunk;
-  tn_split(M, N, Kp, 32, ksplit, kchunk);
-  int pair_blocks = 0;
+  float *dq2[kMaxJobs], *dq1[kMaxJobs], *gdw[kMaxJobs], *gdb[kMaxJobs];
+  const float *gx[kMaxJobs], *gw[kMaxJobs];
   for (int q = 0; q < n; ++q) {
     const Branch& br = st->branches[which[q]];
     L0[q] = &br.layers[0];
@@ -643,15 +717,10 @@ static void small_branches_bwd(TrainState* st, const std::vector<int>& which, in
     dq2[q] = d2 + (size_t)q * M * kTD;
     dq1[q] = d1 + (size_t)q * M * 64;
     rn[q] = RownormJob{dcat + br.slot * kTD, nullptr, dq2[q], st->cat + br.slot * kTD, br.save_n};
-    GemmPair& p = gp.p[q];
-    p.tn = GemmArgs{dq2[q], L0[q]->a, T_(st, L1[q]->prefix + ".0.weight").grad, nullptr, N, Kp, M, N, Kp, Kp, 0, 1, kchunk,
-                    T_(st, L1[q]->prefix + ".0.bias").grad, tl_gemm_bf16};
-    p.nn = GemmArgs{dq2[q], T_(st, L1[q]->prefix + ".0.weight").data, dq1[q], nullptr, M, Kp, N, N, Kp, Kp, 0, 0, N, nullptr, tl_gemm_bf16};
-    p.tn_gx = Kp / 32;
-    p.tn_gy = N / 32;
-    p.tn_blocks = p.tn_gx * p.tn_gy * ksplit;
-    p.nn_gx = Kp / 32;
-    pair_blocks = p.tn_blocks + p.nn_gx * ((M + 31) / 32);
+    gx[q] = L0[q]->a;
+    gdw[q] = T_(st, L1[q]->prefix + ".0.weight").grad;
+    gdb[q] = T_(st, L1[q]->prefix + ".0.bias").grad;
+    gw[q] = T_(st, L1[q]->prefix + ".0.weight").data;
     sk.j[q].x = br.x;
     sk.j[q].K = br.k_in;
     sk.j[q].standardize = br.standardize;
@@ -663,7 +732,7 @@ static void small_branches_bwd(TrainState* st, const std::vector<int>& which, in
   const BnMulti b0 = bn_jobs(st, n, L0, dq1, M);
   rownorm_launch(false, rn, n, M, Kc, s);
   bn_relu_bwd(st, b1, n, s);
-  hipLaunchKernelGGL(gemm_pair_multi_kernel, dim3(pair_blocks, n), dim3(256), 0, s, gp);
+  gemm_tn_nn_multi(n, dq2, gx, gdw, gdb, gw, dq1, M, kTD, 64, s);
   bn_relu_bwd(st, b0, n, s);
   hipLaunchKernelGGL(smallk_bwd_kernel, dim3((M + 31) / 32, n), dim3(256), 0, s, sk);
 }
@@ -782,8 +851,7 @@ int train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, float p, uint32
   st->out = st->ws.take<float>((size_t)B * kTD);
   st->pool_n = st->ws.take<float>(B);
   st->pool_arg = st->ws.take<int32_t>((size_t)B * kTD);
-  hipLaunchKernelGGL(pool_norm_fwd_kernel, dim3(B), dim3(256), 0, s, x, st->out, st->pool_arg, st->pool_n, out_emb, acc_base(ctx, st),
-                     kBnStride * kBnSlots * 2);
+  pool_norm_fwd_launch(x, st->out, st->pool_arg, st->pool_n, out_emb, acc_base(ctx, st), kBnStride * kBnSlots * 2, B, s);
   event_end(ctx, "train_forward", s);
   T2L_HIP(ctx, hipGetLastError());
   st->fwd_acc_clean = true;
@@ -830,7 +898,7 @@ int train_backward_impl(t2l_ctx* ctx, const float* grad_emb, float* grad_pn_feat
     st->ws.off = mark;
     return fail(ctx, T2L_ENOMEM, "t2l_encode_cells_backward: workspace bound exceeded (internal error)");
   }
-  hipLaunchKernelGGL(pool_norm_bwd_kernel, dim3(B), dim3(256), 0, s, grad_emb, st->out, st->pool_arg, st->pool_n, dcur);
+  pool_norm_bwd_launch(grad_emb, st->out, st->pool_arg, st->pool_n, dcur, B, s);
   const Products pr{ctx, false};
   for (int l = (int)st->layers.size() - 1; l >= 0; --l) {
     float* dx = enc_layer_bwd<kTD, 16>(pr, st->t, st->layers[l], st->seed, st->p, sc, dcur, true, s);
@@ -1039,12 +1107,7 @@ static int text_train_bind_body(t2l_ctx* ctx, const t2l_train_tensor* tensors, i
   bool kept;
   if ((rc = st->adam.build(ctx, st->t, old, &kept))) return rc;
   if (kept) st->step = old_step;
-  static PerDeviceOnce once;
-  if (once.need(ctx->device)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<256, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<256, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    once.mark(ctx->device);
-  }
+  attn256_allow_lds(ctx->device);
   return T2L_OK;
 }
 
@@ -1088,8 +1151,7 @@ int text_train_forward_impl(t2l_ctx* ctx, const float* hidden, int n_sent, int L
   enc_layer_fwd<1024>(pr, st->t, A, seed, p, tmp, s);
   st->pooled = st->ws.take<float>((size_t)n_sent * 1024);
   st->tok_arg = st->ws.take<int32_t>((size_t)n_sent * 1024);
-  hipLaunchKernelGGL(seq_max_fwd_kernel, dim3((unsigned)(((size_t)n_sent * 1024 + 255) / 256)), dim3(256), 0, s, (const float*)A.x2, (const float*)nullptr,
-                     n_sent, L, 1024, st->pooled, st->tok_arg);
+  seq_max_fwd_launch(A.x2, nullptr, n_sent, L, 1024, st->pooled, st->tok_arg, s);
   const int D = st->D;
   st->mlp_y = st->ws.take<float>((size_t)n_sent * D);
   st->mlp_out = st->ws.take<float>((size_t)n_sent * D);
@@ -1122,8 +1184,7 @@ int text_train_forward_impl(t2l_ctx* ctx, const float* hidden, int n_sent, int L
   enc_layer_fwd<256>(pr, st->t, I, seed, p, tmp, s);
   st->out = st->ws.take<float>((size_t)n_desc * 256);
   st->sent_arg = st->ws.take<int32_t>((size_t)n_desc * 256);
-  hipLaunchKernelGGL(seq_max_fwd_kernel, dim3((unsigned)(((size_t)n_desc * 256 + 255) / 256)), dim3(256), 0, s, (const float*)I.x2,
-                     (const float*)st->mlp_out, n_desc, S, 256, st->out, st->sent_arg);
+  seq_max_fwd_launch(I.x2, st->mlp_out, n_desc, S, 256, st->out, st->sent_arg, s);
   T2L_HIP(ctx, hipMemcpyAsync(out, st->out, sizeof(float) * (size_t)n_desc * 256, hipMemcpyDeviceToDevice, s));
   event_end(ctx, "text_train_forward", s);
   T2L_HIP(ctx, hipGetLastError());
@@ -1151,8 +1212,7 @@ int text_train_backward_impl(t2l_ctx* ctx, const float* grad_out, hipStream_t s)
   } else {
     // max over the sentences: the gradient goes to the arg-max row of (x + layer(x)) — to the layer's output AND to the residual x
     float* dY2 = st->ws.take<float>((size_t)n_sent * 256);
-    hipLaunchKernelGGL(seq_max_bwd_kernel, dim3((unsigned)(((size_t)n_sent * 256 + 255) / 256)), dim3(256), 0, s, grad_out, (const int32_t*)st->sent_arg,
-                       n_desc, S, 256, dY2);
+    seq_max_bwd_launch(grad_out, st->sent_arg, n_desc, S, 256, dY2, s);
     dX = enc_layer_bwd<256, 4>(pr, st->t, st->inter, st->seed, st->p, enc_scratch_take<256>(st->ws, n_sent, 1024), dY2, true, s);
     hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)(((size_t)n_sent * 256 + 255) / 256)), dim3(256), 0, s, dX, (const float*)dY2, (size_t)n_sent * 256);
   }
@@ -1171,8 +1231,7 @@ int text_train_backward_impl(t2l_ctx* ctx, const float* grad_out, hipStream_t s)
                n_sent, D, 1024, 0, nullptr, nullptr, s);
   // max over the tokens, then the d = 1024 layer (its input, T5's hidden states, is a constant: no dX)
   float* dX2 = st->ws.take<float>((size_t)n_sent * L * 1024);
-  hipLaunchKernelGGL(seq_max_bwd_kernel, dim3((unsigned)(((size_t)n_sent * L * 1024 + 255) / 256)), dim3(256), 0, s, (const float*)dpool,
-                     (const int32_t*)st->tok_arg, n_sent, L, 1024, dX2);
+  seq_max_bwd_launch(dpool, st->tok_arg, n_sent, L, 1024, dX2, s);
   enc_layer_bwd<1024, 4>(pr, st->t, st->intra, st->seed, st->p, enc_scratch_take<1024>(st->ws, n_sent * L, 4096), dX2, false, s);
   event_end(ctx, "text_train_backward", s);
   const bool over = st->ws.off > st->ws.cap;

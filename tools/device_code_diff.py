@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """Compare the device code of two csrc trees kernel by kernel — the check behind "this refactor is a re-spelling". No GPU needed.
 
-    python tools/device_code_diff.py PARENT_CSRC NEW_CSRC
+    python tools/device_code_diff.py PARENT_CSRC NEW_CSRC [--same-as NEW_UNIT=PARENT_UNIT]
 
 Every *.hip of both trees is compiled to an assembly listing (`hipcc <make print-flags> -S --cuda-device-only`, as
 tests/test_mfma_hazard_scan.py does). A listing is cut into one piece per function symbol: its instructions, its `.amdhsa_*` block and
 its resource `.set` lines, plus its entry in the metadata (arguments, VGPRs, SGPRs, LDS, scratch). What says nothing about the code
 is dropped: comment text, `.loc` / `.file` / `.ident`, the per-compilation `__hip_cuid_*` symbol, and the function's running number
 in local labels (`.LBB3_7`, `.Lfunc_end3`). One line per kernel: identical, changed (with the first differing line), or only in one
-tree. Exit status 1 unless everything is identical."""
+tree. `--same-as train_blocks.hip=train.hip`: a unit that exists only in the new tree because it re-compiles another one (it #includes
+it) is held against the PARENT's listing of that other unit. Exit status 1 unless everything is identical."""
 import argparse
 import glob
 import os
@@ -108,12 +109,15 @@ def main():
     ap.add_argument("parent_csrc")
     ap.add_argument("new_csrc")
     ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))
+    ap.add_argument("--same-as", action="append", default=[], metavar="NEW_UNIT=PARENT_UNIT")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         sides = []
         for name, csrc in (("parent", args.parent_csrc), ("new", args.new_csrc)):
             os.mkdir(os.path.join(tmp, name))
             sides.append(_listings(os.path.abspath(csrc), os.path.join(tmp, name), args.jobs))
+    for new_unit, parent_unit in (pair.split("=", 1) for pair in args.same_as):
+        sides[0][new_unit] = sides[0][parent_unit]
     counts = {}
     for unit in sorted(set(sides[0]) | set(sides[1])):
         for sym, verdict, detail in compare_listings(sides[0].get(unit, ""), sides[1].get(unit, "")):
