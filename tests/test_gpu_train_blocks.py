@@ -1,5 +1,6 @@
 """GPU tier of the training-block tests: every product of gemm_f32.h as the step's launchers launch it, and the
-attention / LayerNorm / pool + normalise / seq-max kernels, ONE launch at a time through the dev library libt2l_blocks.so
+attention / LayerNorm / F.normalize / dropout / pool + normalise / seq-max kernels (the row kernels at the fine step's width 128 too),
+ONE launch at a time through the dev library libt2l_blocks.so
 (csrc/train_blocks.hip), each held element by element against the float64 references and derived bounds of tests/train_blocks.py.
 
 Inputs are Gaussian from fixed seeds and sit between NaN halos (a read past an end enters the arithmetic); every output is carved from a
@@ -261,7 +262,7 @@ def test_attention(lib, HD, sizes):
 
 
 # ---- LayerNorm ----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("D,waves", [(256, (16, 4)), (1024, (4,))])
+@pytest.mark.parametrize("D,waves", [(256, (16, 4)), (1024, (4,)), (128, (4,))])
 def test_layernorm(lib, D, waves):
     """forward, and the backward with every LN_WAVES the step instantiates; T is not a multiple of the row stride"""
     wf, wb, wp = Worst(f"ln_fwd D={D}"), Worst(f"ln_bwd D={D}"), Worst(f"ln_bwd_dgamma_dbeta D={D}")
@@ -296,6 +297,95 @@ def test_layernorm(lib, D, waves):
     wp.report()
 
 
+# ---- F.normalize of a row ------------------------------------------------------------------------------------------------------
+def slot(t, D):
+    """the middle D-wide slot of a [M, 3 D] tensor, as the pointer the wrapper takes"""
+    return ctypes.c_void_p(t.data_ptr() + 4 * D)
+
+
+def rownorm_case(lib, w, D, x, dy, wide, what):
+    """forward and backward of one (x, dy) [M, D]; wide: the strided side is the middle slot of a 3 D-wide row between pre-filled
+    neighbours (forward: they must come back bit-unchanged; backward: they are NaN, a read of them enters the result)"""
+    M, ld = x.shape[0], (3 * D if wide else D)
+    (y_ref, y_tol), (n_ref, n_tol) = TB.layer_tol(TB.rownorm_fwd, x)
+    d_x, save_n = dev(x), fresh(M)
+    if wide:
+        side = TB.gauss((TB.SEED, 72, D, M), M, 3 * D)
+        cat = dev(side)
+        ok(lib, lib.t2l_blk_rownorm_fwd(ptr(d_x), M, D, slot(cat, D), ld, ptr(save_n)))
+        check_buffers((d_x, cat), (save_n,), what)
+        got = cat.cpu().numpy().astype(np.float64)
+        assert np.array_equal(got[:, :D], side[:, :D]) and np.array_equal(got[:, 2 * D:], side[:, 2 * D:]), f"{what}: a neighbouring slot changed"
+        y = cat[:, D:2 * D]
+    else:
+        y = fresh(M, D)
+        ok(lib, lib.t2l_blk_rownorm_fwd(ptr(d_x), M, D, ptr(y), ld, ptr(save_n)))
+        check_buffers((d_x,), (y, save_n), what)
+    w[0].hold(ratio(y, y_ref, y_tol), what + " y")
+    w[0].hold(ratio(save_n, n_ref, n_tol), what + " save_n")
+    yy, n = f32(y_ref), f32(n_ref)
+    ((dx_ref, dx_tol),) = TB.layer_tol(TB.rownorm_bwd, dy, yy, n)
+    d_n, dx = dev(n), fresh(M, D)
+    if wide:
+        pad = np.full((M, D), np.nan)
+        d_dy, d_yy = dev(np.concatenate([pad, dy, pad], axis=1)), dev(np.concatenate([pad, yy, pad], axis=1))
+        ok(lib, lib.t2l_blk_rownorm_bwd(slot(d_dy, D), slot(d_yy, D), ld, ptr(d_n), M, D, ptr(dx)))
+    else:
+        d_dy, d_yy = dev(dy), dev(yy)
+        ok(lib, lib.t2l_blk_rownorm_bwd(ptr(d_dy), ptr(d_yy), ld, ptr(d_n), M, D, ptr(dx)))
+    check_buffers((d_dy, d_yy, d_n), (dx,), what)
+    w[1].hold(ratio(dx, dx_ref, dx_tol), what + " dx")
+
+
+@pytest.mark.parametrize("D", (128, 256))
+def test_rownorm(lib, D):
+    """the fine step's width and the coarse step's; a lone row, a ragged last workgroup (four rows each), more than one workgroup"""
+    w = Worst(f"rownorm_fwd D={D}"), Worst(f"rownorm_bwd D={D}")
+    for M in (1, 3, 4, 5, 33):
+        x, dy = TB.gauss((TB.SEED, 70, D, M), M, D), TB.gauss((TB.SEED, 71, D, M), M, D)
+        for wide in (False, True):
+            rownorm_case(lib, w, D, x, dy, wide, f"M={M} ld={3 * D if wide else D}")
+    w[0].report()
+    w[1].report()
+
+
+@pytest.mark.parametrize("D", (128, 256))
+def test_rownorm_zero_rows(lib, D):
+    """all-zero rows, in tensors of their own (dx = dy / 1e-12 there would widen every other row's bound): the forward clamps the norm
+    at 1e-12 and returns zeros, the backward takes its n <= 1e-12 branch"""
+    w = Worst(f"rownorm_zero_fwd D={D}"), Worst(f"rownorm_zero_bwd D={D}")
+    rownorm_case(lib, w, D, np.zeros((2, D)), TB.gauss((TB.SEED, 73, D), 2, D), False, "zero rows")
+    w[0].report()
+    w[1].report()
+
+
+# ---- element-wise dropout, ReLU + dropout backward -------------------------------------------------------------------------------
+def test_dropout(lib):
+    """one element, a workgroup less one / exactly / plus one, several workgroups; the mask source has negative and exactly-zero
+    entries. A dropped or masked element is exactly the reference's zero (its bound is 0)."""
+    wf, wb = Worst("drop_fwd"), Worst("relu_drop_bwd")
+    for n in (1, 255, 256, 257, 1000):
+        h, d = TB.gauss((TB.SEED, 80, n), n), TB.gauss((TB.SEED, 81, n), n)
+        h[::7] = 0.0
+        if n == 1:
+            h[0] = 1.5  # (the lone element is live, so that both paths of it are seen over the two p)
+        assert n == 1 or ((h < 0).any() and (h == 0).any() and (h > 0).any())
+        d_h = dev(h)
+        for p in (0.0, TB.P_DROP):
+            what = f"n={n} p={p:.1f}"
+            fac = TB.drop_factor(TB.SEED, 6, p, (n,))
+            hd = fresh(n)
+            ok(lib, lib.t2l_blk_drop_fwd(ptr(d_h), n, ptr(hd), TB.SEED, 6, p))
+            check_buffers((d_h,), (hd,), what)
+            wf.hold(ratio(hd, *TB.drop_reference(h, fac)), what)
+            d_d = dev(d)  # in place: the gradient goes in, the masked gradient comes out
+            ok(lib, lib.t2l_blk_relu_drop_bwd(ptr(d_d), ptr(d_h), n, TB.SEED, 6, p))
+            check_buffers((d_h,), (d_d,), what)
+            wb.hold(ratio(d_d, *TB.drop_reference(h, fac, d)), what)
+    wf.report()
+    wb.report()
+
+
 # ---- pool + normalise, seq-max ------------------------------------------------------------------------------------------------
 def int_equal(t, ref):
     return np.array_equal(t.cpu().numpy().reshape(ref.shape), ref)
@@ -327,9 +417,10 @@ def test_pool_norm(lib):
     wb.report()
 
 
-@pytest.mark.parametrize("B,D,residual", [(3, 1024, False), (5, 256, True)])
+@pytest.mark.parametrize("B,D,residual", [(3, 1024, False), (5, 256, True), (3, 128, False)])
 def test_seq_max(lib, B, D, residual):
-    """the text head's two calls: over the tokens of a sentence (D 1024), over the sentences of a description with the residual (D 256)"""
+    """the text head's two calls: over the tokens of a sentence (D 1024), over the sentences of a description with the residual (D 256);
+    the fine step's: over a pair's hints (D 128)"""
     import torch
 
     wf, wb = Worst(f"seq_max_fwd D={D}"), Worst(f"seq_max_bwd D={D}")

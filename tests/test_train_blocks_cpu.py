@@ -2,6 +2,8 @@
 involved. For every product case of the GPU tier a float32 numpy.matmul of the modelled operands stays inside ``tol`` everywhere, and
 every mutant of the reference — the ways a tile kernel goes subtly wrong — leaves ``tol`` on at least one element. The wrappers'
 contract refusals need the dev library and no GPU."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -179,7 +181,7 @@ def test_wrappers_refuse_shapes_outside_the_contract(blocks):
         (L.t2l_blk_seq_max_bwd(n, n, 2, 64, 1024, n), "S > 32"),
         # instances the step does not build, empty problems, options out of range
         (L.t2l_blk_attn_fwd(n, n, n, 1, 8, 128, 1, 0, 0.0), "head dim"),
-        (L.t2l_blk_ln_fwd(n, n, 4, 512, n, n, n, n, n, 1, 0, 0.0), "D 256 or 1024"),
+        (L.t2l_blk_ln_fwd(n, n, 4, 512, n, n, n, n, n, 1, 0, 0.0), "D 128, 256 or 1024"),
         (L.t2l_blk_ln_bwd(n, n, n, 4, 1024, 16, n, n, n, n, n, 1, 0, 0.0), "(D, waves)"),
         (L.t2l_blk_ln_bwd(n, n, n, 0, 256, 16, n, n, n, n, n, 1, 0, 0.0), "T >= 1"),
         (L.t2l_blk_pool_norm_fwd(n, n, n, n, n, 0), "at least one cell"),
@@ -191,6 +193,55 @@ def test_wrappers_refuse_shapes_outside_the_contract(blocks):
     assert L.t2l_blk_gemm_nn(n, n, n, 64, 24, 64, 0, 2, 0) == -1 and b"multiple of 16" in L.t2l_blk_last_error()
     assert L.t2l_blk_attn_fwd(n, n, n, 1, 33, 64, 1, 0, 0.0) == -1 and b"S > 32" in L.t2l_blk_last_error()
     assert L.t2l_blk_gemm_tn(n, n, n, n, 64, 48, 64, 0, 0) == -1 and b"multiple of 32" in L.t2l_blk_last_error()
+
+
+def test_row_kernel_wrappers_name_the_reason_they_refuse(blocks):
+    """LayerNorm at the widths the steps build (128, 256, 1024), F.normalize at 128 and 256, the element-wise dropout pair: every
+    refusal is -1 with its reason, before any launch"""
+    L = blocks
+    n = None
+    x = ctypes.c_void_p(256)  # a non-null pointer that is never followed: the shape checks come first
+
+    def refused(rc, reason):
+        assert rc == -1 and reason in L.t2l_blk_last_error(), (rc, reason, L.t2l_blk_last_error())
+
+    for D in (0, 64, 192, 512, 2048):
+        refused(L.t2l_blk_ln_fwd(x, x, 4, D, x, x, x, x, x, 1, 0, 0.0), b"D 128, 256 or 1024")
+        refused(L.t2l_blk_ln_bwd(x, x, x, 4, D, 4, x, x, x, x, x, 1, 0, 0.0), b"(D, waves)")
+    for D, waves in ((128, 16), (1024, 16), (256, 8), (128, 0)):
+        refused(L.t2l_blk_ln_bwd(x, x, x, 4, D, waves, x, x, x, x, x, 1, 0, 0.0), b"(D, waves)")
+    for D in (128, 256, 1024):
+        refused(L.t2l_blk_ln_fwd(x, x, 0, D, x, x, x, x, x, 1, 0, 0.0), b"T >= 1")
+        refused(L.t2l_blk_ln_bwd(x, x, x, -1, D, 4, x, x, x, x, x, 1, 0, 0.0), b"T >= 1")
+        for p in (-0.1, 1.0, float("nan")):
+            refused(L.t2l_blk_ln_fwd(x, x, 4, D, x, x, x, x, x, 1, 0, p), b"p must be in [0, 1)")
+            refused(L.t2l_blk_ln_bwd(x, x, x, 4, D, 4, x, x, x, x, x, 1, 0, p), b"p must be in [0, 1)")
+        refused(L.t2l_blk_ln_fwd(n, n, 4, D, n, n, n, n, n, 1, 0, 0.0), b"null pointer")
+        refused(L.t2l_blk_ln_bwd(n, n, n, 4, D, 4, n, n, n, n, n, 1, 0, 0.0), b"null pointer")
+    for D in (0, 64, 192, 512, 1024):
+        refused(L.t2l_blk_rownorm_fwd(x, 4, D, x, 1024, x), b"D must be 128 or 256")
+        refused(L.t2l_blk_rownorm_bwd(x, x, 1024, x, 4, D, x), b"D must be 128 or 256")
+    for D in (128, 256):
+        for M in (0, -3):
+            refused(L.t2l_blk_rownorm_fwd(x, M, D, x, D, x), b"M >= 1")
+            refused(L.t2l_blk_rownorm_bwd(x, x, D, x, M, D, x), b"M >= 1")
+        for ld in (D - 1, 0, -D):
+            refused(L.t2l_blk_rownorm_fwd(x, 4, D, x, ld, x), b"ld < D")
+            refused(L.t2l_blk_rownorm_bwd(x, x, ld, x, 4, D, x), b"ld < D")
+        for args in ((n, 4, D, x, D, x), (x, 4, D, n, D, x), (x, 4, D, x, D, n)):
+            refused(L.t2l_blk_rownorm_fwd(*args), b"null pointer")
+        for args in ((n, x, D, x, 4, D, x), (x, n, D, x, 4, D, x), (x, x, D, n, 4, D, x), (x, x, D, x, 4, D, n)):
+            refused(L.t2l_blk_rownorm_bwd(*args), b"null pointer")
+    for cnt in (0, -1):
+        refused(L.t2l_blk_drop_fwd(x, cnt, x, 1, 0, 0.1), b"n >= 1")
+        refused(L.t2l_blk_relu_drop_bwd(x, x, cnt, 1, 0, 0.1), b"n >= 1")
+    for p in (-0.1, 1.0, float("nan")):
+        refused(L.t2l_blk_drop_fwd(x, 8, x, 1, 0, p), b"p must be in [0, 1)")
+        refused(L.t2l_blk_relu_drop_bwd(x, x, 8, 1, 0, p), b"p must be in [0, 1)")
+    refused(L.t2l_blk_drop_fwd(n, 8, x, 1, 0, 0.1), b"null pointer")
+    refused(L.t2l_blk_drop_fwd(x, 8, n, 1, 0, 0.1), b"null pointer")
+    refused(L.t2l_blk_relu_drop_bwd(n, x, 8, 1, 0, 0.1), b"null pointer")
+    refused(L.t2l_blk_relu_drop_bwd(x, n, 8, 1, 0, 0.1), b"null pointer")
 
 
 def test_wrappers_refuse_null_pointers_at_legal_shapes(blocks):

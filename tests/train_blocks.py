@@ -1,8 +1,8 @@
 """TEST INFRASTRUCTURE — float64 references, derived tolerances and the case lists of the training-block tier
 (tests/test_train_blocks_cpu.py, tests/test_gpu_train_blocks.py).
 
-Every block of the training step — a product of gemm_f32.h with its epilogue, attention, LayerNorm, pool + normalise, seq-max — is a
-continuous function of its inputs or takes its mask / arg-max as an input, so it has an exact float64 reference and an element-wise
+Every block of the training steps — a product of gemm_f32.h with its epilogue, attention, LayerNorm, F.normalize of a row, element-wise
+dropout, pool + normalise, seq-max — is a continuous function of its inputs or takes its mask / arg-max as an input, so it has an exact float64 reference and an element-wise
 bound. numpy only; the arithmetic comes from ``oracle.arith`` and ``oracle.t2l_oracle_train.dropout_keep``, never from the product.
 
 Products.  ``ref = arith.product(A, B, arithmetic) (+ bias) (+ C0)`` then the epilogue; per element
@@ -244,6 +244,32 @@ def ln_param_grads(dout, xhat, dg0, db0):
     return {"dgamma": colsum(dout * xhat, dg0), "dbeta": colsum(dout, db0)}
 
 
+def rownorm_fwd(x, dtype):
+    """x [M, D] -> (y, n): F.normalize(x, dim=-1) and the norm it divides by (clamped at 1e-12)"""
+    x = x.astype(dtype)
+    n = np.maximum(np.sqrt((x * x).sum(axis=1, dtype=dtype)), dtype(NORM_EPS))
+    return x / n[:, None], n
+
+
+def rownorm_bwd(dy, y, n, dtype):
+    """-> (dx [M, D],): (dy - y (dy . y)) / n, and dy / 1e-12 for a row whose norm sits at the clamp"""
+    dy, y, n = dy.astype(dtype), y.astype(dtype), n.astype(dtype)[:, None]
+    t = (dy * y).sum(axis=1, keepdims=True, dtype=dtype)
+    return (np.where(n <= dtype(NORM_EPS), dy / dtype(NORM_EPS), (dy - y * t) / n),)
+
+
+def drop_reference(h, factor, d=None):
+    """(ref, tol) of drop_fwd — hd = h * factor — or, with d, of relu_drop_bwd — d * factor where h > 0, else 0. ``layer_tol``'s bound
+    on the elements that are kept; 0 (the value must be the reference's exactly) on the dropped and the masked ones."""
+    live = factor > 0 if d is None else (factor > 0) & (h > 0)
+
+    def fn(v, dtype):
+        return (np.where(live, v.astype(dtype) * factor.astype(dtype), dtype(0.0)),)
+
+    ((ref, tol),) = layer_tol(fn, h if d is None else d)
+    return ref, np.where(live, tol, 0.0)
+
+
 def pool_norm_fwd(X, dtype):
     """X [B, 28, 256] -> (out [B, 256], save_n [B]); the arg-max is ``first_argmax(X)`` (exact: no arithmetic before the comparison)"""
     mx = X.astype(dtype).max(axis=1)
@@ -298,6 +324,10 @@ def load_blocks():
         "t2l_blk_attn_bwd": [p, p, p, p, i, i, i, u, i, f],
         "t2l_blk_ln_fwd": [p, p, i, i, p, p, p, p, p, u, i, f],
         "t2l_blk_ln_bwd": [p, p, p, i, i, i, p, p, p, p, p, u, i, f],
+        "t2l_blk_rownorm_fwd": [p, i, i, p, i, p],
+        "t2l_blk_rownorm_bwd": [p, p, i, p, i, i, p],
+        "t2l_blk_drop_fwd": [p, C.c_int64, p, u, i, f],
+        "t2l_blk_relu_drop_bwd": [p, p, C.c_int64, u, i, f],
         "t2l_blk_pool_norm_fwd": [p, p, p, p, p, i],
         "t2l_blk_pool_norm_bwd": [p, p, p, p, p, i],
         "t2l_blk_seq_max_fwd": [p, p, i, i, i, p, p],

@@ -10,11 +10,20 @@
 //                             state of this context's own)
 //   t2l_fine_train_backward : d offsets -> parameter gradients ADDED into the bound .grad buffers, d hint encodings, d features2,
 //                             and on through the backbone after a points forward when it is bound with gradients
-// Everything is f32 on the vector ALU: a row-major tiled GEMM (64x64 tiles, strided operands so one kernel serves X·Wᵀ, dY·W and
-// the weight gradients dYᵀ·X, the latter split over the rows with float atomics), one workgroup per (pair, head) for attention
-// forward / backward, one wave per 128-wide row for residual + dropout + LayerNorm and F.normalize, one workgroup per column for
-// BatchNorm. Activations of the last forward stay in a context-owned arena until the next forward (backward may run again on
-// them: it reads the saved activations only). DESIGN.md §3.7b.
+// Everything is f32 on the vector ALU. Residual + dropout + LayerNorm, F.normalize, the feed-forward dropout with its ReLU backward
+// and the max over the hints are the coarse step's row kernels (train_kernels.h) at width 128, reached through train.hip's launchers
+// (train_common.h). The kernels below are the ones the coarse step has no counterpart for:
+//   k_gemm / k_colsum        a row-major tiled GEMM (64x64 tiles) over STRIDED operands, so one kernel serves X·Wᵀ, dY·W and the weight
+//                            gradients dYᵀ·X (split over the rows with float atomics), at K = 1 or 3 and N = 2 too (gemm_f32.h wants
+//                            N % 32 == 0 and K % 16 == 0)
+//   k_attn_fwd / k_attn_bwd  one workgroup per (pair, head), CROSS-attention: Tq != Tk, separate Q / K / V strides (the coarse kernel
+//                            is self-attention on packed qkv, its S = 28 instance latency-tuned); dmask is their dropout factor
+//   k_bn_fwd / k_bn_bwd      BatchNorm + ReLU over plain rows, one workgroup per column (the coarse forms are per-job accumulators or
+//                            have no ReLU)
+//   k_gather / k_scatter_add / k_num_in   the embedding lookup that answers an out-of-range index with a zero row, its backward,
+//                            num_encoder's input
+// Moving one of these would change arithmetic or speed, not spelling. Activations of the last forward stay in a context-owned arena
+// until the next forward (backward may run again on them: it reads the saved activations only). DESIGN.md §3.7b.
 #include <math.h>
 #include <string.h>
 
@@ -25,21 +34,18 @@ namespace t2l {
 namespace ft {
 
 constexpr int kW = 128, kObj = 16, kHintMax = 8, kHeads = 4, kHd = 32, kFF = 512;
-constexpr float kLnEps = 1e-5f, kBnEps = 1e-5f, kBnMom = 0.1f, kNormEps = 1e-12f;
+constexpr float kBnEps = 1e-5f, kBnMom = 0.1f;
+constexpr int kLnWaves = 4;  // waves per workgroup of the LayerNorm backward (train.hip: ln_bwd_launch)
 
-// shared with the coarse step (train_common.h): the a9 dropout rule — Drop, keep_bit, make_drop(seed, site, p) — and num_encoder's constants
+// shared with the coarse step (train_common.h): the a9 dropout rule — Drop, keep_bit, make_drop(seed, site, p) —, num_encoder's
+// constants, the arena and the row kernels' launchers
+using train::Arena;
 using train::Drop;
 using train::keep_bit;
 using train::make_drop;
 
 __device__ __forceinline__ float dmask(const Drop& d, uint32_t idx) {
   return d.thr ? (keep_bit(d.key, idx, d.thr) ? d.scale : 0.f) : 1.f;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // ---- C[M,N] (=|+=) A[M,K]·B[K,N] (+ bias[n]) (ReLU); A(m,k) = A[m*sam + k*sak], B(k,n) = B[k*sbk + n*sbn] -------------
@@ -196,34 +202,6 @@ __global__ __launch_bounds__(256) void k_bn_bwd(const float* dout, const float* 
   }
 }
 
-// F.normalize over 128-wide rows, one wave per row
-__global__ __launch_bounds__(256) void k_l2n_fwd(const float* X, int64_t ldx, int M, float* Y, int64_t ldy, float* nrm) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
-  if (row >= M) return;
-  const float a = X[(int64_t)row * ldx + l], b = X[(int64_t)row * ldx + l + 64];
-  const float n = fmaxf(sqrtf(wave_sum(a * a + b * b)), kNormEps);
-  Y[(int64_t)row * ldy + l] = a / n;
-  Y[(int64_t)row * ldy + l + 64] = b / n;
-  if (l == 0) nrm[row] = n;
-}
-
-__global__ __launch_bounds__(256) void k_l2n_bwd(const float* dY, int64_t ldd, const float* Y, int64_t ldy, const float* nrm, int M,
-                                                 float* dX, int64_t ldx) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
-  if (row >= M) return;
-  const float da = dY[(int64_t)row * ldd + l], db = dY[(int64_t)row * ldd + l + 64];
-  const float ya = Y[(int64_t)row * ldy + l], yb = Y[(int64_t)row * ldy + l + 64];
-  const float n = nrm[row];
-  if (n <= kNormEps) {
-    dX[(int64_t)row * ldx + l] = da / kNormEps;
-    dX[(int64_t)row * ldx + l + 64] = db / kNormEps;
-    return;
-  }
-  const float dot = wave_sum(ya * da + yb * db);
-  dX[(int64_t)row * ldx + l] = (da - ya * dot) / n;
-  dX[(int64_t)row * ldx + l + 64] = (db - yb * dot) / n;
-}
-
 // nn.Embedding lookup and its backward (padding_idx = 0 gets no gradient; out-of-range rows read zero and get nothing)
 __global__ void k_gather(const float* table, int rows, const int32_t* idx, int M, float* out) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -347,98 +325,6 @@ __global__ __launch_bounds__(256) void k_attn_bwd(const float* Q, int64_t ldq, c
   }
 }
 
-// Y = LayerNorm(X + dropout(S)) over 128-wide rows (one wave per row); x̂ and 1/σ saved
-__global__ __launch_bounds__(256) void k_add_ln_fwd(const float* X, const float* S, int M, const float* g, const float* b, Drop dr,
-                                                    float* xhat, float* rstd, float* Y) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
-  if (row >= M) return;
-  const int64_t i0 = (int64_t)row * kW + l, i1 = i0 + 64;
-  const float z0 = X[i0] + S[i0] * dmask(dr, (uint32_t)i0), z1 = X[i1] + S[i1] * dmask(dr, (uint32_t)i1);
-  const float mean = wave_sum(z0 + z1) * (1.f / kW);
-  const float d0 = z0 - mean, d1 = z1 - mean;
-  const float r = 1.f / sqrtf(wave_sum(d0 * d0 + d1 * d1) * (1.f / kW) + kLnEps);
-  const float x0 = d0 * r, x1 = d1 * r;
-  xhat[i0] = x0;
-  xhat[i1] = x1;
-  Y[i0] = fmaf(x0, g[l], b[l]);
-  Y[i1] = fmaf(x1, g[l + 64], b[l + 64]);
-  if (l == 0) rstd[row] = r;
-}
-
-// backward of k_add_ln_fwd: dZ = d loss / d (X + dropout(S)) (the residual's gradient), dS = dZ through the dropout mask;
-// dg / db summed over the block's 32 rows, then added with float atomics
-__global__ __launch_bounds__(256) void k_ln_bwd(const float* dY, const float* xhat, const float* rstd, const float* g, int M,
-                                                Drop dr, float* dZ, float* dS, float* dg, float* db) {
-  __shared__ float red[2][4][kW];
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  float g0 = 0.f, g1 = 0.f, b0 = 0.f, b1 = 0.f;
-  const float ga = g[l], gb = g[l + 64];
-  for (int rr = 0; rr < 8; ++rr) {
-    const int row = blockIdx.x * 32 + w * 8 + rr;
-    if (row >= M) break;
-    const int64_t i0 = (int64_t)row * kW + l, i1 = i0 + 64;
-    const float y0 = dY[i0], y1 = dY[i1], x0 = xhat[i0], x1 = xhat[i1];
-    g0 += y0 * x0;
-    g1 += y1 * x1;
-    b0 += y0;
-    b1 += y1;
-    const float h0 = y0 * ga, h1 = y1 * gb;
-    const float m1 = wave_sum(h0 + h1) * (1.f / kW), m2 = wave_sum(h0 * x0 + h1 * x1) * (1.f / kW);
-    const float r = rstd[row];
-    const float z0 = r * (h0 - m1 - x0 * m2), z1 = r * (h1 - m1 - x1 * m2);
-    dZ[i0] = z0;
-    dZ[i1] = z1;
-    dS[i0] = z0 * dmask(dr, (uint32_t)i0);
-    dS[i1] = z1 * dmask(dr, (uint32_t)i1);
-  }
-  red[0][w][l] = g0;
-  red[0][w][l + 64] = g1;
-  red[1][w][l] = b0;
-  red[1][w][l + 64] = b1;
-  __syncthreads();
-  const int c = threadIdx.x & 127, which = threadIdx.x >> 7;
-  const float v = red[which][0][c] + red[which][1][c] + red[which][2][c] + red[which][3][c];
-  float* dst = which ? db : dg;
-  if (dst) atomicAdd(&dst[c], v);
-}
-
-// the feed-forward dropout after ReLU(linear1): forward Y = X·mask, backward dX = dY·mask·[H > 0] (in place)
-__global__ void k_dropout(const float* X, int64_t n, Drop dr, float* Y) {
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e < n) Y[e] = X[e] * dmask(dr, (uint32_t)e);
-}
-
-__global__ void k_drop_relu_bwd(float* dY, const float* H, int64_t n, Drop dr) {
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e < n) dY[e] = H[e] > 0.f ? dY[e] * dmask(dr, (uint32_t)e) : 0.f;
-}
-
-// max over the hints (first maximum wins a tie) and its backward
-__global__ void k_pool(const float* X, int P, int H, float* out, int32_t* arg) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= P * kW) return;
-  const int p = e / kW, c = e % kW;
-  float m = X[((int64_t)p * H) * kW + c];
-  int a = 0;
-  for (int t = 1; t < H; ++t) {
-    const float v = X[((int64_t)p * H + t) * kW + c];
-    if (v > m) {
-      m = v;
-      a = t;
-    }
-  }
-  out[e] = m;
-  arg[e] = a;
-}
-
-__global__ void k_pool_bwd(const float* dOut, const int32_t* arg, int P, int H, float* dX) {
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (int64_t)P * H * kW) return;
-  const int64_t p = e / ((int64_t)H * kW);
-  const int t = (int)((e / kW) % H), c = (int)(e % kW);
-  dX[e] = arg[p * kW + c] == t ? dOut[p * kW + c] : 0.f;
-}
-
 // ------------------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------------------
@@ -490,13 +376,13 @@ struct FineTrain {
   // backward scratch
   float *gA0, *gB0, *gA1, *gB1, *t_dx1, *t_dx2, *t_ds, *t_do, *t_dq, *t_dkv, *t_dh, *dE, *ta, *tb, *dpool, *da1;
   float* dpn = nullptr;  // d features2 on its way into the backbone's backward (when the caller passes no grad_pn_feat)
-  char* arena = nullptr;
-  size_t cap = 0;
+  float* sink = nullptr;  // [2][128], never read: where the LayerNorm backward adds d weight / d bias of a frozen norm
+  Arena ws;               // one allocation for all of the above
 };
 
 static void free_ft(FineTrain* st) {
   if (!st) return;
-  if (st->arena) (void)hipFree(st->arena);
+  if (st->ws.base) (void)hipFree(st->ws.base);
   pn_train_release(st->pn);
   delete st;
 }
@@ -535,19 +421,8 @@ static void lin_dw(hipStream_t s, const float* dY, int64_t ldd, const float* X, 
   if (db) hipLaunchKernelGGL(k_colsum, dim3(nblk(N, 64), nblk(M, 256)), dim3(256), 0, s, dY, ldd, M, N, db);
 }
 
-struct Bump {
-  char* base;
-  size_t off = 0;
-  template <class T>
-  T* take(int64_t n) {
-    T* p = base ? (T*)(base + off) : nullptr;
-    off += ((size_t)n * sizeof(T) + 255) & ~(size_t)255;
-    return p;
-  }
-};
-
 // every pointer of the step inside one arena (count pass with base == null, then the real pass)
-static void plan(FineTrain* st, Bump& a, int P, int H, float p) {
+static void plan(FineTrain* st, Arena& a, int P, int H, float p) {
   const int M0 = P * kObj, M1 = P * H, Mx = M0 > M1 ? M0 : M1;
   for (auto& b : st->br) {
     if (!b.used) continue;
@@ -614,53 +489,54 @@ static void plan(FineTrain* st, Bump& a, int P, int H, float p) {
   st->dpool = a.take<float>((int64_t)P * kW);
   st->da1 = a.take<float>((int64_t)P * 64);
   st->dpn = st->pn ? a.take<float>((int64_t)M0 * 256) : nullptr;
+  st->sink = a.take<float>(2 * kW);
 }
 
-static void add_ln(hipStream_t s, const float* X, const float* S, int M, const Ten& g, const Ten& b, Drop dr, float* xh, float* r, float* Y) {
-  hipLaunchKernelGGL(k_add_ln_fwd, dim3(nblk(M, 4)), dim3(256), 0, s, X, S, M, g.d, b.d, dr, xh, r, Y);
-}
-
-// one nn.TransformerDecoderLayer (post-norm, ReLU, no masks) in training mode: L.x [P*Tq,128] attends itself, then L.mem
-static void dec_fwd(FineTrain* st, DecLayer& L, float p, uint32_t seed, float* tmp, hipStream_t s) {
+// one nn.TransformerDecoderLayer (post-norm, ReLU, no masks) in training mode: L.x [P*Tq,128] attends itself, then L.mem.
+// false (here and in dec_bwd): a row kernel has no instance of width 128
+static bool dec_fwd(FineTrain* st, DecLayer& L, float p, uint32_t seed, float* tmp, hipStream_t s) {
   const int P = st->P, M = P * L.Tq, Mm = P * L.Tk;
+  // Y = LayerNorm(X + dropout(S)); x̂ and 1/σ saved
+  auto ln_fwd = [&](const float* X, const float* S, const Ten& g, const Ten& b, int site, float* xh, float* r, float* Y) {
+    return ln_fwd_rows(kW, X, S, M, g.d, b.d, make_drop(seed, site, p), Y, xh, r, s);
+  };
   // self-attention block + dropout1 + norm1
   lin_fwd(s, L.x, kW, M, kW, L.in_w.d, kW, L.in_b.d, 3 * kW, L.qkv, 3 * kW);
   hipLaunchKernelGGL(k_attn_fwd, dim3(P * kHeads), dim3(256), 0, s, L.qkv, (int64_t)3 * kW, L.qkv + kW, (int64_t)3 * kW, L.qkv + 2 * kW,
                      (int64_t)3 * kW, L.Tq, L.Tq, L.Ps, L.os, (int64_t)kW, make_drop(seed, L.site + 0, p));
   lin_fwd(s, L.os, kW, M, kW, L.out_w.d, kW, L.out_b.d, kW, tmp, kW);
-  add_ln(s, L.x, tmp, M, L.n1_w, L.n1_b, make_drop(seed, L.site + 1, p), L.xh1, L.r1, L.x1);
+  bool ok = ln_fwd(L.x, tmp, L.n1_w, L.n1_b, L.site + 1, L.xh1, L.r1, L.x1);
   // cross-attention block + dropout2 + norm2
   lin_fwd(s, L.x1, kW, M, kW, L.cin_w.d, kW, L.cin_b.d, kW, L.q2, kW);
   lin_fwd(s, L.mem, kW, Mm, kW, L.cin_w.d + kW * kW, kW, L.cin_b.d + kW, 2 * kW, L.kv2, 2 * kW);
   hipLaunchKernelGGL(k_attn_fwd, dim3(P * kHeads), dim3(256), 0, s, L.q2, (int64_t)kW, L.kv2, (int64_t)2 * kW, L.kv2 + kW, (int64_t)2 * kW,
                      L.Tq, L.Tk, L.Pc, L.oc, (int64_t)kW, make_drop(seed, L.site + 2, p));
   lin_fwd(s, L.oc, kW, M, kW, L.cout_w.d, kW, L.cout_b.d, kW, tmp, kW);
-  add_ln(s, L.x1, tmp, M, L.n2_w, L.n2_b, make_drop(seed, L.site + 3, p), L.xh2, L.r2, L.x2);
+  ok = ln_fwd(L.x1, tmp, L.n2_w, L.n2_b, L.site + 3, L.xh2, L.r2, L.x2) && ok;
   // feed-forward block + dropout3 + norm3
   lin_fwd(s, L.x2, kW, M, kW, L.l1_w.d, kW, L.l1_b.d, kFF, L.h1, kFF, 1);
-  if (L.h1d != L.h1)
-    hipLaunchKernelGGL(k_dropout, dim3(nblk((int64_t)M * kFF, 256)), dim3(256), 0, s, L.h1, (int64_t)M * kFF, make_drop(seed, L.site + 4, p),
-                       L.h1d);
+  if (L.h1d != L.h1) drop_fwd_launch(L.h1, (size_t)M * kFF, make_drop(seed, L.site + 4, p), L.h1d, s);
   lin_fwd(s, L.h1d, kFF, M, kFF, L.l2_w.d, kFF, L.l2_b.d, kW, tmp, kW);
-  add_ln(s, L.x2, tmp, M, L.n3_w, L.n3_b, make_drop(seed, L.site + 5, p), L.xh3, L.r3, L.out);
+  return ln_fwd(L.x2, tmp, L.n3_w, L.n3_b, L.site + 5, L.xh3, L.r3, L.out) && ok;
 }
 
 // backward of dec_fwd: dout -> dx (written), d mem ADDED to dmem
-static void dec_bwd(FineTrain* st, DecLayer& L, float p, uint32_t seed, const float* dout, float* dx, float* dmem, hipStream_t s) {
+static bool dec_bwd(FineTrain* st, DecLayer& L, float p, uint32_t seed, const float* dout, float* dx, float* dmem, hipStream_t s) {
   const int P = st->P, M = P * L.Tq, Mm = P * L.Tk;
   float *dx2 = st->t_dx2, *dx1 = st->t_dx1, *ds = st->t_ds, *dob = st->t_do, *dq = st->t_dq, *dkv = st->t_dkv, *dh = st->t_dh;
+  // dZ = d loss / d (X + dropout(S)) (the residual's gradient), dS = dZ through the dropout mask; d weight / d bias added
+  auto ln_bwd = [&](const float* dY, const float* xh, const float* r, const Ten& g, const Ten& b, int site, float* dZ) {
+    return ln_bwd_rows(kW, kLnWaves, dY, xh, r, M, g.d, make_drop(seed, site, p), dZ, ds, g.g ? g.g : st->sink, b.g ? b.g : st->sink + kW, s);
+  };
   // norm3 / dropout3 / feed-forward
-  hipLaunchKernelGGL(k_ln_bwd, dim3(nblk(M, 32)), dim3(256), 0, s, dout, L.xh3, L.r3, L.n3_w.d, M, make_drop(seed, L.site + 5, p), dx2, ds,
-                     L.n3_w.g, L.n3_b.g);
+  bool ok = ln_bwd(dout, L.xh3, L.r3, L.n3_w, L.n3_b, L.site + 5, dx2);
   lin_dw(s, ds, kW, L.h1d, kFF, M, kW, kFF, L.l2_w.g, kFF, L.l2_b.g);
   lin_dx(s, ds, kW, M, kW, L.l2_w.d, kFF, kFF, dh, kFF, 0);
-  hipLaunchKernelGGL(k_drop_relu_bwd, dim3(nblk((int64_t)M * kFF, 256)), dim3(256), 0, s, dh, L.h1, (int64_t)M * kFF,
-                     make_drop(seed, L.site + 4, p));
+  relu_drop_bwd_launch(dh, L.h1, (size_t)M * kFF, make_drop(seed, L.site + 4, p), s);
   lin_dw(s, dh, kFF, L.x2, kW, M, kFF, kW, L.l1_w.g, kW, L.l1_b.g);
   lin_dx(s, dh, kFF, M, kFF, L.l1_w.d, kW, kW, dx2, kW, 1);
   // norm2 / dropout2 / cross-attention
-  hipLaunchKernelGGL(k_ln_bwd, dim3(nblk(M, 32)), dim3(256), 0, s, dx2, L.xh2, L.r2, L.n2_w.d, M, make_drop(seed, L.site + 3, p), dx1, ds,
-                     L.n2_w.g, L.n2_b.g);
+  ok = ln_bwd(dx2, L.xh2, L.r2, L.n2_w, L.n2_b, L.site + 3, dx1) && ok;
   lin_dw(s, ds, kW, L.oc, kW, M, kW, kW, L.cout_w.g, kW, L.cout_b.g);
   lin_dx(s, ds, kW, M, kW, L.cout_w.d, kW, kW, dob, kW, 0);
   hipLaunchKernelGGL(k_attn_bwd, dim3(P * kHeads), dim3(256), 0, s, L.q2, (int64_t)kW, L.kv2, (int64_t)2 * kW, L.kv2 + kW, (int64_t)2 * kW,
@@ -671,8 +547,7 @@ static void dec_bwd(FineTrain* st, DecLayer& L, float p, uint32_t seed, const fl
   lin_dw(s, dkv, 2 * kW, L.mem, kW, Mm, 2 * kW, kW, L.cin_w.g ? L.cin_w.g + kW * kW : nullptr, kW, L.cin_b.g ? L.cin_b.g + kW : nullptr);
   lin_dx(s, dkv, 2 * kW, Mm, 2 * kW, L.cin_w.d + kW * kW, kW, kW, dmem, kW, 1);
   // norm1 / dropout1 / self-attention
-  hipLaunchKernelGGL(k_ln_bwd, dim3(nblk(M, 32)), dim3(256), 0, s, dx1, L.xh1, L.r1, L.n1_w.d, M, make_drop(seed, L.site + 1, p), dx, ds,
-                     L.n1_w.g, L.n1_b.g);
+  ok = ln_bwd(dx1, L.xh1, L.r1, L.n1_w, L.n1_b, L.site + 1, dx) && ok;
   lin_dw(s, ds, kW, L.os, kW, M, kW, kW, L.out_w.g, kW, L.out_b.g);
   lin_dx(s, ds, kW, M, kW, L.out_w.d, kW, kW, dob, kW, 0);
   hipLaunchKernelGGL(k_attn_bwd, dim3(P * kHeads), dim3(256), 0, s, L.qkv, (int64_t)3 * kW, L.qkv + kW, (int64_t)3 * kW, L.qkv + 2 * kW,
@@ -680,6 +555,7 @@ static void dec_bwd(FineTrain* st, DecLayer& L, float p, uint32_t seed, const fl
                      L.Tq, L.Tq, make_drop(seed, L.site + 0, p));
   lin_dw(s, dq, 3 * kW, L.x, kW, M, 3 * kW, kW, L.in_w.g, kW, L.in_b.g);
   lin_dx(s, dq, 3 * kW, M, 3 * kW, L.in_w.d, kW, kW, dx, kW, 1);
+  return ok;
 }
 
 static void bn_layer_fwd(BnLayer& l, const float* x, int M, hipStream_t s) {
@@ -868,18 +744,17 @@ int fine_train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, const floa
     L.Tq = L.obj ? kObj : n_hints;
     L.Tk = L.obj ? n_hints : kObj;
   }
-  Bump count{nullptr};
+  Arena count;  // (no base: the count pass)
   plan(st, count, n_pairs, n_hints, p);
-  if (count.off > st->cap) {
+  if (count.off > st->ws.cap) {
     T2L_HIP(ctx, hipStreamSynchronize(s));  // the old arena may still be read by queued work of this stream
-    if (st->arena) (void)hipFree(st->arena);
-    st->arena = nullptr;
-    st->cap = 0;
-    T2L_HIP(ctx, hipMalloc(&st->arena, count.off));
-    st->cap = count.off;
+    if (st->ws.base) (void)hipFree(st->ws.base);
+    st->ws = Arena{};
+    T2L_HIP(ctx, hipMalloc(&st->ws.base, count.off));
+    st->ws.cap = count.off;
   }
-  Bump real{st->arena};
-  plan(st, real, n_pairs, n_hints, p);
+  st->ws.off = 0;
+  plan(st, st->ws, n_pairs, n_hints, p);
   st->class_idx = in->class_idx;
   st->color_idx = in->color_idx;
   st->rgb = in->rgb;
@@ -888,7 +763,8 @@ int fine_train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, const floa
   st->pn_feat = pn_feat;
   st->hint = hint_desc;
   const int P = n_pairs, M0 = P * kObj;
-  const int64_t ldE = (int64_t)st->n_feat * kW;
+  const int ldE = st->n_feat * kW;
+  bool ok = true;  // every row kernel has its instance of width 128
   // ---- ObjectEncoder (object_encoder.py:102-149) + F.normalize (cross_matcher.py:103-104)
   int col = 0;
   for (int f = 0; f < 4; ++f) {
@@ -908,7 +784,7 @@ int fine_train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, const floa
       }
       last = x;
     }
-    hipLaunchKernelGGL(k_l2n_fwd, dim3(nblk(M0, 4)), dim3(256), 0, s, last, (int64_t)kW, M0, st->E + col * kW, ldE, br.nrm);
+    ok = rownorm_rows(true, kW, last, nullptr, st->E + col * kW, br.nrm, M0, ldE, s) && ok;
     ++col;
   }
   if (st->pn_stats) bn_layer_fwd(st->pn_only, pn_feat, M0, s);  // running statistics only
@@ -917,20 +793,21 @@ int fine_train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, const floa
     bn_layer_fwd(st->merge, st->E, M0, s);
     feat = st->merge.out;
   }
-  hipLaunchKernelGGL(k_l2n_fwd, dim3(nblk(M0, 4)), dim3(256), 0, s, feat, (int64_t)kW, M0, st->D0, (int64_t)kW, st->nrm0);
+  ok = rownorm_rows(true, kW, feat, nullptr, st->D0, st->nrm0, M0, kW, s) && ok;
   // ---- CCAT (cross_matcher.py:109-124)
   const float *obj = st->D0, *hint = hint_desc;
   for (auto& L : st->dec) {
     L.x = L.obj ? obj : hint;
     L.mem = L.obj ? hint : obj;
-    dec_fwd(st, L, p, seed, st->t_ds, s);
+    ok = dec_fwd(st, L, p, seed, st->t_ds, s) && ok;
     (L.obj ? obj : hint) = L.out;
   }
   // ---- max over the hints + mlp_offsets (cross_matcher.py:126-131)
-  hipLaunchKernelGGL(k_pool, dim3(nblk((int64_t)P * kW, 256)), dim3(256), 0, s, hint, P, n_hints, st->pool, st->arg);
+  seq_max_fwd_launch(hint, nullptr, P, n_hints, kW, st->pool, st->arg, s);
   lin_fwd(s, st->pool, kW, P, kW, st->o0w.d, kW, st->o0b.d, 64, st->a1, 64, 1);
   lin_fwd(s, st->a1, 64, P, 64, st->o2w.d, 64, st->o2b.d, 2, out, 2);
   T2L_HIP(ctx, hipGetLastError());
+  if (!ok) return fail(ctx, T2L_ESTATE, "fine_train_forward: the row kernels have no instance of width 128");
   st->have_fwd = true;
   st->p = p;
   st->seed = seed;
@@ -971,20 +848,21 @@ int fine_train_backward_impl(t2l_ctx* ctx, const float* grad_offsets, float* gra
   // head
   lin_dw(s, grad_offsets, 2, st->a1, 64, P, 2, 64, st->o2w.g, 64, st->o2b.g);
   lin_dx(s, grad_offsets, 2, P, 2, st->o2w.d, 64, 64, st->da1, 64, 0);
-  hipLaunchKernelGGL(k_drop_relu_bwd, dim3(nblk((int64_t)P * 64, 256)), dim3(256), 0, s, st->da1, st->a1, (int64_t)P * 64, Drop{});
+  relu_drop_bwd_launch(st->da1, st->a1, (size_t)P * 64, Drop{}, s);  // (no dropout: the plain ReLU backward)
   lin_dw(s, st->da1, 64, st->pool, kW, P, 64, kW, st->o0w.g, kW, st->o0b.g);
   lin_dx(s, st->da1, 64, P, 64, st->o0w.d, kW, kW, st->dpool, kW, 0);
   float *g1 = st->gA1, *g1n = st->gB1, *g0 = st->gA0, *g0n = st->gB0;
-  hipLaunchKernelGGL(k_pool_bwd, dim3(nblk((int64_t)M1 * kW, 256)), dim3(256), 0, s, st->dpool, st->arg, P, H, g1);
+  seq_max_bwd_launch(st->dpool, st->arg, P, H, kW, g1, s);
+  bool ok = true;
   T2L_HIP(ctx, hipMemsetAsync(g0, 0, (size_t)M0 * kW * sizeof(float), s));
   // CCAT, reverse cascade order
   for (int i = (int)st->dec.size() - 1; i >= 0; --i) {
     DecLayer& L = st->dec[i];
     if (L.obj) {
-      dec_bwd(st, L, p, seed, g0, g0n, g1, s);
+      ok = dec_bwd(st, L, p, seed, g0, g0n, g1, s) && ok;
       std::swap(g0, g0n);
     } else {
-      dec_bwd(st, L, p, seed, g1, g1n, g0, s);
+      ok = dec_bwd(st, L, p, seed, g1, g1n, g0, s) && ok;
       std::swap(g1, g1n);
     }
   }
@@ -992,17 +870,16 @@ int fine_train_backward_impl(t2l_ctx* ctx, const float* grad_offsets, float* gra
   if (grad_pn && st->pn_stats)  // features2 fed the statistics only: d loss / d features2 = 0
     T2L_HIP(ctx, hipMemsetAsync(grad_pn, 0, (size_t)M0 * 256 * sizeof(float), s));
   // ObjectEncoder
-  const int64_t ldE = (int64_t)st->n_feat * kW;
+  const int ldE = st->n_feat * kW;
   float* dfeat = st->n_feat > 1 ? st->ta : st->dE;
-  hipLaunchKernelGGL(k_l2n_bwd, dim3(nblk(M0, 4)), dim3(256), 0, s, g0, (int64_t)kW, st->D0, (int64_t)kW, st->nrm0, M0, dfeat, (int64_t)kW);
+  ok = rownorm_rows(false, kW, g0, st->D0, dfeat, st->nrm0, M0, kW, s) && ok;
   if (st->n_feat > 1) bn_layer_bwd(st->merge, st->ta, M0, st->tb, st->dE, s);
   int col = 0;
   for (int f = 0; f < 4; ++f) {
     Branch& br = st->br[f];
     if (!br.used) continue;
     float* draw = br.embed ? st->ta : st->gA0;  // d of the branch output before its F.normalize
-    hipLaunchKernelGGL(k_l2n_bwd, dim3(nblk(M0, 4)), dim3(256), 0, s, st->dE + col * kW, ldE, st->E + col * kW, ldE, br.nrm, M0, draw,
-                       (int64_t)kW);
+    ok = rownorm_rows(false, kW, st->dE + col * kW, st->E + col * kW, draw, br.nrm, M0, ldE, s) && ok;
     if (br.embed) {
       if (br.table.g)
         hipLaunchKernelGGL(k_scatter_add, dim3(nblk((int64_t)M0 * kW, 256)), dim3(256), 0, s, st->ta, (int)(br.table.n / kW),
@@ -1019,6 +896,7 @@ int fine_train_backward_impl(t2l_ctx* ctx, const float* grad_offsets, float* gra
     ++col;
   }
   T2L_HIP(ctx, hipGetLastError());
+  if (!ok) return fail(ctx, T2L_ESTATE, "fine_train_backward: the row kernels have no instance of width 128");
   if (pn_bwd) return pn_train_backward_on(ctx, st->pn, "fine_train_backward", dpn, s);
   return T2L_OK;
 }

@@ -299,6 +299,14 @@ static void gemm_tn_nn_multi(int n, const float* const* dY, const float* const* 
   }
   hipLaunchKernelGGL(gemm_pair_multi_kernel, dim3(pair_blocks, n), dim3(256), 0, s, gp);
 }
+// element-wise dropout of n values (the feed-forward hidden dropout), and the ReLU (h > 0) + dropout backward in place; both training
+// steps' (train_common.h)
+void drop_fwd_launch(const float* h, size_t n, const Drop& dr, float* hd, hipStream_t s) {
+  hipLaunchKernelGGL(drop_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h, n, dr, hd);
+}
+void relu_drop_bwd_launch(float* d, const float* h, size_t n, const Drop& dr, hipStream_t s) {
+  hipLaunchKernelGGL(relu_drop_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d, h, n, dr);
+}
 // ---- one TransformerEncoderLayer, for the object branch and the text head alike -----------------------------------------------
 // What differs between the two states' Linear products. The text head's run on the tiled LDS-ring GEMM of text_head.hip (fast_gemm:
 // 256 x 256 tiles, bf16 planes, split-bf16 by default — 466 GFLOP per step at B = 64 are GEMM-shaped work that the object branch's
@@ -323,10 +331,7 @@ static void t_gemm_tn_nn(const Products& pr, const float* dY, const float* X, fl
     (void)fast_gemm(pr.ctx, dY, true, X, true, nullptr, dW, N, Kp, M, 0, 1, single, s, db);  // (db: column sums of dY, in its split pass)
     if (dX) {
       (void)fast_gemm(pr.ctx, dY, false, W, true, nullptr, dX, M, Kp, N, 0, accumulate, single, s);
-      if (mask_src) {
-        const size_t n = (size_t)M * Kp;
-        hipLaunchKernelGGL(relu_drop_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dX, mask_src, n, *drop);
-      }
+      if (mask_src) relu_drop_bwd_launch(dX, mask_src, (size_t)M * Kp, *drop, s);
     }
     return;
   }
@@ -380,11 +385,12 @@ static void pool_norm_fwd_launch(const float* x, float* out, int32_t* arg, float
 static void pool_norm_bwd_launch(const float* gout, const float* out, const int32_t* arg, const float* save_n, float* dX, int B, hipStream_t s) {
   hipLaunchKernelGGL(pool_norm_bwd_kernel, dim3(B), dim3(256), 0, s, gout, out, arg, save_n, dX);
 }
-// out[b][c] = max over the S rows of group b of (X + R) (R optional) with its argument, and the scatter back (text head)
-static void seq_max_fwd_launch(const float* X, const float* R, int B, int S, int D, float* out, int32_t* arg, hipStream_t s) {
+// out[b][c] = max over the S rows of group b of (X + R) (R optional) with its argument, and the scatter back (the text head's tokens and
+// sentences, the fine step's hints: train_common.h)
+void seq_max_fwd_launch(const float* X, const float* R, int B, int S, int D, float* out, int32_t* arg, hipStream_t s) {
   hipLaunchKernelGGL(seq_max_fwd_kernel, dim3((unsigned)(((size_t)B * D + 255) / 256)), dim3(256), 0, s, X, R, B, S, D, out, arg);
 }
-static void seq_max_bwd_launch(const float* g, const int32_t* arg, int B, int S, int D, float* dX, hipStream_t s) {
+void seq_max_bwd_launch(const float* g, const int32_t* arg, int B, int S, int D, float* dX, hipStream_t s) {
   hipLaunchKernelGGL(seq_max_bwd_kernel, dim3((unsigned)(((size_t)B * S * D + 255) / 256)), dim3(256), 0, s, g, arg, B, S, D, dX);
 }
 
@@ -416,10 +422,7 @@ static void enc_layer_fwd(const Products& pr, const TensorMap& t, EncLayer& L, u
   ln_fwd_launch<D>(L.x_in, tmp, T, W(".norm1.weight").data, W(".norm1.bias").data, make_drop(seed, L.site0 + 1, p), L.x1, L.xhat1, L.rstd1, s);
   if (t_fast(pr, T, FF, D)) {  // linear1 + ReLU in the GEMM's epilogue (h is kept for backward); the dropout behind it as one pass
     (void)fast_gemm(pr.ctx, L.x1, false, W(".linear1.weight").data, false, W(".linear1.bias").data, L.h, T, FF, D, 1, 0, pr.ctx->text_train_bf16 == 1, s);
-    if (p > 0.f) {
-      const size_t n = (size_t)T * FF;
-      hipLaunchKernelGGL(drop_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)L.h, n, make_drop(seed, L.site0 + 2, p), L.hd);
-    }
+    if (p > 0.f) drop_fwd_launch(L.h, (size_t)T * FF, make_drop(seed, L.site0 + 2, p), L.hd, s);
   } else {  // ... and the dropout too in the same epilogue (hd feeds linear2)
     GemmArgs g{L.x1, W(".linear1.weight").data, L.h, W(".linear1.bias").data, T, FF, D, D, D, FF, 1, 0, D, nullptr, tl_gemm_bf16};
     if (p > 0.f) {
@@ -642,14 +645,44 @@ static void bn_relu_bwd(TrainState* st, const BnMulti& b, int n, hipStream_t s) 
   sync_slots(st->ctx, b.j[0].acc, n, s);
   hipLaunchKernelGGL(bn_apply_bwd_kernel, dim3((unsigned)(((size_t)b.M * b.C + 255) / 256), n), dim3(256), 0, s, b);
 }
-// F.normalize of n jobs' 256-wide rows into (forward) / out of (backward) their slots of the concatenated feature row
+// F.normalize of n jobs' D-wide rows into (forward) / out of (backward) their slots of the concatenated feature row
+template <int D = kTD>
 static void rownorm_launch(bool fwd, const RownormJob* j, int n, int M, int Kc, hipStream_t s) {
   RownormMulti rn{};
   rn.M = M;
   rn.ld = Kc;
   for (int q = 0; q < n; ++q) rn.j[q] = j[q];
-  if (fwd) hipLaunchKernelGGL(rownorm_fwd_kernel, dim3((M + 3) / 4, n), dim3(256), 0, s, rn);
-  else hipLaunchKernelGGL(rownorm_bwd_kernel, dim3((M + 3) / 4, n), dim3(256), 0, s, rn);
+  if (fwd) hipLaunchKernelGGL(rownorm_fwd_kernel<D>, dim3((M + 3) / 4, n), dim3(256), 0, s, rn);
+  else hipLaunchKernelGGL(rownorm_bwd_kernel<D>, dim3((M + 3) / 4, n), dim3(256), 0, s, rn);
+}
+
+// ---- the row kernels by run-time width, for callers outside this translation unit (train_common.h: the fine step at 128, the block
+// tests at every width). false: no instance of that width — nothing was launched
+bool ln_fwd_rows(int D, const float* x, const float* y, int T, const float* gamma, const float* beta, const Drop& dr, float* out, float* xhat,
+                 float* rstd, hipStream_t s) {
+  if (D == 128) ln_fwd_launch<128>(x, y, T, gamma, beta, dr, out, xhat, rstd, s);
+  else if (D == 256) ln_fwd_launch<256>(x, y, T, gamma, beta, dr, out, xhat, rstd, s);
+  else if (D == 1024) ln_fwd_launch<1024>(x, y, T, gamma, beta, dr, out, xhat, rstd, s);
+  else return false;
+  return true;
+}
+bool ln_bwd_rows(int D, int waves, const float* dout, const float* xhat, const float* rstd, int T, const float* gamma, const Drop& dr,
+                 float* d_res, float* d_y, float* dgamma, float* dbeta, hipStream_t s) {
+  if (D == 128 && waves == 4) ln_bwd_launch<128, 4>(dout, xhat, rstd, T, gamma, dr, d_res, d_y, dgamma, dbeta, s);
+  else if (D == 256 && waves == 16) ln_bwd_launch<256, 16>(dout, xhat, rstd, T, gamma, dr, d_res, d_y, dgamma, dbeta, s);
+  else if (D == 256 && waves == 4) ln_bwd_launch<256, 4>(dout, xhat, rstd, T, gamma, dr, d_res, d_y, dgamma, dbeta, s);
+  else if (D == 1024 && waves == 4) ln_bwd_launch<1024, 4>(dout, xhat, rstd, T, gamma, dr, d_res, d_y, dgamma, dbeta, s);
+  else return false;
+  return true;
+}
+// forward: dst[m] (row stride ld) = normalize(src[m]) (contiguous), the norms to save_n; backward: dst[m] (contiguous) from src = dy
+// and y (both row stride ld) and the saved norms. A job list of one, no embedding lookup.
+bool rownorm_rows(bool fwd, int D, const float* src, const float* y, float* dst, float* save_n, int M, int ld, hipStream_t s) {
+  const RownormJob j{src, nullptr, dst, y, save_n};
+  if (D == 128) rownorm_launch<128>(fwd, &j, 1, M, ld, s);
+  else if (D == 256) rownorm_launch<256>(fwd, &j, 1, M, ld, s);
+  else return false;
+  return true;
 }
 
 // ---- forward ---------------------------------------------------------------------------------------------------

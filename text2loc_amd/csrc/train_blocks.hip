@@ -1,8 +1,9 @@
 // Dev-only block library (libt2l_blocks.so; never shipped, not part of include/t2l.h): the training step's products and layer kernels
 // one launch at a time, so that tests/test_gpu_train_blocks.py can hold each against a float64 reference element by element.
 // This translation unit IS train.hip plus the wrappers below: it reaches the step's own static launchers (gemm_nt_args, gemm_nn,
-// gemm_tn, gemm_tn_nn, gemm_nt_multi, gemm_tn_nn_multi, attn_*_launch, ln_*_launch, pool_norm_*_launch, seq_max_*_launch) and the
-// thread-local operand arithmetic / block option they read. No grid expression lives here.
+// gemm_tn, gemm_tn_nn, gemm_nt_multi, gemm_tn_nn_multi, attn_*_launch, pool_norm_*_launch), the launchers it shares with the fine step
+// (train_common.h: ln_*_rows, rownorm_rows, seq_max_*_launch, drop_fwd_launch, relu_drop_bwd_launch — one width switch for everybody)
+// and the thread-local operand arithmetic / block option they read. No grid expression lives here.
 //
 // Every wrapper takes device pointers and refuses, with -1 and a message (t2l_blk_last_error), any shape outside the contract of the
 // kernel it launches BEFORE it launches (gemm_f32.h's header, train_kernels.h): a mistaken test gets an error, never an out-of-bounds
@@ -175,31 +176,74 @@ int t2l_blk_attn_bwd(const float* qkv, const float* P, const float* dO, float* d
   return finish("t2l_blk_attn_bwd");
 }
 
-// out = LayerNorm(x + dropout(y)) over T rows of D (256 or 1024); xhat and rstd saved
+// out = LayerNorm(x + dropout(y)) over T rows of D (128, 256 or 1024); xhat and rstd saved
 int t2l_blk_ln_fwd(const float* x, const float* y, int T, int D, const float* gamma, const float* beta, float* out, float* xhat, float* rstd,
                    uint32_t seed, int site, float p) {
   const std::string who = "t2l_blk_ln_fwd";
   if (!(p >= 0.f && p < 1.f)) return refuse(who + ": p must be in [0, 1)");
-  if (T < 1 || (D != 256 && D != 1024)) return refuse(who + ": need T >= 1 and D 256 or 1024 (the instances the step builds)");
+  const std::string shape = who + ": need T >= 1 and D 128, 256 or 1024 (the instances the steps build)";
+  if (T < 1 || (D != 128 && D != 256 && D != 1024)) return refuse(shape);
   if (!x || !y || !gamma || !beta || !out || !xhat || !rstd) return refuse(who + ": null pointer");
-  const Drop dr = make_drop(seed, site, p);
-  if (D == 256) ln_fwd_launch<256>(x, y, T, gamma, beta, dr, out, xhat, rstd, nullptr);
-  else ln_fwd_launch<1024>(x, y, T, gamma, beta, dr, out, xhat, rstd, nullptr);
+  if (!ln_fwd_rows(D, x, y, T, gamma, beta, make_drop(seed, site, p), out, xhat, rstd, nullptr)) return refuse(shape);
   return finish("t2l_blk_ln_fwd");
 }
-// its backward: d_res, d_y written, dgamma / dbeta added to. (D, waves): (256, 16) the object branch, (256, 4) and (1024, 4) the text head
+// its backward: d_res, d_y written, dgamma / dbeta added to. (D, waves): (256, 16) the object branch, (256, 4) and (1024, 4) the text
+// head, (128, 4) the fine step
 int t2l_blk_ln_bwd(const float* dout, const float* xhat, const float* rstd, int T, int D, int waves, const float* gamma, float* d_res, float* d_y,
                    float* dgamma, float* dbeta, uint32_t seed, int site, float p) {
   const std::string who = "t2l_blk_ln_bwd";
   if (!(p >= 0.f && p < 1.f)) return refuse(who + ": p must be in [0, 1)");
-  const int inst = D == 256 && waves == 16 ? 0 : D == 256 && waves == 4 ? 1 : D == 1024 && waves == 4 ? 2 : -1;
-  if (T < 1 || inst < 0) return refuse(who + ": need T >= 1 and (D, waves) one of (256, 16), (256, 4), (1024, 4) (the instances the step builds)");
+  const std::string shape = who + ": need T >= 1 and (D, waves) one of (128, 4), (256, 16), (256, 4), (1024, 4) (the instances the steps build)";
+  const bool inst = (waves == 4 && (D == 128 || D == 256 || D == 1024)) || (waves == 16 && D == 256);
+  if (T < 1 || !inst) return refuse(shape);
   if (!dout || !xhat || !rstd || !gamma || !d_res || !d_y || !dgamma || !dbeta) return refuse(who + ": null pointer");
-  const Drop dr = make_drop(seed, site, p);
-  if (inst == 0) ln_bwd_launch<256, 16>(dout, xhat, rstd, T, gamma, dr, d_res, d_y, dgamma, dbeta, nullptr);
-  else if (inst == 1) ln_bwd_launch<256, 4>(dout, xhat, rstd, T, gamma, dr, d_res, d_y, dgamma, dbeta, nullptr);
-  else ln_bwd_launch<1024, 4>(dout, xhat, rstd, T, gamma, dr, d_res, d_y, dgamma, dbeta, nullptr);
+  if (!ln_bwd_rows(D, waves, dout, xhat, rstd, T, gamma, make_drop(seed, site, p), d_res, d_y, dgamma, dbeta, nullptr)) return refuse(shape);
   return finish("t2l_blk_ln_bwd");
+}
+
+// F.normalize of M rows of D (128 or 256). Forward: dst[m] (row stride ld >= D) = src[m] / max(|src[m]|, 1e-12) from contiguous src, the
+// norms to save_n. Backward: dx[m] (contiguous) from dy and y (both row stride ld) and the saved norms.
+static int rownorm_shape(const std::string& who, int M, int D, int ld) {
+  if (M < 1) return refuse(who + ": need M >= 1");
+  if (D != 128 && D != 256) return refuse(who + ": D must be 128 or 256 (the instances the steps build)");
+  if (ld < D) return refuse(who + ": ld < D (the strided side holds a whole row)");
+  return 0;
+}
+int t2l_blk_rownorm_fwd(const float* src, int M, int D, float* dst, int ld, float* save_n) {
+  const std::string who = "t2l_blk_rownorm_fwd";
+  if (int rc = rownorm_shape(who, M, D, ld)) return rc;
+  if (!src || !dst || !save_n) return refuse(who + ": null pointer");
+  if (!rownorm_rows(true, D, src, nullptr, dst, save_n, M, ld, nullptr)) return refuse(who + ": no instance of this width");
+  return finish("t2l_blk_rownorm_fwd");
+}
+int t2l_blk_rownorm_bwd(const float* dy, const float* y, int ld, const float* save_n, int M, int D, float* dx) {
+  const std::string who = "t2l_blk_rownorm_bwd";
+  if (int rc = rownorm_shape(who, M, D, ld)) return rc;
+  if (!dy || !y || !save_n || !dx) return refuse(who + ": null pointer");
+  if (!rownorm_rows(false, D, dy, y, dx, const_cast<float*>(save_n), M, ld, nullptr)) return refuse(who + ": no instance of this width");
+  return finish("t2l_blk_rownorm_bwd");
+}
+
+// hd = dropout(h) over n elements; d = dropout'(d) where h > 0, else 0, in place
+static int drop_shape(const std::string& who, int64_t n, float p) {
+  if (!(p >= 0.f && p < 1.f)) return refuse(who + ": p must be in [0, 1)");
+  if (n < 1) return refuse(who + ": need n >= 1");
+  if (n >= (1ll << 32)) return refuse(who + ": n >= 2^32 (the dropout counters are 32 bits wide)");
+  return 0;
+}
+int t2l_blk_drop_fwd(const float* h, int64_t n, float* hd, uint32_t seed, int site, float p) {
+  const std::string who = "t2l_blk_drop_fwd";
+  if (int rc = drop_shape(who, n, p)) return rc;
+  if (!h || !hd) return refuse(who + ": null pointer");
+  drop_fwd_launch(h, (size_t)n, make_drop(seed, site, p), hd, nullptr);
+  return finish("t2l_blk_drop_fwd");
+}
+int t2l_blk_relu_drop_bwd(float* d, const float* h, int64_t n, uint32_t seed, int site, float p) {
+  const std::string who = "t2l_blk_relu_drop_bwd";
+  if (int rc = drop_shape(who, n, p)) return rc;
+  if (!d || !h) return refuse(who + ": null pointer");
+  relu_drop_bwd_launch(d, h, (size_t)n, make_drop(seed, site, p), nullptr);
+  return finish("t2l_blk_relu_drop_bwd");
 }
 
 // max over the 28 slots of each of B cells + F.normalize: X [B 28][256] -> out, out2 [B][256], arg [B][256], save_n [B]

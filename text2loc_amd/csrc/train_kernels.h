@@ -1,10 +1,13 @@
 // Device kernels of the object-branch TRAINING step: forward in model.train() mode with saved
-// activations, backward, Adam. gfx950 only. All arithmetic is f32 (the reference trains in f32); contractions run on
+// activations, backward, Adam. gfx950 only. The row kernels (LayerNorm, F.normalize, element-wise dropout, max over a group's rows) also
+// serve the fine step (fine_train.hip, through train.hip's launchers in train_common.h): row widths 128, 256 and 1024. All arithmetic is f32 (the reference trains in f32); contractions run on
 // v_mfma_f32_32x32x2_f32. The step is small (B=64 cells -> 1,792 tokens, ~12 GFLOP fwd+bwd) and latency-bound, so the
 // kernels are modular (one per op of the autograd graph) rather than fused per cell like the eval encoder.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "gemm_f32.h"
 #include "train_common.h"
@@ -38,6 +41,44 @@ __device__ __forceinline__ float wsum(float v) {
     v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
   }
   return v;
+}
+
+// A lane's share of a row, for the row kernels below (F.normalize, LayerNorm) at every width they serve — 128 (the fine step), 256 and
+// 1024: VW = min(4, D / 64) consecutive floats of each 64 VW-column chunk, so float4 at `chunk * 256 + lane * 4` from D = 256 up and
+// float2 at `lane * 2` at D = 128. vmap: f over the components of one or more vectors; vacc: s += a; vatomic_add: p[0 .. VW) += a with
+// float atomics; vsum, vdot_pair: LayerNorm's pairwise lane sums; vdot: the sequential one of F.normalize; vdrop: the dropout rule on
+// the VW elements from index o on. (Spelled so that the 256 and 1024 instances keep the code they had with float4 written out:
+// profiles/fine_train_rows.md.)
+template <int D>
+struct RowVec {
+  static_assert(D == 128 || (D >= 256 && D % 256 == 0), "row width: 128 or a multiple of 256");
+  static constexpr int VW = D < 256 ? D / 64 : 4, CW = 64 * VW, NV = D / CW;
+  using type = typename std::conditional<VW == 2, float2, float4>::type;
+};
+template <typename F, typename... R>
+__device__ __forceinline__ float2 vmap(F f, float2 a, R... r) {
+  return make_float2(f(a.x, r.x...), f(a.y, r.y...));
+}
+template <typename F, typename... R>
+__device__ __forceinline__ float4 vmap(F f, float4 a, R... r) {
+  return make_float4(f(a.x, r.x...), f(a.y, r.y...), f(a.z, r.z...), f(a.w, r.w...));
+}
+__device__ __forceinline__ void vacc(float2& s, float2 a) { s.x += a.x; s.y += a.y; }
+__device__ __forceinline__ void vacc(float4& s, float4 a) { s.x += a.x; s.y += a.y; s.z += a.z; s.w += a.w; }
+__device__ __forceinline__ void vatomic_add(float* p, float2 a) { unsafeAtomicAdd(p + 0, a.x); unsafeAtomicAdd(p + 1, a.y); }
+__device__ __forceinline__ void vatomic_add(float* p, float4 a) {
+  unsafeAtomicAdd(p + 0, a.x); unsafeAtomicAdd(p + 1, a.y); unsafeAtomicAdd(p + 2, a.z); unsafeAtomicAdd(p + 3, a.w);
+}
+__device__ __forceinline__ float vsum(float2 a) { return a.x + a.y; }
+__device__ __forceinline__ float vsum(float4 a) { return (a.x + a.y) + (a.z + a.w); }
+__device__ __forceinline__ float vdot_pair(float2 a, float2 b) { return a.x * b.x + a.y * b.y; }
+__device__ __forceinline__ float vdot_pair(float4 a, float4 b) { return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w); }
+__device__ __forceinline__ float vdot(float2 a, float2 b) { return a.x * b.x + a.y * b.y; }
+__device__ __forceinline__ float vdot(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
+__device__ __forceinline__ float drop1(float v, const Drop& dr, uint32_t i) { return keep_bit(dr.key, i, dr.thr) ? v * dr.scale : 0.f; }
+__device__ __forceinline__ float2 vdrop(float2 v, const Drop& dr, uint32_t o) { return make_float2(drop1(v.x, dr, o), drop1(v.y, dr, o + 1)); }
+__device__ __forceinline__ float4 vdrop(float4 v, const Drop& dr, uint32_t o) {
+  return make_float4(drop1(v.x, dr, o), drop1(v.y, dr, o + 1), drop1(v.z, dr, o + 2), drop1(v.w, dr, o + 3));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -239,33 +280,40 @@ __global__ __launch_bounds__(256) void bn_apply_bwd_kernel(BnMulti m) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// F.normalize over 256-wide rows: one wave per row, 4 floats per lane.
+// F.normalize over D-wide rows (D = 256: the coarse step, 128: the fine step): one wave per row, D / 64 floats per lane.
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float4 norm_fwd(float4 v, float& n) {
-  n = fmaxf(sqrtf(wsum(v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w)), kNormEps);
-  return make_float4(v.x / n, v.y / n, v.z / n, v.w / n);
+template <typename V>
+__device__ __forceinline__ V norm_fwd(V v, float& n) {
+  n = fmaxf(sqrtf(wsum(vdot(v, v))), kNormEps);
+  const float nn = n;
+  return vmap([nn](float a) { return a / nn; }, v);
 }
-__device__ __forceinline__ float4 norm_bwd(float4 dy, float4 y, float n) {
-  if (n <= kNormEps) return make_float4(dy.x / kNormEps, dy.y / kNormEps, dy.z / kNormEps, dy.w / kNormEps);
-  const float t = wsum(dy.x * y.x + dy.y * y.y + dy.z * y.z + dy.w * y.w);
-  return make_float4((dy.x - y.x * t) / n, (dy.y - y.y * t) / n, (dy.z - y.z * t) / n, (dy.w - y.w * t) / n);
+template <typename V>
+__device__ __forceinline__ V norm_bwd(V dy, V y, float n) {
+  if (n <= kNormEps) return vmap([](float d) { return d / kNormEps; }, dy);
+  const float t = wsum(vdot(dy, y));
+  return vmap([t, n](float d, float yy) { return (d - yy * t) / n; }, dy, y);
 }
-// src row = table[idx[m]] when idx != nullptr (embedding lookup) else src[m]; dst row stride ldd (a 256-wide slot of cat)
+// src row = table[idx[m]] when idx != nullptr (embedding lookup: the coarse step's, the index is not tested) else src[m]; dst row stride
+// ldd (a D-wide slot of cat)
+template <int D>
 __device__ __forceinline__ void rownorm_fwd_body(const float* __restrict__ src, const int32_t* __restrict__ idx, int M, float* __restrict__ dst,
                                                  int ldd, float* __restrict__ save_n, unsigned bx) {
+  using V = typename RowVec<D>::type;
+  constexpr int VW = RowVec<D>::VW;
   const int m = (bx * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
   if (m >= M) return;
   const size_t row = idx ? (size_t)idx[m] : (size_t)m;
-  const float4 v = *reinterpret_cast<const float4*>(src + row * kTD + lane * 4);
+  const V v = *reinterpret_cast<const V*>(src + row * D + lane * VW);
   float n;
-  const float4 y = norm_fwd(v, n);
-  *reinterpret_cast<float4*>(dst + (size_t)m * ldd + lane * 4) = y;
+  const V y = norm_fwd(v, n);
+  *reinterpret_cast<V*>(dst + (size_t)m * ldd + lane * VW) = y;
   if (lane == 0) save_n[m] = n;
 }
 struct RownormJob {
   const float* src;      // forward: rows to normalise (or the embedding table); backward: dy (a slot of dcat)
   const int32_t* idx;    // forward: embedding lookup or nullptr
-  float* dst;            // forward: slot of cat; backward: dx [M][256]
+  float* dst;            // forward: slot of cat; backward: dx [M][D]
   const float* y;        // backward: the normalised rows (slot of cat)
   float* save_n;
 };
@@ -273,22 +321,27 @@ struct RownormMulti {
   RownormJob j[kMaxJobs];
   int M, ld;
 };
+template <int D>
 __global__ void rownorm_fwd_kernel(RownormMulti m) {
   const RownormJob& j = m.j[blockIdx.y];
-  rownorm_fwd_body(j.src, j.idx, m.M, j.dst, m.ld, j.save_n, blockIdx.x);
+  rownorm_fwd_body<D>(j.src, j.idx, m.M, j.dst, m.ld, j.save_n, blockIdx.x);
 }
 // dx[m] = normalize_bwd(dy[m], y[m], n[m])
+template <int D>
 __device__ __forceinline__ void rownorm_bwd_body(const float* __restrict__ dy, const float* __restrict__ y, int ld,
                                                  const float* __restrict__ save_n, int M, float* __restrict__ dx, unsigned bx) {
+  using V = typename RowVec<D>::type;
+  constexpr int VW = RowVec<D>::VW;
   const int m = (bx * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
   if (m >= M) return;
-  const float4 d = *reinterpret_cast<const float4*>(dy + (size_t)m * ld + lane * 4);
-  const float4 yy = *reinterpret_cast<const float4*>(y + (size_t)m * ld + lane * 4);
-  *reinterpret_cast<float4*>(dx + (size_t)m * kTD + lane * 4) = norm_bwd(d, yy, save_n[m]);
+  const V d = *reinterpret_cast<const V*>(dy + (size_t)m * ld + lane * VW);
+  const V yy = *reinterpret_cast<const V*>(y + (size_t)m * ld + lane * VW);
+  *reinterpret_cast<V*>(dx + (size_t)m * D + lane * VW) = norm_bwd(d, yy, save_n[m]);
 }
+template <int D>
 __global__ void rownorm_bwd_kernel(RownormMulti m) {
   const RownormJob& j = m.j[blockIdx.y];
-  rownorm_bwd_body(j.src, j.y, m.ld, j.save_n, m.M, j.dst, blockIdx.x);
+  rownorm_bwd_body<D>(j.src, j.y, m.ld, j.save_n, m.M, j.dst, blockIdx.x);
 }
 // Embedding-table gradient, stage 2 (stage 1 = rownorm_bwd_kernel writing g[M,256] = normalize_bwd per object):
 // dtable[r] += sum over the objects with idx == r of g[m]. grid (table rows - 1, kEmbSplit): row 0 = padding_idx never
@@ -505,47 +558,43 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
   }
 }
 
-// out = LayerNorm(x + dropout(y)) over D columns, one wave per row (D / 256 float4 per lane, each wave-load 1 KiB contiguous).
-// Saves xhat and rstd.
+// out = LayerNorm(x + dropout(y)) over D columns (128, 256, 1024), one wave per row (RowVec<D>: D / 256 float4 per lane, each wave-load
+// 1 KiB contiguous; one float2 at D = 128). Saves xhat and rstd.
 template <int D>
 __global__ void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y, int T, const float* __restrict__ gamma,
                               const float* __restrict__ beta, Drop dr, float* __restrict__ out, float* __restrict__ xhat,
                               float* __restrict__ save_rstd) {
-  constexpr int NV = D / 256;
+  using V = typename RowVec<D>::type;
+  constexpr int VW = RowVec<D>::VW, CW = RowVec<D>::CW, NV = RowVec<D>::NV;
   const int t = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
   if (t >= T) return;
-  float4 a[NV];
+  V a[NV];
   float s1 = 0.f;
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
-    const size_t o = (size_t)t * D + j * 256 + lane * 4;
-    a[j] = *reinterpret_cast<const float4*>(x + o);
-    float4 f = *reinterpret_cast<const float4*>(y + o);
-    if (dr.thr) {
-      f.x = keep_bit(dr.key, (uint32_t)o + 0, dr.thr) ? f.x * dr.scale : 0.f;
-      f.y = keep_bit(dr.key, (uint32_t)o + 1, dr.thr) ? f.y * dr.scale : 0.f;
-      f.z = keep_bit(dr.key, (uint32_t)o + 2, dr.thr) ? f.z * dr.scale : 0.f;
-      f.w = keep_bit(dr.key, (uint32_t)o + 3, dr.thr) ? f.w * dr.scale : 0.f;
-    }
-    a[j].x += f.x; a[j].y += f.y; a[j].z += f.z; a[j].w += f.w;
-    s1 += (a[j].x + a[j].y) + (a[j].z + a[j].w);
+    const size_t o = (size_t)t * D + j * CW + lane * VW;
+    a[j] = *reinterpret_cast<const V*>(x + o);
+    V f = *reinterpret_cast<const V*>(y + o);
+    if (dr.thr) f = vdrop(f, dr, (uint32_t)o);
+    vacc(a[j], f);
+    s1 += vsum(a[j]);
   }
   const float mu = wsum(s1) * (1.f / D);
   float s2 = 0.f;
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
-    a[j].x -= mu; a[j].y -= mu; a[j].z -= mu; a[j].w -= mu;
-    s2 += (a[j].x * a[j].x + a[j].y * a[j].y) + (a[j].z * a[j].z + a[j].w * a[j].w);
+    a[j] = vmap([mu](float p) { return p - mu; }, a[j]);
+    s2 += vdot_pair(a[j], a[j]);
   }
   const float rstd = 1.0f / sqrtf(wsum(s2) * (1.f / D) + kLnEps);
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
-    const size_t o = (size_t)t * D + j * 256 + lane * 4;
-    const float4 h = make_float4(a[j].x * rstd, a[j].y * rstd, a[j].z * rstd, a[j].w * rstd);
-    const float4 g = *reinterpret_cast<const float4*>(gamma + j * 256 + lane * 4);
-    const float4 be = *reinterpret_cast<const float4*>(beta + j * 256 + lane * 4);
-    *reinterpret_cast<float4*>(xhat + o) = h;
-    *reinterpret_cast<float4*>(out + o) = make_float4(h.x * g.x + be.x, h.y * g.y + be.y, h.z * g.z + be.z, h.w * g.w + be.w);
+    const size_t o = (size_t)t * D + j * CW + lane * VW;
+    const V h = vmap([rstd](float p) { return p * rstd; }, a[j]);
+    const V g = *reinterpret_cast<const V*>(gamma + j * CW + lane * VW);
+    const V be = *reinterpret_cast<const V*>(beta + j * CW + lane * VW);
+    *reinterpret_cast<V*>(xhat + o) = h;
+    *reinterpret_cast<V*>(out + o) = vmap([](float p, float q, float r) { return p * q + r; }, h, g, be);
   }
   if (lane == 0) save_rstd[t] = rstd;
 }
@@ -559,14 +608,15 @@ __global__ __launch_bounds__(WAVES * 64) void ln_bwd_kernel(const float* __restr
                                                             const float* __restrict__ save_rstd, int T, const float* __restrict__ gamma,
                                                             Drop dr, float* __restrict__ d_res, float* __restrict__ d_y,
                                                             float* __restrict__ dgamma, float* __restrict__ dbeta) {
-  constexpr int NV = D / 256;
-  __shared__ float4 rg[WAVES * 64 * NV], rb[WAVES * 64 * NV];
+  using V = typename RowVec<D>::type;
+  constexpr int VW = RowVec<D>::VW, CW = RowVec<D>::CW, NV = RowVec<D>::NV;
+  __shared__ V rg[WAVES * 64 * NV], rb[WAVES * 64 * NV];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  float4 g[NV], ag[NV], ab[NV], d[NV], h[NV];
+  V g[NV], ag[NV], ab[NV], d[NV], h[NV];
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
-    g[j] = *reinterpret_cast<const float4*>(gamma + j * 256 + lane * 4);
-    ag[j] = ab[j] = d[j] = h[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    g[j] = *reinterpret_cast<const V*>(gamma + j * CW + lane * VW);
+    ag[j] = ab[j] = d[j] = h[j] = V{};
   }
   // a wave walks several rows: the next row's operands are loaded before the current row is reduced and stored (written as
   // load -> reduce -> store per row, every row paid its own L2 round trip behind the previous row's stores: 11.4 us per launch
@@ -577,46 +627,40 @@ __global__ __launch_bounds__(WAVES * 64) void ln_bwd_kernel(const float* __restr
   if (t < T) {
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
-      const size_t o = (size_t)t * D + j * 256 + lane * 4;
-      d[j] = *reinterpret_cast<const float4*>(dout + o);
-      h[j] = *reinterpret_cast<const float4*>(xhat + o);
+      const size_t o = (size_t)t * D + j * CW + lane * VW;
+      d[j] = *reinterpret_cast<const V*>(dout + o);
+      h[j] = *reinterpret_cast<const V*>(xhat + o);
     }
     rstd = save_rstd[t];
   }
   while (t < T) {
     const int tn = min(t + stride, T - 1);  // (clamped: the last prefetch re-reads a valid row and is dropped)
-    float4 nd[NV], nh[NV], dh[NV];
+    V nd[NV], nh[NV], dh[NV];
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
-      const size_t on = (size_t)tn * D + j * 256 + lane * 4;
-      nd[j] = *reinterpret_cast<const float4*>(dout + on);
-      nh[j] = *reinterpret_cast<const float4*>(xhat + on);
+      const size_t on = (size_t)tn * D + j * CW + lane * VW;
+      nd[j] = *reinterpret_cast<const V*>(dout + on);
+      nh[j] = *reinterpret_cast<const V*>(xhat + on);
     }
     const float nrstd = save_rstd[tn];
     float m1 = 0.f, m2 = 0.f;
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
-      ag[j].x += d[j].x * h[j].x; ag[j].y += d[j].y * h[j].y; ag[j].z += d[j].z * h[j].z; ag[j].w += d[j].w * h[j].w;
-      ab[j].x += d[j].x; ab[j].y += d[j].y; ab[j].z += d[j].z; ab[j].w += d[j].w;
-      dh[j] = make_float4(d[j].x * g[j].x, d[j].y * g[j].y, d[j].z * g[j].z, d[j].w * g[j].w);
-      m1 += (dh[j].x + dh[j].y) + (dh[j].z + dh[j].w);
-      m2 += (dh[j].x * h[j].x + dh[j].y * h[j].y) + (dh[j].z * h[j].z + dh[j].w * h[j].w);
+      ag[j] = vmap([](float acc, float p, float q) { return acc + p * q; }, ag[j], d[j], h[j]);
+      vacc(ab[j], d[j]);
+      dh[j] = vmap([](float p, float q) { return p * q; }, d[j], g[j]);
+      m1 += vsum(dh[j]);
+      m2 += vdot_pair(dh[j], h[j]);
     }
     m1 = wsum(m1) * (1.f / D);
     m2 = wsum(m2) * (1.f / D);
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
-      const size_t o = (size_t)t * D + j * 256 + lane * 4;
-      float4 dz = make_float4(rstd * (dh[j].x - m1 - h[j].x * m2), rstd * (dh[j].y - m1 - h[j].y * m2),
-                              rstd * (dh[j].z - m1 - h[j].z * m2), rstd * (dh[j].w - m1 - h[j].w * m2));
-      *reinterpret_cast<float4*>(d_res + o) = dz;
-      if (dr.thr) {
-        dz.x = keep_bit(dr.key, (uint32_t)o + 0, dr.thr) ? dz.x * dr.scale : 0.f;
-        dz.y = keep_bit(dr.key, (uint32_t)o + 1, dr.thr) ? dz.y * dr.scale : 0.f;
-        dz.z = keep_bit(dr.key, (uint32_t)o + 2, dr.thr) ? dz.z * dr.scale : 0.f;
-        dz.w = keep_bit(dr.key, (uint32_t)o + 3, dr.thr) ? dz.w * dr.scale : 0.f;
-      }
-      *reinterpret_cast<float4*>(d_y + o) = dz;
+      const size_t o = (size_t)t * D + j * CW + lane * VW;
+      V dz = vmap([rstd, m1, m2](float p, float q) { return rstd * (p - m1 - q * m2); }, dh[j], h[j]);
+      *reinterpret_cast<V*>(d_res + o) = dz;
+      if (dr.thr) dz = vdrop(dz, dr, (uint32_t)o);
+      *reinterpret_cast<V*>(d_y + o) = dz;
       d[j] = nd[j];
       h[j] = nh[j];
     }
@@ -632,16 +676,14 @@ __global__ __launch_bounds__(WAVES * 64) void ln_bwd_kernel(const float* __restr
   if (w == 0) {
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
-      float4 sg = ag[j], sb = ab[j];
+      V sg = ag[j], sb = ab[j];
       for (int i = 1; i < WAVES; ++i) {
-        const float4 a = rg[(lane + 64 * i) * NV + j], c = rb[(lane + 64 * i) * NV + j];
-        sg.x += a.x; sg.y += a.y; sg.z += a.z; sg.w += a.w;
-        sb.x += c.x; sb.y += c.y; sb.z += c.z; sb.w += c.w;
+        const V a = rg[(lane + 64 * i) * NV + j], c = rb[(lane + 64 * i) * NV + j];
+        vacc(sg, a);
+        vacc(sb, c);
       }
-      float* pg = dgamma + j * 256 + lane * 4;
-      float* pb = dbeta + j * 256 + lane * 4;
-      unsafeAtomicAdd(pg + 0, sg.x); unsafeAtomicAdd(pg + 1, sg.y); unsafeAtomicAdd(pg + 2, sg.z); unsafeAtomicAdd(pg + 3, sg.w);
-      unsafeAtomicAdd(pb + 0, sb.x); unsafeAtomicAdd(pb + 1, sb.y); unsafeAtomicAdd(pb + 2, sb.z); unsafeAtomicAdd(pb + 3, sb.w);
+      vatomic_add(dgamma + j * CW + lane * VW, sg);
+      vatomic_add(dbeta + j * CW + lane * VW, sb);
     }
   }
 }

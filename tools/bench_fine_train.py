@@ -2,7 +2,7 @@
 torch.optim.Adam) on the engine (t2l_fine_train_*) and, beside it, the same step on PyTorch-ROCm: the package's CrossMatch
 parameter containers (nn.Linear / nn.BatchNorm1d / nn.TransformerDecoderLayer, float32, dropout 0.1) run as
 models/cross_matcher.py:86-135 runs them. Same weights, inputs and batch. Device events around `--iters` steps after
-`--warmup` steps; the median of `--reps` repetitions. Prints one JSON line.
+`--warmup` steps; the median of `--reps` repetitions and their spread (max - min). Prints one JSON line.
 
 `--points`: the published configuration instead — features2 from the PointNet++ backbone on each pair's point batch
 (t2l_fine_train_forward_points), trained jointly (the backward continues into it, Adam steps it too). Engine only: the
@@ -109,7 +109,8 @@ def bench(embed, B, iters, warmup, reps):
         eng.fine_train_backward(out.grad, gh, gp)
         opt_e.step()
 
-    ms_engine = time_steps(engine_step, iters, warmup, reps)
+    reps_engine = time_steps(engine_step, iters, warmup, reps, all_reps=True)
+    ms_engine = float(np.median(reps_engine))
     eng.close()
     # ---- PyTorch-ROCm: the same step through torch's own modules (fresh copy of the weights)
     model2, _, _, _, _ = problem(embed, B)
@@ -125,8 +126,8 @@ def bench(embed, B, iters, warmup, reps):
 
     ms_torch = time_steps(torch_step, iters, warmup, reps)
     del params
-    return {"mode": "embed" if embed else "features2", "B": B, "ms_engine": round(ms_engine, 4), "ms_pytorch": round(ms_torch, 4),
-            "speedup": round(ms_torch / ms_engine, 3)}
+    return {"mode": "embed" if embed else "features2", "B": B, "ms_engine": round(ms_engine, 4),
+            "spread_ms": round(max(reps_engine) - min(reps_engine), 4), "ms_pytorch": round(ms_torch, 4), "speedup": round(ms_torch / ms_engine, 3)}
 
 
 def bench_points(B, iters, warmup, reps):
@@ -166,9 +167,10 @@ def bench_points(B, iters, warmup, reps):
     engine_step()
     torch.cuda.synchronize()
     claimed = free0 - torch.cuda.mem_get_info()[0]
-    ms = time_steps(engine_step, iters, warmup, reps)
+    ms = time_steps(engine_step, iters, warmup, reps, all_reps=True)
     eng.close()
-    return {"mode": "points (backbone trained)", "B": B, "objects": 16 * B, "ms_engine": round(ms, 4), "ms_pytorch": None,
+    return {"mode": "points (backbone trained)", "B": B, "objects": 16 * B, "ms_engine": round(float(np.median(ms)), 4),
+            "spread_ms": round(max(ms) - min(ms), 4), "ms_pytorch": None,
             "first_step_device_gb": round(claimed / 1e9, 3)}
 
 
