@@ -42,6 +42,32 @@ struct PointNetWeights {
   // workspace
   char* ws = nullptr;
   size_t ws_cap = 0;
+  int last_n_obj = 0;  // objects of the last t2l_pointnet_features call whose launches were all issued (0: none yet)
+  bool last_flags = false;  // ... and whether it kept per-object flags (a split launch)
+};
+
+// The level buffers of one call inside the workspace, for ALL objects (105 KB per object; 288 GB of HBM hold the whole
+// KITTI360Pose DB at once): centres p and features x of the three levels, the global MLP's f0, lin1's f1, then the cell base
+// and the magnitude-watch flag of every object.
+struct PointNetLevels {
+  float *p1, *x1, *p2, *x2, *p3, *x3, *f0, *f1;
+  int32_t *base, *flags;
+  static size_t bytes(int n_obj) {
+    const size_t per_obj = sizeof(float) * (128 * 3 + 128 * 64 + 64 * 3 + 64 * 128 + 32 * 3 + 32 * 256 + 1024 + 512) + 2 * sizeof(int32_t);
+    return per_obj * (size_t)n_obj + 4096;
+  }
+  PointNetLevels(char* ws, int n_obj) {
+    p1 = reinterpret_cast<float*>(ws);
+    x1 = p1 + (size_t)n_obj * 128 * 3;
+    p2 = x1 + (size_t)n_obj * 128 * 64;
+    x2 = p2 + (size_t)n_obj * 64 * 3;
+    p3 = x2 + (size_t)n_obj * 64 * 128;
+    x3 = p3 + (size_t)n_obj * 32 * 3;
+    f0 = x3 + (size_t)n_obj * 32 * 256;
+    f1 = f0 + (size_t)n_obj * 1024;
+    base = reinterpret_cast<int32_t*>(f1 + (size_t)n_obj * 512);
+    flags = base + n_obj;
+  }
 };
 
 void free_pointnet(t2l_ctx* ctx) {
@@ -1252,9 +1278,8 @@ int pointnet_features_impl(t2l_ctx* ctx, const float* pos, const float* rgb, con
     if (cell_offsets[c + 1] < cell_offsets[c]) return fail(ctx, T2L_EINVAL, "t2l_pointnet_features: cell_offsets must be non-decreasing");
     for (int o = cell_offsets[c]; o < cell_offsets[c + 1]; ++o) base[o] = cell_offsets[c];
   }
-  // level buffers for ALL objects (105 KB per object; 288 GB of HBM hold the whole KITTI360Pose DB at once)
-  const size_t per_obj = sizeof(float) * (128 * 3 + 128 * 64 + 64 * 3 + 64 * 128 + 32 * 3 + 32 * 256 + 1024 + 512) + 2 * sizeof(int32_t);
-  const size_t need = per_obj * (size_t)n_obj + 4096;
+  const size_t need = PointNetLevels::bytes(n_obj);
+  W->last_n_obj = 0;
   if (need > W->ws_cap) {
     if (W->ws) (void)hipFree(W->ws);
     W->ws = nullptr;
@@ -1262,17 +1287,11 @@ int pointnet_features_impl(t2l_ctx* ctx, const float* pos, const float* rgb, con
     T2L_HIP(ctx, hipMalloc(&W->ws, need));
     W->ws_cap = need;
   }
-  float* p1 = reinterpret_cast<float*>(W->ws);
-  float* x1 = p1 + (size_t)n_obj * 128 * 3;
-  float* p2 = x1 + (size_t)n_obj * 128 * 64;
-  float* x2 = p2 + (size_t)n_obj * 64 * 3;
-  float* p3 = x2 + (size_t)n_obj * 64 * 128;
-  float* x3 = p3 + (size_t)n_obj * 32 * 3;
-  float* f0 = x3 + (size_t)n_obj * 32 * 256;
-  float* f1 = f0 + (size_t)n_obj * 1024;
-  int32_t* d_base = reinterpret_cast<int32_t*>(f1 + (size_t)n_obj * 512);
+  const PointNetLevels L(W->ws, n_obj);
+  float *const p1 = L.p1, *const x1 = L.x1, *const p2 = L.p2, *const x2 = L.x2, *const p3 = L.p3, *const x3 = L.x3, *const f0 = L.f0, *const f1 = L.f1;
+  int32_t* const d_base = L.base;
   const bool split = !ctx->encoder_f32;
-  int32_t* d_flags = split ? d_base + n_obj : nullptr;
+  int32_t* d_flags = split ? L.flags : nullptr;
   if (split) T2L_HIP(ctx, hipMemsetAsync(d_flags, 0, sizeof(int32_t) * n_obj, s));
   T2L_HIP(ctx, hipMemcpyAsync(d_base, base.data(), sizeof(int32_t) * n_obj, hipMemcpyHostToDevice, s));
   T2L_HIP(ctx, hipStreamSynchronize(s));  // `base` is a host temporary
@@ -1315,6 +1334,8 @@ int pointnet_features_impl(t2l_ctx* ctx, const float* pos, const float* rgb, con
   }
   event_end(ctx, "pointnet", s);
   T2L_HIP(ctx, hipGetLastError());
+  W->last_n_obj = n_obj;
+  W->last_flags = split;
   return T2L_OK;
 }
 

@@ -11,17 +11,17 @@
 //   arith: 0 f32, 1 bf16, 2 split-bf16 operands (GemmArgs::bf16);  block: 1 = 64 x 64 output blocks where the shape allows
 //   (seed, site, p): the dropout site, through make_drop
 #include "train.hip"
+#include "blocks_common.h"
 
 namespace t2l {
-namespace {
 
-thread_local std::string tl_blk_error;
+static thread_local std::string tl_blk_error;
 
-int refuse(const std::string& msg) {
+int blk_refuse(const std::string& msg) {  // (shared with pointnet_blocks.hip)
   tl_blk_error = msg;
   return -1;
 }
-int finish(const char* who) {
+int blk_finish(const char* who) {
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
   if (e != hipSuccess) {
@@ -30,6 +30,11 @@ int finish(const char* who) {
   }
   return 0;
 }
+
+namespace {
+
+int refuse(const std::string& msg) { return blk_refuse(msg); }
+int finish(const char* who) { return blk_finish(who); }
 bool bad_option(int arith, int block, float p) { return arith < 0 || arith > 2 || block < 0 || block > 1 || !(p >= 0.f && p < 1.f); }
 void set_options(int arith, int block) {
   tl_gemm_bf16 = arith;

@@ -144,20 +144,24 @@ EXPORTS = {
 _lib = None
 
 
-def load_library() -> C.CDLL:
+def load_library(path: Optional[str] = None) -> C.CDLL:
     """dlopen libt2l.so and declare every symbol of include/t2l.h. Raises if the library is absent:
-    there is deliberately no fallback (build it with ``python -c 'import __graft_entry__ as g; g.build()'``)."""
+    there is deliberately no fallback (build it with ``python -c 'import __graft_entry__ as g; g.build()'``).
+    ``path``: another library that carries the whole C ABI (the dev-only libt2l_blocks.so of the block tests) — declared the same
+    way, returned un-cached, and never what ``load_library()`` or ``Engine()`` hand out afterwards."""
     global _lib
-    if _lib is not None:
+    if path is None and _lib is not None:
         return _lib
-    if not osp.exists(_LIB_PATH):
-        raise T2LError(f"{_LIB_PATH} is missing: the HIP extension is not built and there is no CPU fallback")
-    lib = C.CDLL(_LIB_PATH)
+    lib_path = _LIB_PATH if path is None else path
+    if not osp.exists(lib_path):
+        raise T2LError(f"{lib_path} is missing: the HIP extension is not built and there is no CPU fallback")
+    lib = C.CDLL(lib_path)
     for name, (res, args) in EXPORTS.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
-    _lib = lib
+    if path is None:
+        _lib = lib
     return lib
 
 
@@ -191,8 +195,9 @@ class Engine:
             raise T2LError(f"{name}: tensor is on cuda:{t.device.index}, this engine drives cuda:{self.device}")
         return _dev_ptr(t, dtype, name, align)
 
-    def __init__(self, device: Optional[int] = None):
-        self.lib = load_library()
+    def __init__(self, device: Optional[int] = None, lib: Optional[C.CDLL] = None):
+        """``lib``: a library from ``load_library(path)`` to drive instead of the shipped one (dev builds only)."""
+        self.lib = load_library() if lib is None else lib
         if not torch.cuda.is_available():
             raise T2LError("no MI355X visible: the engine needs a GPU (there is no CPU fallback)")
         self.device = torch.cuda.current_device() if device is None else int(device)
