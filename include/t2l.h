@@ -37,7 +37,7 @@ extern "C" {
 #define T2L_ABI_VERSION 2
 #define T2L_EMBED_DIM 256
 #define T2L_OBJECT_SIZE 28 /* args.object_size, models/cell_retrieval.py:32 */
-#define T2L_MAX_LOSS_BATCH 1024 /* rows of the contrastive matrix (one fused launch up to 128, a short chain beyond) */
+#define T2L_MAX_LOSS_BATCH 1024 /* rows of the contrastive / ranking-loss matrix (one fused launch up to 128, a short chain beyond) */
 #define T2L_MAX_TOPK 26    /* max(top_k) supported by the fused search (eval default is 10) */
 
 enum {
@@ -269,6 +269,25 @@ int t2l_search_counters(t2l_ctx* ctx, int32_t* out8);
 int t2l_contrastive_loss(t2l_ctx* ctx, const float* anchor, const float* positive, int32_t batch,
                          float temperature, float* loss, float* grad_anchor, float* grad_positive,
                          void* stream);
+
+/* ---- pairwise and hardest ranking losses ------------------------------------------------------- */
+/* Replaces: PairwiseRankingLoss.forward (training/losses.py:192-217; --ranking_loss pairwise, the default of training/args.py:41
+ * with --margin 0.35, :44) and the HardestRankingLoss in force (the module's second class, training/losses.py:321-355; both of its
+ * maxima run along dim=1), each with its autograd backward; selected as training/coarse.py:263-266 does.
+ * im/s: dev f32[batch,256] (T2L_EMBED_DIM; re-normalised inside, :193-194), 16-byte aligned. c = im^ . s^T, d_i = c_ii, B = batch:
+ *   pairwise  loss = scale/B * sum_{i != j} (max(0, margin - d_i + c_ij) + max(0, margin - d_j + c_ij))      (the reference: scale 1)
+ *   hardest   loss = scale/B * sum_i (max(0, max_{j != i} margin - d_i + c_ij) + max(0, max_{j != i} margin - d_j + c_ij))  (scale 64)
+ * An exact tie of a row's maximum goes to the lowest column (torch's CPU rule); batch 1 gives loss 0 and zero gradients.
+ * out_loss: dev f32[1]; grad_im/grad_s: dev f32[batch,256] = d loss/d input, both or neither (NULL, NULL: forward only).
+ * batch <= 128 is ONE launch; 128 < batch <= T2L_MAX_LOSS_BATCH (the global batch of data-parallel training,
+ * text2loc_amd.losses.PairwiseRankingLoss(group=...)) is six launches over two [batch][batch] matrices in the workspace the
+ * contrastive loss uses. No atomics: the same bits every run. T2L_EINVAL, before any launch: batch outside [1, T2L_MAX_LOSS_BATCH],
+ * an unknown kind, a negative or non-finite margin, a non-finite scale, a null im / s / out_loss, one gradient without the other,
+ * im or s off a 16-byte boundary, an output off a 4-byte one. */
+#define T2L_RANK_PAIRWISE 0
+#define T2L_RANK_HARDEST 1
+int t2l_ranking_loss(t2l_ctx* ctx, const float* im, const float* s, int32_t batch, int32_t kind, float margin,
+                     float scale, float* out_loss, float* grad_im, float* grad_s, void* stream);
 
 /* ---- text head after the frozen T5 encoder (f-4a), eval mode ------------------------------------ */
 /* Replaces: LanguageEncoder.forward from `description_encodings = out.last_hidden_state` up to and including `self.inter_mlp`
@@ -603,7 +622,7 @@ int t2l_set_option(t2l_ctx* ctx, const char* name, double value);
 /* Per-kernel device time measured with hipEvent pairs recorded on the caller's stream around each launch
  * (no synchronisation while recording; enabled by option "profile_events" >= 1, off by default).
  * Returns the average duration (ms) and the number of launches recorded since the previous call for
- * name = "search_scan" | "search_rerank" | "encode_cells" | "contrastive_loss" | "reduce_objects" | "train_forward" |
+ * name = "search_scan" | "search_rerank" | "encode_cells" | "contrastive_loss" | "ranking_loss" | "reduce_objects" | "train_forward" |
  * "train_backward" | "adam_step" | "pointnet" | "fine_objects" | "fine_match" | "search_fallback" | "search_exact" | "search_small" (at most
  * the last 512), "pointnet_train_index" | "pointnet_train_forward" | "pointnet_train_backward";
  * "search_scan_span" and "search_scan_busy" need no option: every workgroup of the paired scan stamps its own start and end

@@ -1,5 +1,6 @@
 // C ABI of libt2l.so (see include/t2l.h): context, database shard, options, timing.
 #include <limits.h>
+#include <math.h>
 #include <string.h>
 
 #include "t2l_internal.h"
@@ -399,6 +400,24 @@ int t2l_contrastive_loss(t2l_ctx* ctx, const float* anchor, const float* positiv
     return fail(ctx, T2L_EINVAL, "t2l_contrastive_loss: pass both gradients or neither");
   T2L_HIP(ctx, hipSetDevice(ctx->device));
   return loss_impl(ctx, anchor, positive, batch, temperature, loss, grad_anchor, grad_positive, (hipStream_t)stream);
+}
+
+int t2l_ranking_loss(t2l_ctx* ctx, const float* im, const float* s, int32_t batch, int32_t kind, float margin, float scale,
+                     float* out_loss, float* grad_im, float* grad_s, void* stream) {
+  if (!ctx) return T2L_EINVAL;
+  if (batch < 1 || batch > T2L_MAX_LOSS_BATCH) return fail(ctx, T2L_EINVAL, "t2l_ranking_loss: need 1 <= batch <= 1024");
+  if (kind != T2L_RANK_PAIRWISE && kind != T2L_RANK_HARDEST)
+    return fail(ctx, T2L_EINVAL, "t2l_ranking_loss: unknown kind (T2L_RANK_PAIRWISE or T2L_RANK_HARDEST)");
+  if (!(margin >= 0.f) || !isfinite(margin)) return fail(ctx, T2L_EINVAL, "t2l_ranking_loss: margin must be finite and >= 0");
+  if (!isfinite(scale)) return fail(ctx, T2L_EINVAL, "t2l_ranking_loss: scale must be finite");
+  if (!im || !s || !out_loss) return fail(ctx, T2L_EINVAL, "t2l_ranking_loss: null buffer");
+  if ((grad_im == nullptr) != (grad_s == nullptr)) return fail(ctx, T2L_EINVAL, "t2l_ranking_loss: pass both gradients or neither");
+  // rows are read as float4 (sim_tiles_lds, sim_tile, cl_norm_kernel); everything else one float at a time
+  if (((uintptr_t)im | (uintptr_t)s) % 16 != 0) return fail(ctx, T2L_EINVAL, "t2l_ranking_loss: im and s must be 16-byte aligned");
+  if (((uintptr_t)out_loss | (uintptr_t)grad_im | (uintptr_t)grad_s) % 4 != 0)
+    return fail(ctx, T2L_EINVAL, "t2l_ranking_loss: out_loss, grad_im and grad_s must be 4-byte aligned");
+  T2L_HIP(ctx, hipSetDevice(ctx->device));
+  return ranking_loss_impl(ctx, im, s, batch, kind, margin, scale, out_loss, grad_im, grad_s, (hipStream_t)stream);
 }
 
 int t2l_text_head_load_weights(t2l_ctx* ctx, const t2l_weight_desc* w, int32_t n, const char* prefix) {

@@ -97,7 +97,7 @@ struct t2l_ctx {
   int32_t* seg_idx = nullptr;    // per-segment results when the shard exceeds one scan launch
   double* seg_score = nullptr;
   size_t cand_cap = 0, flag_cap = 0, seg_idx_cap = 0, seg_score_cap = 0;  // bytes
-  void* loss_ws = nullptr;       // [B][B] matrix + row vectors of the contrastive loss beyond 128 rows (loss.hip)
+  void* loss_ws = nullptr;       // [B][B] matrices + row vectors of the contrastive and ranking losses beyond 128 rows (loss.hip)
   size_t loss_ws_cap = 0;
   void* reduce_ws = nullptr;     // work items + float64 accumulators of t2l_reduce_objects
   size_t reduce_ws_cap = 0;
@@ -284,5 +284,7 @@ struct PerDeviceOnce {  // (static instances are shared by the contexts of every
 
 int loss_impl(t2l_ctx* ctx, const float* a, const float* p, int B, float temp, float* loss, float* ga, float* gp,
               hipStream_t s);
+int ranking_loss_impl(t2l_ctx* ctx, const float* im, const float* s, int B, int kind, float margin, float scale, float* loss,
+                      float* g_im, float* g_s, hipStream_t stream);
 
 }  // namespace t2l

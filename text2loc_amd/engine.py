@@ -105,6 +105,8 @@ EXPORTS = {
     "t2l_search_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "t2l_contrastive_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "t2l_ranking_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "t2l_text_head_load_weights": (C.c_int, [C.c_void_p, C.POINTER(_WeightDesc), C.c_int32, C.c_char_p]),
     "t2l_text_head_load_weights_heads": (C.c_int, [C.c_void_p, C.POINTER(_WeightDesc), C.c_int32, C.c_char_p, C.c_int32]),
     "t2l_text_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -841,6 +843,24 @@ class Engine:
             float(temperature), loss.data_ptr(), self._ptr(ga, torch.float32, "ga"), self._ptr(gp, torch.float32, "gp"),
             _stream_ptr(self.device)))
         return loss, ga, gp
+
+    RANK_KINDS = {"pairwise": 0, "hardest": 1}  # T2L_RANK_PAIRWISE, T2L_RANK_HARDEST
+
+    def ranking_loss(self, im: torch.Tensor, s: torch.Tensor, kind, margin: float, scale: float = 1.0, need_grad=True):
+        """--ranking_loss pairwise | hardest on [B,256] rows (t2l_ranking_loss): (loss[1], d loss/d im, d loss/d s), the gradients
+        None when ``need_grad`` is false. ``kind``: "pairwise" / "hardest" or the header's constant."""
+        if isinstance(kind, str):
+            if kind not in self.RANK_KINDS:
+                raise T2LError(f"ranking_loss: unknown kind {kind!r} (pairwise or hardest)")
+            kind = self.RANK_KINDS[kind]
+        B = int(im.shape[0])
+        loss = torch.empty((1,), dtype=torch.float32, device=im.device)
+        g_im = torch.empty_like(im) if need_grad else None
+        g_s = torch.empty_like(s) if need_grad else None
+        self._check(self.lib.t2l_ranking_loss(
+            self._h, self._ptr(im, torch.float32, "im"), self._ptr(s, torch.float32, "s"), B, int(kind), float(margin), float(scale),
+            loss.data_ptr(), self._ptr(g_im, torch.float32, "g_im"), self._ptr(g_s, torch.float32, "g_s"), _stream_ptr(self.device)))
+        return loss, g_im, g_s
 
     # ------------------------------------------------------------------ knobs
     def set_option(self, name: str, value: float):
