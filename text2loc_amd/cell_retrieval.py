@@ -32,6 +32,8 @@ import torch.nn.functional as F
 
 from . import packing
 from .engine import EMBED_DIM, OBJECT_SIZE, TRAIN_SHAPE_MSG, Engine, T2LError, check_compiled_shape, is_published_shape
+from .plumbing import (_point_field, adopt_grad, bump_batches_tracked, check_token, engine_for, hook_leaf,  # noqa: F401
+                       is_point_batch, new_token, pack_objects, point_batch_tensors, read_object_points, rebind, tensors_version)
 
 
 def get_mlp(channels: Sequence[int], add_batchnorm: bool = True, last_relu: bool = True) -> nn.Sequential:
@@ -82,29 +84,6 @@ class PointNet2Params(nn.Module):
         self.color_classifier = nn.Linear(256, num_colors)
 
 
-def _point_field(p, name):
-    return p[name] if isinstance(p, dict) else getattr(p, name, None)
-
-
-def is_point_batch(p) -> bool:
-    """A cell's point batch as the reference's dataloader builds it: a PyG ``Batch`` or anything with ``.pos`` / ``.x``
-    [n*256,3], or a dict with those keys (anything else in ``object_points`` is a precomputed features2 array / tensor)."""
-    return not isinstance(p, (torch.Tensor, np.ndarray)) and _point_field(p, "pos") is not None
-
-
-def point_batch_tensors(object_points, use_color: bool, dev):
-    """Per-cell point batches -> (pos f32[n,256,3], rgb f32[n,256,3], objects per cell) on ``dev``. Without ``use_color`` the
-    colours are voided, as the reference's ObjectEncoder does (object_encoder.py:87-90); the caller's arrays are not touched."""
-    if use_color:
-        xs = [torch.as_tensor(_point_field(p, "x")) for p in object_points]
-    else:  # ablation of the reference: void all colours (object_encoder.py:87-90)
-        xs = [torch.zeros_like(torch.as_tensor(_point_field(p, "x"))) for p in object_points]
-    pos = torch.cat([torch.as_tensor(_point_field(p, "pos")).reshape(-1, 256, 3) for p in object_points]).to(dev, torch.float32)
-    rgb = torch.cat([x.reshape(-1, 256, 3) for x in xs]).to(dev, torch.float32)
-    counts = [int(torch.as_tensor(_point_field(p, "pos")).shape[0]) // 256 for p in object_points]
-    return pos.contiguous(), rgb.contiguous(), counts
-
-
 class ObjectEncoderParams(nn.Module):
     """Parameters of models/object_encoder.py:28-64 under the same names (PointNet++ sub-module excluded)."""
 
@@ -135,14 +114,13 @@ class _TextHeadTrainFn(torch.autograd.Function):
     def forward(ctx, hook, hidden, enc, batch_size, p_drop, seed):
         out = enc._th_train_engine.text_head_train(hidden, batch_size, dropout_p=p_drop, seed=seed)
         ctx.enc = enc
-        ctx.token = enc._th_train_token = object()
+        ctx.token = new_token(enc, "_th_train_token")
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         enc = ctx.enc
-        if enc._th_train_token is not ctx.token:
-            raise T2LError("backward of a stale text-head call: the engine keeps the activations of the LAST training-mode forward only")
+        check_token(enc, "_th_train_token", ctx.token, "text-head call")
         enc._th_train_engine.text_head_backward(grad_out.contiguous().float())
         return None, None, None, None, None, None
 
@@ -239,19 +217,21 @@ class LanguageEncoder(nn.Module):
 
     def _head_engine(self, device) -> Optional[Engine]:
         """The engine context holding this head's packed weights on ``device`` (re-packed when a tensor changes)."""
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        version = (idx, self._head_generation) + tuple((t.data_ptr(), t._version) for t in self._head_params())
-        if getattr(self, "_th_version", None) != version:
-            if getattr(self, "_th_engine", None) is None or self._th_engine.device != idx:
-                self._th_engine = Engine(idx)
+        eng, is_new = engine_for(self._th_engine, device, "the text head")
+        if is_new:
+            self._th_engine, self._th_version = eng, None
+        if self._th_version != (self._head_generation,) + tensors_version(self._head_params()):
             sd = {"language_encoder." + n: t for n, t in self.state_dict().items()
                   if n.startswith(("intra_module.", "inter_mlp.", "inter_module."))}
             inter = getattr(self, "inter_module", None)  # (the fine head has none; the loader's default then)
             self._th_engine.text_head_load_weights(sd, inter_num_heads=inter[0].self_attn.num_heads if inter is not None and len(inter) else 4)
             self._th_params = None  # (load_state_dict may have swapped tensors: re-collect)
-            version = (idx, self._head_generation) + tuple((t.data_ptr(), t._version) for t in self._head_params())
-            self._th_version = version
+            self._th_version = (self._head_generation,) + tensors_version(self._head_params())
         return self._th_engine
+
+    def _memo_version(self):
+        """What a memoised sentence vector depends on besides (sentence, L): the path and the head's weights."""
+        return (bool(self.use_engine_head), self._head_generation) + tensors_version(self._head_params())
 
     # Overflow handling. An engine call raises a device flag when a value entering an f16 product left the f16 range; the batch
     # must then be re-run on the PyTorch path. Default: read the flag after every call (one 4-byte copy + stream sync, as in
@@ -302,6 +282,9 @@ class LanguageEncoder(nn.Module):
     # ---- training mode: the whole head after T5 in the engine (t2l_text_head_train / _backward) ------------------------------------
     use_engine_train_head = True
     _head_generation = 0
+    _th_engine = None
+    _th_version = None
+    _th_train_hook = None
     train_engine_calls = 0
     _th_train_engine = None
     _th_train_token = None
@@ -365,9 +348,9 @@ class LanguageEncoder(nn.Module):
         self._th_train_engine.text_zero_grad()
 
     def _bind_text_train(self, device):
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        if self._th_train_engine is None or self._th_train_engine.device != idx:
-            self._th_train_engine, self._th_train_key = Engine(idx), None
+        eng, is_new = engine_for(self._th_train_engine, device, "the text head")
+        if is_new:
+            self._th_train_engine, self._th_train_key = eng, None
         tensors = {}
         for n, t in self.state_dict(keep_vars=True).items():
             if not n.startswith(("intra_module.0.", "inter_mlp.0.", "inter_module.0.")) or n.endswith("num_batches_tracked"):
@@ -378,13 +361,8 @@ class LanguageEncoder(nn.Module):
                 tensors["language_encoder." + n] = (t.data, t.grad)
             else:
                 tensors["language_encoder." + n] = (t, None)
-        key = tuple((d.data_ptr(), 0 if g is None else g.data_ptr()) for d, g in tensors.values())
-        if key != self._th_train_key:
-            # same head, moved storage (model.to(), a re-assigned .grad): the engine-side Adam moments must survive the re-bind
-            self._th_train_engine.set_option("train_keep_adam_state", 1 if self._th_train_key is not None else 0)
-            self._th_train_engine.text_train_bind(tensors)
-            self._th_train_key = key
-        _apply_sync_bn(self._th_train_engine, getattr(self, "_sync_bn_cfg", None))
+        self._th_train_key = rebind(eng, tensors, self._th_train_key, eng.text_train_bind)
+        _apply_sync_bn(eng, getattr(self, "_sync_bn_cfg", None))
 
     def head(self, hidden: torch.Tensor, batch_size: int) -> torch.Tensor:
         """hidden: last_hidden_state [n_sentences_total, L, C] -> [B, D], or [B, n_hints, D] for the fine head
@@ -395,11 +373,9 @@ class LanguageEncoder(nn.Module):
             LanguageEncoder.train_engine_calls += 1
             self._th_drop_calls += 1
             seed = (torch.initial_seed() * 0x9E3779B1 + self._th_drop_calls * 0x85EBCA6B) & 0xFFFFFFFF
-            hook = torch.zeros((), device=hidden.device, requires_grad=True)
-            bn = self.inter_mlp[0][1]
-            if bn.num_batches_tracked is not None:
-                bn.num_batches_tracked += 1
-            out = _TextHeadTrainFn.apply(hook, hidden.contiguous().float(), self, batch_size, p_drop, seed)
+            self._th_train_hook = hook_leaf(self._th_train_hook, hidden.device)
+            bump_batches_tracked(self.inter_mlp.named_modules(), lambda name: True)
+            out = _TextHeadTrainFn.apply(self._th_train_hook, hidden.contiguous().float(), self, batch_size, p_drop, seed)
             return out.view(batch_size, hidden.shape[0] // batch_size, -1) if self.is_fine else out
         self._open_call(hidden.device)
         n_eng = LanguageEncoder.head_engine_calls
@@ -451,7 +427,7 @@ class LanguageEncoder(nn.Module):
         LanguageEncoder.cache_calls += 1
         inference = not self.training and not torch.is_grad_enabled()
         if inference and self.memoise_sentence_vectors:
-            version = (bool(self.use_engine_head), self._head_generation) + tuple((t.data_ptr(), t._version) for t in self._head_params())
+            version = self._memo_version()
             deferred, self._deferred = getattr(self, "_deferred", None), None  # (the memo is checked synchronously: never cache a poisoned batch)
             try:
                 vec = cache.sentence_vectors(self, L, version)
@@ -524,7 +500,7 @@ class LanguageEncoder(nn.Module):
         starts = np.arange(0, n, batch_size)
         L_desc = np.repeat(np.maximum.reduceat(tok, starts), np.diff(np.append(starts, n)))
         rows = torch.from_numpy(ia).to(cache.device)
-        version = (bool(self.use_engine_head), self._head_generation) + tuple((t.data_ptr(), t._version) for t in self._head_params())
+        version = self._memo_version()
         x = None
         deferred, self._deferred = getattr(self, "_deferred", None), None  # (the memos are checked synchronously, as in _from_cache)
         try:
@@ -555,7 +531,7 @@ class _EncodeObjectsTrainFn(torch.autograd.Function):
         eng = model._engine
         out = eng.encode_cells_train(packed, dropout_p=p_drop, seed=seed)
         ctx.model = model
-        ctx.token = model._train_token = object()
+        ctx.token = new_token(model, "_train_token")
         ctx.need_pn = pn_feat is not None and pn_feat.requires_grad
         ctx.pn_engine = bool(model._pn_in_engine)  # features2 came from t2l_pointnet_features_train of a trainable backbone
         ctx.pn_shape = None if pn_feat is None else pn_feat.shape
@@ -564,9 +540,7 @@ class _EncodeObjectsTrainFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         model = ctx.model
-        if model._train_token is not ctx.token:
-            raise T2LError("backward of a stale encode_objects call: the engine keeps the activations of the LAST "
-                           "training-mode forward only (the reference's loop does one forward per backward too)")
+        check_token(model, "_train_token", ctx.token, "encode_objects call")
         gpn = torch.empty(ctx.pn_shape, dtype=torch.float32, device=grad_out.device) if (ctx.need_pn or ctx.pn_engine) else None
         model._engine.encode_cells_backward(grad_out.contiguous().float(), gpn)
         if ctx.pn_engine:
@@ -647,21 +621,16 @@ class CellRetrievalNetwork(nn.Module):
         a = self.args
         if not ("class" in a.use_features and not bool(getattr(a, "class_embed", False))):
             return None
-        if object_points is None or any(p is None for p in object_points):
-            raise T2LError("class_embed is off: object_points must hold, per cell, PointNet++ features2 [n_i,256] or the "
-                           "cell's point batch (.pos/.x [n_i*256,3])")
-        dev = self.device
-        if all(_point_field(p, "pos") is not None for p in object_points if not isinstance(p, (torch.Tensor, np.ndarray))) and \
-                not isinstance(object_points[0], (torch.Tensor, np.ndarray)):
-            pos, rgb, counts = point_batch_tensors(object_points, "color" in a.use_features, dev)
+        got = read_object_points(object_points, "color" in a.use_features, self.device)
+        if isinstance(got, tuple):
+            pos, rgb, counts = got
             offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
             if train:
                 self._pn_in_engine = any(p.requires_grad for p in self.object_encoder.pointnet.lin2.parameters())
                 self._pn_train_cells = len(counts)
                 return eng.pointnet_features_train(pos, rgb, offs)
             return eng.pointnet_features(pos, rgb, offs)
-        return torch.cat([p if isinstance(p, torch.Tensor) else torch.as_tensor(np.asarray(p)) for p in object_points],
-                         dim=0).to(dev, torch.float32).reshape(-1, 256)
+        return got
 
     # ---- training mode ----------------------------------------------------------------
     def _train_tensors(self):
@@ -710,14 +679,8 @@ class CellRetrievalNetwork(nn.Module):
             if isinstance(t, nn.Parameter) and not t.requires_grad:
                 out[n] = (t.data, None)  # --pointnet_freeze (object_encoder.py:53-55): forward only
             elif isinstance(t, nn.Parameter):
-                g = self._train_grads[n]
-                if t.grad is None:
-                    t.grad = g  # hand the persistent buffer back (zero_grad(set_to_none=True) only drops the reference)
-                    g.zero_()
-                elif t.grad.data_ptr() != g.data_ptr():
-                    g.copy_(t.grad)  # a gradient assigned from outside keeps its VALUE; the storage stays the flat buffer's
-                    t.grad = g
-                out[n] = (t.data, g)
+                adopt_grad(t, self._train_grads[n])
+                out[n] = (t.data, self._train_grads[n])  # (always the view of the flat buffer)
             else:
                 out[n] = (t, None)
         return out
@@ -730,25 +693,12 @@ class CellRetrievalNetwork(nn.Module):
         """The engine with the training path bound to the CURRENT parameter / gradient / buffer storage."""
         if not self.published_shape:
             raise T2LError("train_engine: " + TRAIN_SHAPE_MSG)
-        dev = self.device
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        if self._engine is None or self._engine.device != idx:
-            self._engine = Engine(idx)
-            self._weights_version = None
-            self._pn_weights_version = None
-            self._train_bound = None
-        tensors = self._train_tensors()
-        key = tuple((n, d.data_ptr(), None if g is None else g.data_ptr()) for n, (d, g) in tensors.items())
-        if key != self._train_bound:
-            a = self.args
-            # same model, moved storage (model.to(), re-assigned .grad): the optimizer state must survive the re-bind
-            self._engine.set_option("train_keep_adam_state", 1 if self._train_bound is not None else 0)
-            self._engine.train_bind(tensors, class_embed=bool(getattr(a, "class_embed", False)),
-                                    color_embed=bool(getattr(a, "color_embed", False)), use_features=tuple(a.use_features),
-                                    num_layers=a.object_inter_module_num_layers, num_heads=a.object_inter_module_num_heads)
-            self._train_bound = key
-        _apply_sync_bn(self._engine, getattr(self, "_sync_bn_cfg", None))
-        return self._engine
+        eng, a = self._device_engine(), self.args
+        self._train_bound = rebind(eng, self._train_tensors(), self._train_bound, lambda tensors: eng.train_bind(
+            tensors, class_embed=bool(getattr(a, "class_embed", False)), color_embed=bool(getattr(a, "color_embed", False)),
+            use_features=tuple(a.use_features), num_layers=a.object_inter_module_num_layers, num_heads=a.object_inter_module_num_heads))
+        _apply_sync_bn(eng, getattr(self, "_sync_bn_cfg", None))
+        return eng
 
     def sync_batchnorm(self, group=None, enable: bool = True):
         """Data-parallel training with the reference's batch statistics: every BatchNorm1d of the object branch
@@ -761,58 +711,34 @@ class CellRetrievalNetwork(nn.Module):
         if hasattr(self.language_encoder, "_bind_text_train"):
             self.language_encoder._sync_bn_cfg = cfg
 
-    def _encode_objects_train(self, objects, object_points):
-        dev = self.device
-        if dev.type != "cuda":
-            raise T2LError("encode_objects runs on the MI355X only (model.to('cuda')); there is no CPU fallback")
-        eng = self.train_engine()
-        self._pn_train_cells = 0
-        pn = self._pn_features(object_points, eng, train=True)  # reads the LIVE backbone tensors (t2l_train_bind)
-        if any(getattr(o, "_t2l_feat", None) is None for objs in objects for o in objs):
-            packed = packing.pack_cells_gpu(eng, objects, self.object_encoder.known_classes,
-                                            self.object_encoder.known_colors, dev)
-        else:
-            packed = packing.to_device(packing.pack_cells(objects, self.object_encoder.known_classes,
-                                                          self.object_encoder.known_colors, None), dev)
+    def _packed_input(self, eng: Engine, objects, object_points, train: bool = False):
+        """-> (the packed cells on the GPU, features2 among them in the published feature mode; features2 as ``_pn_features`` made it)."""
+        pn = self._pn_features(object_points, eng, train)  # (train: reads the LIVE backbone tensors, t2l_train_bind)
+        packed = pack_objects(eng, objects, self.object_encoder, self.device)
         if pn is not None:
             if int(pn.shape[0]) != int(packed["offsets"][-1]):
                 raise T2LError("object_points must describe exactly the objects of each cell")
             packed["pn_feat"] = pn.detach().contiguous()
+        return packed, pn
+
+    def _encode_objects_train(self, objects, object_points):
+        eng = self.train_engine()
+        self._pn_train_cells = 0
+        packed, pn = self._packed_input(eng, objects, object_points, train=True)
         layer = self.obj_inter_module[0] if len(self.obj_inter_module) else None
         p_drop = float(layer.dropout.p) if layer is not None else 0.0  # nn.TransformerEncoderLayer default 0.1
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())       # torch.manual_seed governs the masks
-        if self._train_hook is None or self._train_hook.device != dev:
-            self._train_hook = torch.zeros(1, device=dev, requires_grad=True)
+        self._train_hook = hook_leaf(self._train_hook, self.device)
         out = _EncodeObjectsTrainFn.apply(self._train_hook, pn, self, packed, p_drop, seed)
         used = {k for k, _, _ in self._train_bound}
-        for name, m in self.named_modules():  # BatchNorm1d.train() side effect the engine does not see (int64)
-            if isinstance(m, nn.BatchNorm1d) and m.num_batches_tracked is not None and name + ".running_mean" in used:
-                if name.startswith("object_encoder.pointnet."):
-                    m.num_batches_tracked += self._pn_train_cells  # one backbone call per cell (object_encoder.py:92-95)
-                else:
-                    m.num_batches_tracked += 1
+        bump_batches_tracked(self.named_modules(), lambda name: name + ".running_mean" in used, "object_encoder.pointnet.",
+                             self._pn_train_cells)
         self._train_generation += 1  # running statistics moved: the eval-path weights must be re-folded
         return out
 
     def _encode_objects_eval(self, objects, object_points=None):
-        dev = self.device
-        if dev.type != "cuda":
-            raise T2LError("encode_objects runs on the MI355X only (model.to('cuda')); there is no CPU fallback")
         eng = self.engine()
-        pn = self._pn_features(object_points, eng)
-        if any(getattr(o, "_t2l_feat", None) is None for objs in objects for o in objs):
-            # raw points not reduced yet: one HBM pass on the GPU (t2l_reduce_objects) instead of three numpy
-            # reductions per object on the host (what the reference redoes on every call)
-            packed = packing.pack_cells_gpu(eng, objects, self.object_encoder.known_classes,
-                                            self.object_encoder.known_colors, dev)
-        else:
-            packed = packing.to_device(packing.pack_cells(objects, self.object_encoder.known_classes,
-                                                          self.object_encoder.known_colors, None), dev)
-        if pn is not None:
-            if int(pn.shape[0]) != int(packed["offsets"][-1]):
-                raise T2LError("object_points must describe exactly the objects of each cell")
-            packed["pn_feat"] = pn.detach().contiguous()
-        return eng.encode_cells(packed)
+        return eng.encode_cells(self._packed_input(eng, objects, object_points)[0])
 
     @torch.no_grad()
     def encode_cell_set(self, cell_set, points: bool = False, transform: str = "fixed", seed: int = 0,
@@ -825,10 +751,8 @@ class CellRetrievalNetwork(nn.Module):
         ``points``: the published feature mode (class_embed off) — per chunk, FixedPoints(256) under ``transform`` on the GPU
         (t2l_sample_object_points, draws keyed on (seed, chunk, object, point)) -> PointNet++ (t2l_pointnet_features) ->
         ``pn_feat``. The per-object reductions (a1) run once per dataset and device (``PackedCellSet.reduced``)."""
-        dev = self.device
-        if dev.type != "cuda":
-            raise T2LError("encode_cell_set runs on the MI355X only (model.to('cuda')); there is no CPU fallback")
-        a = self.args
+        dev, a = self.device, self.args
+        self._device_engine("encode_cell_set")  # (refuses a CPU model under this method's name)
         eng = self.engine()
         need_pn = "class" in a.use_features and not bool(getattr(a, "class_embed", False))
         if need_pn and not points:
@@ -860,23 +784,23 @@ class CellRetrievalNetwork(nn.Module):
         return out
 
     # ---- engine plumbing --------------------------------------------------------------------------------
+    def _device_engine(self, what: str = "encode_objects") -> Engine:
+        eng, is_new = engine_for(self._engine, self.device, what)
+        if is_new:
+            self._engine, self._weights_version, self._pn_weights_version, self._train_bound = eng, None, None, None
+        return eng
+
     def engine(self) -> Engine:
         """The engine holding the CURRENT object-branch weights. Checked on every call — an optimizer steps parameters in place
         behind the module's back — but against a cached parameter list: (data_ptr, _version) over it costs ~24 us where walking
         ``state_dict(keep_vars=True)`` cost ~200 us per ``encode_objects`` call (as much host time as the GPU needs for eight
         cells). The list is rebuilt whenever the module tree may have changed hands: ``train()/eval()``, ``load_state_dict``,
         ``to()/cuda()/float()`` (``_apply``)."""
-        dev = self.device
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        if self._engine is None or self._engine.device != idx:
-            self._engine = Engine(idx)
-            self._weights_version = None
-            self._pn_weights_version = None
-            self._train_bound = None
+        self._device_engine()
         params = self._obj_param_list
         if params is None:
             params = self._obj_param_list = list(self._object_params())
-        version = (self._train_generation, tuple([(p.data_ptr(), p._version) for p in params]))
+        version = (self._train_generation, tensors_version(params))
         if version != self._weights_version:
             self.sync_weights()
             self._weights_version = version
@@ -902,8 +826,7 @@ class CellRetrievalNetwork(nn.Module):
                 yield p
 
     def _pn_version(self):
-        return tuple((p.data_ptr(), p._version) for n, p in self.state_dict(keep_vars=True).items()
-                     if n.startswith("object_encoder.pointnet."))
+        return tensors_version(p for n, p in self.state_dict(keep_vars=True).items() if n.startswith("object_encoder.pointnet."))
 
     def sync_weights(self):
         """Fold BatchNorm, re-lay out and upload the object-branch weights (t2l_load_weights)."""

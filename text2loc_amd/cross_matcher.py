@@ -41,8 +41,10 @@ import torch
 import torch.nn as nn
 
 from . import packing
-from .cell_retrieval import LanguageEncoder, ObjectEncoderParams, is_point_batch, point_batch_tensors
+from .cell_retrieval import LanguageEncoder, ObjectEncoderParams
 from .engine import Engine, T2LError
+from .plumbing import (adopt_grad, bind_key, bump_batches_tracked, check_token, engine_for, hook_leaf, new_token, pack_objects,
+                       read_object_points, tensors_version)
 
 FINE_DIM, PAD_SIZE = 128, 16
 BACKBONE = "object_encoder.pointnet."
@@ -127,19 +129,15 @@ class CrossMatch(nn.Module):
 
     # ---- engine plumbing ----------------------------------------------------------------------------------
     def _device_engine(self) -> Engine:
-        dev = self.device
-        if dev.type != "cuda":
-            raise T2LError("the fine stage runs on the MI355X only (model.to('cuda')); there is no CPU fallback")
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        if self._engine is None or self._engine.device != idx:
-            self._engine = Engine(idx)
-            self._weights_version = None
-        return self._engine
+        eng, is_new = engine_for(self._engine, self.device, "the fine stage")
+        if is_new:
+            self._engine, self._weights_version, self._fine_train_bound = eng, None, None
+        return eng
 
     def engine(self) -> Engine:
         self._device_engine()
         params = [p for n, p in self.state_dict(keep_vars=True).items() if not n.startswith("language_encoder.")]
-        version = (tuple((p.data_ptr(), p._version) for p in params), self._train_generation)
+        version = (tensors_version(params), self._train_generation)
         if version != self._weights_version:
             a = self.args
             sd = {k: v for k, v in self.state_dict().items() if not k.startswith("language_encoder.")}
@@ -149,6 +147,16 @@ class CrossMatch(nn.Module):
             self._weights_version = version
         return self._engine
 
+    def _read_points(self, objects, object_points):
+        """``read_object_points`` for exactly the cells of ``objects`` (the engine takes the cell count from ``objects`` and reads
+        ``pad_size`` rows per cell): -> features2 f32[B*16,256], or the point batches' (pos, rgb, counts)."""
+        got = read_object_points(object_points, "color" in self.args.use_features, self.device, PAD_SIZE)
+        rows = int((got[0] if isinstance(got, tuple) else got).shape[0])
+        if rows != len(objects) * PAD_SIZE:
+            raise T2LError(f"object_points must describe exactly the objects of each cell: {len(objects)} cells of {PAD_SIZE}, "
+                           f"got {rows} objects in all")
+        return got
+
     # ---- the two halves -----------------------------------------------------------------------------------
     @torch.no_grad()
     def encode_cells(self, objects, object_points=None) -> torch.Tensor:
@@ -157,26 +165,13 @@ class CrossMatch(nn.Module):
             raise T2LError("the fine stage is eval-only here (call model.eval()); its training step is not built")
         if any(len(o) != PAD_SIZE for o in objects):
             raise T2LError(f"every cell must hold exactly pad_size={PAD_SIZE} objects (cross_matcher.pad_objects pads / cuts)")
-        eng = self.engine()
-        dev = self.device
-        oe = self.object_encoder
-        if any(getattr(o, "_t2l_feat", None) is None for objs in objects for o in objs):
-            packed = packing.pack_cells_gpu(eng, objects, oe.known_classes, oe.known_colors, dev)
-        else:
-            packed = packing.to_device(packing.pack_cells(objects, oe.known_classes, oe.known_colors), dev)
-        a = self.args
+        eng, a = self.engine(), self.args
+        packed = pack_objects(eng, objects, self.object_encoder, self.device)
         if "class" in a.use_features and not bool(getattr(a, "class_embed", False)):
-            if object_points is None or any(p is None for p in object_points):
-                raise T2LError("class_embed is off: object_points must hold, per cell, features2 [16,256] or the point batch")
-            first = object_points[0]
-            if isinstance(first, (torch.Tensor, np.ndarray)):
-                pn = torch.cat([torch.as_tensor(np.asarray(p) if not isinstance(p, torch.Tensor) else p) for p in object_points]).to(dev, torch.float32)
-            else:
-                get = lambda p, n: p[n] if isinstance(p, dict) else getattr(p, n)
-                pos = torch.cat([torch.as_tensor(get(p, "pos")).reshape(-1, 256, 3) for p in object_points]).to(dev, torch.float32)
-                rgb = torch.cat([torch.as_tensor(get(p, "x")).reshape(-1, 256, 3) for p in object_points]).to(dev, torch.float32)
-                pn = eng.pointnet_features(pos.contiguous(), rgb.contiguous(), np.arange(0, len(objects) * PAD_SIZE + 1, PAD_SIZE, dtype=np.int32))
-            packed["pn_feat"] = pn.reshape(-1, 256).contiguous()
+            pn = self._read_points(objects, object_points)
+            if isinstance(pn, tuple):  # point batches: the backbone in the engine
+                pn = eng.pointnet_features(pn[0], pn[1], np.arange(0, len(objects) * PAD_SIZE + 1, PAD_SIZE, dtype=np.int32))
+            packed["pn_feat"] = pn.contiguous()
         return eng.fine_encode_objects(packed)
 
     @torch.no_grad()
@@ -237,12 +232,8 @@ class CrossMatch(nn.Module):
                 g = self._fine_train_grads[n] = torch.zeros_like(t.data)
             if n.startswith(BACKBONE):
                 self._fine_train_pn_live.append((t, g))
-            elif t.grad is None:
-                t.grad = g  # hand the persistent buffer back (zero_grad(set_to_none=True) only drops the reference)
-                g.zero_()
-            elif t.grad.data_ptr() != g.data_ptr():
-                g.copy_(t.grad)  # a gradient assigned from outside keeps its VALUE; the storage stays the bound buffer
-                t.grad = g
+            else:
+                adopt_grad(t, g)
             out[n] = (t.data, g)
         for n, b in self.named_buffers():
             if n.startswith(run) and n.endswith(("running_mean", "running_var")):
@@ -266,7 +257,7 @@ class CrossMatch(nn.Module):
         the step reads the live tensors)."""
         eng = self._device_engine()
         tensors = self._fine_train_tensors()
-        key = (id(eng),) + tuple((n, d.data_ptr(), None if g is None else g.data_ptr()) for n, (d, g) in tensors.items())
+        key = bind_key(tensors)
         if key != self._fine_train_bound:
             a = self.args
             eng.fine_train_bind(tensors, class_embed=bool(getattr(a, "class_embed", False)), color_embed=bool(getattr(a, "color_embed", False)),
@@ -277,60 +268,26 @@ class CrossMatch(nn.Module):
     def _forward_train(self, objects, hints, object_points):
         if any(len(o) != PAD_SIZE for o in objects):
             raise T2LError(f"every cell must hold exactly pad_size={PAD_SIZE} objects (cross_matcher.pad_objects pads / cuts)")
-        a = self.args
-        want_pn = not bool(getattr(a, "class_embed", False))  # object_encoder.py:86-99: features2 whenever class_embed is off
-        points = False
-        if want_pn:
-            if object_points is None or any(p is None for p in object_points):
-                raise T2LError("class_embed is off: object_points must hold, per cell, features2 [16,256] or the cell's point batch "
-                               "(.pos/.x [16*256,3])")
-            kinds = {is_point_batch(p) for p in object_points}
-            if len(kinds) > 1:
-                raise T2LError("object_points mixes point batches and features2 tensors: pass one kind for every cell")
-            points = kinds == {True}
-            if points and self.device.type != "cuda":
-                raise T2LError("training the fine stage on point batches needs the jointly trained PointNet++ backbone, which is not "
-                               "built for the fine stage on the host: it runs on the MI355X only (model.to('cuda')); there is no CPU fallback")
-        p_drop = self._fine_train_dropout()                         # nn.TransformerDecoderLayer default 0.1
-        dev = self.device
-        if dev.type != "cuda":
-            raise T2LError("the fine stage runs on the MI355X only (model.to('cuda')); there is no CPU fallback")
+        a, dev = self.args, self.device
         pn = pts = None
-        if points:
-            get = lambda p, n: p[n] if isinstance(p, dict) else getattr(p, n, None)
-            for p in object_points:
-                shapes = [tuple(np.shape(get(p, n))) if get(p, n) is not None else None for n in ("pos", "x")]
-                if any(sh != (PAD_SIZE * 256, 3) for sh in shapes):
-                    raise T2LError(f"a point batch must hold {PAD_SIZE}*256 points per cell (.pos and .x [{PAD_SIZE * 256},3]), got {shapes}")
-            pos, rgb, _ = point_batch_tensors(object_points, "color" in a.use_features, dev)
-            pts = (pos, rgb)
-        elif want_pn:
-            pn = torch.cat([p if isinstance(p, torch.Tensor) else torch.from_numpy(np.asarray(p)) for p in object_points]).to(dev, torch.float32)
-            if tuple(pn.shape) != (len(objects) * PAD_SIZE, 256):
-                raise T2LError(f"features2 must be [16,256] per cell, got {tuple(pn.shape)} in all")
+        if not bool(getattr(a, "class_embed", False)):  # object_encoder.py:86-99: features2 whenever class_embed is off
+            pn = self._read_points(objects, object_points)
+            if isinstance(pn, tuple):
+                pn, pts = None, pn[:2]
+                if dev.type != "cuda":
+                    raise T2LError("training the fine stage on point batches needs the jointly trained PointNet++ backbone, which is not "
+                                   "built for the fine stage on the host: it runs on the MI355X only (model.to('cuda')); there is no CPU fallback")
+        p_drop = self._fine_train_dropout()                         # nn.TransformerDecoderLayer default 0.1
         eng = self._fine_train_engine()
-        oe = self.object_encoder
-        if any(getattr(o, "_t2l_feat", None) is None for objs in objects for o in objs):
-            packed = packing.pack_cells_gpu(eng, objects, oe.known_classes, oe.known_colors, dev)
-        else:
-            packed = packing.to_device(packing.pack_cells(objects, oe.known_classes, oe.known_colors), dev)
+        packed = pack_objects(eng, objects, self.object_encoder, dev)
         hint_enc = self.language_encoder(hints)  # [B, n_hints, 128]  (cross_matcher.py:95): the engine's training head behind T5
         if hint_enc.dim() != 3 or hint_enc.shape[0] != len(objects) or not 1 <= hint_enc.shape[1] <= 8 or hint_enc.shape[2] != FINE_DIM:
             raise T2LError(f"hint encodings must be [B={len(objects)}, 1..8, 128], got {tuple(hint_enc.shape)}")
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())        # torch.manual_seed governs the masks
-        if self._fine_train_hook is None or self._fine_train_hook.device != dev:
-            self._fine_train_hook = torch.zeros(1, device=dev, requires_grad=True)
+        self._fine_train_hook = hook_leaf(self._fine_train_hook, dev)
         out = _FineTrainFn.apply(self._fine_train_hook, hint_enc, pn, self, packed, p_drop, seed, pts)
         run, _ = self._fine_train_modules()
-        for name, m in self.object_encoder.named_modules():  # BatchNorm1d.train() side effect the engine does not see (int64)
-            full = f"object_encoder.{name}."
-            if not (isinstance(m, nn.BatchNorm1d) and m.num_batches_tracked is not None and full.startswith(run)):
-                continue
-            if full.startswith(BACKBONE):
-                if points:
-                    m.num_batches_tracked += len(objects)  # one backbone call per cell in the reference (object_encoder.py:92-95)
-            else:
-                m.num_batches_tracked += 1
+        bump_batches_tracked(self.named_modules(), lambda name: (name + ".").startswith(run), BACKBONE, len(objects) if pts is not None else 0)
         self._train_generation += 1  # running statistics moved: the eval path must re-load its weights
         return out
 
@@ -351,7 +308,7 @@ class _FineTrainFn(torch.autograd.Function):
         else:
             out = model._engine.fine_train_forward(packed, pn_c, hint_c, dropout_p=p_drop, seed=seed)
         ctx.model = model
-        ctx.token = model._fine_train_token = object()
+        ctx.token = new_token(model, "_fine_train_token")
         ctx.hint_shape, ctx.hint_dtype = hint_c.shape, hint_enc.dtype
         ctx.pn_shape = None if pn is None else pn_c.shape
         ctx.pn_live = list(model._fine_train_pn_live) if pts is not None else []  # the backbone's backward will run
@@ -360,19 +317,17 @@ class _FineTrainFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         model = ctx.model
-        if model._fine_train_token is not ctx.token:
-            raise T2LError("backward of a stale CrossMatch training forward: the engine keeps the activations of the LAST "
-                           "training-mode forward only (the reference's loop does one forward per backward too)")
+        check_token(model, "_fine_train_token", ctx.token, "CrossMatch training forward")
         need_hint, need_pn = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         gh = torch.empty(ctx.hint_shape, dtype=torch.float32, device=grad_out.device) if need_hint else None
         gp = torch.empty(ctx.pn_shape, dtype=torch.float32, device=grad_out.device) if need_pn else None
-        for t, g in ctx.pn_live:  # the engine ADDS into the bound buffers: give them the value .grad has now
+        for t, g in ctx.pn_live:  # the engine ADDS into the bound buffers: give them the value .grad has now ...
             if t.grad is None:
                 g.zero_()
             elif t.grad.data_ptr() != g.data_ptr():
                 g.copy_(t.grad)
         model._engine.fine_train_backward(grad_out.contiguous().float(), gh, gp)
-        for t, g in ctx.pn_live:
+        for t, g in ctx.pn_live:  # ... and hand them out only once the backward went through the backbone (adopt_grad in two halves)
             t.grad = g
         return None, (gh.to(ctx.hint_dtype) if gh is not None else None), gp, None, None, None, None, None
 

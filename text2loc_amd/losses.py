@@ -6,12 +6,13 @@ from __future__ import annotations
 import torch
 
 from .engine import Engine
+from .plumbing import device_index
 
-_engines = {}
+_engines = {}  # device index -> the losses' own engine context (one per device, shared by every criterion)
 
 
 def _engine_for(device: torch.device) -> Engine:
-    idx = device.index if device.index is not None else torch.cuda.current_device()
+    idx = device_index(device, "the loss")
     if idx not in _engines:
         _engines[idx] = Engine(idx)
     return _engines[idx]
