@@ -127,7 +127,7 @@ def test_missing_weight_key_is_loud(eng):
 
     sd = synth.make_object_branch_weights(0)
     del sd["obj_inter_module.1.linear2.weight"]
-    with pytest.raises(T2LError, match="missing required key"):
+    with pytest.raises(T2LError, match="t2l_load_weights: missing tensor 'obj_inter_module.1.linear2.weight'"):
         eng.load_weights(sd, class_embed=True, color_embed=True)
 
 

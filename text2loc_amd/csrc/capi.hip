@@ -59,6 +59,32 @@ void event_end(t2l_ctx* ctx, const char* name, hipStream_t s) {
   if (e.count < kEventRing) ++e.count;
 }
 
+int upload_staging(t2l_ctx* ctx, const char* who, const Staging& st, char** blob) {
+  char* d = nullptr;
+  if (hipMalloc(&d, st.bytes()) != hipSuccess) return fail(ctx, T2L_ENOMEM, std::string(who) + ": hipMalloc of " + std::to_string(st.bytes()) + " bytes failed");
+  if (hipMemcpy(d, st.data(), st.bytes(), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(d);
+    return fail(ctx, T2L_EHIP, std::string(who) + ": upload failed");
+  }
+  st.bind(d);
+  *blob = d;
+  return T2L_OK;
+}
+
+// A state dict's optional object_encoder.pointnet.* group is validated before `load` (which validates, then commits its own part)
+// and committed after it: a list either part refuses changes neither.
+template <typename Load>
+int load_with_backbone(t2l_ctx* ctx, const char* who, const t2l_weight_desc* w, int n, Load load) {
+  PointNetStaged* pn = nullptr;
+  int rc = pointnet_stage(ctx, who, w, n, &pn);
+  if (rc) return rc;
+  if ((rc = load())) {
+    pointnet_discard(pn);
+    return rc;
+  }
+  return pointnet_commit(ctx, who, pn);
+}
+
 }  // namespace t2l
 
 using namespace t2l;
@@ -127,16 +153,15 @@ int t2l_load_weights(t2l_ctx* ctx, const t2l_weight_desc* w, int32_t n, const t2
   if (!ctx) return T2L_EINVAL;
   if (!w || n <= 0 || !cfg) return fail(ctx, T2L_EINVAL, "t2l_load_weights: null/empty arguments");
   T2L_HIP(ctx, hipSetDevice(ctx->device));
-  const int rc = load_weights_impl(ctx, w, n, cfg, T2L_EMBED_DIM, T2L_OBJECT_SIZE);
-  return rc ? rc : pointnet_load_impl(ctx, w, n);
+  return load_with_backbone(ctx, "t2l_load_weights", w, n, [&] { return load_weights_impl(ctx, w, n, cfg, T2L_EMBED_DIM, T2L_OBJECT_SIZE); });
 }
 
 int t2l_load_weights_shaped(t2l_ctx* ctx, const t2l_weight_desc* w, int32_t n, const t2l_model_config* cfg, const t2l_model_shape* shape) {
   if (!ctx) return T2L_EINVAL;
   if (!w || n <= 0 || !cfg || !shape) return fail(ctx, T2L_EINVAL, "t2l_load_weights_shaped: null/empty arguments");
   T2L_HIP(ctx, hipSetDevice(ctx->device));
-  const int rc = load_weights_impl(ctx, w, n, cfg, shape->embed_dim, shape->object_size);
-  return rc ? rc : pointnet_load_impl(ctx, w, n);
+  return load_with_backbone(ctx, "t2l_load_weights", w, n,
+                            [&] { return load_weights_impl(ctx, w, n, cfg, shape->embed_dim, shape->object_size); });
 }
 
 int t2l_embed_dim(const t2l_ctx* ctx) { return ctx ? encoder_embed_dim(ctx) : T2L_EINVAL; }
@@ -523,8 +548,9 @@ int t2l_text_inter(t2l_ctx* ctx, const float* sent, int32_t n_descriptions, int3
 int t2l_fine_load_weights(t2l_ctx* ctx, const t2l_weight_desc* w, int32_t n, const t2l_model_config* cfg) {
   if (!ctx) return T2L_EINVAL;
   T2L_HIP(ctx, hipSetDevice(ctx->device));
-  const int rc = fine_load_impl(ctx, w, n, cfg);
-  return rc ? rc : pointnet_load_impl(ctx, w, n);  // the fine checkpoint carries its own object_encoder.pointnet.* (optional group)
+  if (!w || n <= 0 || !cfg) return fail(ctx, T2L_EINVAL, "t2l_fine_load_weights: null argument");
+  // the fine checkpoint carries its own object_encoder.pointnet.* (optional group)
+  return load_with_backbone(ctx, "t2l_fine_load_weights", w, n, [&] { return fine_load_impl(ctx, w, n, cfg); });
 }
 
 int t2l_fine_encode_objects(t2l_ctx* ctx, const t2l_packed_cells* in, float* out_desc, void* stream) {

@@ -30,6 +30,8 @@
 #include <math.h>
 #include <string.h>
 
+#include <memory>
+
 #include "t2l_internal.h"
 #include "encode_shared.h"
 
@@ -768,50 +770,6 @@ int text_inter_fused_launch(t2l_ctx* ctx, const InterFusedW& W, int D, int heads
 // ---- host side: BN folding, fragment packing, upload -------------------------------------------
 namespace {
 
-struct Blob {
-  std::vector<float> h;
-  size_t add(const std::vector<float>& v) {
-    const size_t off = (h.size() + 3) / 4 * 4;  // 16-byte aligned
-    h.resize(off);
-    h.insert(h.end(), v.begin(), v.end());
-    return off;
-  }
-};
-
-using WMap = std::unordered_map<std::string, const t2l_weight_desc*>;
-
-const float* need(t2l_ctx* ctx, const WMap& m, const std::string& name, int64_t numel, int* rc) {
-  auto it = m.find(name);
-  if (it == m.end()) {
-    *rc = fail(ctx, T2L_EINVAL, "t2l_load_weights: missing required key " + name);
-    return nullptr;
-  }
-  if (numel > 0 && it->second->numel != numel) {
-    *rc = fail(ctx, T2L_EINVAL, "t2l_load_weights: wrong size for " + name);
-    return nullptr;
-  }
-  return it->second->data;
-}
-
-// Linear(+BatchNorm1d eval) -> W' [out][in], b' [out]
-bool fold(t2l_ctx* ctx, const WMap& m, const std::string& lin, const std::string& bn, int out, int in,
-          std::vector<float>* W, std::vector<float>* b, int* rc) {
-  const float* w = need(ctx, m, lin + ".weight", (int64_t)out * in, rc);
-  const float* bb = need(ctx, m, lin + ".bias", out, rc);
-  if (!w || !bb) return false;
-  W->assign(w, w + (size_t)out * in);
-  b->assign(bb, bb + out);
-  if (!bn.empty()) {
-    const float* g = need(ctx, m, bn + ".weight", out, rc);
-    const float* be = need(ctx, m, bn + ".bias", out, rc);
-    const float* rm = need(ctx, m, bn + ".running_mean", out, rc);
-    const float* rv = need(ctx, m, bn + ".running_var", out, rc);
-    if (!g || !be || !rm || !rv) return false;
-    fold_batchnorm(W->data(), b->data(), out, in, g, be, rm, rv);
-  }
-  return true;
-}
-
 std::vector<float> pack_h(const std::vector<float>& W, int N, int K) { return pack_split_f16(W.data(), nullptr, N, K, K); }
 float max_abs(const float* v, size_t n) { return h3_max_abs(v, n); }
 float max_row_norm(const float* W, int rows, int cols) { return h3_max_row_norm(W, rows, cols); }
@@ -827,18 +785,16 @@ std::vector<float> normalized_rows(const float* t, int rows, int D) {
   return o;
 }
 
-struct SmallOff {
-  size_t w1, b1, w2p, b2;
-};
+constexpr size_t kEncAlign = 16;  // the encoder's arrays sit 16-byte aligned in its blob (float4 / uint4 loads)
 
-bool add_small(t2l_ctx* ctx, const WMap& m, const std::string& pre, int in, int D, Blob* blob, SmallOff* off, int* rc) {
+bool add_small(WeightTable& T, const std::string& pre, int in, int D, Staging* st, SmallMlp* m) {
   std::vector<float> W1, b1, W2, b2;
-  if (!fold(ctx, m, pre + ".0.0", pre + ".0.1", 64, in, &W1, &b1, rc)) return false;
-  if (!fold(ctx, m, pre + ".1.0", pre + ".1.1", D, 64, &W2, &b2, rc)) return false;
-  off->w1 = blob->add(W1);
-  off->b1 = blob->add(b1);
-  off->w2p = blob->add(pack_half_split(W2, nullptr, D, 64, 64));
-  off->b2 = blob->add(b2);
+  if (!fold_linear(T, pre + ".0.0", pre + ".0.1", 64, in, &W1, &b1)) return false;
+  if (!fold_linear(T, pre + ".1.0", pre + ".1.1", D, 64, &W2, &b2)) return false;
+  st->place(&m->w1, W1, kEncAlign);
+  st->place(&m->b1, b1, kEncAlign);
+  st->place(&m->w2p, pack_half_split(W2, nullptr, D, 64, 64), kEncAlign);
+  st->place(&m->b2, b2, kEncAlign);
   return true;
 }
 
@@ -860,48 +816,47 @@ int load_weights_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const t2l_m
   if (cfg->num_layers < 1 || cfg->num_layers > 4) return fail(ctx, T2L_EINVAL, "t2l_load_weights: num_layers must be 1..4");
   const int nfeat = (cfg->use_class != 0) + (cfg->use_color != 0) + (cfg->use_position != 0) + (cfg->use_num != 0);
   if (nfeat < 1) return fail(ctx, T2L_EINVAL, "t2l_load_weights: use_features is empty");
-  WMap m;
-  for (int i = 0; i < n; ++i) {
-    if (!w[i].name || !w[i].data) return fail(ctx, T2L_EINVAL, "t2l_load_weights: null name/data");
-    m[w[i].name] = &w[i];
-  }
-  int rc = T2L_OK;
-  Blob blob;
+  WeightTable T("t2l_load_weights", w, n);
+  Staging blob;
+  std::unique_ptr<EncoderWeights> ew(new EncoderWeights());
+  EncParams& P = ew->p;
+  memset(&P, 0, sizeof(P));
+  auto put = [&](auto** field, const std::vector<float>& v) { blob.place(field, v, kEncAlign); };
+  auto refused = [&]() { return fail(ctx, T2L_EINVAL, T.error()); };
+  if (!T.ok()) return refused();
   const std::string oe = "object_encoder.";
-  size_t class_tab = 0, color_tab = 0, pn_wp = 0, pn_b = 0, merge_wp = 0, merge_hp = 0, merge_b = 0;
+  // an embedding table [rows][D], rows L2-normalised
+  auto table = [&](const std::string& name, int* rows, const float** tab) -> bool {
+    int64_t n_rows = 0;
+    const float* t = T.need_rows(name, D, &n_rows);
+    if (t) put(tab, normalized_rows(t, *rows = (int)n_rows, D));
+    return t != nullptr;
+  };
   // split-f16 safety (file header): largest weight, and an upper bound on |activation| entering a split GEMM
   float w_absmax = 0.f, act_bound = 1.f;  // merge inputs are unit rows
-  int n_class = 0, n_color = 0;
-  SmallOff pos{}, color{}, num{};
   if (cfg->use_class) {
     if (cfg->class_embed) {
-      auto it = m.find(oe + "class_embedding.weight");
-      if (it == m.end() || it->second->numel % D) return fail(ctx, T2L_EINVAL, "missing/odd class_embedding.weight");
-      n_class = (int)(it->second->numel / D);
-      class_tab = blob.add(normalized_rows(it->second->data, n_class, D));
+      if (!table(oe + "class_embedding.weight", &P.n_class, &P.class_tab)) return refused();
     } else {
       std::vector<float> W, b;
-      if (!fold(ctx, m, oe + "mlp_pointnet.0.0", oe + "mlp_pointnet.0.1", D, 256, &W, &b, &rc)) return rc;  // features2 is 256 wide at every D
-      pn_wp = blob.add(pack_half_split(W, nullptr, D, 256, 256));
-      pn_b = blob.add(b);
+      if (!fold_linear(T, oe + "mlp_pointnet.0.0", oe + "mlp_pointnet.0.1", D, 256, &W, &b)) return refused();  // features2 is 256 wide at every D
+      put(&P.pn_wp, pack_half_split(W, nullptr, D, 256, 256));
+      put(&P.pn_b, b);
       w_absmax = fmaxf(w_absmax, max_abs(W.data(), W.size()));
     }
   }
   if (cfg->use_color) {
     if (cfg->color_embed) {
-      auto it = m.find(oe + "color_embedding.weight");
-      if (it == m.end() || it->second->numel % D) return fail(ctx, T2L_EINVAL, "missing/odd color_embedding.weight");
-      n_color = (int)(it->second->numel / D);
-      color_tab = blob.add(normalized_rows(it->second->data, n_color, D));
-    } else if (!add_small(ctx, m, oe + "color_encoder", 3, D, &blob, &color, &rc)) {
-      return rc;
+      if (!table(oe + "color_embedding.weight", &P.n_color, &P.color_tab)) return refused();
+    } else if (!add_small(T, oe + "color_encoder", 3, D, &blob, &P.color)) {
+      return refused();
     }
   }
-  if (cfg->use_position && !add_small(ctx, m, oe + "pos_encoder", 3, D, &blob, &pos, &rc)) return rc;
-  if (cfg->use_num && !add_small(ctx, m, oe + "num_encoder", 1, D, &blob, &num, &rc)) return rc;
+  if (cfg->use_position && !add_small(T, oe + "pos_encoder", 3, D, &blob, &P.pos)) return refused();
+  if (cfg->use_num && !add_small(T, oe + "num_encoder", 1, D, &blob, &P.num)) return refused();
   if (nfeat > 1) {
     std::vector<float> W, b;
-    if (!fold(ctx, m, oe + "mlp_merge.0.0", oe + "mlp_merge.0.1", D, nfeat * D, &W, &b, &rc)) return rc;
+    if (!fold_linear(T, oe + "mlp_merge.0.0", oe + "mlp_merge.0.1", D, nfeat * D, &W, &b)) return refused();
     {  // one (N=256, K=256) packing per feature slot, consecutive
       std::vector<float> all, all_h;
       for (int sl = 0; sl < nfeat; ++sl) {
@@ -913,50 +868,46 @@ int load_weights_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const t2l_m
         const std::vector<float> ph = pack_h(Ws, D, D);
         all_h.insert(all_h.end(), ph.begin(), ph.end());
       }
-      merge_wp = blob.add(all);
-      merge_hp = blob.add(all_h);
+      put(&P.merge_wp, all);
+      put(&P.merge_hp, all_h);
       w_absmax = fmaxf(w_absmax, max_abs(W.data(), W.size()));
     }
-    merge_b = blob.add(b);
+    put(&P.merge_b, b);
   }
-  struct LOff {
-    size_t in_wp, in_b, out_wp, out_b, ff1_wp, ff1_b, ff2_wp, ff2_b, ln1_w, ln1_b, ln2_w, ln2_b;
-    size_t in_hp, out_hp, ff1_hp, ff2_hp;
-  } lo[4];
   float x_norm = 1.f;  // bound on the 2-norm of a token row entering the layer (layer 0: unit rows or zero pads)
   for (int l = 0; l < cfg->num_layers; ++l) {
     const std::string p = "obj_inter_module." + std::to_string(l) + ".";
-    auto lin = [&](const std::string& wn, const std::string& bn, int out, int in, size_t* wp, size_t* hp, size_t* bo) -> bool {
-      const float* W = need(ctx, m, p + wn, (int64_t)out * in, &rc);
-      const float* b = need(ctx, m, p + bn, out, &rc);
+    LayerW& L = P.layer[l];
+    auto lin = [&](const std::string& wn, const std::string& bn, int out, int in, const float4** wp, const uint4** hp, const float** bo) -> bool {
+      const float* W = T.need(p + wn, (int64_t)out * in);
+      const float* b = T.need(p + bn, out);
       if (!W || !b) return false;
       const std::vector<float> Wv(W, W + (size_t)out * in);
-      *wp = blob.add(pack_half_split(Wv, nullptr, out, in, in));
-      *hp = blob.add(pack_h(Wv, out, in));
-      *bo = blob.add(std::vector<float>(b, b + out));
+      put(wp, pack_half_split(Wv, nullptr, out, in, in));
+      put(hp, pack_h(Wv, out, in));
+      put(bo, std::vector<float>(b, b + out));
       w_absmax = fmaxf(w_absmax, max_abs(W, Wv.size()));
       return true;
     };
-    auto vec = [&](const std::string& name, size_t* o) -> bool {
-      const float* v = need(ctx, m, p + name, D, &rc);
+    auto vec = [&](const std::string& name, const float** o) -> bool {
+      const float* v = T.need(p + name, D);
       if (!v) return false;
-      *o = blob.add(std::vector<float>(v, v + D));
+      put(o, std::vector<float>(v, v + D));
       return true;
     };
-    if (!lin("self_attn.in_proj_weight", "self_attn.in_proj_bias", 3 * D, D, &lo[l].in_wp, &lo[l].in_hp, &lo[l].in_b)) return rc;
-    if (!lin("self_attn.out_proj.weight", "self_attn.out_proj.bias", D, D, &lo[l].out_wp, &lo[l].out_hp, &lo[l].out_b)) return rc;
-    if (!lin("linear1.weight", "linear1.bias", 2 * D, D, &lo[l].ff1_wp, &lo[l].ff1_hp, &lo[l].ff1_b)) return rc;
-    if (!lin("linear2.weight", "linear2.bias", D, 2 * D, &lo[l].ff2_wp, &lo[l].ff2_hp, &lo[l].ff2_b)) return rc;
-    if (!vec("norm1.weight", &lo[l].ln1_w) || !vec("norm1.bias", &lo[l].ln1_b) || !vec("norm2.weight", &lo[l].ln2_w) ||
-        !vec("norm2.bias", &lo[l].ln2_b))
-      return rc;
+    if (!lin("self_attn.in_proj_weight", "self_attn.in_proj_bias", 3 * D, D, &L.in_wp, &L.in_hp, &L.in_b) ||
+        !lin("self_attn.out_proj.weight", "self_attn.out_proj.bias", D, D, &L.out_wp, &L.out_hp, &L.out_b) ||
+        !lin("linear1.weight", "linear1.bias", 2 * D, D, &L.ff1_wp, &L.ff1_hp, &L.ff1_b) ||
+        !lin("linear2.weight", "linear2.bias", D, 2 * D, &L.ff2_wp, &L.ff2_hp, &L.ff2_b) || !vec("norm1.weight", &L.ln1_w) ||
+        !vec("norm1.bias", &L.ln1_b) || !vec("norm2.weight", &L.ln2_w) || !vec("norm2.bias", &L.ln2_b))
+      return refused();
     {  // bounds on what enters this layer's split GEMMs (|LayerNorm(.)| <= sqrt(255) |gain| + |bias| per element)
-      const float* Wi = m.at(p + "self_attn.in_proj_weight")->data;
-      const float* bi = m.at(p + "self_attn.in_proj_bias")->data;
-      const float* W1 = m.at(p + "linear1.weight")->data;
-      const float* b1 = m.at(p + "linear1.bias")->data;
+      const float* Wi = T.find(p + "self_attn.in_proj_weight")->data;
+      const float* bi = T.find(p + "self_attn.in_proj_bias")->data;
+      const float* W1 = T.find(p + "linear1.weight")->data;
+      const float* b1 = T.find(p + "linear1.bias")->data;
       auto ln_elem = [&](const char* wn, const char* bn) {
-        return 16.f * max_abs(m.at(p + wn)->data, D) + max_abs(m.at(p + bn)->data, D);
+        return 16.f * max_abs(T.find(p + wn)->data, D) + max_abs(T.find(p + bn)->data, D);
       };
       act_bound = fmaxf(act_bound, x_norm);                                                                   // q/k/v input
       act_bound = fmaxf(act_bound, x_norm * max_row_norm(Wi, 2 * D, D) + max_abs(bi, 2 * D));              // q, k: operands of the split S = K Q^T
@@ -967,42 +918,6 @@ int load_weights_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const t2l_m
       x_norm = 16.f * ln_elem("norm2.weight", "norm2.bias");                                                 // next layer's rows
     }
   }
-
-  free_weights(ctx);
-  EncoderWeights* ew = new EncoderWeights();
-  if (hipMalloc(&ew->blob, blob.h.size() * sizeof(float)) != hipSuccess) {
-    delete ew;
-    return fail(ctx, T2L_ENOMEM, "t2l_load_weights: hipMalloc failed");
-  }
-  if (hipMemcpy(ew->blob, blob.h.data(), blob.h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(ew->blob);
-    delete ew;
-    return fail(ctx, T2L_EHIP, "t2l_load_weights: upload failed");
-  }
-  const float* B = ew->blob;
-  auto f4 = [&](size_t off) { return reinterpret_cast<const float4*>(B + off); };
-  EncParams& P = ew->p;
-  memset(&P, 0, sizeof(P));
-  P.class_tab = B + class_tab;
-  P.color_tab = B + color_tab;
-  P.n_class = n_class;
-  P.n_color = n_color;
-  auto sm = [&](const SmallOff& o) { return SmallMlp{B + o.w1, B + o.b1, f4(o.w2p), B + o.b2}; };
-  P.pos = sm(pos);
-  P.color = sm(color);
-  P.num = sm(num);
-  auto u4 = [&](size_t off) { return reinterpret_cast<const uint4*>(B + off); };
-  P.pn_wp = f4(pn_wp);
-  P.pn_hp = nullptr;
-  P.pn_b = B + pn_b;
-  P.merge_wp = f4(merge_wp);
-  P.merge_hp = u4(merge_hp);
-  P.merge_b = B + merge_b;
-  for (int l = 0; l < cfg->num_layers; ++l)
-    P.layer[l] = LayerW{f4(lo[l].in_wp),  f4(lo[l].out_wp), f4(lo[l].ff1_wp), f4(lo[l].ff2_wp),
-                        u4(lo[l].in_hp),  u4(lo[l].out_hp), u4(lo[l].ff1_hp), u4(lo[l].ff2_hp),
-                        B + lo[l].in_b,   B + lo[l].out_b,  B + lo[l].ff1_b,  B + lo[l].ff2_b,
-                        B + lo[l].ln1_w,  B + lo[l].ln1_b,  B + lo[l].ln2_w,  B + lo[l].ln2_b};
   P.split_ok = (w_absmax < kSplitF16Safe && act_bound < kSplitF16Safe) ? 1 : 0;
   P.num_layers = cfg->num_layers;
   P.class_embed = cfg->class_embed;
@@ -1015,7 +930,10 @@ int load_weights_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const t2l_m
   ew->embed_dim = D;
   ew->object_size = object_size;
   ew->num_heads = cfg->num_heads;
-  ctx->enc = ew;
+  // everything is validated and staged: one allocation, one copy, then the old set goes and the new one is published
+  if (const int rc = upload_staging(ctx, "t2l_load_weights", blob, &ew->blob)) return rc;
+  free_weights(ctx);
+  ctx->enc = ew.release();
   return T2L_OK;
 }
 

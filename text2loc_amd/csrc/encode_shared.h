@@ -42,7 +42,7 @@ struct EncParams {
 
 struct EncoderWeights {
   EncParams p;
-  float* blob = nullptr;
+  char* blob = nullptr;  // every array p points at, one allocation (weight_table.h: Staging)
   // the shape the weights were loaded for (t2l_load_weights_shaped); the published one has the two-cell kernel of encode.hip in
   // front of the shape-templated kernel of encode_shaped.hip
   int embed_dim = kD, object_size = kS, num_heads = 4;

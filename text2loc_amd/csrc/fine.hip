@@ -14,6 +14,8 @@
 #include <math.h>
 #include <string.h>
 
+#include <memory>
+
 #include "t2l_internal.h"
 #include "tile_blocks.h"
 
@@ -52,7 +54,7 @@ struct FineParams {
 constexpr float kFGuardNorm = 64.f;  // run-time guard on the raw descriptor rows a workgroup loads (unit rows in the reference's pipeline)
 struct FineWeights {
   FineParams p{};
-  std::vector<void*> blobs;
+  char* blob = nullptr;         // every array p points at, one allocation (weight_table.h: Staging)
   int32_t* wg_flags = nullptr;  // per-workgroup guard verdicts of the split-f16 match launch
   size_t flag_cap = 0;
 };
@@ -60,36 +62,24 @@ struct FineWeights {
 void free_fine(t2l_ctx* ctx) {
   FineWeights* W = reinterpret_cast<FineWeights*>(ctx->fine);
   if (!W) return;
-  for (void* b : W->blobs) (void)hipFree(b);
+  if (W->blob) (void)hipFree(W->blob);
   if (W->wg_flags) (void)hipFree(W->wg_flags);
   delete W;
   ctx->fine = nullptr;
 }
 
-using WMap = std::unordered_map<std::string, const t2l_weight_desc*>;
-
-static const float* fget(const WMap& m, const std::string& k, int64_t n) {
-  auto it = m.find(k);
-  return (it == m.end() || it->second->numel != n) ? nullptr : it->second->data;
-}
-static int fupload(t2l_ctx* ctx, FineWeights* W, const std::vector<float>& v, const float** dst) {
-  float* d = nullptr;
-  T2L_HIP(ctx, hipMalloc(&d, v.size() * sizeof(float)));
-  W->blobs.push_back(d);
-  T2L_HIP(ctx, hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
-  *dst = d;
-  return T2L_OK;
-}
+// The loader's steps: each looks its tensors up in T, stages what the kernels read and aims the parameter struct's fields at it
+// (Staging::place); false, with the error in T, when a tensor is missing or mis-sized.
 // Linear [N,K] (+ optional eval BatchNorm `bn` folded in) -> transposed [K][N] + bias. Not fold_batchnorm (mfma32.h): the bias here is
 // b*s + (be - rm*s), there (b - rm)*s + be — the two differ in the last bit, and the loaded weights are part of what the goldens pin.
-static int flinear(t2l_ctx* ctx, FineWeights* W, const WMap& m, const std::string& lin, const std::string& bn, int K, int N, FLinear* out) {
-  const float *w = fget(m, lin + ".weight", (int64_t)N * K), *b = fget(m, lin + ".bias", N);
-  if (!w || !b) return fail(ctx, T2L_EINVAL, "t2l_fine_load_weights: missing or mis-shaped '" + lin + "'");
+static bool flinear(WeightTable& T, Staging& st, const std::string& lin, const std::string& bn, int K, int N, FLinear* out) {
+  const float *w = T.need(lin + ".weight", (int64_t)N * K), *b = T.need(lin + ".bias", N);
+  if (!w || !b) return false;
   std::vector<float> wt((size_t)K * N), bb(N);
   std::vector<float> s(N, 1.f), sh(N, 0.f);
   if (!bn.empty()) {
-    const float *g = fget(m, bn + ".weight", N), *be = fget(m, bn + ".bias", N), *rm = fget(m, bn + ".running_mean", N), *rv = fget(m, bn + ".running_var", N);
-    if (!g || !be || !rm || !rv) return fail(ctx, T2L_EINVAL, "t2l_fine_load_weights: missing or mis-shaped '" + bn + "'");
+    const float *g = T.need(bn + ".weight", N), *be = T.need(bn + ".bias", N), *rm = T.need(bn + ".running_mean", N), *rv = T.need(bn + ".running_var", N);
+    if (!g || !be || !rm || !rv) return false;
     for (int n = 0; n < N; ++n) {
       s[n] = g[n] / sqrtf(rv[n] + 1e-5f);
       sh[n] = be[n] - rm[n] * s[n];
@@ -99,98 +89,88 @@ static int flinear(t2l_ctx* ctx, FineWeights* W, const WMap& m, const std::strin
     for (int k = 0; k < K; ++k) wt[(size_t)k * N + n] = w[(size_t)n * K + k] * s[n];
     bb[n] = b[n] * s[n] + sh[n];
   }
-  int rc;
-  if ((rc = fupload(ctx, W, wt, &out->wt))) return rc;
-  return fupload(ctx, W, bb, &out->b);
+  st.place(&out->wt, wt);
+  st.place(&out->b, bb);
+  return true;
 }
-// Linear [N,K] as stored by torch -> half-split MFMA packing + bias (decoder layers: no BatchNorm)
-static int fpacked(t2l_ctx* ctx, FineWeights* W, const WMap& m, const std::string& wname, const std::string& bname, int K, int N, FPacked* out) {
-  const float *w = fget(m, wname, (int64_t)N * K), *b = fget(m, bname, N);
-  if (!w || !b) return fail(ctx, T2L_EINVAL, "t2l_fine_load_weights: missing or mis-shaped '" + wname + "'");
-  const std::vector<float> packed = pack_half_split(std::vector<float>(w, w + (size_t)N * K), nullptr, N, K, K);
-  const float* d = nullptr;
-  int rc;
-  if ((rc = fupload(ctx, W, packed, &d))) return rc;
-  out->w = reinterpret_cast<const float4*>(d);
-  const float* dh = nullptr;
-  if ((rc = fupload(ctx, W, pack_split_f16(w, nullptr, N, K, K), &dh))) return rc;
-  out->h = reinterpret_cast<const uint4*>(dh);
-  return fupload(ctx, W, std::vector<float>(b, b + N), &out->b);
+// Linear [N,K] as stored by torch -> half-split MFMA packing + split-f16 fragments + bias (decoder layers: no BatchNorm)
+static bool fpacked(WeightTable& T, Staging& st, const std::string& wname, const std::string& bname, int K, int N, FPacked* out) {
+  const float *w = T.need(wname, (int64_t)N * K), *b = T.need(bname, N);
+  if (!w || !b) return false;
+  st.place(&out->w, pack_half_split(std::vector<float>(w, w + (size_t)N * K), nullptr, N, K, K));
+  st.place(&out->h, pack_split_f16(w, nullptr, N, K, K));
+  st.place(&out->b, b, (size_t)N);
+  return true;
 }
-static int fraw(t2l_ctx* ctx, FineWeights* W, const WMap& m, const std::string& k, int64_t n, const float** dst) {
-  const float* p = fget(m, k, n);
-  if (!p) return fail(ctx, T2L_EINVAL, "t2l_fine_load_weights: missing or mis-shaped '" + k + "'");
-  return fupload(ctx, W, std::vector<float>(p, p + n), dst);
+static bool fraw(WeightTable& T, Staging& st, const std::string& k, int64_t n, const float** dst) {
+  const float* p = T.need(k, n);
+  if (p) st.place(dst, p, (size_t)n);
+  return p != nullptr;
 }
 
 int fine_load_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const t2l_model_config* cfg) {
-  if (!w || n <= 0 || !cfg) return fail(ctx, T2L_EINVAL, "t2l_fine_load_weights: null argument");
+  const char* who = "t2l_fine_load_weights";
   if (cfg->num_heads != kFHeads || cfg->num_layers < 0 || cfg->num_layers > 4)
     return fail(ctx, T2L_EINVAL, "t2l_fine_load_weights: built for 4 decoder heads and 0..4 decoder layers (0 = the single cross_hints layer)");
-  free_fine(ctx);
-  FineWeights* W = new FineWeights();
-  ctx->fine = W;
+  std::unique_ptr<FineWeights> W(new FineWeights());
   FineParams& P = W->p;
-  WMap m;
-  for (int i = 0; i < n; ++i)
-    if (w[i].name) m[w[i].name] = &w[i];
   P.class_embed = cfg->class_embed; P.color_embed = cfg->color_embed;
   P.use_class = cfg->use_class; P.use_color = cfg->use_color; P.use_pos = cfg->use_position; P.use_num = cfg->use_num;
   P.n_feat = (P.use_class != 0) + (P.use_color != 0) + (P.use_pos != 0) + (P.use_num != 0);
   P.n_layers = cfg->num_layers;
   if (P.n_feat < 2) return fail(ctx, T2L_EINVAL, "t2l_fine_load_weights: needs at least two of the class/color/position/num features");
+  WeightTable T(who, w, n);
+  Staging st;
   const std::string oe = "object_encoder.";
-  int rc;
-  auto emb = [&](const std::string& k, const float** dst) -> int {
-    auto it = m.find(k);
-    if (it == m.end() || it->second->numel % kFD) return fail(ctx, T2L_EINVAL, "t2l_fine_load_weights: missing '" + k + "'");
-    return fupload(ctx, W, std::vector<float>(it->second->data, it->second->data + it->second->numel), dst);
+  auto emb = [&](const std::string& k, const float** dst) -> bool {  // an embedding table [rows][128]
+    int64_t rows = 0;
+    const float* t = T.need_rows(k, kFD, &rows);
+    if (t) st.place(dst, t, (size_t)rows * kFD);
+    return t != nullptr;
   };
-  if (P.use_class) {
-    if (P.class_embed) { if ((rc = emb(oe + "class_embedding.weight", &P.class_emb))) return rc; }
-    else if ((rc = flinear(ctx, W, m, oe + "mlp_pointnet.0.0", oe + "mlp_pointnet.0.1", 256, kFD, &P.pn))) return rc;
-  }
-  if (P.use_color) {
-    if (P.color_embed) { if ((rc = emb(oe + "color_embedding.weight", &P.color_emb))) return rc; }
-    else if ((rc = flinear(ctx, W, m, oe + "color_encoder.0.0", oe + "color_encoder.0.1", 3, 64, &P.col1)) ||
-             (rc = flinear(ctx, W, m, oe + "color_encoder.1.0", oe + "color_encoder.1.1", 64, kFD, &P.col2))) return rc;
-  }
-  if (P.use_pos && ((rc = flinear(ctx, W, m, oe + "pos_encoder.0.0", oe + "pos_encoder.0.1", 3, 64, &P.pos1)) ||
-                    (rc = flinear(ctx, W, m, oe + "pos_encoder.1.0", oe + "pos_encoder.1.1", 64, kFD, &P.pos2)))) return rc;
-  if (P.use_num && ((rc = flinear(ctx, W, m, oe + "num_encoder.0.0", oe + "num_encoder.0.1", 1, 64, &P.num1)) ||
-                    (rc = flinear(ctx, W, m, oe + "num_encoder.1.0", oe + "num_encoder.1.1", 64, kFD, &P.num2)))) return rc;
-  if ((rc = flinear(ctx, W, m, oe + "mlp_merge.0.0", oe + "mlp_merge.0.1", P.n_feat * kFD, kFD, &P.merge))) return rc;
-  // fine_num_decoder_layers == 0 (cross_matcher.py:75-79, 119-120): ONE decoder layer, keys "cross_hints.*" without an index, no
-  // cross_objects — the hints attend the raw object descriptors once. Loaded as hint[0]; the kernel branches on n_layers == 0.
-  for (int l = 0; l < std::max(1, P.n_layers); ++l)
-    for (int which = (P.n_layers == 0 ? 1 : 0); which < 2; ++which) {
-      const std::string p = P.n_layers == 0 ? std::string("cross_hints") : std::string(which ? "cross_hints." : "cross_objects.") + std::to_string(l);
-      FDecoder& D = which ? P.hint[l] : P.obj[l];
-      if ((rc = fpacked(ctx, W, m, p + ".self_attn.in_proj_weight", p + ".self_attn.in_proj_bias", kFD, 3 * kFD, &D.sa_in)) ||
-          (rc = fpacked(ctx, W, m, p + ".self_attn.out_proj.weight", p + ".self_attn.out_proj.bias", kFD, kFD, &D.sa_out)) ||
-          (rc = fpacked(ctx, W, m, p + ".multihead_attn.in_proj_weight", p + ".multihead_attn.in_proj_bias", kFD, 3 * kFD, &D.ca_in)) ||
-          (rc = fpacked(ctx, W, m, p + ".multihead_attn.out_proj.weight", p + ".multihead_attn.out_proj.bias", kFD, kFD, &D.ca_out)) ||
-          (rc = fpacked(ctx, W, m, p + ".linear1.weight", p + ".linear1.bias", kFD, 4 * kFD, &D.l1)) ||
-          (rc = fpacked(ctx, W, m, p + ".linear2.weight", p + ".linear2.bias", 4 * kFD, kFD, &D.l2)) ||
-          (rc = fraw(ctx, W, m, p + ".norm1.weight", kFD, &D.g1)) || (rc = fraw(ctx, W, m, p + ".norm1.bias", kFD, &D.b1)) ||
-          (rc = fraw(ctx, W, m, p + ".norm2.weight", kFD, &D.g2)) || (rc = fraw(ctx, W, m, p + ".norm2.bias", kFD, &D.b2)) ||
-          (rc = fraw(ctx, W, m, p + ".norm3.weight", kFD, &D.g3)) || (rc = fraw(ctx, W, m, p + ".norm3.bias", kFD, &D.b3)))
-        return rc;
-    }
-  if ((rc = flinear(ctx, W, m, "mlp_offsets.0", "", kFD, kFD / 2, &P.off0)) || (rc = flinear(ctx, W, m, "mlp_offsets.2", "", kFD / 2, 2, &P.off2)))
-    return rc;
+  auto lin = [&](const char* l, const char* bn, int K, int N, FLinear* out) { return flinear(T, st, oe + l, oe + bn, K, N, out); };
+  auto stage = [&]() -> bool {  // false at the first tensor T refuses
+    if (P.use_class && !(P.class_embed ? emb(oe + "class_embedding.weight", &P.class_emb) : lin("mlp_pointnet.0.0", "mlp_pointnet.0.1", 256, kFD, &P.pn)))
+      return false;
+    if (P.use_color && !(P.color_embed ? emb(oe + "color_embedding.weight", &P.color_emb)
+                                       : lin("color_encoder.0.0", "color_encoder.0.1", 3, 64, &P.col1) &&
+                                             lin("color_encoder.1.0", "color_encoder.1.1", 64, kFD, &P.col2)))
+      return false;
+    if (P.use_pos && !(lin("pos_encoder.0.0", "pos_encoder.0.1", 3, 64, &P.pos1) && lin("pos_encoder.1.0", "pos_encoder.1.1", 64, kFD, &P.pos2))) return false;
+    if (P.use_num && !(lin("num_encoder.0.0", "num_encoder.0.1", 1, 64, &P.num1) && lin("num_encoder.1.0", "num_encoder.1.1", 64, kFD, &P.num2))) return false;
+    if (!lin("mlp_merge.0.0", "mlp_merge.0.1", P.n_feat * kFD, kFD, &P.merge)) return false;
+    // fine_num_decoder_layers == 0 (cross_matcher.py:75-79, 119-120): ONE decoder layer, keys "cross_hints.*" without an index, no
+    // cross_objects — the hints attend the raw object descriptors once. Loaded as hint[0]; the kernel branches on n_layers == 0.
+    for (int l = 0; l < std::max(1, P.n_layers); ++l)
+      for (int which = (P.n_layers == 0 ? 1 : 0); which < 2; ++which) {
+        const std::string p = P.n_layers == 0 ? std::string("cross_hints") : std::string(which ? "cross_hints." : "cross_objects.") + std::to_string(l);
+        FDecoder& D = which ? P.hint[l] : P.obj[l];
+        if (!(fpacked(T, st, p + ".self_attn.in_proj_weight", p + ".self_attn.in_proj_bias", kFD, 3 * kFD, &D.sa_in) &&
+              fpacked(T, st, p + ".self_attn.out_proj.weight", p + ".self_attn.out_proj.bias", kFD, kFD, &D.sa_out) &&
+              fpacked(T, st, p + ".multihead_attn.in_proj_weight", p + ".multihead_attn.in_proj_bias", kFD, 3 * kFD, &D.ca_in) &&
+              fpacked(T, st, p + ".multihead_attn.out_proj.weight", p + ".multihead_attn.out_proj.bias", kFD, kFD, &D.ca_out) &&
+              fpacked(T, st, p + ".linear1.weight", p + ".linear1.bias", kFD, 4 * kFD, &D.l1) &&
+              fpacked(T, st, p + ".linear2.weight", p + ".linear2.bias", 4 * kFD, kFD, &D.l2) &&
+              fraw(T, st, p + ".norm1.weight", kFD, &D.g1) && fraw(T, st, p + ".norm1.bias", kFD, &D.b1) &&
+              fraw(T, st, p + ".norm2.weight", kFD, &D.g2) && fraw(T, st, p + ".norm2.bias", kFD, &D.b2) &&
+              fraw(T, st, p + ".norm3.weight", kFD, &D.g3) && fraw(T, st, p + ".norm3.bias", kFD, &D.b3)))
+          return false;
+      }
+    return flinear(T, st, "mlp_offsets.0", "", kFD, kFD / 2, &P.off0) && flinear(T, st, "mlp_offsets.2", "", kFD / 2, 2, &P.off2);
+  };
+  if (!T.ok() || !stage()) return fail(ctx, T2L_EINVAL, T.error());
   {  // split-f16 safety: bound every activation that enters a split product, given input rows of norm <= kFGuardNorm
     const float sq = 11.32f;  // > sqrt(128): |LayerNorm(.)| <= sqrt(127) |gain| + |bias| per element, row norm <= sqrt(128) x that
     float wmax = 0.f, amax = kFGuardNorm, n_obj = kFGuardNorm, n_hint = kFGuardNorm;
     auto dec = [&](const std::string& p, float xn, float mn) -> float {  // returns the norm bound of the rows it leaves in x
-      auto W_ = [&](const char* k, int64_t n) { return fget(m, p + k, n); };
+      auto W_ = [&](const char* k, int64_t) { return T.find(p + k)->data; };  // (every one was sized above)
       const float *sa = W_(".self_attn.in_proj_weight", 3 * kFD * kFD), *sab = W_(".self_attn.in_proj_bias", 3 * kFD);
       const float *ca = W_(".multihead_attn.in_proj_weight", 3 * kFD * kFD), *cab = W_(".multihead_attn.in_proj_bias", 3 * kFD);
       const float *l1 = W_(".linear1.weight", 4 * kFD * kFD), *l1b = W_(".linear1.bias", 4 * kFD);
       for (const char* k : {".self_attn.in_proj_weight", ".self_attn.out_proj.weight", ".multihead_attn.in_proj_weight",
                             ".multihead_attn.out_proj.weight", ".linear1.weight", ".linear2.weight"}) {
-        auto it = m.find(p + k);
-        wmax = fmaxf(wmax, h3_max_abs(it->second->data, (size_t)it->second->numel));
+        const t2l_weight_desc* d = T.find(p + k);
+        wmax = fmaxf(wmax, h3_max_abs(d->data, (size_t)d->numel));
       }
       auto ln = [&](const char* g, const char* b) { return sq * h3_max_abs(W_(g, kFD), kFD) + h3_max_abs(W_(b, kFD), kFD); };
       amax = fmaxf(amax, fmaxf(xn, mn));                                                                          // q/k/v inputs
@@ -213,6 +193,10 @@ int fine_load_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const t2l_mode
     if (P.n_layers == 0) n_hint = dec("cross_hints", n_hint, n_obj);
     P.split_ok = (wmax < kSplitF16Safe && amax < kSplitF16Safe) ? 1 : 0;
   }
+  // everything is validated and staged: one allocation, one copy, then the old set goes and the new one is published
+  if (const int rc = upload_staging(ctx, who, st, &W->blob)) return rc;
+  free_fine(ctx);
+  ctx->fine = W.release();
   return T2L_OK;
 }
 

@@ -6,7 +6,10 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <string>
 #include <vector>
+
+#include "weight_table.h"
 
 namespace t2l {
 
@@ -37,6 +40,22 @@ static inline void fold_batchnorm(float* W, float* b, int out, int in, const flo
     for (int k = 0; k < in; ++k) W[(size_t)o * in + k] *= s;
     b[o] = (b[o] - rm[o]) * s + be[o];
   }
+}
+
+// `lin` = Linear [out][in] from a loader's table, with the eval-mode BatchNorm1d `bn` behind it (none: "") folded in: W' [out][in],
+// b' [out]. false, with the error in T, when a tensor is missing or mis-sized.
+static inline bool fold_linear(WeightTable& T, const std::string& lin, const std::string& bn, int out, int in, std::vector<float>* W,
+                               std::vector<float>* b) {
+  const float *w = T.need(lin + ".weight", (int64_t)out * in), *bb = T.need(lin + ".bias", out);
+  if (!w || !bb) return false;
+  W->assign(w, w + (size_t)out * in);
+  b->assign(bb, bb + out);
+  if (bn.empty()) return true;
+  const float *g = T.need(bn + ".weight", out), *be = T.need(bn + ".bias", out), *rm = T.need(bn + ".running_mean", out),
+              *rv = T.need(bn + ".running_var", out);
+  if (!g || !be || !rm || !rv) return false;
+  fold_batchnorm(W->data(), b->data(), out, in, g, be, rm, rv);
+  return true;
 }
 
 // acc += A[32 x 8*S4] (this lane's row half, LDS, float4 per 4 k-steps) * B (packed weights, global: wp[s4*64], lane folded in),

@@ -39,6 +39,7 @@ struct PointNetWeights {
   float4 *ga1 = nullptr, *ga2 = nullptr;
   float* gab2 = nullptr;
   float *lin1w = nullptr, *lin1b = nullptr, *lin2w = nullptr, *lin2b = nullptr;
+  char* blob = nullptr;  // every array above, one allocation (weight_table.h: Staging)
   // workspace
   char* ws = nullptr;
   size_t ws_cap = 0;
@@ -73,11 +74,8 @@ struct PointNetLevels {
 void free_pointnet(t2l_ctx* ctx) {
   PointNetWeights* P = reinterpret_cast<PointNetWeights*>(ctx->pn);
   if (!P) return;
-  for (int l = 0; l < 3; ++l)
-    for (void* p : {(void*)P->w1[l], (void*)P->w2[l], (void*)P->b2[l], (void*)P->w1h[l], (void*)P->w2h[l], (void*)P->wsh[l]})
-      if (p) (void)hipFree(p);
-  for (void* p : {(void*)P->gash, (void*)P->ga1, (void*)P->ga2, (void*)P->gab2, (void*)P->lin1w, (void*)P->lin1b, (void*)P->lin2w, (void*)P->lin2b, (void*)P->ws})
-    if (p) (void)hipFree(p);
+  if (P->blob) (void)hipFree(P->blob);
+  if (P->ws) (void)hipFree(P->ws);
   delete P;
   ctx->pn = nullptr;
 }
@@ -85,23 +83,6 @@ void free_pointnet(t2l_ctx* ctx) {
 // ---------------------------------------------------------------------------------------------------------------
 // host: fold BatchNorm, pack
 // ---------------------------------------------------------------------------------------------------------------
-using WMap = std::unordered_map<std::string, const t2l_weight_desc*>;
-
-// get_mlp block i of `prefix`: returns W' [cout][cin] and b' [cout] with eval-mode BatchNorm folded in
-static bool fold_block(const WMap& m, const std::string& prefix, int i, int cin, int cout, std::vector<float>& W, std::vector<float>& b) {
-  auto get = [&](const std::string& k, int64_t n) -> const float* {
-    auto it = m.find(prefix + "." + std::to_string(i) + k);
-    return (it == m.end() || it->second->numel != n) ? nullptr : it->second->data;
-  };
-  const float *w = get(".0.weight", (int64_t)cin * cout), *bb = get(".0.bias", cout), *g = get(".1.weight", cout), *be = get(".1.bias", cout),
-              *rm = get(".1.running_mean", cout), *rv = get(".1.running_var", cout);
-  if (!w || !bb || !g || !be || !rm || !rv) return false;
-  W.assign(w, w + (size_t)cin * cout);
-  b.assign(bb, bb + cout);
-  fold_batchnorm(W.data(), b.data(), cout, cin, g, be, rm, rv);
-  return true;
-}
-
 // layer 2 of an SA block, B operand: [h2/32][h1/32][4][64] float4: lane (n, kh): W[nt*32+n][ft*32 + 8*rq + 4*kh + 0..3]
 static std::vector<float> pack_sa_l2(const std::vector<float>& W, int h2, int h1) {
   std::vector<float> out((size_t)h2 * h1);
@@ -137,13 +118,6 @@ static std::vector<float> pack_sa_l2_h(const std::vector<float>& W, int h2, int 
   return p;
 }
 
-template <typename T>
-static int upload(t2l_ctx* ctx, T** dst, const std::vector<float>& v) {
-  T2L_HIP(ctx, hipMalloc(dst, v.size() * sizeof(float)));
-  T2L_HIP(ctx, hipMemcpy(*dst, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
-  return T2L_OK;
-}
-
 constexpr int kCin[3] = {3, 64, 128}, kH1[3] = {32, 128, 256}, kH2[3] = {64, 128, 256};
 constexpr int kWsChunk = 8;  // WStream: packed-weight steps (64 lanes x [hi 16 B | lo 16 B] = 2 KiB) per chunk of the LDS ring
 
@@ -165,46 +139,74 @@ static std::vector<float> pack_sa_stream(const std::vector<float>& l1h, const st
 constexpr int k1p(int cin) { return ((cin + 4 + 7) / 8) * 8; }  // [x | pos_j - pos_i | 1 | 0...] padded to 8
 constexpr int k1ph(int cin) { return ((cin + 4 + 15) / 16) * 16; }  // the same row padded to 16 (split-f16 steps of 16)
 
-// Returns T2L_OK with ctx->pn == nullptr when the state_dict carries no PointNet++ tensors at all.
-int pointnet_load_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n) {
-  free_pointnet(ctx);
+struct PointNetStaged {
+  Staging st;
+  PointNetWeights w;  // its pointer fields are placed in st
+};
+
+void pointnet_discard(PointNetStaged* staged) { delete staged; }
+
+int pointnet_stage(t2l_ctx* ctx, const char* who, const t2l_weight_desc* w, int n, PointNetStaged** out) {
+  *out = nullptr;
   const std::string p = "object_encoder.pointnet.";
-  WMap m;
-  for (int i = 0; i < n; ++i)
-    if (w[i].name && !strncmp(w[i].name, p.c_str(), p.size())) m[w[i].name] = &w[i];
-  if (m.empty()) return T2L_OK;
-  PointNetWeights* P = new PointNetWeights();
-  ctx->pn = P;
-  int rc;
-  std::vector<float> W, b;
-  for (int l = 0; l < 3; ++l) {
-    const std::string pre = p + "sa" + std::to_string(l + 1) + ".point_conv.local_nn";
-    if (!fold_block(m, pre, 0, kCin[l] + 3, kH1[l], W, b)) return fail(ctx, T2L_EINVAL, "t2l_load_weights: incomplete " + pre + ".0");
-    if ((rc = upload(ctx, &P->w1[l], pack_half_split(W, &b, kH1[l], kCin[l] + 3, k1p(kCin[l]))))) return rc;
-    const std::vector<float> l1h = pack_split_f16(W.data(), b.data(), kH1[l], kCin[l] + 3, k1ph(kCin[l]));
-    if (kCin[l] < 64 && (rc = upload(ctx, &P->w1h[l], l1h))) return rc;
-    if (!fold_block(m, pre, 1, kH1[l], kH2[l], W, b)) return fail(ctx, T2L_EINVAL, "t2l_load_weights: incomplete " + pre + ".1");
-    if ((rc = upload(ctx, &P->w2[l], pack_sa_l2(W, kH2[l], kH1[l])))) return rc;
-    const std::vector<float> l2h = pack_sa_l2_h(W, kH2[l], kH1[l]);
-    if (kCin[l] < 64 && (rc = upload(ctx, &P->w2h[l], l2h))) return rc;
-    if (kCin[l] >= 64 && (rc = upload(ctx, &P->wsh[l], pack_sa_stream(l1h, l2h, kH1[l] / 32, k1ph(kCin[l]) / 16)))) return rc;
-    if ((rc = upload(ctx, &P->b2[l], b))) return rc;
-  }
-  if (!fold_block(m, p + "ga.mlp", 0, 259, 512, W, b)) return fail(ctx, T2L_EINVAL, "t2l_load_weights: incomplete " + p + "ga.mlp.0");
-  if ((rc = upload(ctx, &P->ga1, pack_half_split(W, &b, 512, 259, 264)))) return rc;
-  const std::vector<float> ga1h = pack_split_f16(W.data(), b.data(), 512, 259, 272);
-  if (!fold_block(m, p + "ga.mlp", 1, 512, 1024, W, b)) return fail(ctx, T2L_EINVAL, "t2l_load_weights: incomplete " + p + "ga.mlp.1");
-  if ((rc = upload(ctx, &P->gash, pack_sa_stream(ga1h, pack_sa_l2_h(W, 1024, 512), 512 / 32, 272 / 16)))) return rc;
-  if ((rc = upload(ctx, &P->ga2, pack_half_split(W, nullptr, 1024, 512, 512)))) return rc;
-  if ((rc = upload(ctx, &P->gab2, b))) return rc;
-  auto raw = [&](const char* name, int64_t numel, float** dst) -> int {
-    auto it = m.find(p + name);
-    if (it == m.end() || it->second->numel != numel) return fail(ctx, T2L_EINVAL, std::string("t2l_load_weights: missing ") + p + name);
-    return upload(ctx, dst, std::vector<float>(it->second->data, it->second->data + numel));
+  WeightTable T(who, w, n, p.c_str());
+  if (T.ok() && T.empty()) return T2L_OK;  // a state dict without the backbone
+  PointNetStaged* S = new PointNetStaged();
+  Staging& st = S->st;
+  PointNetWeights* P = &S->w;
+  auto raw = [&](const char* name, int64_t numel, float** dst) {
+    const float* v = T.need(p + name, numel);
+    if (v) st.place(dst, v, (size_t)numel);
+    return v != nullptr;
   };
-  if ((rc = raw("lin1.weight", 512 * 1024, &P->lin1w)) || (rc = raw("lin1.bias", 512, &P->lin1b)) ||
-      (rc = raw("lin2.weight", 256 * 512, &P->lin2w)) || (rc = raw("lin2.bias", 256, &P->lin2b)))
-    return rc;
+  std::vector<float> W, b;
+  // get_mlp block i of `prefix` ({i}.0 Linear, {i}.1 BatchNorm1d, folded) into W [cout][cin], b [cout]
+  auto fold_block = [&](const std::string& prefix, int i, int cin, int cout) {
+    const std::string k = prefix + "." + std::to_string(i);
+    return fold_linear(T, k + ".0", k + ".1", cout, cin, &W, &b);
+  };
+  auto stage = [&]() -> bool {  // false at the first tensor T refuses
+    for (int l = 0; l < 3; ++l) {
+      const std::string pre = p + "sa" + std::to_string(l + 1) + ".point_conv.local_nn";
+      if (!fold_block(pre, 0, kCin[l] + 3, kH1[l])) return false;
+      st.place(&P->w1[l], pack_half_split(W, &b, kH1[l], kCin[l] + 3, k1p(kCin[l])));
+      const std::vector<float> l1h = pack_split_f16(W.data(), b.data(), kH1[l], kCin[l] + 3, k1ph(kCin[l]));
+      if (kCin[l] < 64) st.place(&P->w1h[l], l1h);
+      if (!fold_block(pre, 1, kH1[l], kH2[l])) return false;
+      st.place(&P->w2[l], pack_sa_l2(W, kH2[l], kH1[l]));
+      const std::vector<float> l2h = pack_sa_l2_h(W, kH2[l], kH1[l]);
+      if (kCin[l] < 64) st.place(&P->w2h[l], l2h);
+      else st.place(&P->wsh[l], pack_sa_stream(l1h, l2h, kH1[l] / 32, k1ph(kCin[l]) / 16));
+      st.place(&P->b2[l], b);
+    }
+    if (!fold_block(p + "ga.mlp", 0, 259, 512)) return false;
+    st.place(&P->ga1, pack_half_split(W, &b, 512, 259, 264));
+    const std::vector<float> ga1h = pack_split_f16(W.data(), b.data(), 512, 259, 272);
+    if (!fold_block(p + "ga.mlp", 1, 512, 1024)) return false;
+    st.place(&P->gash, pack_sa_stream(ga1h, pack_sa_l2_h(W, 1024, 512), 512 / 32, 272 / 16));
+    st.place(&P->ga2, pack_half_split(W, nullptr, 1024, 512, 512));
+    st.place(&P->gab2, b);
+    return raw("lin1.weight", 512 * 1024, &P->lin1w) && raw("lin1.bias", 512, &P->lin1b) && raw("lin2.weight", 256 * 512, &P->lin2w) &&
+           raw("lin2.bias", 256, &P->lin2b);
+  };
+  if (!T.ok() || !stage()) {
+    delete S;
+    return fail(ctx, T2L_EINVAL, T.error());
+  }
+  *out = S;
+  return T2L_OK;
+}
+
+int pointnet_commit(t2l_ctx* ctx, const char* who, PointNetStaged* staged) {
+  PointNetWeights* P = nullptr;
+  if (staged) {
+    const int rc = upload_staging(ctx, who, staged->st, &staged->w.blob);
+    if (rc == T2L_OK) P = new PointNetWeights(staged->w);
+    delete staged;
+    if (rc) return rc;
+  }
+  free_pointnet(ctx);
+  ctx->pn = P;
   return T2L_OK;
 }
 

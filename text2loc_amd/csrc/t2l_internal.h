@@ -13,6 +13,7 @@
 #include "t2l.h"
 #include "search_plan.h"
 #include "text_inter_plan.h"
+#include "weight_table.h"
 
 namespace t2l {
 
@@ -195,6 +196,9 @@ int search_small_impl(t2l_ctx* ctx, const float* q, int Q, int K, int32_t* out_i
 // search_exact.hip
 int exact_stage_impl(t2l_ctx* ctx, const float* db, int n_rows, int row_offset, const float* q, int Q, int K, int32_t* out_idx,
                      double* out_score, hipStream_t s);
+// capi.hip: the last step of every eval-mode weight load (weight_table.h), after the whole list is validated and staged on the host —
+// ONE allocation and ONE copy; *blob is the device copy and st's placed pointer fields point into it. On failure nothing is allocated.
+int upload_staging(t2l_ctx* ctx, const char* who, const Staging& st, char** blob);
 // encode.hip
 int load_weights_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const t2l_model_config* cfg, int embed_dim, int object_size);
 int encoder_embed_dim(const t2l_ctx* ctx);  // of the loaded object branch (T2L_EMBED_DIM before any load)
@@ -243,8 +247,13 @@ void train_sync_changed(t2l_ctx* ctx);  // the accumulator slots moved: the next
 int text_train_bind_impl(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n, const char* prefix);
 int text_train_forward_impl(t2l_ctx* ctx, const float* hidden, int n_sent, int L, int n_desc, float p, uint32_t seed, float* out, hipStream_t s);
 int text_train_backward_impl(t2l_ctx* ctx, const float* grad_out, hipStream_t s);
-// pointnet.hip
-int pointnet_load_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n);
+// pointnet.hip. The backbone rides in the object branch's and in the fine stage's state dict, so its load is two steps around theirs:
+// stage (host only; *out stays null when the list has no object_encoder.pointnet.* tensor) before the other part commits, commit
+// (upload; then the context's backbone goes and `staged`, if any, is published) after it. Both own `staged` from then on.
+struct PointNetStaged;
+int pointnet_stage(t2l_ctx* ctx, const char* who, const t2l_weight_desc* w, int n, PointNetStaged** out);
+int pointnet_commit(t2l_ctx* ctx, const char* who, PointNetStaged* staged);
+void pointnet_discard(PointNetStaged* staged);
 int pointnet_features_impl(t2l_ctx* ctx, const float* pos, const float* rgb, const int32_t* cell_offsets, int n_cells, float* out,
                            hipStream_t s);
 int sample_points_impl(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets_dev, int n_objects, uint32_t seed,

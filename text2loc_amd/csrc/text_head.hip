@@ -32,6 +32,9 @@
 //                     registers (0.3 % of the FLOPs)
 //   th_ln_kernel      LayerNorm over 1024 columns from T32, two-pass in registers; writes T16 planes, or (POOL) the max over
 //                     each sentence's tokens
+#include <memory>
+
+#include "mfma32.h"
 #include "mfma_h3.h"
 #include "search_dev.h"
 #include "t2l_internal.h"
@@ -693,14 +696,12 @@ struct Weights {
   bool has_inter = false;
   int inter_dim = 0, inter_heads = 0;  // what has_inter was recorded for
   InterFusedW fused;  // the inter layer in the encoder's fragment packing (text_inter_fused2_kernel, encode.hip)
-  float *i_qkv_b = nullptr, *i_out_b = nullptr, *i_ff1_b = nullptr, *i_ff2_b = nullptr, *i_ln1_g = nullptr, *i_ln1_b = nullptr, *i_ln2_g = nullptr,
-        *i_ln2_b = nullptr;
+  char* blob = nullptr;  // every array above, one allocation (weight_table.h: Staging)
   // workspace
   char* ws = nullptr;
   size_t ws_cap = 0;
   int* flag = nullptr;        // device overflow flag
   int* flag_host = nullptr;   // pinned copy target
-  std::vector<void*> owned;
 };
 
 static void pack_t16(const float* W, int rows, int rows_pad, int K, std::vector<uint16_t>& hi, std::vector<uint16_t>& lo) {
@@ -721,16 +722,10 @@ static void pack_t16(const float* W, int rows, int rows_pad, int K, std::vector<
 
 using th::Weights;
 
-static const t2l_weight_desc* th_find(const t2l_weight_desc* w, int n, const std::string& name, int64_t numel) {
-  for (int i = 0; i < n; ++i)
-    if (w[i].name && name == w[i].name) return w[i].numel == numel ? &w[i] : nullptr;
-  return nullptr;
-}
-
 void free_text_head(t2l_ctx* ctx) {
   Weights* W = (Weights*)ctx->text_head;
   if (!W) return;
-  for (void* p : W->owned) (void)hipFree(p);
+  if (W->blob) (void)hipFree(W->blob);
   if (W->ws) (void)hipFree(W->ws);
   if (W->flag) (void)hipFree(W->flag);
   if (W->flag_host) (void)hipHostFree(W->flag_host);
@@ -740,112 +735,91 @@ void free_text_head(t2l_ctx* ctx) {
 
 int text_head_load_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const char* prefix, int inter_num_heads) {
   using namespace th;
+  const char* who = "t2l_text_head_load_weights";
   const std::string P = prefix ? prefix : "language_encoder.";
-  const std::string L0 = P + "intra_module.0.";
-  if (th_find(w, n, P + "intra_module.1.linear1.weight", (int64_t)kFF * kDM))
+  WeightTable T(who, w, n);
+  Staging st((size_t)4 * (3 * kDM + kDM + 2 * kFF + kTile) * kDM + (4u << 20));  // hi + lo planes of the five matrices, 2 B each, + the rest
+  std::unique_ptr<Weights> W(new Weights());
+  auto refused = [&]() { return fail(ctx, T2L_EINVAL, T.error()); };
+  if (!T.ok()) return refused();
+  if (T.find(P + "intra_module.1.linear1.weight"))
     return fail(ctx, T2L_EINVAL, "t2l_text_head_load_weights: the engine's text head is built for intra_module_num_layers = 1");
-  struct Req { const char* key; int64_t numel; };
-  const Req req[] = {{"self_attn.in_proj_weight", 3ll * kDM * kDM}, {"self_attn.in_proj_bias", 3 * kDM},
-                     {"self_attn.out_proj.weight", (int64_t)kDM * kDM}, {"self_attn.out_proj.bias", kDM},
-                     {"linear1.weight", (int64_t)kFF * kDM}, {"linear1.bias", kFF}, {"linear2.weight", (int64_t)kDM * kFF},
-                     {"linear2.bias", kDM}, {"norm1.weight", kDM}, {"norm1.bias", kDM}, {"norm2.weight", kDM}, {"norm2.bias", kDM}};
-  const t2l_weight_desc* t[12];
-  for (int i = 0; i < 12; ++i) {
-    t[i] = th_find(w, n, L0 + req[i].key, req[i].numel);
-    if (!t[i]) return fail(ctx, T2L_EINVAL, "t2l_text_head_load_weights: missing or mis-sized tensor " + L0 + req[i].key +
-                                                " (the engine's text head is built for d_model 1024, dim_feedforward 4096)");
-  }
+  std::vector<uint16_t> hi, lo;
+  auto planes = [&](const float* src, int rows, int K, char** dh, char** dl) {  // T16 planes of W [rows][K], rows padded to whole tiles
+    pack_t16(src, rows, (rows + kTile - 1) / kTile * kTile, K, hi, lo);
+    st.place(dh, hi);
+    st.place(dl, lo);
+  };
+  // the intra layer (d_model 1024, dim_feedforward 4096): matrix -> planes, vector -> as it is
+  auto matrix = [&](const std::string& name, int rows, int K, char** dh, char** dl) {
+    const float* m = T.need(name, (int64_t)rows * K);
+    if (m) planes(m, rows, K, dh, dl);
+    return m != nullptr;
+  };
+  auto vec = [&](const std::string& name, int nn, auto** d) {
+    const float* v = T.need(name, nn);
+    if (v) st.place(d, v, (size_t)nn);
+    return v != nullptr;
+  };
+  const std::string L0 = P + "intra_module.0.";
+  if (!(matrix(L0 + "self_attn.in_proj_weight", 3 * kDM, kDM, &W->qkv_h, &W->qkv_l) && vec(L0 + "self_attn.in_proj_bias", 3 * kDM, &W->qkv_b) &&
+        matrix(L0 + "self_attn.out_proj.weight", kDM, kDM, &W->out_h, &W->out_l) && vec(L0 + "self_attn.out_proj.bias", kDM, &W->out_b) &&
+        matrix(L0 + "linear1.weight", kFF, kDM, &W->ff1_h, &W->ff1_l) && vec(L0 + "linear1.bias", kFF, &W->ff1_b) &&
+        matrix(L0 + "linear2.weight", kDM, kFF, &W->ff2_h, &W->ff2_l) && vec(L0 + "linear2.bias", kDM, &W->ff2_b) &&
+        vec(L0 + "norm1.weight", kDM, &W->ln1_g) && vec(L0 + "norm1.bias", kDM, &W->ln1_b) && vec(L0 + "norm2.weight", kDM, &W->ln2_g) &&
+        vec(L0 + "norm2.bias", kDM, &W->ln2_b)))
+    return refused();
   // inter_mlp = Linear(1024 -> D) + BatchNorm1d, eval mode: folded
   const std::string M0 = P + "inter_mlp.0.";
-  int D = 0;
-  const t2l_weight_desc* mw = nullptr;
-  for (int i = 0; i < n; ++i)
-    if (w[i].name && M0 + "0.weight" == w[i].name) { mw = &w[i]; D = (int)(w[i].numel / kDM); }
-  if (!mw || D <= 0 || D > 256 || (int64_t)D * kDM != mw->numel || D % 4)
-    return fail(ctx, T2L_EINVAL, "t2l_text_head_load_weights: inter_mlp.0.0.weight missing or not [D <= 256][1024]");
-  const t2l_weight_desc *mb = th_find(w, n, M0 + "0.bias", D), *bg = th_find(w, n, M0 + "1.weight", D), *bb = th_find(w, n, M0 + "1.bias", D),
-                        *bm = th_find(w, n, M0 + "1.running_mean", D), *bv = th_find(w, n, M0 + "1.running_var", D);
-  if (!mb || !bg || !bb || !bm || !bv) return fail(ctx, T2L_EINVAL, "t2l_text_head_load_weights: inter_mlp.0 Linear/BatchNorm tensors missing");
-  free_text_head(ctx);
-  Weights* W = new Weights();
-  ctx->text_head = W;
+  int64_t rows = 0;
+  if (!T.need_rows(M0 + "0.weight", kDM, &rows)) return refused();
+  const int D = (int)rows;
+  if (D > 256 || D % 4) {
+    T.wrong_size(M0 + "0.weight", "[D][1024] with D <= 256 a multiple of 4");
+    return refused();
+  }
   W->out_dim = D;
-  std::vector<uint16_t> hi, lo;
-  auto upload = [&](const void* host, size_t bytes, void** dev) -> int {
-    T2L_HIP(ctx, hipMalloc(dev, bytes));
-    W->owned.push_back(*dev);
-    T2L_HIP(ctx, hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
-    return T2L_OK;
-  };
-  auto planes = [&](const float* src, int rows, int K, char** dh, char** dl) -> int {
-    const int rows_pad = (rows + kTile - 1) / kTile * kTile;
-    pack_t16(src, rows, rows_pad, K, hi, lo);
-    int rc = upload(hi.data(), hi.size() * 2, (void**)dh);
-    return rc ? rc : upload(lo.data(), lo.size() * 2, (void**)dl);
-  };
-  auto vec = [&](const float* src, int nn, int pad, float** d) -> int {
-    std::vector<float> v(pad, 0.f);
-    memcpy(v.data(), src, sizeof(float) * nn);
-    return upload(v.data(), sizeof(float) * pad, (void**)d);
-  };
-  int rc;
-  if ((rc = planes(t[0]->data, 3 * kDM, kDM, &W->qkv_h, &W->qkv_l)) || (rc = vec(t[1]->data, 3 * kDM, 3 * kDM, &W->qkv_b)) ||
-      (rc = planes(t[2]->data, kDM, kDM, &W->out_h, &W->out_l)) || (rc = vec(t[3]->data, kDM, kDM, &W->out_b)) ||
-      (rc = planes(t[4]->data, kFF, kDM, &W->ff1_h, &W->ff1_l)) || (rc = vec(t[5]->data, kFF, kFF, &W->ff1_b)) ||
-      (rc = planes(t[6]->data, kDM, kFF, &W->ff2_h, &W->ff2_l)) || (rc = vec(t[7]->data, kDM, kDM, &W->ff2_b)) ||
-      (rc = vec(t[8]->data, kDM, kDM, &W->ln1_g)) || (rc = vec(t[9]->data, kDM, kDM, &W->ln1_b)) ||
-      (rc = vec(t[10]->data, kDM, kDM, &W->ln2_g)) || (rc = vec(t[11]->data, kDM, kDM, &W->ln2_b)))
-    return rc;
-  {  // y = ((x W^T + b) - mean) * gamma / sqrt(var + eps) + beta
-    std::vector<float> wf((size_t)D * kDM), bf(kTile, 0.f);
-    for (int o = 0; o < D; ++o) {
-      const float sc = bg->data[o] / sqrtf(bv->data[o] + 1e-5f);
-      for (int k = 0; k < kDM; ++k) wf[(size_t)o * kDM + k] = mw->data[(size_t)o * kDM + k] * sc;
-      bf[o] = (mb->data[o] - bm->data[o]) * sc + bb->data[o];
-    }
-    if ((rc = planes(wf.data(), D, kDM, &W->mlp_h, &W->mlp_l)) || (rc = upload(bf.data(), sizeof(float) * kTile, (void**)&W->mlp_b))) return rc;
+  {
+    std::vector<float> wf, bf;
+    if (!fold_linear(T, M0 + "0", M0 + "1", D, kDM, &wf, &bf)) return refused();
+    bf.resize(kTile, 0.f);
+    planes(wf.data(), D, kDM, &W->mlp_h, &W->mlp_l);
+    st.place(&W->mlp_b, bf);
   }
   // inter_module.0 (language_encoder.py:101,143-144), when present and of a compiled shape: width D = that of inter_mlp in {128, 256},
   // inter_num_heads heads of 32 or 64 features (the state dict does not carry the head count), ff 4 D, no second layer. Any other
   // width or head count, a second layer, mis-sized tensors: has_inter stays false (t2l_text_inter then answers T2L_ESTATE).
-  if (text_inter_shape_is_compiled(D, inter_num_heads)) {
+  if (text_inter_shape_is_compiled(D, inter_num_heads) && !T.find(P + "inter_module.1.linear1.weight")) {
     const int ID = D, IF = 4 * D;
     const std::string I0 = P + "inter_module.0.";
-    const Req ireq[] = {{"self_attn.in_proj_weight", 3ll * ID * ID}, {"self_attn.in_proj_bias", 3 * ID}, {"self_attn.out_proj.weight", (int64_t)ID * ID},
-                        {"self_attn.out_proj.bias", ID}, {"linear1.weight", (int64_t)IF * ID}, {"linear1.bias", IF}, {"linear2.weight", (int64_t)ID * IF},
-                        {"linear2.bias", ID}, {"norm1.weight", ID}, {"norm1.bias", ID}, {"norm2.weight", ID}, {"norm2.bias", ID}};
-    const t2l_weight_desc* it[12];
-    bool all = !th_find(w, n, P + "inter_module.1.linear1.weight", (int64_t)IF * ID);
-    for (int i = 0; i < 12 && all; ++i) all = (it[i] = th_find(w, n, I0 + ireq[i].key, ireq[i].numel)) != nullptr;
+    InterFusedW& F = W->fused;
+    struct Part {
+      const char* key;
+      int rows, cols;       // cols 0: a vector, staged as it is; else a matrix, staged as split-f16 MFMA fragments (mfma_h3.h packing;
+      void* field;          // 1.5 MB at 256, 0.4 MB at 128)
+    };
+    const Part parts[] = {{"self_attn.in_proj_weight", 3 * ID, ID, &F.in_hp}, {"self_attn.in_proj_bias", 3 * ID, 0, &F.in_b},
+                          {"self_attn.out_proj.weight", ID, ID, &F.out_hp},   {"self_attn.out_proj.bias", ID, 0, &F.out_b},
+                          {"linear1.weight", IF, ID, &F.ff1_hp},              {"linear1.bias", IF, 0, &F.ff1_b},
+                          {"linear2.weight", ID, IF, &F.ff2_hp},              {"linear2.bias", ID, 0, &F.ff2_b},
+                          {"norm1.weight", ID, 0, &F.ln1_w},                  {"norm1.bias", ID, 0, &F.ln1_b},
+                          {"norm2.weight", ID, 0, &F.ln2_w},                  {"norm2.bias", ID, 0, &F.ln2_b}};
+    bool all = true;
+    for (const Part& q : parts) {
+      const t2l_weight_desc* d = T.find(I0 + q.key);
+      all = all && d && d->numel == (int64_t)q.rows * (q.cols ? q.cols : 1);
+    }
     if (all) {
-      if ((rc = vec(it[1]->data, 3 * ID, 3 * ID, &W->i_qkv_b)) || (rc = vec(it[3]->data, ID, ID, &W->i_out_b)) ||
-          (rc = vec(it[5]->data, IF, IF, &W->i_ff1_b)) || (rc = vec(it[7]->data, ID, ID, &W->i_ff2_b)) ||
-          (rc = vec(it[8]->data, ID, ID, &W->i_ln1_g)) || (rc = vec(it[9]->data, ID, ID, &W->i_ln1_b)) ||
-          (rc = vec(it[10]->data, ID, ID, &W->i_ln2_g)) || (rc = vec(it[11]->data, ID, ID, &W->i_ln2_b)))
-        return rc;
-      {  // the four matrices as split-f16 MFMA fragments (mfma_h3.h packing; 1.5 MB at 256, 0.4 MB at 128)
-        auto frag = [&](const float* Wm, int rows, int cols, const uint4** dst) -> int {
-          const std::vector<float> pk = pack_split_f16(Wm, nullptr, rows, cols, cols);
-          void* d = nullptr;
-          const int r = upload(pk.data(), pk.size() * sizeof(float), &d);
-          *dst = reinterpret_cast<const uint4*>(d);
-          return r;
-        };
-        if ((rc = frag(it[0]->data, 3 * ID, ID, &W->fused.in_hp)) || (rc = frag(it[2]->data, ID, ID, &W->fused.out_hp)) ||
-            (rc = frag(it[4]->data, IF, ID, &W->fused.ff1_hp)) || (rc = frag(it[6]->data, ID, IF, &W->fused.ff2_hp)))
-          return rc;
-        W->fused.in_b = W->i_qkv_b; W->fused.out_b = W->i_out_b; W->fused.ff1_b = W->i_ff1_b; W->fused.ff2_b = W->i_ff2_b;
-        W->fused.ln1_w = W->i_ln1_g; W->fused.ln1_b = W->i_ln1_b; W->fused.ln2_w = W->i_ln2_g; W->fused.ln2_b = W->i_ln2_b;
+      for (const Part& q : parts) {
+        const float* src = T.find(I0 + q.key)->data;
+        if (q.cols) st.place(static_cast<const uint4**>(q.field), pack_split_f16(src, nullptr, q.rows, q.cols, q.cols));
+        else st.place(static_cast<const float**>(q.field), src, (size_t)q.rows);
       }
       W->has_inter = true;
       W->inter_dim = ID;
       W->inter_heads = inter_num_heads;
     }
   }
-  T2L_HIP(ctx, hipMalloc(&W->flag, sizeof(int)));
-  T2L_HIP(ctx, hipMemset(W->flag, 0, sizeof(int)));
-  T2L_HIP(ctx, hipHostMalloc((void**)&W->flag_host, sizeof(int), hipHostMallocDefault));
-  *W->flag_host = 0;
   static PerDeviceOnce attr_done;
   if (attr_done.need(ctx->device)) {
     const int lds = kSlots * kSlotBytes;
@@ -857,6 +831,20 @@ int text_head_load_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const cha
     T2L_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&th_ln_kernel<true, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, 32 * 260 * 4));
     attr_done.mark(ctx->device);
   }
+  // everything is validated and staged: the overflow flag pair, one allocation and one copy of the weights, then the old set goes and
+  // the new one is published
+  hipError_t e = hipMalloc(&W->flag, sizeof(int));
+  if (e == hipSuccess) e = hipMemset(W->flag, 0, sizeof(int));
+  if (e == hipSuccess) e = hipHostMalloc((void**)&W->flag_host, sizeof(int), hipHostMallocDefault);
+  const int rc = e == hipSuccess ? upload_staging(ctx, who, st, &W->blob) : fail(ctx, T2L_EHIP, std::string(who) + ": " + hipGetErrorString(e));
+  if (rc) {
+    if (W->flag) (void)hipFree(W->flag);
+    if (W->flag_host) (void)hipHostFree(W->flag_host);
+    return rc;
+  }
+  *W->flag_host = 0;
+  free_text_head(ctx);
+  ctx->text_head = W.release();
   return T2L_OK;
 }
 

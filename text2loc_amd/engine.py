@@ -167,6 +167,20 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     return lib
 
 
+def _weight_descs(state_dict: Dict[str, object], wanted):
+    """The ``t2l_weight_desc`` array of the tensors whose name ``wanted`` accepts (``num_batches_tracked`` never), as contiguous fp32
+    host arrays, and those arrays: the descriptors point into them, so the caller holds both until the load call returns."""
+    keep, descs = [], []
+    for name, v in state_dict.items():
+        if name.endswith("num_batches_tracked") or not wanted(name):
+            continue
+        a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        keep.append(a)
+        descs.append(_WeightDesc(name.encode(), a.ctypes.data, a.size))
+    return (_WeightDesc * len(descs))(*descs), keep
+
+
 def _stream_ptr(device=None) -> int:
     """torch's current stream ON THE ENGINE'S DEVICE (the current device may be another GPU of the same process)."""
     return int(torch.cuda.current_stream(device).cuda_stream)
@@ -234,22 +248,12 @@ class Engine:
         """state_dict: name -> torch.Tensor | np.ndarray (fp32), keys as in the reference checkpoint. ``embed_dim`` /
         ``object_size`` / ``num_heads``: any compiled shape (``COMPILED_SHAPES``); ``encode_cells`` then returns ``embed_dim`` columns."""
         check_compiled_shape(int(embed_dim), int(num_heads), int(object_size), int(num_layers))
-        keep, descs = [], []
-        for name, v in state_dict.items():
-            if not (name.startswith("object_encoder.") or name.startswith("obj_inter_module.")):
-                continue
-            if name.endswith("num_batches_tracked"):
-                continue
-            a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            keep.append(a)
-            descs.append(_WeightDesc(name.encode(), a.ctypes.data, a.size))
-        arr = (_WeightDesc * len(descs))(*descs)
+        arr, _keep = _weight_descs(state_dict, lambda name: name.startswith(("object_encoder.", "obj_inter_module.")))
         cfg = _ModelConfig(int(class_embed), int(color_embed), int("class" in use_features),
                            int("color" in use_features), int("position" in use_features), int("num" in use_features),
                            int(num_layers), int(num_heads))
         shape = _ModelShape(int(embed_dim), int(object_size))
-        self._check(self.lib.t2l_load_weights_shaped(self._h, arr, len(descs), C.byref(cfg), C.byref(shape)))
+        self._check(self.lib.t2l_load_weights_shaped(self._h, arr, len(arr), C.byref(cfg), C.byref(shape)))
 
     @property
     def embed_dim(self) -> int:
@@ -336,19 +340,11 @@ class Engine:
         """state_dict: name -> tensor / ndarray holding ``<prefix>intra_module.0.*`` and ``<prefix>inter_mlp.0.*`` (fp32), and for the
         coarse model ``<prefix>inter_module.0.*``; ``inter_num_heads``: that layer's head count (inter_module_num_heads — a state dict
         does not carry it). ``text_inter`` serves the layer when (inter_mlp width, heads) is (128, 2 | 4) or (256, 4 | 8)."""
-        keep, descs = [], []
-        for name, v in state_dict.items():
-            if not name.startswith((prefix + "intra_module.", prefix + "inter_mlp.", prefix + "inter_module.")) or name.endswith("num_batches_tracked"):
-                continue
-            a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            keep.append(a)
-            descs.append(_WeightDesc(name.encode(), a.ctypes.data, a.size))
-        if not descs:
+        arr, _keep = _weight_descs(state_dict, lambda name: name.startswith((prefix + "intra_module.", prefix + "inter_mlp.", prefix + "inter_module.")))
+        if not len(arr):
             raise T2LError(f"text_head_load_weights: no tensors under {prefix}intra_module / {prefix}inter_mlp")
-        arr = (_WeightDesc * len(descs))(*descs)
-        self._text_head_dim = None
-        self._check(self.lib.t2l_text_head_load_weights_heads(self._h, arr, len(descs), prefix.encode(), int(inter_num_heads)))
+        self._check(self.lib.t2l_text_head_load_weights_heads(self._h, arr, len(arr), prefix.encode(), int(inter_num_heads)))
+        # (a refused load raised above: the context, and this width with it, still serve the head loaded before)
         self._text_head_dim = int(state_dict[prefix + "inter_mlp.0.0.weight"].shape[0])  # also the inter layer's width
 
     def text_head(self, hidden: torch.Tensor, check: bool = True):
@@ -386,18 +382,10 @@ class Engine:
     # ------------------------------------------------------------------ fine stage (f-1)
     def fine_load_weights(self, state_dict: Dict[str, object], class_embed: bool, color_embed: bool,
                           use_features=("class", "color", "position", "num"), num_layers: int = 2, num_heads: int = 4):
-        keep, descs = [], []
-        for name, v in state_dict.items():
-            if name.startswith("language_encoder.") or name.endswith("num_batches_tracked"):
-                continue
-            a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            keep.append(a)
-            descs.append(_WeightDesc(name.encode(), a.ctypes.data, a.size))
-        arr = (_WeightDesc * len(descs))(*descs)
+        arr, _keep = _weight_descs(state_dict, lambda name: not name.startswith("language_encoder."))
         cfg = _ModelConfig(int(class_embed), int(color_embed), int("class" in use_features), int("color" in use_features),
                            int("position" in use_features), int("num" in use_features), int(num_layers), int(num_heads))
-        self._check(self.lib.t2l_fine_load_weights(self._h, arr, len(descs), C.byref(cfg)))
+        self._check(self.lib.t2l_fine_load_weights(self._h, arr, len(arr), C.byref(cfg)))
 
     def fine_encode_objects(self, packed: Dict[str, torch.Tensor]) -> torch.Tensor:
         """packed cells of exactly 16 objects each -> f32[n_cells,16,128] unit-row object descriptors."""
