@@ -799,6 +799,78 @@ static T* pn_bump(PnTrain* pt, size_t count) {
 }
 static inline unsigned pn_blocks(size_t n) { return (unsigned)((n + 255) / 256); }
 
+// ---- the launches of the index / gather / layout kernels: one grid expression each, shared by pn_forward_core / pn_backward_core and
+// the dev library's wrappers (train_blocks.hip). `half`: the edge-row tensors are bf16 (PnTrain::half).
+// FPS, then the ball query, of one level: ns = source points per object (256 / 128 / 64 — false for any other)
+static bool pn_fps_launch(int ns, const float* pos, int n_obj, int nd, float* pos_out, hipStream_t s) {
+  using namespace train;
+  const unsigned fg = (unsigned)((n_obj + 3) / 4);
+  if (ns == 256) hipLaunchKernelGGL((pt_fps_kernel<4>), dim3(fg), dim3(256), 0, s, pos, n_obj, nd, pos_out);
+  else if (ns == 128) hipLaunchKernelGGL((pt_fps_kernel<2>), dim3(fg), dim3(256), 0, s, pos, n_obj, nd, pos_out);
+  else if (ns == 64) hipLaunchKernelGGL((pt_fps_kernel<1>), dim3(fg), dim3(256), 0, s, pos, n_obj, nd, pos_out);
+  else return false;
+  return true;
+}
+static bool pn_ball_launch(int ns, const float* pos_src, const float* pos_ctr, int n_obj, int nd, float r2, const int32_t* cell_base,
+                           int self_loops, int32_t* nbr33, int32_t* cnt_g, hipStream_t s) {
+  using namespace train;
+  const unsigned bg = (unsigned)(((size_t)n_obj * nd + 3) / 4);
+  if (ns == 256)
+    hipLaunchKernelGGL((pt_ball_kernel<4>), dim3(bg), dim3(256), 0, s, pos_src, pos_ctr, n_obj, nd, r2, cell_base, self_loops, nbr33, cnt_g);
+  else if (ns == 128)
+    hipLaunchKernelGGL((pt_ball_kernel<2>), dim3(bg), dim3(256), 0, s, pos_src, pos_ctr, n_obj, nd, r2, cell_base, self_loops, nbr33, cnt_g);
+  else if (ns == 64)
+    hipLaunchKernelGGL((pt_ball_kernel<1>), dim3(bg), dim3(256), 0, s, pos_src, pos_ctr, n_obj, nd, r2, cell_base, self_loops, nbr33, cnt_g);
+  else return false;
+  return true;
+}
+static void pn_compact_launch(const int32_t* nbr33, const int32_t* goff, size_t G, int nd, const int32_t* cell_of_obj, int32_t* src,
+                              int32_t* row_group, int32_t* row_cell, hipStream_t s) {
+  hipLaunchKernelGGL(train::pt_compact_kernel, dim3(pn_blocks(G * 33)), dim3(256), 0, s, nbr33, goff, G, nd, cell_of_obj, src, row_group, row_cell);
+}
+static void pn_iota_launch(size_t E, int per, const int32_t* cell_of_obj, int32_t* src, int32_t* row_group, int32_t* row_cell, int32_t* goff,
+                           hipStream_t s) {
+  hipLaunchKernelGGL(train::pt_iota_rows_kernel, dim3(pn_blocks(E + 1)), dim3(256), 0, s, E, per, cell_of_obj, src, row_group, row_cell, goff);
+}
+static void pn_gather_launch(bool half, const float* x_src, const float* pos_src, const float* pos_ctr, const int32_t* src,
+                             const int32_t* row_group, size_t E, int cin, int kp, float* X, hipStream_t s) {
+  using namespace train;
+  if (half)
+    hipLaunchKernelGGL((pt_gather_kernel<pn_bf16>), dim3(pn_blocks(E * (kp / 4))), dim3(256), 0, s, x_src, pos_src, pos_ctr, src, row_group, E, cin,
+                       kp, reinterpret_cast<pn_bf16*>(X));
+  else
+    hipLaunchKernelGGL((pt_gather_kernel<float>), dim3(pn_blocks(E * (kp / 4))), dim3(256), 0, s, x_src, pos_src, pos_ctr, src, row_group, E, cin,
+                       kp, X);
+}
+static void pn_pad_launch(const float* W, int rows, int kin, int kp, float* Wp, hipStream_t s) {
+  hipLaunchKernelGGL(train::pt_pad_kernel, dim3(pn_blocks((size_t)rows * kp)), dim3(256), 0, s, W, rows, kin, kp, Wp);
+}
+static void pn_segmax_launch(bool half, const float* y, const int32_t* goff, size_t G, int C, int nd, const int32_t* cell_of_obj,
+                             const float* mean, const float* rstd, const float* gamma, const float* beta, float* xout, int32_t* arg,
+                             float* ysel, hipStream_t s) {
+  using namespace train;
+  if (half)
+    hipLaunchKernelGGL((pt_segmax_kernel<pn_bf16>), dim3(pn_blocks(G * C / 4)), dim3(256), 0, s, reinterpret_cast<const pn_bf16*>(y), goff, G, C, nd,
+                       cell_of_obj, mean, rstd, gamma, beta, xout, arg, ysel);
+  else
+    hipLaunchKernelGGL((pt_segmax_kernel<float>), dim3(pn_blocks(G * C / 4)), dim3(256), 0, s, y, goff, G, C, nd, cell_of_obj, mean, rstd, gamma,
+                       beta, xout, arg, ysel);
+}
+static void pn_slice_launch(bool half, const float* dX, size_t rows, int cin, int kp, float* out, hipStream_t s) {
+  using namespace train;
+  if (half)
+    hipLaunchKernelGGL((pt_slice_kernel<pn_bf16>), dim3(pn_blocks(rows * cin)), dim3(256), 0, s, reinterpret_cast<const pn_bf16*>(dX), rows, cin, kp,
+                       out);
+  else
+    hipLaunchKernelGGL((pt_slice_kernel<float>), dim3(pn_blocks(rows * cin)), dim3(256), 0, s, dX, rows, cin, kp, out);
+}
+static void pn_relu_mask_launch(float* d, const float* f, size_t n, hipStream_t s) {
+  hipLaunchKernelGGL(train::pt_relu_mask_kernel, dim3(pn_blocks(n)), dim3(256), 0, s, d, f, n);
+}
+static void pn_transpose_launch(const float* W, int N, int Kp, float* Wt, hipStream_t s) {
+  hipLaunchKernelGGL(pt_transpose_kernel, dim3((unsigned)((N * Kp + 255) / 256)), dim3(256), 0, s, W, N, Kp, Wt);
+}
+
 // Every activation / table of the forward pass and the backward's scratch, laid out from pt->ws (E and G of every level are
 // known: the index phase ran). Called twice: with pt->ws == nullptr to measure, then for real.
 static size_t pn_layout(PnTrain* pt) {
@@ -992,20 +1064,8 @@ static int pn_forward_core(t2l_ctx* ctx, PnTrain* pt, const std::string& who, co
     for (int l = 0; l < 3; ++l) {
       PnLevel& L = pt->lv[l];
       const float r2 = radius[l] * radius[l];  // float32 product, as the restatement
-      const unsigned fg = (unsigned)((n_obj + 3) / 4), bg = (unsigned)((L.G + 3) / 4);
-      if (L.ns == 256) {
-        hipLaunchKernelGGL((pt_fps_kernel<4>), dim3(fg), dim3(256), 0, s, cur_pos, n_obj, L.nd, L.pos_out);
-        hipLaunchKernelGGL((pt_ball_kernel<4>), dim3(bg), dim3(256), 0, s, cur_pos, (const float*)L.pos_out, n_obj, L.nd, r2,
-                           (const int32_t*)i_cell_base, ctx->pn_self_loops, L.nbr33, L.cnt_g);
-      } else if (L.ns == 128) {
-        hipLaunchKernelGGL((pt_fps_kernel<2>), dim3(fg), dim3(256), 0, s, cur_pos, n_obj, L.nd, L.pos_out);
-        hipLaunchKernelGGL((pt_ball_kernel<2>), dim3(bg), dim3(256), 0, s, cur_pos, (const float*)L.pos_out, n_obj, L.nd, r2,
-                           (const int32_t*)i_cell_base, ctx->pn_self_loops, L.nbr33, L.cnt_g);
-      } else {
-        hipLaunchKernelGGL((pt_fps_kernel<1>), dim3(fg), dim3(256), 0, s, cur_pos, n_obj, L.nd, L.pos_out);
-        hipLaunchKernelGGL((pt_ball_kernel<1>), dim3(bg), dim3(256), 0, s, cur_pos, (const float*)L.pos_out, n_obj, L.nd, r2,
-                           (const int32_t*)i_cell_base, ctx->pn_self_loops, L.nbr33, L.cnt_g);
-      }
+      (void)pn_fps_launch(L.ns, cur_pos, n_obj, L.nd, L.pos_out, s);  // (ns is 256 / 128 / 64: set above)
+      (void)pn_ball_launch(L.ns, cur_pos, L.pos_out, n_obj, L.nd, r2, i_cell_base, ctx->pn_self_loops, L.nbr33, L.cnt_g, s);
       cur_pos = L.pos_out;
     }
   }
@@ -1060,31 +1120,15 @@ static int pn_forward_core(t2l_ctx* ctx, PnTrain* pt, const std::string& who, co
   const float* cur_x = rgb;
   for (int l = 0; l < 4; ++l) {
     PnLevel& L = pt->lv[l];
-    if (L.sa)
-      hipLaunchKernelGGL(pt_compact_kernel, dim3(pn_blocks(L.G * 33)), dim3(256), 0, s, (const int32_t*)L.nbr33, (const int32_t*)L.goff, L.G,
-                         L.nd, (const int32_t*)pt->cell_of_obj, L.src, L.row_group, L.row_cell);
-    else
-      hipLaunchKernelGGL(pt_iota_rows_kernel, dim3(pn_blocks(L.E + 1)), dim3(256), 0, s, L.E, 32, (const int32_t*)pt->cell_of_obj, L.src,
-                         L.row_group, L.row_cell, L.goff);
-    if (pt->half)
-      hipLaunchKernelGGL((pt_gather_kernel<pn_bf16>), dim3(pn_blocks(L.E * (L.kp / 4))), dim3(256), 0, s, cur_x, cur_pos,
-                         L.sa ? (const float*)L.pos_out : nullptr, (const int32_t*)L.src, (const int32_t*)L.row_group, L.E, L.cin, L.kp,
-                         reinterpret_cast<pn_bf16*>(L.X));
-    else
-      hipLaunchKernelGGL((pt_gather_kernel<float>), dim3(pn_blocks(L.E * (L.kp / 4))), dim3(256), 0, s, cur_x, cur_pos,
-                         L.sa ? (const float*)L.pos_out : nullptr, (const int32_t*)L.src, (const int32_t*)L.row_group, L.E, L.cin, L.kp, L.X);
-    hipLaunchKernelGGL(pt_pad_kernel, dim3(pn_blocks((size_t)L.h1 * L.kp)), dim3(256), 0, s, (const float*)PT(pt, L.prefix + ".0.0.weight").data,
-                       L.h1, L.kin, L.kp, L.w1p);
+    if (L.sa) pn_compact_launch(L.nbr33, L.goff, L.G, L.nd, pt->cell_of_obj, L.src, L.row_group, L.row_cell, s);
+    else pn_iota_launch(L.E, 32, pt->cell_of_obj, L.src, L.row_group, L.row_cell, L.goff, s);
+    pn_gather_launch(pt->half, cur_x, cur_pos, L.sa ? (const float*)L.pos_out : nullptr, L.src, L.row_group, L.E, L.cin, L.kp, L.X, s);
+    pn_pad_launch(PT(pt, L.prefix + ".0.0.weight").data, L.h1, L.kin, L.kp, L.w1p, s);
     pn_block_fwd(pt, L, 0, L.X, L.w1p, L.kp, L.h1, L.y1, L.a1, L.mean1, L.rstd1, L.rg1, false, s);
     pn_block_fwd(pt, L, 1, L.a1 ? L.a1 : L.y1, PT(pt, L.prefix + ".1.0.weight").data, L.h1, L.h2, L.y2, nullptr, L.mean2, L.rstd2, nullptr,
                  L.a1 == nullptr, s);
-#define T2L_PN_SEGMAX(ST_)                                                                                                                        \
-  hipLaunchKernelGGL((pt_segmax_kernel<ST_>), dim3(pn_blocks(L.G * L.h2 / 4)), dim3(256), 0, s, reinterpret_cast<const ST_*>(L.y2),               \
-                     (const int32_t*)L.goff, L.G, L.h2, L.nd, (const int32_t*)pt->cell_of_obj, (const float*)L.mean2, (const float*)L.rstd2,       \
-                     (const float*)PT(pt, L.prefix + ".1.1.weight").data, (const float*)PT(pt, L.prefix + ".1.1.bias").data, L.xout, L.arg, L.ysel)
-    if (pt->half) T2L_PN_SEGMAX(pn_bf16);
-    else T2L_PN_SEGMAX(float);
-#undef T2L_PN_SEGMAX
+    pn_segmax_launch(pt->half, L.y2, L.goff, L.G, L.h2, L.nd, pt->cell_of_obj, L.mean2, L.rstd2, PT(pt, L.prefix + ".1.1.weight").data,
+                     PT(pt, L.prefix + ".1.1.bias").data, L.xout, L.arg, L.ysel, s);
     if (L.sa) {
       cur_pos = L.pos_out;
       cur_x = L.xout;
@@ -1130,10 +1174,10 @@ static int pn_backward_core(t2l_ctx* ctx, PnTrain* pt, const std::string& who, c
   float* dx = pn_bump<float>(pt, (size_t)n_obj * 8192);  // gradient w.r.t. the current level's output ...
   float* dx_next = pn_bump<float>(pt, (size_t)n_obj * 8192);  // ... and w.r.t. the output of the level below
   T2L_HIP(ctx, hipMemcpyAsync(d2, grad_f2, sizeof(float) * (size_t)n_obj * 256, hipMemcpyDeviceToDevice, s));
-  hipLaunchKernelGGL(pt_relu_mask_kernel, dim3(pn_blocks((size_t)n_obj * 256)), dim3(256), 0, s, d2, (const float*)pt->f2, (size_t)n_obj * 256);
+  pn_relu_mask_launch(d2, pt->f2, (size_t)n_obj * 256, s);
   gemm_tn(d2, pt->f1, PT(pt, P + "lin2.weight").grad, PT(pt, P + "lin2.bias").grad, n_obj, 256, 512, s);
   gemm_nn(d2, PT(pt, P + "lin2.weight").data, d1, n_obj, 256, 512, 0, s);
-  hipLaunchKernelGGL(pt_relu_mask_kernel, dim3(pn_blocks((size_t)n_obj * 512)), dim3(256), 0, s, d1, (const float*)pt->f1, (size_t)n_obj * 512);
+  pn_relu_mask_launch(d1, pt->f1, (size_t)n_obj * 512, s);
   gemm_tn(d1, pt->f0, PT(pt, P + "lin1.weight").grad, PT(pt, P + "lin1.bias").grad, n_obj, 512, 1024, s);
   gemm_nn(d1, PT(pt, P + "lin1.weight").data, dx, n_obj, 512, 1024, 0, s);
   for (int l = 3; l >= 0; --l) {
@@ -1147,8 +1191,7 @@ static int pn_backward_core(t2l_ctx* ctx, PnTrain* pt, const std::string& who, c
       if (!gemm_tn2(dA2, L.a1 ? L.a1 : L.y1, PT(pt, L.prefix + ".1.0.weight").grad, PT(pt, L.prefix + ".1.0.bias").grad, L.E, L.h2, L.h1, L.h1,
                     L.h1, L.a1 ? nullptr : L.mean1, L.a1 ? nullptr : L.rg1, L.a1 ? nullptr : be1, L.row_cell, s))
         return fail(ctx, T2L_EHIP, who + ": no tn2_kernel instance for this layer shape (internal error)");
-      hipLaunchKernelGGL(pt_transpose_kernel, dim3((unsigned)((L.h2 * L.h1 + 255) / 256)), dim3(256), 0, s,
-                         (const float*)PT(pt, L.prefix + ".1.0.weight").data, L.h2, L.h1, pt->wt);
+      pn_transpose_launch(PT(pt, L.prefix + ".1.0.weight").data, L.h2, L.h1, pt->wt, s);
       gemm_rows2(dA2, pt->wt, nullptr, dA1, L.E, L.h1, L.h2, nullptr, nullptr, nullptr, nullptr, nullptr, s);
     }
     pn_block_bwd(pt, L, 0, dA1, L.y1, L.a1, L.h1, L.mean1, L.rstd1, L.rg1, nullptr, s);
@@ -1162,21 +1205,15 @@ static int pn_backward_core(t2l_ctx* ctx, PnTrain* pt, const std::string& who, c
       const size_t nprev = Lb.G * Lb.h2;
       if (L.sa) {  // the product's epilogue scatters (atomics through src): no [E, kp] gradient, no scatter launch
         T2L_HIP(ctx, hipMemsetAsync(dx_next, 0, sizeof(float) * nprev, s));
-        hipLaunchKernelGGL(pt_transpose_kernel, dim3((unsigned)((L.h1 * L.kp + 255) / 256)), dim3(256), 0, s, (const float*)L.w1p, L.h1, L.kp,
-                           pt->wt);
+        pn_transpose_launch(L.w1p, L.h1, L.kp, pt->wt, s);
         // (only the tiles that hold feature columns: N = cin rounded up to 32)
         gemm_rows2(dA1, pt->wt, nullptr, nullptr, L.E, (L.cin + 31) / 32 * 32, L.h1, nullptr, nullptr, nullptr, nullptr, nullptr, s,
                    (const int32_t*)L.src, dx_next, L.cin);
       } else {
         float* dX = reinterpret_cast<float*>(pn_bump<char>(pt, L.E * L.kp * es));  // (the global level: no sampling, the rows ARE the level below's)
-        hipLaunchKernelGGL(pt_transpose_kernel, dim3((unsigned)((L.h1 * L.kp + 255) / 256)), dim3(256), 0, s, (const float*)L.w1p, L.h1, L.kp,
-                           pt->wt);
+        pn_transpose_launch(L.w1p, L.h1, L.kp, pt->wt, s);
         gemm_rows2(dA1, pt->wt, nullptr, dX, L.E, L.kp, L.h1, nullptr, nullptr, nullptr, nullptr, nullptr, s);
-        if (pt->half)
-          hipLaunchKernelGGL((pt_slice_kernel<pn_bf16>), dim3(pn_blocks(L.E * L.cin)), dim3(256), 0, s, reinterpret_cast<const pn_bf16*>(dX), L.E, L.cin,
-                             L.kp, dx_next);
-        else
-          hipLaunchKernelGGL((pt_slice_kernel<float>), dim3(pn_blocks(L.E * L.cin)), dim3(256), 0, s, (const float*)dX, L.E, L.cin, L.kp, dx_next);
+        pn_slice_launch(pt->half, dX, L.E, L.cin, L.kp, dx_next, s);
       }
       std::swap(dx, dx_next);
     }
