@@ -135,11 +135,35 @@ int t2l_reduce_objects(t2l_ctx* ctx, const float* xyz, const float* rgb, const i
  * xyz, rgb: dev f32[n_points,3] (objects concatenated); point_offsets: DEV i64[n_objects+1]; out_pos / out_rgb: dev
  * f32[n_objects,256,3] — the inputs of t2l_pointnet_features. Sampling is counter-based (the reference uses numpy's global RNG: equal
  * in distribution, not in the draw): index j of object o is floor(u * n_o) with u = (lowbias32(j * 0x9E3779B1 + key_o) >> 8) / 2^24,
- * key_o = seed ^ o * 0x85EBCA77; the angle is rotate_deg * (2u' - 1) with u' = (lowbias32(0xA5A5A5A5 + key_o) >> 8) / 2^24. */
+ * key_o = seed ^ o * 0x85EBCA77; the angle is rotate_deg * (2u' - 1) with u' = (lowbias32(0xA5A5A5A5 + key_o) >> 8) / 2^24.
+ * The transforms' arithmetic is fixed operation by operation, so that oracle/t2l_oracle_pointnet.py's restatement gives the same bits:
+ * float32 throughout, every product, sum and quotient rounded on its own (no FMA contraction); x' = x c - y s, y' = x s + y c with
+ * (s, c) from a float32 routine (round-to-nearest quadrant, three-step Cody-Waite reduction by pi/2 with FMAs, polynomials of degree 9 /
+ * 8 — the scheme numpy's float32 sin / cos use; |angle| < 71476); the mean is the float64 sum of the 256 sampled positions / 256
+ * rounded to float32; scale = (1 / max |coordinate - mean|) * 0.999999. */
 #define T2L_SAMPLE_NORMALIZE 1
 #define T2L_SAMPLE_ROTATE 2
 int t2l_sample_object_points(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets, int32_t n_objects,
                              uint32_t seed, int32_t transform_flags, float rotate_deg, float* out_pos, float* out_rgb, void* stream);
+
+/* The same draws for a LIST OF ROWS of arrays that stay resident: the point batches of a fine-stage training batch.
+ * Replaces: batch_object_points (dataloading/kitti360pose/utils.py:91-147) as load_pose_and_cell runs it once per item over the item's
+ * 16 padded objects (dataloading/kitti360pose/poses.py:153), redrawn on every fetch.
+ * xyz, rgb, point_offsets (DEV i64[n_objects+1]): as above, e.g. a whole dataset's objects plus one pad object. object_ids: HOST
+ * i32[n_rows], each in [0, n_objects); salts: HOST u32[n_rows] or NULL (= every salt 0); out_pos / out_rgb: dev f32[n_rows,256,3].
+ * Row r samples object g = object_ids[r] with exactly the draws documented above under key = (seed ^ salts[r]) ^ g * 0x85EBCA77. So:
+ *   - row r equals row g of a whole-set t2l_sample_object_points call with seed `seed ^ salts[r]`, bit for bit, under all three
+ *     transforms (both kernels run one per-object body, one workgroup per output row), and equals the numpy restatement bit for bit;
+ *   - how the caller chunks, orders or repeats rows cannot change a draw — the position in the call is not part of the key.
+ * An object without points yields a row of zeros (from both entry points).
+ * The ids are host arrays so that they are range-checked before anything is launched: an id outside [0, n_objects), n_rows < 0,
+ * n_objects < 0, an unknown flag or a null array is T2L_EINVAL and no output byte is written; n_rows == 0 is T2L_OK and touches nothing.
+ * ids and salts are copied into a pinned buffer the context owns and from there to the device on `stream`; the arrays may be reused
+ * as soon as the call returns. The stream is NOT synchronised. The one wait: before the staging buffer is reused, the call waits on
+ * the host for the previous indexed call's kernel (an event). The launch is one workgroup per row, independent of n_objects. */
+int t2l_sample_object_points_indexed(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets, int32_t n_objects,
+                                     const int32_t* object_ids, const uint32_t* salts, int32_t n_rows, uint32_t seed,
+                                     int32_t transform_flags, float rotate_deg, float* out_pos, float* out_rgb, void* stream);
 
 /* ---- PointNet++ object backbone (a3), eval mode ------------------------------------------------ */
 /* Replaces: PointNet2.forward(...).features2 (models/pointcloud/pointnet2.py:66-100) as ObjectEncoder.forward calls it

@@ -131,6 +131,7 @@ void t2l_destroy(t2l_ctx* ctx) {
   free_train(ctx);
   free_text_train(ctx);
   free_pointnet(ctx);
+  free_sample_stage(ctx);
   free_fine(ctx);
   free_fine_train(ctx);
   free_text_head(ctx);
@@ -171,6 +172,15 @@ int t2l_sample_object_points(t2l_ctx* ctx, const float* xyz, const float* rgb, c
   if (!ctx) return T2L_EINVAL;
   T2L_HIP(ctx, hipSetDevice(ctx->device));
   return sample_points_impl(ctx, xyz, rgb, point_offsets, n_objects, seed, transform_flags, rotate_deg, out_pos, out_rgb, (hipStream_t)stream);
+}
+
+int t2l_sample_object_points_indexed(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets, int32_t n_objects,
+                                     const int32_t* object_ids, const uint32_t* salts, int32_t n_rows, uint32_t seed,
+                                     int32_t transform_flags, float rotate_deg, float* out_pos, float* out_rgb, void* stream) {
+  if (!ctx) return T2L_EINVAL;
+  T2L_HIP(ctx, hipSetDevice(ctx->device));
+  return sample_points_indexed_impl(ctx, xyz, rgb, point_offsets, n_objects, object_ids, salts, n_rows, seed, transform_flags, rotate_deg,
+                                    out_pos, out_rgb, (hipStream_t)stream);
 }
 
 int t2l_pointnet_features(t2l_ctx* ctx, const float* pos, const float* rgb, const int32_t* cell_offsets, int32_t n_cells,

@@ -58,7 +58,9 @@ __device__ __forceinline__ void grad_rowblock(const float* __restrict__ G, int l
   for (int t = 0; t < 8; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  const int gi = i0 + col;  // A-operand row of this lane
+  // A-operand row of this lane, clamped like every other row here: in a ragged last block the rows past B - 1 are computed and thrown
+  // away, and unclamped they read G up to 31 rows past its end — at B = 129 13 KB past the end of the whole workspace
+  const int gi = min(i0 + col, B - 1);
 #pragma unroll 8  // the operands of 8 steps in flight: every step's loads come from L2 and nothing else hides their latency
   for (int k0 = 0; k0 < B; k0 += 2) {
     const int k = k0 + half;

@@ -1139,49 +1139,192 @@ __device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
   return x;
 }
 
-__global__ __launch_bounds__(256) void sample_points_kernel(const float* __restrict__ xyz, const float* __restrict__ rgb,
-                                                            const int64_t* __restrict__ offsets, uint32_t seed, int flags,
-                                                            float rotate_rad, float* __restrict__ out_pos, float* __restrict__ out_rgb) {
-  __shared__ float red[4][4];
-  const int o = blockIdx.x, j = threadIdx.x, lane = j & 63, w = j >> 6;
+// The arithmetic of the two transforms is DEFINED, operation by operation, so that the numpy restatement (oracle/t2l_oracle_pointnet.py:
+// sample_object_points) and the kernels give the same bits: every float32 product, sum and quotient is rounded on its own (mul_rn / add_rn /
+// sub_rn below keep the compiler from contracting them into FMAs), the mean of the 256 sampled positions is a
+// float64 sum rounded to float32 once, and the angle's sine and cosine are the float32 routine below.
+//
+// sin / cos of a float32 angle, |x| < 71476: the widely used single-precision scheme that numpy's float32 loops also run — quadrant by the
+// round-to-nearest magic number, three-step Cody-Waite reduction by pi/2 with FMAs, an even polynomial of degree 8 for the cosine and an
+// odd one of degree 9 for the sine, chosen and signed by the quadrant. Held against numpy over all 2^24 angles the sampler can draw at
+// rotate_deg = 120: the same bits (a device libm cosf differs from it in the last bit for 19 % of them).
+// One rounding per operation. The HIP headers spell __fmul_rn / __fadd_rn / __fsub_rn as plain operators compiled under their own
+// contraction mode, so a product and a sum written with them still fuse into an FMA after inlining; these carry the pragma themselves.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ float sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+__device__ __forceinline__ void sincos_f32(float x, float* sn, float* cs) {
+#pragma clang fp contract(off)
+  const float magic = 0x1.8p+23f;
+  const float qm = add_rn(mul_rn(x, 0x1.45f306p-1f), magic);
+  const int iq = __float_as_int(qm);
+  const float q = sub_rn(qm, magic);
+  float r = __builtin_fmaf(q, -0x1.921fb0p+00f, x);
+  r = __builtin_fmaf(q, -0x1.5110b4p-22f, r);
+  r = __builtin_fmaf(q, -0x1.846988p-48f, r);
+  const float r2 = mul_rn(r, r);
+  float c = __builtin_fmaf(0x1.98e616p-16f, r2, -0x1.6c06dcp-10f);
+  c = __builtin_fmaf(c, r2, 0x1.55553cp-05f);
+  c = __builtin_fmaf(c, r2, -0.5f);
+  c = __builtin_fmaf(c, r2, 1.0f);
+  float t = __builtin_fmaf(0x1.7d3bbcp-19f, r2, -0x1.a06bbap-13f);
+  t = __builtin_fmaf(t, r2, 0x1.11119ap-07f);
+  t = __builtin_fmaf(t, r2, -0x1.555556p-03f);
+  t = mul_rn(t, r2);
+  t = __builtin_fmaf(t, r, r);
+  const float s_out = (iq & 1) ? c : t, c_out = ((iq + 1) & 1) ? c : t;
+  *sn = (iq & 2) ? -s_out : s_out;
+  *cs = ((iq + 1) & 2) ? -c_out : c_out;
+}
+
+struct SampleRed {  // LDS of one sampler workgroup: per wave the float64 sums of x, y, z and the largest |coordinate|
+  double sum[4][3];
+  float peak[4];
+};
+
+// The per-object body both sampler kernels run, one 256-thread workgroup per OUTPUT row: object `o` of the resident arrays, drawn under
+// `okey`, written to row `row` of the outputs. The whole-set kernel calls it with row = o and okey = seed ^ o * 0x85EBCA77; the indexed
+// kernel with o = object_ids[row] and okey = (seed ^ salts[row]) ^ o * 0x85EBCA77 — the same instructions in the same reduction order,
+// which is what makes a row of the one equal the row of the other bit for bit under every transform.
+__device__ __forceinline__ void sample_object_row(const float* __restrict__ xyz, const float* __restrict__ rgb,
+                                                  const int64_t* __restrict__ offsets, int o, uint32_t okey, size_t row, int flags,
+                                                  float rotate_rad, float* __restrict__ out_pos, float* __restrict__ out_rgb,
+                                                  SampleRed* red) {
+#pragma clang fp contract(off)
+  const int j = threadIdx.x, lane = j & 63, w = j >> 6;
   const int64_t p0 = offsets[o];
   const uint32_t n = (uint32_t)(offsets[o + 1] - p0);
-  const uint32_t okey = seed ^ ((uint32_t)o * 0x85EBCA77u);
+  const size_t ob = (row * 256 + j) * 3;
+  if (n == 0) {  // an object without points has nothing to gather (the whole workgroup takes this branch): zeros, no read
+    out_rgb[ob] = 0.f; out_rgb[ob + 1] = 0.f; out_rgb[ob + 2] = 0.f;
+    out_pos[ob] = 0.f; out_pos[ob + 1] = 0.f; out_pos[ob + 2] = 0.f;
+    return;
+  }
   const uint32_t x = lowbias32((uint32_t)j * 0x9E3779B1u + okey);
   const uint32_t idx = (uint32_t)(((uint64_t)(x >> 8) * n) >> 24);
   const float* src = xyz + (size_t)(p0 + idx) * 3;
   float px = src[0], py = src[1], pz = src[2];
   const float* col = rgb + (size_t)(p0 + idx) * 3;
-  const size_t ob = ((size_t)o * 256 + j) * 3;
   out_rgb[ob] = col[0]; out_rgb[ob + 1] = col[1]; out_rgb[ob + 2] = col[2];
   if (flags & T2L_SAMPLE_ROTATE) {  // pos @ [[c, s, 0], [-s, c, 0], [0, 0, 1]]
-    const float u = (float)(lowbias32(0xA5A5A5A5u + okey) >> 8) * (1.f / 16777216.f);
-    const float ang = rotate_rad * (2.f * u - 1.f);
-    const float c = cosf(ang), sn = sinf(ang);
-    const float rx = px * c - py * sn, ry = px * sn + py * c;
+    const float u = mul_rn((float)(lowbias32(0xA5A5A5A5u + okey) >> 8), 1.f / 16777216.f);
+    const float ang = mul_rn(rotate_rad, sub_rn(mul_rn(2.f, u), 1.f));
+    float c, sn;
+    sincos_f32(ang, &sn, &c);
+    const float rx = sub_rn(mul_rn(px, c), mul_rn(py, sn)), ry = add_rn(mul_rn(px, sn), mul_rn(py, c));
     px = rx; py = ry;
   }
   if (!(flags & T2L_SAMPLE_NORMALIZE)) {  // uniform branch
     out_pos[ob] = px; out_pos[ob + 1] = py; out_pos[ob + 2] = pz;
     return;
   }
-  float sx = px, sy = py, sz = pz;
+  // float64 sums: 256 float32 values of one object add up exactly unless their exponents span more than 21 bits, so the order of the
+  // butterfly is not part of the result (and where it is, by one part in 2^53 before the rounding to float32)
+  double sx = (double)px, sy = (double)py, sz = (double)pz;
 #pragma unroll
   for (int off = 32; off; off >>= 1) { sx += __shfl_xor(sx, off); sy += __shfl_xor(sy, off); sz += __shfl_xor(sz, off); }
-  if (lane == 0) { red[w][0] = sx; red[w][1] = sy; red[w][2] = sz; }
+  if (lane == 0) { red->sum[w][0] = sx; red->sum[w][1] = sy; red->sum[w][2] = sz; }
   __syncthreads();
-  const float mx = (red[0][0] + red[1][0] + red[2][0] + red[3][0]) * (1.f / 256.f);
-  const float my = (red[0][1] + red[1][1] + red[2][1] + red[3][1]) * (1.f / 256.f);
-  const float mz = (red[0][2] + red[1][2] + red[2][2] + red[3][2]) * (1.f / 256.f);
-  px -= mx; py -= my; pz -= mz;
+  const float mx = (float)((((red->sum[0][0] + red->sum[1][0]) + red->sum[2][0]) + red->sum[3][0]) * (1.0 / 256.0));
+  const float my = (float)((((red->sum[0][1] + red->sum[1][1]) + red->sum[2][1]) + red->sum[3][1]) * (1.0 / 256.0));
+  const float mz = (float)((((red->sum[0][2] + red->sum[1][2]) + red->sum[2][2]) + red->sum[3][2]) * (1.0 / 256.0));
+  px = sub_rn(px, mx); py = sub_rn(py, my); pz = sub_rn(pz, mz);
   float m = fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz));
 #pragma unroll
   for (int off = 32; off; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+  if (lane == 0) red->peak[w] = m;
   __syncthreads();
-  if (lane == 0) red[w][3] = m;
-  __syncthreads();
-  const float scale = (1.0f / fmaxf(fmaxf(red[0][3], red[1][3]), fmaxf(red[2][3], red[3][3]))) * 0.999999f;
-  out_pos[ob] = px * scale; out_pos[ob + 1] = py * scale; out_pos[ob + 2] = pz * scale;
+  const float peak = fmaxf(fmaxf(red->peak[0], red->peak[1]), fmaxf(red->peak[2], red->peak[3]));
+  const float scale = mul_rn(__fdiv_rn(1.0f, peak), 0.999999f);
+  out_pos[ob] = mul_rn(px, scale); out_pos[ob + 1] = mul_rn(py, scale); out_pos[ob + 2] = mul_rn(pz, scale);
+}
+
+__global__ __launch_bounds__(256) void sample_points_kernel(const float* __restrict__ xyz, const float* __restrict__ rgb,
+                                                            const int64_t* __restrict__ offsets, uint32_t seed, int flags,
+                                                            float rotate_rad, float* __restrict__ out_pos, float* __restrict__ out_rgb) {
+  __shared__ SampleRed red;
+  const int o = blockIdx.x;
+  sample_object_row(xyz, rgb, offsets, o, seed ^ ((uint32_t)o * 0x85EBCA77u), (size_t)o, flags, rotate_rad, out_pos, out_rgb, &red);
+}
+
+// Row r of the outputs = object ids[r] (range-checked on the host before the launch) under seed ^ salts[r]. The grid is the row list:
+// nothing here depends on how many objects the resident arrays hold.
+__global__ __launch_bounds__(256) void sample_points_indexed_kernel(const float* __restrict__ xyz, const float* __restrict__ rgb,
+                                                                    const int64_t* __restrict__ offsets, const int32_t* __restrict__ ids,
+                                                                    const uint32_t* __restrict__ salts, uint32_t seed, int flags,
+                                                                    float rotate_rad, float* __restrict__ out_pos,
+                                                                    float* __restrict__ out_rgb) {
+  __shared__ SampleRed red;
+  const int r = blockIdx.x, o = ids[r];
+  const uint32_t row_seed = salts ? seed ^ salts[r] : seed;
+  sample_object_row(xyz, rgb, offsets, o, row_seed ^ ((uint32_t)o * 0x85EBCA77u), (size_t)r, flags, rotate_rad, out_pos, out_rgb, &red);
+}
+
+void free_sample_stage(t2l_ctx* ctx) {
+  if (ctx->sample_done) (void)hipEventDestroy(ctx->sample_done);
+  if (ctx->sample_host) (void)hipHostFree(ctx->sample_host);
+  if (ctx->sample_dev) (void)hipFree(ctx->sample_dev);
+  ctx->sample_done = nullptr;
+  ctx->sample_host = ctx->sample_dev = nullptr;
+  ctx->sample_cap = 0;
+  ctx->sample_pending = false;
+}
+
+int sample_points_indexed_impl(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets_dev, int n_objects,
+                               const int32_t* ids, const uint32_t* salts, int n_rows, uint32_t seed, int flags, float rotate_deg,
+                               float* out_pos, float* out_rgb, hipStream_t s) {
+  const char* who = "t2l_sample_object_points_indexed: ";
+  if (n_rows < 0 || n_objects < 0) return fail(ctx, T2L_EINVAL, std::string(who) + "negative count");
+  if (n_rows == 0) return T2L_OK;
+  if (!xyz || !rgb || !point_offsets_dev || !ids || !out_pos || !out_rgb) return fail(ctx, T2L_EINVAL, std::string(who) + "null argument");
+  if (flags & ~(T2L_SAMPLE_NORMALIZE | T2L_SAMPLE_ROTATE)) return fail(ctx, T2L_EINVAL, std::string(who) + "unknown transform flag");
+  for (int r = 0; r < n_rows; ++r)
+    if (ids[r] < 0 || ids[r] >= n_objects)
+      return fail(ctx, T2L_EINVAL, std::string(who) + "object_ids[" + std::to_string(r) + "] = " + std::to_string(ids[r]) + " is outside [0, " +
+                                       std::to_string(n_objects) + ")");
+  // ids | salts staged through the context's pinned buffer and its device twin. Both are reused by the next call, so that call first
+  // waits (on the host, on an event) for THIS call's kernel — the only wait there is, and over before it starts unless calls are
+  // issued back to back faster than a sampler launch runs. The caller's stream is never synchronised.
+  const size_t words = (size_t)n_rows * (salts ? 2 : 1);
+  if (ctx->sample_pending) {
+    T2L_HIP(ctx, hipEventSynchronize(ctx->sample_done));
+    ctx->sample_pending = false;
+  }
+  if (words > ctx->sample_cap) {
+    const size_t cap = words < 4096 ? 4096 : words + words / 2;
+    void *h = nullptr, *d = nullptr;
+    T2L_HIP(ctx, hipHostMalloc(&h, cap * 4, hipHostMallocDefault));
+    if (hipMalloc(&d, cap * 4) != hipSuccess) {
+      (void)hipHostFree(h);
+      return fail(ctx, T2L_ENOMEM, std::string(who) + "staging buffer");
+    }
+    if (ctx->sample_host) (void)hipHostFree(ctx->sample_host);
+    if (ctx->sample_dev) (void)hipFree(ctx->sample_dev);
+    ctx->sample_host = h;
+    ctx->sample_dev = d;
+    ctx->sample_cap = cap;
+  }
+  if (!ctx->sample_done) T2L_HIP(ctx, hipEventCreateWithFlags(&ctx->sample_done, hipEventDisableTiming));
+  memcpy(ctx->sample_host, ids, (size_t)n_rows * 4);
+  if (salts) memcpy(static_cast<char*>(ctx->sample_host) + (size_t)n_rows * 4, salts, (size_t)n_rows * 4);
+  T2L_HIP(ctx, hipMemcpyAsync(ctx->sample_dev, ctx->sample_host, words * 4, hipMemcpyHostToDevice, s));
+  const int32_t* d_ids = static_cast<const int32_t*>(ctx->sample_dev);
+  const uint32_t* d_salts = salts ? reinterpret_cast<const uint32_t*>(d_ids + n_rows) : nullptr;
+  hipLaunchKernelGGL(sample_points_indexed_kernel, dim3(n_rows), dim3(256), 0, s, xyz, rgb, point_offsets_dev, d_ids, d_salts, seed, flags,
+                     rotate_deg * 0.017453292519943295f, out_pos, out_rgb);
+  T2L_HIP(ctx, hipGetLastError());
+  T2L_HIP(ctx, hipEventRecord(ctx->sample_done, s));
+  ctx->sample_pending = true;
+  return T2L_OK;
 }
 
 int sample_points_impl(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets_dev, int n_objects, uint32_t seed,

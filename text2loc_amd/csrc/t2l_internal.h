@@ -102,6 +102,13 @@ struct t2l_ctx {
   size_t loss_ws_cap = 0;
   void* reduce_ws = nullptr;     // work items + float64 accumulators of t2l_reduce_objects
   size_t reduce_ws_cap = 0;
+  // t2l_sample_object_points_indexed: its host lists (ids | salts) go through a pinned buffer and its device twin, both reused by the
+  // next call once `sample_done` (recorded behind this call's kernel) has passed
+  void* sample_host = nullptr;
+  void* sample_dev = nullptr;
+  size_t sample_cap = 0;         // 4-byte words
+  hipEvent_t sample_done = nullptr;
+  bool sample_pending = false;
   // encoder
   t2l::EncoderWeights* enc = nullptr;
   void* train = nullptr;         // t2l::TrainState (train.hip)
@@ -259,6 +266,10 @@ int pointnet_features_impl(t2l_ctx* ctx, const float* pos, const float* rgb, con
 int sample_points_impl(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets_dev, int n_objects, uint32_t seed,
                        int flags, float rotate_deg,
                        float* out_pos, float* out_rgb, hipStream_t s);
+int sample_points_indexed_impl(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets_dev, int n_objects,
+                               const int32_t* ids, const uint32_t* salts, int n_rows, uint32_t seed, int flags, float rotate_deg,
+                               float* out_pos, float* out_rgb, hipStream_t s);
+void free_sample_stage(t2l_ctx* ctx);
 void free_pointnet(t2l_ctx* ctx);
 // fine.hip
 int fine_load_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const t2l_model_config* cfg);

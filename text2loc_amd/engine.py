@@ -84,6 +84,8 @@ EXPORTS = {
     "t2l_encode_cells": (C.c_int, [C.c_void_p, C.POINTER(_PackedCells), C.c_void_p, C.c_void_p]),
     "t2l_sample_object_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.c_float,
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "t2l_sample_object_points_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                                   C.c_int32, C.c_uint32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "t2l_pointnet_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "t2l_reduce_objects": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -300,6 +302,29 @@ class Engine:
                                                       self._ptr(point_offsets, torch.int64, "point_offsets"), n, int(seed) & 0xFFFFFFFF,
                                                       POINT_TRANSFORMS[transform], float(rotate_deg), pos.data_ptr(), col.data_ptr(),
                                                       _stream_ptr(self.device)))
+        return pos, col
+
+    def sample_object_points_indexed(self, xyz: torch.Tensor, rgb: torch.Tensor, point_offsets: torch.Tensor, object_ids, salts=None,
+                                     seed: int = 0, transform: str = "fixed", rotate_deg: float = 120.0):
+        """``sample_object_points`` for a list of rows of resident arrays (t2l_sample_object_points_indexed): ``object_ids`` i32[n_rows]
+        and ``salts`` u32[n_rows] | None are HOST arrays; row r = object ``object_ids[r]`` drawn under ``seed ^ salts[r]``, equal bit
+        for bit to that row of a whole-set call with that seed. -> (pos f32[n_rows,256,3], rgb f32[n_rows,256,3]). An id outside
+        [0, n_objects) raises before anything is launched; the outputs are then never written."""
+        from .packing import POINT_TRANSFORMS
+
+        if transform not in POINT_TRANSFORMS:
+            raise T2LError(f"sample_object_points_indexed: transform must be one of {sorted(POINT_TRANSFORMS)}, got {transform!r}")
+        ids = np.ascontiguousarray(object_ids, dtype=np.int32).reshape(-1)
+        sl = None if salts is None else np.ascontiguousarray(salts, dtype=np.uint32).reshape(-1)
+        if sl is not None and sl.size != ids.size:
+            raise T2LError(f"sample_object_points_indexed: {ids.size} object ids but {sl.size} salts")
+        n = int(point_offsets.numel()) - 1
+        pos = torch.empty((ids.size, 256, 3), dtype=torch.float32, device=xyz.device)
+        col = torch.empty_like(pos)
+        self._check(self.lib.t2l_sample_object_points_indexed(
+            self._h, self._ptr(xyz, torch.float32, "xyz"), self._ptr(rgb, torch.float32, "rgb"),
+            self._ptr(point_offsets, torch.int64, "point_offsets"), n, ids.ctypes.data, None if sl is None else sl.ctypes.data, int(ids.size),
+            int(seed) & 0xFFFFFFFF, POINT_TRANSFORMS[transform], float(rotate_deg), pos.data_ptr(), col.data_ptr(), _stream_ptr(self.device)))
         return pos, col
 
     def pointnet_features(self, pos: torch.Tensor, rgb: torch.Tensor, cell_offsets) -> torch.Tensor:

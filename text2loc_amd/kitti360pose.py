@@ -21,6 +21,11 @@ else under ``--no_pc_augment``, which every published command passes; NormalizeS
 without the flag (dataloading/kitti360pose/utils.py:91-147, evaluation/pipeline.py:215-223, training/coarse.py:182-193).
 ``object_points="sample"`` builds those batches with ``packing.sample_object_points`` (host, seeded) under ``transform``
 ("fixed" by default = the published configuration); ``None`` skips them (class_embed mode does not read them).
+
+The fine stage's counterpart (dataloading/kitti360pose/poses.py:36-172, 368-590) is ``Kitti360FineDataset``: one item per pose,
+what ``load_pose_and_cell`` returns, for ``fine_training.train_epoch``. Its third point mode, ``object_points="ids"``, leaves the
+points on the GPU: an item names 16 rows of the dataset's ``packing.PackedCellSet`` and ``fine_batches`` samples a whole batch of
+them in one launch (t2l_sample_object_points_indexed) in the process that owns the engine.
 """
 from __future__ import annotations
 
@@ -33,6 +38,7 @@ import numpy as np
 import torch.utils.data
 
 from . import packing
+from .tables import CLASS_TO_INDEX, SCENE_NAMES_TEST, SCENE_NAMES_TRAIN, SCENE_NAMES_VAL
 
 _REF_PACKAGE = "datapreparation.kitti360pose"
 
@@ -318,3 +324,227 @@ class Kitti360PoseDataset:
     @staticmethod
     def collate_fn(data):
         return {key: [d[key] for d in data] for key in data[0].keys()}
+
+
+# ---- the fine stage's dataset ---------------------------------------------------------------------------------------------------------
+# regressor_cell x regressor_learn as load_pose_and_cell distinguishes them (poses.py:55-75); with "all" regressor_learn is not read
+FINE_REGRESSORS = (("pose", "closest"), ("pose", "center"), ("best", "closest"), ("best", "center"), ("all", None))
+
+_MAP_CLONING_REFUSAL = (
+    "pmc_prob > 0 (prototype-based map cloning) is not built: in the reference the branch cannot run as published. Its rematching loop "
+    "collects POSITIONS in cell.objects into new_matching (dataloading/kitti360pose/poses.py:427-433, 469-476), and "
+    "load_pose_and_cell_aug2 then looks them up as keys of a dict keyed by obj.id (poses.py:180-183, 219-220); the "
+    "direction/<scene>.json file the branch opens is written by datapreparation/kitti360pose/add_relation.py:71, whose json.dump call "
+    "has its arguments swapped (the file object where the data belongs), so that script cannot write it. See DESIGN.md section 6.")
+
+
+def _mix32(x):
+    """lowbias32 (the sampler's mixer, include/t2l.h) on uint64 arrays holding 32-bit values."""
+    m = np.uint64(0xFFFFFFFF)
+    x = np.asarray(x, dtype=np.uint64) & m
+    x ^= x >> np.uint64(16)
+    x = (x * np.uint64(0x7FEB352D)) & m
+    x ^= x >> np.uint64(15)
+    x = (x * np.uint64(0x846CA68B)) & m
+    x ^= x >> np.uint64(16)
+    return x
+
+
+def draw_salts(epoch: int, item: int, n_slots: int = 16) -> np.ndarray:
+    """The salt of (epoch, item, slot), u32[n_slots]: ``mix(mix(mix(epoch + 0x9E3779B9) ^ item) ^ slot)`` with mix = lowbias32, all
+    in 32 bits. ``t2l_sample_object_points_indexed`` draws slot s of the item under ``seed ^ salt``: every fetch of an object — in
+    another slot, item or epoch — gets its own 256 indices (the reference redraws per fetch from numpy's global stream), and the
+    same (seed, epoch) always gives the same batch. mix is a bijection, so the salts of one item's slots are pairwise different."""
+    h = _mix32((int(epoch) + 0x9E3779B9) & 0xFFFFFFFF)
+    h = _mix32(h ^ np.uint64(int(item) & 0xFFFFFFFF))
+    return _mix32(h ^ np.arange(n_slots, dtype=np.uint64)).astype(np.uint32)
+
+
+class Kitti360FineDataset:
+    """One item per pose over several scenes: ``Kitti360FineDatasetMulti`` over ``Kitti360FineDataset`` (poses.py:368-590), an item
+    being what ``load_pose_and_cell`` (poses.py:36-172) returns.
+
+    ``args``: ``pad_size``, ``num_mentioned``, ``regressor_cell``, ``regressor_learn`` (``FINE_REGRESSORS``; the published command
+    trains with regressor_cell = "all": the pose inside the cell). ``base_path``: a KITTI360Pose directory, or a dict
+    ``{scene: (cells, poses)}`` of records already in memory (``from_records``).
+    Objects of an item: the matched objects in hint order, then the cell's other objects in cell order, cut to ``pad_size`` or
+    padded with ``cross_matcher.PadObject`` — the project's fixed pad, as in ``run_fine`` (the reference draws a pad's 8 points
+    from numpy's global stream on every fetch).
+    ``object_points``: ``None`` (embedding mode: no points); ``"sample"`` (the item's point batch from
+    ``packing.sample_object_points`` on the host, redrawn per (seed, epoch, item)); ``"ids"`` (no points: ``object_rows``
+    i32[pad_size], the objects' rows in ``packed()`` with ``pad_row`` for pads, and ``draw_salts`` u32[pad_size] — ``fine_batches``
+    samples them on the GPU).
+    ``flip_pose`` is accepted and does nothing: ``load_pose_and_cell`` never reads its ``flip_pose`` / ``horizontal_flip`` /
+    ``vertical_flip`` arguments (poses.py:36-37 is their only mention), and training/fine.py:168 passes False."""
+
+    def __init__(self, base_path, scene_names: Sequence[str], args, object_points: Optional[str] = None, transform: str = "fixed",
+                 seed: int = 0, flip_pose: bool = False, pmc_prob: float = 0.0, pmc_threshold: float = 0.4, count_threshold: int = 1):
+        if object_points not in (None, "sample", "ids"):
+            raise ValueError("object_points must be None, 'sample' or 'ids'")
+        if transform not in packing.POINT_TRANSFORMS:
+            raise ValueError(f"transform must be one of {sorted(packing.POINT_TRANSFORMS)}")
+        if pmc_prob > 0.0:
+            raise NotImplementedError(_MAP_CLONING_REFUSAL)
+        cell, learn = getattr(args, "regressor_cell", None), getattr(args, "regressor_learn", None)
+        if (cell, None if cell == "all" else learn) not in FINE_REGRESSORS:
+            raise ValueError(f"regressor_cell / regressor_learn must be one of {FINE_REGRESSORS}, got {(cell, learn)}")
+        from .cross_matcher import PadObject
+
+        self.args, self.pad_size = args, int(args.pad_size)
+        self.scene_names = list(scene_names)
+        self.flip_pose = bool(flip_pose)
+        self._points, self._transform, self._seed, self._epoch = object_points, transform, int(seed), 0
+        self._pad = PadObject()  # ONE pad object per dataset: its reductions are cached on it like any other object's
+        self.all_cells: List[CellRecord] = []
+        self.all_poses: List[PoseRecord] = []
+        self.hint_descriptions: List[List[str]] = []
+        self._pose_cell_row: List[int] = []
+        for s in self.scene_names:
+            cells, poses = base_path[s] if isinstance(base_path, dict) else load_scene(base_path, s)
+            ids = [c.id for c in cells]
+            if len(set(ids)) != len(ids):
+                raise ValueError(f"{s}: cell ids repeat")  # base.py:45-46
+            row = {c.id: len(self.all_cells) + i for i, c in enumerate(cells)}  # per scene, as the reference's per-scene cells_dict
+            self.all_cells.extend(cells)
+            self.all_poses.extend(poses)
+            self._pose_cell_row.extend(row[p.cell_id] for p in poses)
+            self.hint_descriptions.extend(hint_sentences(p) for p in poses)
+        self._packed = None
+        self._positions: Dict[int, Dict[object, int]] = {}
+
+    @classmethod
+    def from_records(cls, cells: Sequence[CellRecord], poses: Sequence[PoseRecord], args, scene_name: str = "in_memory", **kw):
+        """The same dataset over records that are already in memory (one scene): what ``load_scene`` would have returned."""
+        return cls({scene_name: (list(cells), list(poses))}, [scene_name], args, **kw)
+
+    def __len__(self):
+        return len(self.all_poses)
+
+    @property
+    def point_mode(self) -> Optional[str]:
+        return self._points
+
+    @property
+    def point_transform(self) -> str:
+        return self._transform
+
+    @property
+    def point_seed(self) -> int:
+        return self._seed
+
+    def set_epoch(self, epoch: int):
+        """Part of the key of every point draw ("sample": the host generator; "ids": ``draw_salts``)."""
+        self._epoch = int(epoch)
+
+    def packed(self) -> packing.PackedCellSet:
+        """Every cell of the dataset flattened once; ``object_rows`` index its objects, its ``pad_row`` stands for a pad."""
+        if self._packed is None:
+            self._packed = packing.PackedCellSet(self.all_cells)
+        return self._packed
+
+    def get_known_classes(self) -> List[str]:
+        """poses.py:583-587 over base.py:70-71: the sorted names of the class index ('pad' included)."""
+        return sorted(CLASS_TO_INDEX)
+
+    def _offsets(self, pose, cell):
+        a, ds = self.args, pose.descriptions
+        if a.regressor_cell == "all":  # poses.py:74-75: the pose inside the cell, x and y
+            b = cell.bbox_w
+            return np.array([(pose.pose_w[0] - b[0]) / (b[3] - b[0]), (pose.pose_w[1] - b[1]) / (b[4] - b[1])])
+        kind = "offset_" + a.regressor_learn
+        if a.regressor_cell == "pose":  # poses.py:55-58
+            return np.array([getattr(d, kind) for d in ds])[:, 0:2]
+        return np.array([getattr(d, "best_" + kind if d.is_matched else kind)[0:2] for d in ds])  # "best": poses.py:59-72
+
+    def __getitem__(self, idx):
+        idx = int(idx)
+        pose, cell_row = self.all_poses[idx], self._pose_cell_row[idx]
+        cell, hints, ds = self.all_cells[cell_row], self.hint_descriptions[idx], self.all_poses[idx].descriptions
+        if len(ds) != self.args.num_mentioned:
+            raise ValueError(f"pose {idx} carries {len(ds)} descriptions, args.num_mentioned is {self.args.num_mentioned}")
+        where = self._positions.get(cell_row)
+        if where is None:
+            where = self._positions[cell_row] = {o.id: i for i, o in enumerate(cell.objects)}
+        matched_ids = [d.object_id for d in ds if d.is_matched]
+        # the matched objects in hint order, then the rest in cell order (poses.py:89-105); positions in cell.objects
+        order = [where[i] for i in matched_ids] + [i for i, o in enumerate(cell.objects) if o.id not in matched_ids]
+        if len(order) != len(cell.objects):
+            raise ValueError(f"pose {idx}: two hints are matched to one object of cell {cell.id}")  # the reference asserts here
+        matches = [(k, h) for k, h in enumerate(h for h, d in enumerate(ds) if d.is_matched)]
+        order = order[:self.pad_size]  # poses.py:115-121
+        objects = [cell.objects[i] for i in order] + [self._pad] * (self.pad_size - len(order))
+        n_obj, n_hint = len(objects), len(ds)
+        all_matches = list(matches)
+        all_matches += [(n_obj, h) for h, d in enumerate(ds) if not d.is_matched]  # unmatched hints -> the objects' bin
+        all_matches += [(k, n_hint) for k, o in enumerate(objects) if getattr(o, "id", -1) not in matched_ids]  # and vice versa
+        item = {"poses": pose, "cells": cell, "objects": objects, "object_points": None, "hint_descriptions": hints,
+                "texts": " ".join(hints), "matches": np.array(matches), "all_matches": np.array(all_matches),
+                "offsets": self._offsets(pose, cell),
+                "offsets_best_center": np.array([(d.best_offset_center if d.is_matched else d.offset_center)[0:2] for d in ds]),
+                "object_class_indices": [CLASS_TO_INDEX[o.label] for o in objects],
+                "object_color_indices": [packing.COLOR_NAMES.index(packing.COLOR_NAMES[packing.object_features(o)[1]]) for o in objects]}
+        if self._points == "sample":
+            rng = np.random.default_rng([self._seed, self._epoch, idx])
+            item["object_points"] = packing.sample_object_points([objects], 256, rng, transform=self._transform)[0]
+        elif self._points == "ids":
+            ps = self.packed()
+            base = int(ps.offsets[cell_row])
+            item["object_rows"] = np.array([base + i for i in order] + [ps.pad_row] * (self.pad_size - len(order)), dtype=np.int32)
+            item["draw_salts"] = draw_salts(self._epoch, idx, self.pad_size)
+        return item
+
+    @staticmethod
+    def collate_fn(data):
+        return {key: [d[key] for d in data] for key in data[0].keys()}
+
+
+def fine_datasets_from_args(args, object_points: Optional[str] = "sample", seed: int = 0, scenes=None):
+    """(train, val, test) as training/fine.py:153-187 builds them: the transforms from ``--no_pc_augment``
+    (``packing.fine_train_transforms_from_args``: validation and test never rotate), the three scene lists of the KITTI360Pose split
+    (``scenes``: other (train, val, test) lists), ``flip_pose=False``; ``args.pmc_prob`` goes to the training set alone, which
+    refuses it above 0. ``object_points``: the point mode of all three (None with ``--class_embed``)."""
+    train_t, val_t = packing.fine_train_transforms_from_args(args)
+    tr, va, te = scenes if scenes is not None else (SCENE_NAMES_TRAIN, SCENE_NAMES_VAL, SCENE_NAMES_TEST)
+    return (Kitti360FineDataset(args.base_path, tr, args, object_points, train_t, seed, flip_pose=False,
+                                pmc_prob=float(getattr(args, "pmc_prob", 0.0)), pmc_threshold=float(getattr(args, "pmc_threshold", 0.4))),
+            Kitti360FineDataset(args.base_path, va, args, object_points, val_t, seed),
+            Kitti360FineDataset(args.base_path, te, args, object_points, val_t, seed))
+
+
+def fine_batches(dataset: Kitti360FineDataset, batch_size: int, device, shuffle: bool = False, seed: int = 0, epoch: int = 0,
+                 drop_last: bool = False, engine=None):
+    """One epoch of ``Kitti360FineDataset.collate_fn`` batches for ``fine_training.train_epoch`` / ``eval_epoch``. With an
+    ``object_points="ids"`` dataset the batch's 16 * B point rows are sampled on ``device`` in ONE launch
+    (``PackedCellSet.sample_rows``: slot s of item i under ``dataset.point_seed ^ draw_salts(epoch, i)[s]``) and
+    ``batch["object_points"]`` holds per pose the ``{"pos", "x"}`` views [16 * 256, 3] ``CrossMatch`` accepts; the other two point
+    modes are collated as they are. ``shuffle``: the permutation of ``default_rng([seed, epoch])``. The same (dataset seed, seed,
+    epoch) always gives the same batches.
+    GPU work belongs to the process that owns the engine: a DataLoader worker may build host items, it may not run this generator.
+    ``engine``: the ``Engine`` to sample with (e.g. ``model.engine()``); without one the dataset keeps a weightless one per device."""
+    if torch.utils.data.get_worker_info() is not None:
+        raise RuntimeError("fine_batches samples on the GPU and must run in the process that owns the engine, not in a DataLoader "
+                           "worker: let workers build host items (object_points='sample') or iterate fine_batches in the main process")
+    batch_size = int(batch_size)
+    if batch_size <= 0:
+        raise ValueError("batch_size must be positive")
+    dataset.set_epoch(epoch)
+    order = np.random.default_rng([int(seed), int(epoch)]).permutation(len(dataset)) if shuffle else np.arange(len(dataset))
+    on_gpu = dataset.point_mode == "ids"
+    if on_gpu and engine is None:
+        from .plumbing import engine_for
+
+        dev = torch.device(device)
+        engine, _ = engine_for(getattr(dataset, "_sampler_engine", None), dev, "fine_batches")
+        dataset._sampler_engine = engine
+    for lo in range(0, len(order), batch_size):
+        chunk = order[lo:lo + batch_size]
+        if drop_last and len(chunk) < batch_size:
+            return
+        batch = Kitti360FineDataset.collate_fn([dataset[int(i)] for i in chunk])
+        if on_gpu:
+            pos, col = dataset.packed().sample_rows(engine, device, np.concatenate(batch["object_rows"]), np.concatenate(batch["draw_salts"]),
+                                                    seed=dataset.point_seed, transform=dataset.point_transform)
+            n = dataset.pad_size
+            batch["object_points"] = [{"pos": pos[i * n:(i + 1) * n].reshape(-1, 3), "x": col[i * n:(i + 1) * n].reshape(-1, 3)}
+                                      for i in range(len(chunk))]
+        yield batch

@@ -159,17 +159,53 @@ class PackedCellSet:
             out = self._class[key] = np.fromiter((get(lb, 0) for lb in self.labels), dtype=np.int32, count=len(self.labels))
         return out
 
+    # ---- the pad row: ``cross_matcher.PadObject``'s 8 points stored ONCE behind the last object, as object ``n_objects`` ----------
+    # A fine-stage item is 16 object rows of this set; the slots ``pad_objects`` fills with PadObject point at this row.
+    @property
+    def pad_row(self) -> int:
+        return self.n_objects
+
+    @staticmethod
+    def pad_points():
+        """(xyz f32[8,3], rgb f32[8,3]) of the project's fixed pad object."""
+        from .cross_matcher import PadObject
+
+        return np.asarray(PadObject._xyz, dtype=np.float32), np.asarray(PadObject._rgb, dtype=np.float32)
+
+    def row_points(self, row: int):
+        """(xyz, rgb) f32[n,3] of object ``row`` as the sampler sees them; ``row == pad_row`` is the pad object."""
+        row = int(row)
+        if row == self.pad_row:
+            return self.pad_points()
+        if not 0 <= row < self.n_objects:
+            raise IndexError(f"object row {row} outside [0, {self.n_objects}]")
+        lo, hi = int(self.point_offsets[row]), int(self.point_offsets[row + 1])
+        return self.xyz[lo:hi], self.rgb[lo:hi]
+
     def on_device(self, device) -> Dict[str, "torch.Tensor"]:
-        """The points, offsets (and later the reductions) as tensors on ``device``, copied once."""
+        """The points, offsets (and later the reductions) as tensors on ``device``, copied once. The pad row's 8 points follow the
+        last object's in ``xyz`` / ``rgb``; ``point_offsets`` [n_objects+1] ends before them, ``point_offsets_pad`` [n_objects+2]
+        behind them."""
         import torch
 
         key = str(torch.device(device))
         d = self._dev.get(key)
         if d is None:
-            d = self._dev[key] = {"xyz": torch.from_numpy(self.xyz).to(device), "rgb": torch.from_numpy(self.rgb).to(device),
-                                  "point_offsets": torch.from_numpy(self.point_offsets).to(device),
+            pad_xyz, pad_rgb = self.pad_points()
+            poff_pad = np.append(self.point_offsets, self.point_offsets[-1] + len(pad_xyz)).astype(np.int64)
+            d = self._dev[key] = {"xyz": torch.from_numpy(np.concatenate([self.xyz, pad_xyz])).to(device),
+                                  "rgb": torch.from_numpy(np.concatenate([self.rgb, pad_rgb])).to(device),
+                                  "point_offsets_pad": torch.from_numpy(poff_pad).to(device),
                                   "offsets": torch.from_numpy(self.offsets).to(device)}
+            d["point_offsets"] = d["point_offsets_pad"][:-1]
         return d
+
+    def sample_rows(self, engine, device, rows, salts=None, seed: int = 0, transform: str = "fixed"):
+        """FixedPoints(256) (+ the transform) for a list of object rows of this set, ``pad_row`` included, in ONE launch
+        (t2l_sample_object_points_indexed) from the resident points: -> (pos f32[n_rows,256,3], rgb f32[n_rows,256,3]) on ``device``.
+        Row r is drawn under ``seed ^ salts[r]``; chunking, order and repetition of rows do not change a draw."""
+        d = self.on_device(device)
+        return engine.sample_object_points_indexed(d["xyz"], d["rgb"], d["point_offsets_pad"], rows, salts, seed=seed, transform=transform)
 
     def reduced(self, engine, device, known_colors: Optional[Dict[str, int]] = None) -> Dict[str, "torch.Tensor"]:
         """a1 for every object of the dataset in one launch pair (t2l_reduce_objects): mean rgb, nearest colour row, mean xyz,
@@ -213,6 +249,13 @@ def point_transform_from_args(args, train: bool = False, fine: bool = False) -> 
     if flag:
         return "fixed"
     return "rotate_normalize" if train else "normalize"
+
+
+def fine_train_transforms_from_args(args) -> tuple:
+    """(train, val) transforms of the fine TRAINING script (training/fine.py:153-165). It reads ``--no_pc_augment`` — not the
+    ``--no_pc_augment_fine`` the evaluation pipeline reads for its fine stage (``point_transform_from_args(..., fine=True)``) —
+    and validates / tests under the un-rotated transform."""
+    return point_transform_from_args(args, train=True), point_transform_from_args(args, train=False)
 
 
 def sample_object_points(objects: List[List[object]], num: int = 256, rng: Optional[np.random.Generator] = None,
@@ -278,4 +321,4 @@ def to_device(packed: Dict[str, np.ndarray], device) -> Dict[str, "torch.Tensor"
 
 __all__ = ["KNOWN_CLASS", "COLOR_NAMES", "class_table", "color_table", "object_features", "pack_cells", "PackedCellSet",
            "pack_cells_gpu", "sample_object_points", "sample_object_points_gpu", "to_device", "POINT_TRANSFORMS",
-           "point_transform_from_args"]
+           "point_transform_from_args", "fine_train_transforms_from_args"]

@@ -9,6 +9,16 @@ KNOWN_CLASS = [
     "road", "sidewalk", "smallpole", "stop", "terrain", "traffic light", "traffic sign",
     "trash bin", "tunnel", "vegetation", "vending machine", "wall",
 ]
+# KITTI360Pose's class index (utils.py:71-94): what the fine dataset's items carry as ``object_class_indices``; 'pad' comes last.
+CLASS_TO_INDEX = {name: i for i, name in enumerate([
+    "building", "pole", "traffic light", "traffic sign", "garage", "stop", "smallpole", "lamp", "trash bin", "vending machine",
+    "box", "road", "sidewalk", "parking", "wall", "fence", "guard rail", "bridge", "tunnel", "vegetation", "terrain", "pad",
+])}
+# The split of the nine KITTI-360 drives the training scripts use (utils.py:17-31).
+_DRIVE = "2013_05_28_drive_{}_sync"
+SCENE_NAMES_TRAIN = [_DRIVE.format(n) for n in ("0000", "0002", "0004", "0006", "0007")]
+SCENE_NAMES_VAL = [_DRIVE.format("0010")]
+SCENE_NAMES_TEST = [_DRIVE.format(n) for n in ("0003", "0005", "0009")]
 COLOR_NAMES = ["dark-green", "gray", "gray-green", "bright-gray", "gray", "black", "green", "beige"]
 COLORS = np.array(
     [
