@@ -165,6 +165,40 @@ int t2l_sample_object_points_indexed(t2l_ctx* ctx, const float* xyz, const float
                                      const int32_t* object_ids, const uint32_t* salts, int32_t n_rows, uint32_t seed,
                                      int32_t transform_flags, float rotate_deg, float* out_pos, float* out_rgb, void* stream);
 
+/* The indexed sampler for rows of MIRRORED cells: the point batches of a coarse training batch, flips included.
+ * Replaces: flip_pose_in_cell (dataloading/kitti360pose/utils.py:15-88: a deep copy of the cell whose object points are mirrored about
+ * x = 0.5 and / or y = 0.5) followed by batch_object_points over the copy, as Kitti360CoarseDataset.__getitem__ runs them per item
+ * (dataloading/kitti360pose/cells.py:80-107) — the flip first, then FixedPoints and the transform.
+ * Every argument of t2l_sample_object_points_indexed, plus mirror: HOST u8[n_rows] or NULL (= every code 0). Bit 0 of mirror[r]: the
+ * gathered point's x becomes 1.0f - x; bit 1: its y becomes 1.0f - y. Each is ONE float32 subtraction, rounded on its own like the
+ * other defined operations above, applied to the gathered point BEFORE RandomRotate and NormalizeScale. The key of a row does not
+ * contain its code: a mirrored row draws the indices and the angle of the un-mirrored one, out_rgb does not depend on the code, and a
+ * row with code 0 equals that row of t2l_sample_object_points_indexed bit for bit (one per-object body serves all three kernels). A row
+ * with code m equals the numpy restatement run over the arrays with that object's x / y replaced by float32(1) - x / y.
+ * Errors: those of the indexed sampler, and a mirror code above 3 — T2L_EINVAL naming the row, before anything is launched; no output
+ * byte is written. n_rows == 0 is T2L_OK and touches nothing. ids | salts | mirror go through the same pinned buffer and event; the
+ * stream is NOT synchronised. */
+int t2l_sample_object_points_mirrored(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets, int32_t n_objects,
+                                      const int32_t* object_ids, const uint32_t* salts, const uint8_t* mirror, int32_t n_rows, uint32_t seed,
+                                      int32_t transform_flags, float rotate_deg, float* out_pos, float* out_rgb, void* stream);
+
+/* The packed per-object features (t2l_packed_cells' five per-object arrays) of a LIST OF ROWS of resident tables, flips included.
+ * Replaces: per training batch, the host walk over the batch's objects (models/object_encoder.py:74-84,121-145) or a second
+ * t2l_reduce_objects pass over their re-uploaded raw points, when the reductions of the whole dataset already sit on the device
+ * (t2l_reduce_objects over every object once, class indices beside them).
+ * class_idx, color_idx: dev i32[n_objects]; rgb, center: dev f32[n_objects,3]; n_pts: dev f32[n_objects]; object_ids: HOST i32[n_rows],
+ * each in [0, n_objects); mirror: HOST u8[n_rows] or NULL (= every code 0). Outputs: the same five arrays with n_rows rows, on the device.
+ * Row r copies row object_ids[r] bit for bit, except that center.x becomes 1.0f - center.x under bit 0 of mirror[r] and center.y
+ * 1.0f - center.y under bit 1 (one float32 subtraction each): the centre of the object in the mirrored cell to within one rounding of
+ * the mean of its mirrored points. Mean colour, colour row, class and point count do not change under a flip.
+ * Errors: an id outside [0, n_objects), a mirror code above 3 (both name the row), a negative count or a null array (mirror excepted) is
+ * T2L_EINVAL before anything is launched, and no output byte is written; n_rows == 0 is T2L_OK and touches nothing. ids | mirror go
+ * through the sampler's pinned buffer and event; the stream is NOT synchronised. One thread per output element. */
+int t2l_gather_object_rows(t2l_ctx* ctx, const int32_t* class_idx, const int32_t* color_idx, const float* rgb, const float* center,
+                           const float* n_pts, int32_t n_objects, const int32_t* object_ids, const uint8_t* mirror, int32_t n_rows,
+                           int32_t* out_class_idx, int32_t* out_color_idx, float* out_rgb, float* out_center, float* out_n_pts,
+                           void* stream);
+
 /* ---- PointNet++ object backbone (a3), eval mode ------------------------------------------------ */
 /* Replaces: PointNet2.forward(...).features2 (models/pointcloud/pointnet2.py:66-100) as ObjectEncoder.forward calls it
  * once per cell (models/object_encoder.py:92-95): three SetAbstraction layers (FPS 1/2, ball query r = .2/.3/.4 with at most

@@ -183,6 +183,25 @@ int t2l_sample_object_points_indexed(t2l_ctx* ctx, const float* xyz, const float
                                     out_pos, out_rgb, (hipStream_t)stream);
 }
 
+int t2l_sample_object_points_mirrored(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets, int32_t n_objects,
+                                      const int32_t* object_ids, const uint32_t* salts, const uint8_t* mirror, int32_t n_rows, uint32_t seed,
+                                      int32_t transform_flags, float rotate_deg, float* out_pos, float* out_rgb, void* stream) {
+  if (!ctx) return T2L_EINVAL;
+  T2L_HIP(ctx, hipSetDevice(ctx->device));
+  return sample_points_mirrored_impl(ctx, xyz, rgb, point_offsets, n_objects, object_ids, salts, mirror, n_rows, seed, transform_flags,
+                                     rotate_deg, out_pos, out_rgb, (hipStream_t)stream);
+}
+
+int t2l_gather_object_rows(t2l_ctx* ctx, const int32_t* class_idx, const int32_t* color_idx, const float* rgb, const float* center,
+                           const float* n_pts, int32_t n_objects, const int32_t* object_ids, const uint8_t* mirror, int32_t n_rows,
+                           int32_t* out_class_idx, int32_t* out_color_idx, float* out_rgb, float* out_center, float* out_n_pts,
+                           void* stream) {
+  if (!ctx) return T2L_EINVAL;
+  T2L_HIP(ctx, hipSetDevice(ctx->device));
+  return gather_rows_impl(ctx, class_idx, color_idx, rgb, center, n_pts, n_objects, object_ids, mirror, n_rows, out_class_idx,
+                          out_color_idx, out_rgb, out_center, out_n_pts, (hipStream_t)stream);
+}
+
 int t2l_pointnet_features(t2l_ctx* ctx, const float* pos, const float* rgb, const int32_t* cell_offsets, int32_t n_cells,
                           float* out_features2, void* stream) {
   if (!ctx) return T2L_EINVAL;

@@ -1195,9 +1195,12 @@ struct SampleRed {  // LDS of one sampler workgroup: per wave the float64 sums o
 // `okey`, written to row `row` of the outputs. The whole-set kernel calls it with row = o and okey = seed ^ o * 0x85EBCA77; the indexed
 // kernel with o = object_ids[row] and okey = (seed ^ salts[row]) ^ o * 0x85EBCA77 — the same instructions in the same reduction order,
 // which is what makes a row of the one equal the row of the other bit for bit under every transform.
+// `mirror` (the mirrored kernel alone; the other two pass the literal 0 and compile to what they were): bit 0 replaces the gathered x by
+// 1.0f - x, bit 1 the gathered y by 1.0f - y — a cell flipped about x = 0.5 / y = 0.5 — one float32 subtraction each, BEFORE RandomRotate
+// and NormalizeScale, and no part of `okey`: the mirrored row draws the indices and the angle of the un-mirrored one.
 __device__ __forceinline__ void sample_object_row(const float* __restrict__ xyz, const float* __restrict__ rgb,
                                                   const int64_t* __restrict__ offsets, int o, uint32_t okey, size_t row, int flags,
-                                                  float rotate_rad, float* __restrict__ out_pos, float* __restrict__ out_rgb,
+                                                  int mirror, float rotate_rad, float* __restrict__ out_pos, float* __restrict__ out_rgb,
                                                   SampleRed* red) {
 #pragma clang fp contract(off)
   const int j = threadIdx.x, lane = j & 63, w = j >> 6;
@@ -1215,6 +1218,8 @@ __device__ __forceinline__ void sample_object_row(const float* __restrict__ xyz,
   float px = src[0], py = src[1], pz = src[2];
   const float* col = rgb + (size_t)(p0 + idx) * 3;
   out_rgb[ob] = col[0]; out_rgb[ob + 1] = col[1]; out_rgb[ob + 2] = col[2];
+  if (mirror & 1) px = sub_rn(1.0f, px);
+  if (mirror & 2) py = sub_rn(1.0f, py);
   if (flags & T2L_SAMPLE_ROTATE) {  // pos @ [[c, s, 0], [-s, c, 0], [0, 0, 1]]
     const float u = mul_rn((float)(lowbias32(0xA5A5A5A5u + okey) >> 8), 1.f / 16777216.f);
     const float ang = mul_rn(rotate_rad, sub_rn(mul_rn(2.f, u), 1.f));
@@ -1253,7 +1258,7 @@ __global__ __launch_bounds__(256) void sample_points_kernel(const float* __restr
                                                             float rotate_rad, float* __restrict__ out_pos, float* __restrict__ out_rgb) {
   __shared__ SampleRed red;
   const int o = blockIdx.x;
-  sample_object_row(xyz, rgb, offsets, o, seed ^ ((uint32_t)o * 0x85EBCA77u), (size_t)o, flags, rotate_rad, out_pos, out_rgb, &red);
+  sample_object_row(xyz, rgb, offsets, o, seed ^ ((uint32_t)o * 0x85EBCA77u), (size_t)o, flags, 0, rotate_rad, out_pos, out_rgb, &red);
 }
 
 // Row r of the outputs = object ids[r] (range-checked on the host before the launch) under seed ^ salts[r]. The grid is the row list:
@@ -1266,7 +1271,20 @@ __global__ __launch_bounds__(256) void sample_points_indexed_kernel(const float*
   __shared__ SampleRed red;
   const int r = blockIdx.x, o = ids[r];
   const uint32_t row_seed = salts ? seed ^ salts[r] : seed;
-  sample_object_row(xyz, rgb, offsets, o, row_seed ^ ((uint32_t)o * 0x85EBCA77u), (size_t)r, flags, rotate_rad, out_pos, out_rgb, &red);
+  sample_object_row(xyz, rgb, offsets, o, row_seed ^ ((uint32_t)o * 0x85EBCA77u), (size_t)r, flags, 0, rotate_rad, out_pos, out_rgb, &red);
+}
+
+// The indexed kernel with a mirror code per row (0..3, checked on the host; NULL = every code 0): the rows of a flipped cell.
+__global__ __launch_bounds__(256) void sample_points_mirrored_kernel(const float* __restrict__ xyz, const float* __restrict__ rgb,
+                                                                     const int64_t* __restrict__ offsets, const int32_t* __restrict__ ids,
+                                                                     const uint32_t* __restrict__ salts, const uint8_t* __restrict__ mirror,
+                                                                     uint32_t seed, int flags, float rotate_rad,
+                                                                     float* __restrict__ out_pos, float* __restrict__ out_rgb) {
+  __shared__ SampleRed red;
+  const int r = blockIdx.x, o = ids[r];
+  const uint32_t row_seed = salts ? seed ^ salts[r] : seed;
+  const int m = mirror ? (int)mirror[r] : 0;
+  sample_object_row(xyz, rgb, offsets, o, row_seed ^ ((uint32_t)o * 0x85EBCA77u), (size_t)r, flags, m, rotate_rad, out_pos, out_rgb, &red);
 }
 
 void free_sample_stage(t2l_ctx* ctx) {
@@ -1279,22 +1297,26 @@ void free_sample_stage(t2l_ctx* ctx) {
   ctx->sample_pending = false;
 }
 
-int sample_points_indexed_impl(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets_dev, int n_objects,
-                               const int32_t* ids, const uint32_t* salts, int n_rows, uint32_t seed, int flags, float rotate_deg,
-                               float* out_pos, float* out_rgb, hipStream_t s) {
-  const char* who = "t2l_sample_object_points_indexed: ";
-  if (n_rows < 0 || n_objects < 0) return fail(ctx, T2L_EINVAL, std::string(who) + "negative count");
-  if (n_rows == 0) return T2L_OK;
-  if (!xyz || !rgb || !point_offsets_dev || !ids || !out_pos || !out_rgb) return fail(ctx, T2L_EINVAL, std::string(who) + "null argument");
-  if (flags & ~(T2L_SAMPLE_NORMALIZE | T2L_SAMPLE_ROTATE)) return fail(ctx, T2L_EINVAL, std::string(who) + "unknown transform flag");
+// What the row-indexed entry points refuse before anything is launched: an id outside [0, n_objects), a mirror code above 3.
+int check_rows(t2l_ctx* ctx, const char* who, const int32_t* ids, const uint8_t* mirror, int n_rows, int n_objects) {
   for (int r = 0; r < n_rows; ++r)
     if (ids[r] < 0 || ids[r] >= n_objects)
       return fail(ctx, T2L_EINVAL, std::string(who) + "object_ids[" + std::to_string(r) + "] = " + std::to_string(ids[r]) + " is outside [0, " +
                                        std::to_string(n_objects) + ")");
-  // ids | salts staged through the context's pinned buffer and its device twin. Both are reused by the next call, so that call first
-  // waits (on the host, on an event) for THIS call's kernel — the only wait there is, and over before it starts unless calls are
-  // issued back to back faster than a sampler launch runs. The caller's stream is never synchronised.
-  const size_t words = (size_t)n_rows * (salts ? 2 : 1);
+  for (int r = 0; mirror && r < n_rows; ++r)
+    if (mirror[r] > 3)
+      return fail(ctx, T2L_EINVAL, std::string(who) + "mirror[" + std::to_string(r) + "] = " + std::to_string((int)mirror[r]) +
+                                       " is above 3 (bit 0: x, bit 1: y)");
+  return T2L_OK;
+}
+
+// ids | salts | mirror (bytes, padded to a word) staged through the context's pinned buffer and its device twin. Both are reused by the
+// next call, so that call first waits (on the host, on an event) for THIS call's kernel — the only wait there is, and over before it
+// starts unless calls are issued back to back faster than a launch runs. The caller's stream is never synchronised. The caller launches
+// its kernel on `s` behind this and then calls stage_rows_done.
+int stage_rows(t2l_ctx* ctx, const char* who, const int32_t* ids, const uint32_t* salts, const uint8_t* mirror, int n_rows, hipStream_t s,
+               const int32_t** d_ids, const uint32_t** d_salts, const uint8_t** d_mirror) {
+  const size_t n = (size_t)n_rows, words = n * (salts ? 2 : 1) + (mirror ? (n + 3) / 4 : 0);
   if (ctx->sample_pending) {
     T2L_HIP(ctx, hipEventSynchronize(ctx->sample_done));
     ctx->sample_pending = false;
@@ -1314,17 +1336,65 @@ int sample_points_indexed_impl(t2l_ctx* ctx, const float* xyz, const float* rgb,
     ctx->sample_cap = cap;
   }
   if (!ctx->sample_done) T2L_HIP(ctx, hipEventCreateWithFlags(&ctx->sample_done, hipEventDisableTiming));
-  memcpy(ctx->sample_host, ids, (size_t)n_rows * 4);
-  if (salts) memcpy(static_cast<char*>(ctx->sample_host) + (size_t)n_rows * 4, salts, (size_t)n_rows * 4);
+  char* h = static_cast<char*>(ctx->sample_host);
+  const size_t mirror_at = n * (salts ? 8 : 4);
+  memcpy(h, ids, n * 4);
+  if (salts) memcpy(h + n * 4, salts, n * 4);
+  if (mirror) {
+    memset(h + mirror_at, 0, (n + 3) / 4 * 4);
+    memcpy(h + mirror_at, mirror, n);
+  }
   T2L_HIP(ctx, hipMemcpyAsync(ctx->sample_dev, ctx->sample_host, words * 4, hipMemcpyHostToDevice, s));
-  const int32_t* d_ids = static_cast<const int32_t*>(ctx->sample_dev);
-  const uint32_t* d_salts = salts ? reinterpret_cast<const uint32_t*>(d_ids + n_rows) : nullptr;
-  hipLaunchKernelGGL(sample_points_indexed_kernel, dim3(n_rows), dim3(256), 0, s, xyz, rgb, point_offsets_dev, d_ids, d_salts, seed, flags,
-                     rotate_deg * 0.017453292519943295f, out_pos, out_rgb);
+  const char* d = static_cast<const char*>(ctx->sample_dev);
+  *d_ids = reinterpret_cast<const int32_t*>(d);
+  *d_salts = salts ? reinterpret_cast<const uint32_t*>(d + n * 4) : nullptr;
+  *d_mirror = mirror ? reinterpret_cast<const uint8_t*>(d + mirror_at) : nullptr;
+  return T2L_OK;
+}
+
+int stage_rows_done(t2l_ctx* ctx, hipStream_t s) {
   T2L_HIP(ctx, hipGetLastError());
   T2L_HIP(ctx, hipEventRecord(ctx->sample_done, s));
   ctx->sample_pending = true;
   return T2L_OK;
+}
+
+// t2l_sample_object_points_indexed (use_mirror = false: `mirror` is not looked at) and t2l_sample_object_points_mirrored
+static int sample_points_rows_impl(t2l_ctx* ctx, const char* who, const float* xyz, const float* rgb, const int64_t* point_offsets_dev,
+                                   int n_objects, const int32_t* ids, const uint32_t* salts, const uint8_t* mirror, bool use_mirror,
+                                   int n_rows, uint32_t seed, int flags, float rotate_deg, float* out_pos, float* out_rgb, hipStream_t s) {
+  if (n_rows < 0 || n_objects < 0) return fail(ctx, T2L_EINVAL, std::string(who) + "negative count");
+  if (n_rows == 0) return T2L_OK;
+  if (!xyz || !rgb || !point_offsets_dev || !ids || !out_pos || !out_rgb) return fail(ctx, T2L_EINVAL, std::string(who) + "null argument");
+  if (flags & ~(T2L_SAMPLE_NORMALIZE | T2L_SAMPLE_ROTATE)) return fail(ctx, T2L_EINVAL, std::string(who) + "unknown transform flag");
+  if (!use_mirror) mirror = nullptr;
+  if (int rc = check_rows(ctx, who, ids, mirror, n_rows, n_objects)) return rc;
+  const int32_t* d_ids;
+  const uint32_t* d_salts;
+  const uint8_t* d_mirror;
+  if (int rc = stage_rows(ctx, who, ids, salts, mirror, n_rows, s, &d_ids, &d_salts, &d_mirror)) return rc;
+  const float rad = rotate_deg * 0.017453292519943295f;
+  if (use_mirror)
+    hipLaunchKernelGGL(sample_points_mirrored_kernel, dim3(n_rows), dim3(256), 0, s, xyz, rgb, point_offsets_dev, d_ids, d_salts, d_mirror,
+                       seed, flags, rad, out_pos, out_rgb);
+  else
+    hipLaunchKernelGGL(sample_points_indexed_kernel, dim3(n_rows), dim3(256), 0, s, xyz, rgb, point_offsets_dev, d_ids, d_salts, seed, flags,
+                       rad, out_pos, out_rgb);
+  return stage_rows_done(ctx, s);
+}
+
+int sample_points_indexed_impl(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets_dev, int n_objects,
+                               const int32_t* ids, const uint32_t* salts, int n_rows, uint32_t seed, int flags, float rotate_deg,
+                               float* out_pos, float* out_rgb, hipStream_t s) {
+  return sample_points_rows_impl(ctx, "t2l_sample_object_points_indexed: ", xyz, rgb, point_offsets_dev, n_objects, ids, salts, nullptr, false,
+                                 n_rows, seed, flags, rotate_deg, out_pos, out_rgb, s);
+}
+
+int sample_points_mirrored_impl(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets_dev, int n_objects,
+                                const int32_t* ids, const uint32_t* salts, const uint8_t* mirror, int n_rows, uint32_t seed, int flags,
+                                float rotate_deg, float* out_pos, float* out_rgb, hipStream_t s) {
+  return sample_points_rows_impl(ctx, "t2l_sample_object_points_mirrored: ", xyz, rgb, point_offsets_dev, n_objects, ids, salts, mirror, true,
+                                 n_rows, seed, flags, rotate_deg, out_pos, out_rgb, s);
 }
 
 int sample_points_impl(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets_dev, int n_objects, uint32_t seed,

@@ -8,6 +8,8 @@
 // float64 (the reference's float32/float64 numpy sums differ from this by ~1e-6 relative; parity tolerance in the test),
 // reduces across the wave on DPP and writes the packed per-object features the encoder consumes.
 #include <algorithm>
+#include <climits>
+#include <string>
 #include <vector>
 
 #include "search_dev.h"
@@ -158,6 +160,59 @@ int reduce_impl(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t*
   event_end(ctx, "reduce_objects", s);
   T2L_HIP(ctx, hipGetLastError());
   return T2L_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The packed per-object features of a LIST OF ROWS of resident tables (t2l_gather_object_rows): what the kernels above wrote once for a
+// whole dataset, gathered per training batch instead of reduced again. One thread per output element (9 per row: class, colour, rgb,
+// centre, count); row r copies row ids[r] (range-checked on the host). A row of a mirrored cell differs in its centre alone: x -> 1.0f - x
+// under bit 0 of mirror[r], y -> 1.0f - y under bit 1, one float32 subtraction each (a constant minus a value: nothing to contract).
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void gather_rows_kernel(const int32_t* __restrict__ class_idx, const int32_t* __restrict__ color_idx,
+                                                          const float* __restrict__ rgb, const float* __restrict__ center,
+                                                          const float* __restrict__ n_pts, const int32_t* __restrict__ ids,
+                                                          const uint8_t* __restrict__ mirror, int n_rows,
+                                                          int32_t* __restrict__ out_class_idx, int32_t* __restrict__ out_color_idx,
+                                                          float* __restrict__ out_rgb, float* __restrict__ out_center,
+                                                          float* __restrict__ out_n_pts) {
+  const int t = blockIdx.x * 256 + threadIdx.x;  // n_rows * 9 < 2^31: checked by the host
+  if (t >= n_rows * 9) return;
+  const int r = t / 9, e = t % 9;
+  const size_t g = (size_t)ids[r];
+  if (e == 0) {
+    out_class_idx[r] = class_idx[g];
+  } else if (e == 1) {
+    out_color_idx[r] = color_idx[g];
+  } else if (e < 5) {
+    out_rgb[(size_t)r * 3 + (e - 2)] = rgb[g * 3 + (e - 2)];
+  } else if (e < 8) {
+    const int a = e - 5;
+    float c = center[g * 3 + a];
+    if (mirror && a < 2 && ((mirror[r] >> a) & 1)) c = 1.0f - c;
+    out_center[(size_t)r * 3 + a] = c;
+  } else {
+    out_n_pts[r] = n_pts[g];
+  }
+}
+
+int gather_rows_impl(t2l_ctx* ctx, const int32_t* class_idx, const int32_t* color_idx, const float* rgb, const float* center,
+                     const float* n_pts, int n_objects, const int32_t* ids, const uint8_t* mirror, int n_rows, int32_t* out_class_idx,
+                     int32_t* out_color_idx, float* out_rgb, float* out_center, float* out_n_pts, hipStream_t s) {
+  const char* who = "t2l_gather_object_rows: ";
+  if (n_rows < 0 || n_objects < 0) return fail(ctx, T2L_EINVAL, std::string(who) + "negative count");
+  if (n_rows == 0) return T2L_OK;
+  if (!class_idx || !color_idx || !rgb || !center || !n_pts || !ids || !out_class_idx || !out_color_idx || !out_rgb || !out_center ||
+      !out_n_pts)
+    return fail(ctx, T2L_EINVAL, std::string(who) + "null argument");
+  if (n_rows > INT32_MAX / 9) return fail(ctx, T2L_EINVAL, std::string(who) + "more than 2^31 / 9 rows in one call");
+  if (int rc = check_rows(ctx, who, ids, mirror, n_rows, n_objects)) return rc;
+  const int32_t* d_ids;
+  const uint32_t* d_salts;
+  const uint8_t* d_mirror;
+  if (int rc = stage_rows(ctx, who, ids, nullptr, mirror, n_rows, s, &d_ids, &d_salts, &d_mirror)) return rc;
+  hipLaunchKernelGGL(gather_rows_kernel, dim3((n_rows * 9 + 255) / 256), dim3(256), 0, s, class_idx, color_idx, rgb, center, n_pts, d_ids,
+                     d_mirror, n_rows, out_class_idx, out_color_idx, out_rgb, out_center, out_n_pts);
+  return stage_rows_done(ctx, s);
 }
 
 }  // namespace t2l

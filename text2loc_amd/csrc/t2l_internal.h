@@ -77,6 +77,9 @@ int merge_gathered_impl(t2l_ctx* ctx, const void* blocks, int64_t block_bytes, i
 int reduce_impl(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* offsets, int n_objects,
                 const float* centers, const int32_t* rows, int n_colors, float* out_rgb, float* out_center,
                 float* out_npts, int32_t* out_color, hipStream_t s);
+int gather_rows_impl(t2l_ctx* ctx, const int32_t* class_idx, const int32_t* color_idx, const float* rgb, const float* center,
+                     const float* n_pts, int n_objects, const int32_t* ids, const uint8_t* mirror, int n_rows, int32_t* out_class_idx,
+                     int32_t* out_color_idx, float* out_rgb, float* out_center, float* out_n_pts, hipStream_t s);
 // encode.hip
 
 }  // namespace t2l
@@ -102,7 +105,7 @@ struct t2l_ctx {
   size_t loss_ws_cap = 0;
   void* reduce_ws = nullptr;     // work items + float64 accumulators of t2l_reduce_objects
   size_t reduce_ws_cap = 0;
-  // t2l_sample_object_points_indexed: its host lists (ids | salts) go through a pinned buffer and its device twin, both reused by the
+  // t2l_sample_object_points_indexed / _mirrored, t2l_gather_object_rows: their host lists (ids | salts | mirror) go through a pinned buffer and its device twin, both reused by the
   // next call once `sample_done` (recorded behind this call's kernel) has passed
   void* sample_host = nullptr;
   void* sample_dev = nullptr;
@@ -269,6 +272,14 @@ int sample_points_impl(t2l_ctx* ctx, const float* xyz, const float* rgb, const i
 int sample_points_indexed_impl(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets_dev, int n_objects,
                                const int32_t* ids, const uint32_t* salts, int n_rows, uint32_t seed, int flags, float rotate_deg,
                                float* out_pos, float* out_rgb, hipStream_t s);
+int sample_points_mirrored_impl(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets_dev, int n_objects,
+                                const int32_t* ids, const uint32_t* salts, const uint8_t* mirror, int n_rows, uint32_t seed, int flags,
+                                float rotate_deg, float* out_pos, float* out_rgb, hipStream_t s);
+// the row lists of the row-indexed entry points: checked, then staged through the context's pinned buffer (ids | salts | mirror)
+int check_rows(t2l_ctx* ctx, const char* who, const int32_t* ids, const uint8_t* mirror, int n_rows, int n_objects);
+int stage_rows(t2l_ctx* ctx, const char* who, const int32_t* ids, const uint32_t* salts, const uint8_t* mirror, int n_rows, hipStream_t s,
+               const int32_t** d_ids, const uint32_t** d_salts, const uint8_t** d_mirror);
+int stage_rows_done(t2l_ctx* ctx, hipStream_t s);
 void free_sample_stage(t2l_ctx* ctx);
 void free_pointnet(t2l_ctx* ctx);
 // fine.hip

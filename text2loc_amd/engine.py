@@ -86,6 +86,11 @@ EXPORTS = {
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "t2l_sample_object_points_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                                    C.c_int32, C.c_uint32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "t2l_sample_object_points_mirrored": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p]),
+    "t2l_gather_object_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                         C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "t2l_pointnet_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "t2l_reduce_objects": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -326,6 +331,59 @@ class Engine:
             self._ptr(point_offsets, torch.int64, "point_offsets"), n, ids.ctypes.data, None if sl is None else sl.ctypes.data, int(ids.size),
             int(seed) & 0xFFFFFFFF, POINT_TRANSFORMS[transform], float(rotate_deg), pos.data_ptr(), col.data_ptr(), _stream_ptr(self.device)))
         return pos, col
+
+    def sample_object_points_mirrored(self, xyz: torch.Tensor, rgb: torch.Tensor, point_offsets: torch.Tensor, object_ids, salts=None,
+                                      mirror=None, seed: int = 0, transform: str = "fixed", rotate_deg: float = 120.0):
+        """``sample_object_points_indexed`` for rows of mirrored cells (t2l_sample_object_points_mirrored): ``mirror`` u8[n_rows] | None
+        is a HOST array of codes 0..3 — bit 0: the gathered x becomes ``1 - x``, bit 1: the gathered y becomes ``1 - y``, one float32
+        subtraction each, before the transform. The code is not part of a row's key: the same indices, the same angle, the same colours
+        as the un-mirrored row. An id out of range or a code above 3 raises before anything is launched."""
+        from .packing import POINT_TRANSFORMS
+
+        if transform not in POINT_TRANSFORMS:
+            raise T2LError(f"sample_object_points_mirrored: transform must be one of {sorted(POINT_TRANSFORMS)}, got {transform!r}")
+        ids = np.ascontiguousarray(object_ids, dtype=np.int32).reshape(-1)
+        sl = None if salts is None else np.ascontiguousarray(salts, dtype=np.uint32).reshape(-1)
+        mi = None if mirror is None else np.ascontiguousarray(mirror, dtype=np.uint8).reshape(-1)
+        if sl is not None and sl.size != ids.size:
+            raise T2LError(f"sample_object_points_mirrored: {ids.size} object ids but {sl.size} salts")
+        if mi is not None and mi.size != ids.size:
+            raise T2LError(f"sample_object_points_mirrored: {ids.size} object ids but {mi.size} mirror codes")
+        n = int(point_offsets.numel()) - 1
+        pos = torch.empty((ids.size, 256, 3), dtype=torch.float32, device=xyz.device)
+        col = torch.empty_like(pos)
+        self._check(self.lib.t2l_sample_object_points_mirrored(
+            self._h, self._ptr(xyz, torch.float32, "xyz"), self._ptr(rgb, torch.float32, "rgb"),
+            self._ptr(point_offsets, torch.int64, "point_offsets"), n, ids.ctypes.data, None if sl is None else sl.ctypes.data,
+            None if mi is None else mi.ctypes.data, int(ids.size), int(seed) & 0xFFFFFFFF, POINT_TRANSFORMS[transform], float(rotate_deg),
+            pos.data_ptr(), col.data_ptr(), _stream_ptr(self.device)))
+        return pos, col
+
+    def gather_object_rows(self, table: Dict[str, torch.Tensor], object_ids, mirror=None) -> Dict[str, torch.Tensor]:
+        """Rows of resident per-object tables (t2l_gather_object_rows). ``table``: class_idx / color_idx i32[n], rgb / center f32[n,3],
+        n_pts f32[n] on the GPU; ``object_ids`` i32[n_rows] and ``mirror`` u8[n_rows] | None are HOST arrays. -> the same five arrays with
+        n_rows rows: row r is row ``object_ids[r]``, its centre's x / y replaced by ``1 - c`` under bit 0 / 1 of ``mirror[r]``. An id out
+        of range or a code above 3 raises before anything is launched; the outputs are then never written."""
+        ids = np.ascontiguousarray(object_ids, dtype=np.int32).reshape(-1)
+        mi = None if mirror is None else np.ascontiguousarray(mirror, dtype=np.uint8).reshape(-1)
+        if mi is not None and mi.size != ids.size:
+            raise T2LError(f"gather_object_rows: {ids.size} object ids but {mi.size} mirror codes")
+        n, rows, dev = int(table["n_pts"].numel()), int(ids.size), table["n_pts"].device
+        for k, w in (("class_idx", 1), ("color_idx", 1), ("rgb", 3), ("center", 3)):
+            if int(table[k].numel()) != n * w:
+                raise T2LError(f"gather_object_rows: {k} holds {int(table[k].numel())} values, n_pts says {n} objects")
+        out = {"class_idx": torch.empty((rows,), dtype=torch.int32, device=dev),
+               "color_idx": torch.empty((rows,), dtype=torch.int32, device=dev),
+               "rgb": torch.empty((rows, 3), dtype=torch.float32, device=dev),
+               "center": torch.empty((rows, 3), dtype=torch.float32, device=dev),
+               "n_pts": torch.empty((rows,), dtype=torch.float32, device=dev)}
+        self._check(self.lib.t2l_gather_object_rows(
+            self._h, self._ptr(table["class_idx"], torch.int32, "class_idx"), self._ptr(table["color_idx"], torch.int32, "color_idx"),
+            self._ptr(table["rgb"], torch.float32, "rgb"), self._ptr(table["center"], torch.float32, "center"),
+            self._ptr(table["n_pts"], torch.float32, "n_pts"), n, ids.ctypes.data, None if mi is None else mi.ctypes.data, rows,
+            out["class_idx"].data_ptr(), out["color_idx"].data_ptr(), out["rgb"].data_ptr(), out["center"].data_ptr(),
+            out["n_pts"].data_ptr(), _stream_ptr(self.device)))
+        return out
 
     def pointnet_features(self, pos: torch.Tensor, rgb: torch.Tensor, cell_offsets) -> torch.Tensor:
         """pos, rgb f32[n_objects,256,3] on the GPU, cell_offsets i32[n_cells+1] (HOST) -> features2 f32[n_objects,256]."""

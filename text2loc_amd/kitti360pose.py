@@ -26,6 +26,8 @@ The fine stage's counterpart (dataloading/kitti360pose/poses.py:36-172, 368-590)
 what ``load_pose_and_cell`` returns, for ``fine_training.train_epoch``. Its third point mode, ``object_points="ids"``, leaves the
 points on the GPU: an item names 16 rows of the dataset's ``packing.PackedCellSet`` and ``fine_batches`` samples a whole batch of
 them in one launch (t2l_sample_object_points_indexed) in the process that owns the engine.
+``Kitti360PoseDataset(object_points="ids")`` with ``coarse_batches`` is the coarse stage's form of it: an item names its cell's rows
+and a flip code instead of carrying a mirrored copy of the cell (t2l_sample_object_points_mirrored, t2l_gather_object_rows).
 """
 from __future__ import annotations
 
@@ -237,16 +239,23 @@ class Kitti360PoseDataset:
     vertically (``flip_pose_in_cell``). Their draws come from ``aug_rng`` — a ``numpy.random.RandomState`` consumed with the
     reference's own call sequence (one ``choice`` without replacement over the hints, then two ``choice((True, False))``), so
     ``RandomState(s)`` here reproduces the reference under ``np.random.seed(s)`` item for item; ``None`` = numpy's global
-    stream, i.e. exactly what the reference draws from."""
+    stream, i.e. exactly what the reference draws from.
+    ``object_points="ids"``: the same draws, texts and (copied, flipped) poses, but the cell is NOT copied and no point is touched.
+    ``item["cells"]`` / ``item["objects"]`` are the resident, UN-MIRRORED record and its objects; the flips are the item's ``mirror``
+    code (bit 0: horizontal, x -> 1 - x; bit 1: vertical, y -> 1 - y), ``cell_row`` is the cell's row in ``all_cells``,
+    ``object_rows`` i32[n_i] its objects' rows in ``packed()`` and ``draw_salts`` u32[n_i] = ``draw_salts(epoch, idx, n_i)``;
+    ``object_points`` is None. ``coarse_batches`` turns such items into batches on the GPU; ``points=False`` leaves the point rows
+    out of them (embedding mode reads none). Resident cost: 24 B per raw point of the split."""
 
     def __init__(self, base_path: str, scene_names: Sequence[str], object_points: Optional[str] = None, seed: int = 0,
-                 transform: str = "fixed", shuffle_hints: bool = False, flip_poses: bool = False, aug_rng=None):
-        if object_points not in (None, "sample"):
-            raise ValueError("object_points must be None or 'sample'")
+                 transform: str = "fixed", shuffle_hints: bool = False, flip_poses: bool = False, aug_rng=None, points: bool = True):
+        if object_points not in (None, "sample", "ids"):
+            raise ValueError("object_points must be None, 'sample' or 'ids'")
         if transform not in packing.POINT_TRANSFORMS:
             raise ValueError(f"transform must be one of {sorted(packing.POINT_TRANSFORMS)}")
         self.scene_names = list(scene_names)
         self._points, self._seed, self._transform = object_points, seed, transform
+        self._ids_points = bool(points)
         self.shuffle_hints, self.flip_poses = bool(shuffle_hints), bool(flip_poses)
         self._aug = aug_rng if aug_rng is not None else np.random
         self._epoch_draw = 0
@@ -284,7 +293,61 @@ class Kitti360PoseDataset:
             return None
         return [" ".join(h) for h in self.hint_descriptions]
 
+    @property
+    def point_mode(self) -> Optional[str]:
+        return self._points
+
+    @property
+    def wants_points(self) -> bool:
+        """Whether a batch carries point rows: "sample" always; "ids" unless built with ``points=False``."""
+        return self._points == "sample" or (self._points == "ids" and self._ids_points)
+
+    @property
+    def point_transform(self) -> str:
+        return self._transform
+
+    @property
+    def point_seed(self) -> int:
+        return int(self._seed)
+
+    def packed(self) -> packing.PackedCellSet:
+        """Every cell of the dataset flattened once (shared with ``get_cell_dataset()``); ``object_rows`` index its objects."""
+        ps = self._packed_holder.get("set")
+        if ps is None:
+            ps = self._packed_holder["set"] = packing.PackedCellSet(self.all_cells)
+        return ps
+
+    def _ids_item(self, idx):
+        """The "ids" item: the draws of ``__getitem__`` in its order; the flips become a code, a flipped POSE copy and the swapped text."""
+        import copy
+
+        pose = self.all_poses[idx]
+        cell = self.cells_dict[pose.cell_id]
+        hints = self.hint_descriptions[idx]
+        if self.shuffle_hints:  # cells.py:80-81
+            hints = self._aug.choice(hints, size=len(hints), replace=False)
+        text = " ".join(hints)
+        mirror = 0
+        if self.flip_poses:     # cells.py:86-90
+            for bit, ax, a, b in ((1, 0, "east", "west"), (2, 1, "north", "south")):
+                if self._aug.choice((True, False)):
+                    if not mirror:
+                        pose = copy.deepcopy(pose)  # as flip_pose_in_cell does; a pose is a few hundred bytes
+                    mirror |= bit
+                    pose.pose[ax] = 1.0 - pose.pose[ax]
+                    for d in pose.descriptions:
+                        d.closest_point[ax] = 1.0 - d.closest_point[ax]
+                    text = _swap_words(text, a, b)
+        ps, row = self.packed(), self._cell_row[cell.id]
+        lo, hi = int(ps.offsets[row]), int(ps.offsets[row + 1])
+        return {"poses": pose, "cells": cell, "objects": cell.objects, "object_points": None, "texts": text,
+                "cell_ids": pose.cell_id, "scene_names": self._pose_scene[idx], "debug_hint_descriptions": hints,
+                "cell_row": row, "mirror": mirror, "object_rows": np.arange(lo, hi, dtype=np.int32),
+                "draw_salts": draw_salts(self._epoch, idx, hi - lo)}
+
     def __getitem__(self, idx):
+        if self._points == "ids":
+            return self._ids_item(int(idx))
         pose = self.all_poses[idx]
         cell = self.cells_dict[pose.cell_id]
         hints = self.hint_descriptions[idx]
@@ -319,7 +382,8 @@ class Kitti360PoseDataset:
         return list(packing.KNOWN_CLASS)
 
     def get_cell_dataset(self) -> CellOnlyDataset:
-        return CellOnlyDataset(self.all_cells, self._points, self._seed, self._transform, self._packed_holder)
+        points = self._points if self._points != "ids" else ("sample" if self._ids_points else None)  # the eval path is not row-indexed
+        return CellOnlyDataset(self.all_cells, points, self._seed, self._transform, self._packed_holder)
 
     @staticmethod
     def collate_fn(data):
@@ -548,3 +612,82 @@ def fine_batches(dataset: Kitti360FineDataset, batch_size: int, device, shuffle:
             batch["object_points"] = [{"pos": pos[i * n:(i + 1) * n].reshape(-1, 3), "x": col[i * n:(i + 1) * n].reshape(-1, 3)}
                                       for i in range(len(chunk))]
         yield batch
+
+
+# ---- coarse training batches from the resident cell set -------------------------------------------------------------------------------
+class CoarseBatchObjects(list):
+    """``batch["objects"]`` of ``coarse_batches``: per cell the resident (un-mirrored) object list, as any collated batch holds — plus
+    where those objects sit in the dataset's ``PackedCellSet`` (``cell_set``, ``object_rows``: one i32 array per cell) and each cell's
+    flip code (``mirror`` u8[B]). ``plumbing.pack_objects`` gathers the packed cells from the set by them and never walks the lists."""
+
+    def __init__(self, lists, cell_set, object_rows, mirror):
+        super().__init__(lists)
+        self.cell_set, self.object_rows, self.mirror = cell_set, object_rows, mirror
+
+
+class CoarseBatches:
+    """What ``coarse_batches`` returns: iterate it once per epoch, e.g. by handing it to ``coarse.train_epoch`` as the dataloader."""
+
+    def __init__(self, dataset, batch_size, device, shuffle, seed, drop_last, engine):
+        self.dataset, self.batch_size, self.device = dataset, batch_size, device
+        self.shuffle, self.seed, self.drop_last, self.engine = shuffle, seed, drop_last, engine
+
+    def __len__(self):
+        n = len(self.dataset)
+        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        if torch.utils.data.get_worker_info() is not None:
+            raise RuntimeError(_COARSE_WORKER_REFUSAL)
+        ds = self.dataset
+        epoch = int(getattr(ds, "_epoch", 0))  # train_epoch has advanced it; the items' salts read the same value
+        order = np.random.default_rng([self.seed, epoch]).permutation(len(ds)) if self.shuffle else np.arange(len(ds))
+        on_gpu = ds.point_mode == "ids"
+        engine = self.engine
+        if on_gpu and ds.wants_points and engine is None:
+            from .plumbing import engine_for
+
+            engine, _ = engine_for(getattr(ds, "_sampler_engine", None), torch.device(self.device), "coarse_batches")
+            ds._sampler_engine = engine
+        for lo in range(0, len(order), self.batch_size):
+            chunk = order[lo:lo + self.batch_size]
+            if self.drop_last and len(chunk) < self.batch_size:
+                return
+            batch = Kitti360PoseDataset.collate_fn([ds[int(i)] for i in chunk])
+            if on_gpu:
+                ps, rows = ds.packed(), batch["object_rows"]
+                mirror = np.array(batch["mirror"], dtype=np.uint8)
+                batch["objects"] = CoarseBatchObjects(batch["objects"], ps, rows, mirror)
+                if ds.wants_points:
+                    counts = [len(r) for r in rows]
+                    pos, col = ps.sample_rows(engine, self.device, np.concatenate(rows), np.concatenate(batch["draw_salts"]),
+                                              seed=ds.point_seed, transform=ds.point_transform, mirror=np.repeat(mirror, counts))
+                    ends = np.cumsum(counts)
+                    batch["object_points"] = [{"pos": pos[e - c:e].reshape(-1, 3), "x": col[e - c:e].reshape(-1, 3)}
+                                              for c, e in zip(counts, ends.tolist())]
+            yield batch
+
+
+_COARSE_WORKER_REFUSAL = ("coarse_batches works on the GPU and must run in the process that owns the engine, not in a DataLoader worker: let "
+                          "workers build host items (object_points='sample') or iterate coarse_batches in the main process")
+
+
+def coarse_batches(dataset: Kitti360PoseDataset, batch_size: int, device, shuffle: bool = False, seed: int = 0, drop_last: bool = False,
+                   engine=None) -> CoarseBatches:
+    """The batches of ``coarse.train_epoch`` in place of a DataLoader: a re-iterable with ``.dataset`` and ``__len__``. ``train_epoch``
+    advances ``dataset.set_epoch`` itself; every ``__iter__`` reads the dataset's current epoch, shuffles by
+    ``default_rng([seed, epoch])`` and collates the items. With an ``object_points="ids"`` dataset nothing of a cell is copied or
+    uploaded: ``batch["objects"]`` (``CoarseBatchObjects``) names the cells' rows of the resident ``PackedCellSet`` and their flip
+    codes, from which ``model.encode_objects`` gathers the packed features in one launch (t2l_gather_object_rows); when the dataset
+    wants points, all objects of the batch are sampled in ONE launch (t2l_sample_object_points_mirrored: object row under
+    ``dataset.point_seed ^ draw_salts(epoch, item)[slot]``, its cell's flip code, the dataset's transform — the rotation of
+    "rotate_normalize" does not depend on the code) and ``batch["object_points"]`` holds the per-cell ``{"pos", "x"}`` views.
+    The other point modes are collated as they are. The same (dataset seed, seed, epoch) always gives the same batches.
+    GPU work belongs to the process that owns the engine: iterating inside a DataLoader worker raises.
+    ``engine``: the ``Engine`` to sample with (e.g. ``model.engine()``); without one the dataset keeps a weightless one per device."""
+    if torch.utils.data.get_worker_info() is not None:
+        raise RuntimeError(_COARSE_WORKER_REFUSAL)
+    batch_size = int(batch_size)
+    if batch_size <= 0:
+        raise ValueError("batch_size must be positive")
+    return CoarseBatches(dataset, batch_size, device, bool(shuffle), int(seed), bool(drop_last), engine)

@@ -200,12 +200,17 @@ class PackedCellSet:
             d["point_offsets"] = d["point_offsets_pad"][:-1]
         return d
 
-    def sample_rows(self, engine, device, rows, salts=None, seed: int = 0, transform: str = "fixed"):
+    def sample_rows(self, engine, device, rows, salts=None, seed: int = 0, transform: str = "fixed", mirror=None):
         """FixedPoints(256) (+ the transform) for a list of object rows of this set, ``pad_row`` included, in ONE launch
         (t2l_sample_object_points_indexed) from the resident points: -> (pos f32[n_rows,256,3], rgb f32[n_rows,256,3]) on ``device``.
-        Row r is drawn under ``seed ^ salts[r]``; chunking, order and repetition of rows do not change a draw."""
+        Row r is drawn under ``seed ^ salts[r]``; chunking, order and repetition of rows do not change a draw.
+        ``mirror`` u8[n_rows] (t2l_sample_object_points_mirrored): the rows of flipped cells — bit 0: x -> 1 - x, bit 1: y -> 1 - y on
+        the gathered points, before the transform, with the draws of the un-mirrored row."""
         d = self.on_device(device)
-        return engine.sample_object_points_indexed(d["xyz"], d["rgb"], d["point_offsets_pad"], rows, salts, seed=seed, transform=transform)
+        if mirror is None:
+            return engine.sample_object_points_indexed(d["xyz"], d["rgb"], d["point_offsets_pad"], rows, salts, seed=seed, transform=transform)
+        return engine.sample_object_points_mirrored(d["xyz"], d["rgb"], d["point_offsets_pad"], rows, salts, mirror, seed=seed,
+                                                    transform=transform)
 
     def reduced(self, engine, device, known_colors: Optional[Dict[str, int]] = None) -> Dict[str, "torch.Tensor"]:
         """a1 for every object of the dataset in one launch pair (t2l_reduce_objects): mean rgb, nearest colour row, mean xyz,
@@ -225,6 +230,36 @@ class PackedCellSet:
         if key not in d:
             d[key] = torch.from_numpy(self.class_idx(known_classes)).to(device)
         return d[key]
+
+    def object_table(self, engine, device, known_classes: Dict[str, int], known_colors: Optional[Dict[str, int]] = None):
+        """The five per-object arrays of the packed layout for EVERY object of the set, on ``device``: ``reduced()`` (mean rgb, colour
+        row, mean xyz, point count: one reduction per device) and ``class_idx_on()``. Cached per device and class table; the colour
+        table is the one ``reduced()`` was first called with (the reference knows one: ``color_table()``)."""
+        d = self.on_device(device)
+        key = ("table", tuple(sorted(known_classes.items())))
+        if key not in d:
+            red = self.reduced(engine, device, known_colors)
+            d[key] = {"class_idx": self.class_idx_on(device, known_classes), "color_idx": red["color_idx"], "rgb": red["rgb"],
+                      "center": red["center"], "n_pts": red["n_pts"]}
+        return d[key]
+
+    def gather_rows(self, engine, device, rows, mirror, counts, known_classes: Dict[str, int],
+                    known_colors: Optional[Dict[str, int]] = None) -> Dict[str, "torch.Tensor"]:
+        """The packed cells of a batch in ONE launch (t2l_gather_object_rows) from ``object_table``: ``rows`` i32[n] object rows of this
+        set (cell after cell), ``mirror`` u8[n] | None their cells' flip codes (bit 0: centre x -> 1 - x, bit 1: y -> 1 - y),
+        ``counts`` the objects per cell. -> ``offsets`` i32[B+1], ``class_idx``, ``color_idx``, ``rgb``, ``center``, ``n_pts`` on
+        ``device``. Uploads 4 B per cell and 5 B per object; no object is walked on the host."""
+        import torch
+
+        rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+        if int(counts.sum()) != rows.size or (counts < 0).any():
+            raise ValueError(f"gather_rows: the per-cell counts add up to {int(counts.sum())}, there are {rows.size} rows")
+        offsets = np.zeros(len(counts) + 1, dtype=np.int32)
+        np.cumsum(counts, out=offsets[1:])
+        out = {"offsets": torch.from_numpy(offsets).to(device, non_blocking=True)}
+        out.update(engine.gather_object_rows(self.object_table(engine, device, known_classes, known_colors), rows, mirror))
+        return out
 
     def release_device(self, device=None):
         """Drop the device copies (all devices when ``device`` is None): the raw points are 24 B each."""

@@ -60,8 +60,16 @@ def adopt_grad(param, buf):
 # ---- inputs ------------------------------------------------------------------------------------------------------------------------
 def pack_objects(eng, objects, object_encoder, dev):
     """Packed cells on ``dev``. Raw points not reduced yet: one HBM pass on the GPU (t2l_reduce_objects) instead of three numpy
-    reductions per object on the host (what the reference redoes on every call); reduced before: the cached values, packed on the host."""
+    reductions per object on the host (what the reference redoes on every call); reduced before: the cached values, packed on the host.
+    ``objects`` from ``kitti360pose.coarse_batches`` (a list that carries ``cell_set``, ``object_rows`` and ``mirror``): the rows of the
+    set's resident reductions in one launch (``PackedCellSet.gather_rows``); nothing is walked or uploaded but the row list."""
     oe = object_encoder
+    cell_set, rows, mirror = (getattr(objects, n, None) for n in ("cell_set", "object_rows", "mirror"))
+    if cell_set is not None and rows is not None and mirror is not None:
+        counts = [len(r) for r in rows]
+        flat = np.concatenate(rows) if counts else np.zeros(0, np.int32)
+        return cell_set.gather_rows(eng, dev, flat, np.repeat(np.asarray(mirror, dtype=np.uint8), counts), counts, oe.known_classes,
+                                    oe.known_colors)
     if any(getattr(o, "_t2l_feat", None) is None for objs in objects for o in objs):
         return packing.pack_cells_gpu(eng, objects, oe.known_classes, oe.known_colors, dev)
     return packing.to_device(packing.pack_cells(objects, oe.known_classes, oe.known_colors), dev)
