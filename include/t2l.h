@@ -153,7 +153,7 @@ int t2l_sample_object_points(t2l_ctx* ctx, const float* xyz, const float* rgb, c
  * i32[n_rows], each in [0, n_objects); salts: HOST u32[n_rows] or NULL (= every salt 0); out_pos / out_rgb: dev f32[n_rows,256,3].
  * Row r samples object g = object_ids[r] with exactly the draws documented above under key = (seed ^ salts[r]) ^ g * 0x85EBCA77. So:
  *   - row r equals row g of a whole-set t2l_sample_object_points call with seed `seed ^ salts[r]`, bit for bit, under all three
- *     transforms (both kernels run one per-object body, one workgroup per output row), and equals the numpy restatement bit for bit;
+ *     transforms (whole-set and row kernel run one per-object body, a workgroup per output row), and equals the numpy restatement bit for bit;
  *   - how the caller chunks, orders or repeats rows cannot change a draw — the position in the call is not part of the key.
  * An object without points yields a row of zeros (from both entry points).
  * The ids are host arrays so that they are range-checked before anything is launched: an id outside [0, n_objects), n_rows < 0,
@@ -173,7 +173,7 @@ int t2l_sample_object_points_indexed(t2l_ctx* ctx, const float* xyz, const float
  * gathered point's x becomes 1.0f - x; bit 1: its y becomes 1.0f - y. Each is ONE float32 subtraction, rounded on its own like the
  * other defined operations above, applied to the gathered point BEFORE RandomRotate and NormalizeScale. The key of a row does not
  * contain its code: a mirrored row draws the indices and the angle of the un-mirrored one, out_rgb does not depend on the code, and a
- * row with code 0 equals that row of t2l_sample_object_points_indexed bit for bit (one per-object body serves all three kernels). A row
+ * row with code 0 equals that row of t2l_sample_object_points_indexed bit for bit (which launches this kernel with mirror = NULL). A row
  * with code m equals the numpy restatement run over the arrays with that object's x / y replaced by float32(1) - x / y.
  * Errors: those of the indexed sampler, and a mirror code above 3 — T2L_EINVAL naming the row, before anything is launched; no output
  * byte is written. n_rows == 0 is T2L_OK and touches nothing. ids | salts | mirror go through the same pinned buffer and event; the

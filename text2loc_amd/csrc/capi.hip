@@ -179,8 +179,8 @@ int t2l_sample_object_points_indexed(t2l_ctx* ctx, const float* xyz, const float
                                      int32_t transform_flags, float rotate_deg, float* out_pos, float* out_rgb, void* stream) {
   if (!ctx) return T2L_EINVAL;
   T2L_HIP(ctx, hipSetDevice(ctx->device));
-  return sample_points_indexed_impl(ctx, xyz, rgb, point_offsets, n_objects, object_ids, salts, n_rows, seed, transform_flags, rotate_deg,
-                                    out_pos, out_rgb, (hipStream_t)stream);
+  return sample_points_rows_impl(ctx, "t2l_sample_object_points_indexed: ", xyz, rgb, point_offsets, n_objects, object_ids, salts, nullptr,
+                                 n_rows, seed, transform_flags, rotate_deg, out_pos, out_rgb, (hipStream_t)stream);
 }
 
 int t2l_sample_object_points_mirrored(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets, int32_t n_objects,
@@ -188,8 +188,8 @@ int t2l_sample_object_points_mirrored(t2l_ctx* ctx, const float* xyz, const floa
                                       int32_t transform_flags, float rotate_deg, float* out_pos, float* out_rgb, void* stream) {
   if (!ctx) return T2L_EINVAL;
   T2L_HIP(ctx, hipSetDevice(ctx->device));
-  return sample_points_mirrored_impl(ctx, xyz, rgb, point_offsets, n_objects, object_ids, salts, mirror, n_rows, seed, transform_flags,
-                                     rotate_deg, out_pos, out_rgb, (hipStream_t)stream);
+  return sample_points_rows_impl(ctx, "t2l_sample_object_points_mirrored: ", xyz, rgb, point_offsets, n_objects, object_ids, salts, mirror,
+                                 n_rows, seed, transform_flags, rotate_deg, out_pos, out_rgb, (hipStream_t)stream);
 }
 
 int t2l_gather_object_rows(t2l_ctx* ctx, const int32_t* class_idx, const int32_t* color_idx, const float* rgb, const float* center,

@@ -1192,12 +1192,12 @@ struct SampleRed {  // LDS of one sampler workgroup: per wave the float64 sums o
 };
 
 // The per-object body both sampler kernels run, one 256-thread workgroup per OUTPUT row: object `o` of the resident arrays, drawn under
-// `okey`, written to row `row` of the outputs. The whole-set kernel calls it with row = o and okey = seed ^ o * 0x85EBCA77; the indexed
+// `okey`, written to row `row` of the outputs. The whole-set kernel calls it with row = o and okey = seed ^ o * 0x85EBCA77; the row
 // kernel with o = object_ids[row] and okey = (seed ^ salts[row]) ^ o * 0x85EBCA77 — the same instructions in the same reduction order,
 // which is what makes a row of the one equal the row of the other bit for bit under every transform.
-// `mirror` (the mirrored kernel alone; the other two pass the literal 0 and compile to what they were): bit 0 replaces the gathered x by
-// 1.0f - x, bit 1 the gathered y by 1.0f - y — a cell flipped about x = 0.5 / y = 0.5 — one float32 subtraction each, BEFORE RandomRotate
-// and NormalizeScale, and no part of `okey`: the mirrored row draws the indices and the angle of the un-mirrored one.
+// `mirror` (the row kernel's per-row code; the whole-set kernel passes the literal 0 and compiles to what it was): bit 0 replaces the
+// gathered x by 1.0f - x, bit 1 the gathered y by 1.0f - y — a cell flipped about x = 0.5 / y = 0.5 — one float32 subtraction each, BEFORE
+// RandomRotate and NormalizeScale, and no part of `okey`: the mirrored row draws the indices and the angle of the un-mirrored one.
 __device__ __forceinline__ void sample_object_row(const float* __restrict__ xyz, const float* __restrict__ rgb,
                                                   const int64_t* __restrict__ offsets, int o, uint32_t okey, size_t row, int flags,
                                                   int mirror, float rotate_rad, float* __restrict__ out_pos, float* __restrict__ out_rgb,
@@ -1262,19 +1262,8 @@ __global__ __launch_bounds__(256) void sample_points_kernel(const float* __restr
 }
 
 // Row r of the outputs = object ids[r] (range-checked on the host before the launch) under seed ^ salts[r]. The grid is the row list:
-// nothing here depends on how many objects the resident arrays hold.
-__global__ __launch_bounds__(256) void sample_points_indexed_kernel(const float* __restrict__ xyz, const float* __restrict__ rgb,
-                                                                    const int64_t* __restrict__ offsets, const int32_t* __restrict__ ids,
-                                                                    const uint32_t* __restrict__ salts, uint32_t seed, int flags,
-                                                                    float rotate_rad, float* __restrict__ out_pos,
-                                                                    float* __restrict__ out_rgb) {
-  __shared__ SampleRed red;
-  const int r = blockIdx.x, o = ids[r];
-  const uint32_t row_seed = salts ? seed ^ salts[r] : seed;
-  sample_object_row(xyz, rgb, offsets, o, row_seed ^ ((uint32_t)o * 0x85EBCA77u), (size_t)r, flags, 0, rotate_rad, out_pos, out_rgb, &red);
-}
-
-// The indexed kernel with a mirror code per row (0..3, checked on the host; NULL = every code 0): the rows of a flipped cell.
+// nothing here depends on how many objects the resident arrays hold. `mirror`: a code per row (0..3, checked on the host; NULL = every
+// code 0, which is all the indexed entry point asks for): the rows of a flipped cell.
 __global__ __launch_bounds__(256) void sample_points_mirrored_kernel(const float* __restrict__ xyz, const float* __restrict__ rgb,
                                                                      const int64_t* __restrict__ offsets, const int32_t* __restrict__ ids,
                                                                      const uint32_t* __restrict__ salts, const uint8_t* __restrict__ mirror,
@@ -1359,42 +1348,23 @@ int stage_rows_done(t2l_ctx* ctx, hipStream_t s) {
   return T2L_OK;
 }
 
-// t2l_sample_object_points_indexed (use_mirror = false: `mirror` is not looked at) and t2l_sample_object_points_mirrored
-static int sample_points_rows_impl(t2l_ctx* ctx, const char* who, const float* xyz, const float* rgb, const int64_t* point_offsets_dev,
-                                   int n_objects, const int32_t* ids, const uint32_t* salts, const uint8_t* mirror, bool use_mirror,
-                                   int n_rows, uint32_t seed, int flags, float rotate_deg, float* out_pos, float* out_rgb, hipStream_t s) {
+// t2l_sample_object_points_indexed (`mirror` null: nothing of it is checked, staged or read) and t2l_sample_object_points_mirrored; `who` is
+// the entry point's prefix of every error text
+int sample_points_rows_impl(t2l_ctx* ctx, const char* who, const float* xyz, const float* rgb, const int64_t* point_offsets_dev,
+                            int n_objects, const int32_t* ids, const uint32_t* salts, const uint8_t* mirror, int n_rows, uint32_t seed,
+                            int flags, float rotate_deg, float* out_pos, float* out_rgb, hipStream_t s) {
   if (n_rows < 0 || n_objects < 0) return fail(ctx, T2L_EINVAL, std::string(who) + "negative count");
   if (n_rows == 0) return T2L_OK;
   if (!xyz || !rgb || !point_offsets_dev || !ids || !out_pos || !out_rgb) return fail(ctx, T2L_EINVAL, std::string(who) + "null argument");
   if (flags & ~(T2L_SAMPLE_NORMALIZE | T2L_SAMPLE_ROTATE)) return fail(ctx, T2L_EINVAL, std::string(who) + "unknown transform flag");
-  if (!use_mirror) mirror = nullptr;
   if (int rc = check_rows(ctx, who, ids, mirror, n_rows, n_objects)) return rc;
   const int32_t* d_ids;
   const uint32_t* d_salts;
   const uint8_t* d_mirror;
   if (int rc = stage_rows(ctx, who, ids, salts, mirror, n_rows, s, &d_ids, &d_salts, &d_mirror)) return rc;
-  const float rad = rotate_deg * 0.017453292519943295f;
-  if (use_mirror)
-    hipLaunchKernelGGL(sample_points_mirrored_kernel, dim3(n_rows), dim3(256), 0, s, xyz, rgb, point_offsets_dev, d_ids, d_salts, d_mirror,
-                       seed, flags, rad, out_pos, out_rgb);
-  else
-    hipLaunchKernelGGL(sample_points_indexed_kernel, dim3(n_rows), dim3(256), 0, s, xyz, rgb, point_offsets_dev, d_ids, d_salts, seed, flags,
-                       rad, out_pos, out_rgb);
+  hipLaunchKernelGGL(sample_points_mirrored_kernel, dim3(n_rows), dim3(256), 0, s, xyz, rgb, point_offsets_dev, d_ids, d_salts, d_mirror,
+                     seed, flags, rotate_deg * 0.017453292519943295f, out_pos, out_rgb);
   return stage_rows_done(ctx, s);
-}
-
-int sample_points_indexed_impl(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets_dev, int n_objects,
-                               const int32_t* ids, const uint32_t* salts, int n_rows, uint32_t seed, int flags, float rotate_deg,
-                               float* out_pos, float* out_rgb, hipStream_t s) {
-  return sample_points_rows_impl(ctx, "t2l_sample_object_points_indexed: ", xyz, rgb, point_offsets_dev, n_objects, ids, salts, nullptr, false,
-                                 n_rows, seed, flags, rotate_deg, out_pos, out_rgb, s);
-}
-
-int sample_points_mirrored_impl(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets_dev, int n_objects,
-                                const int32_t* ids, const uint32_t* salts, const uint8_t* mirror, int n_rows, uint32_t seed, int flags,
-                                float rotate_deg, float* out_pos, float* out_rgb, hipStream_t s) {
-  return sample_points_rows_impl(ctx, "t2l_sample_object_points_mirrored: ", xyz, rgb, point_offsets_dev, n_objects, ids, salts, mirror, true,
-                                 n_rows, seed, flags, rotate_deg, out_pos, out_rgb, s);
 }
 
 int sample_points_impl(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets_dev, int n_objects, uint32_t seed,

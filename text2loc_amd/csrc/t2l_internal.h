@@ -269,12 +269,10 @@ int pointnet_features_impl(t2l_ctx* ctx, const float* pos, const float* rgb, con
 int sample_points_impl(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets_dev, int n_objects, uint32_t seed,
                        int flags, float rotate_deg,
                        float* out_pos, float* out_rgb, hipStream_t s);
-int sample_points_indexed_impl(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets_dev, int n_objects,
-                               const int32_t* ids, const uint32_t* salts, int n_rows, uint32_t seed, int flags, float rotate_deg,
-                               float* out_pos, float* out_rgb, hipStream_t s);
-int sample_points_mirrored_impl(t2l_ctx* ctx, const float* xyz, const float* rgb, const int64_t* point_offsets_dev, int n_objects,
-                                const int32_t* ids, const uint32_t* salts, const uint8_t* mirror, int n_rows, uint32_t seed, int flags,
-                                float rotate_deg, float* out_pos, float* out_rgb, hipStream_t s);
+// both row-indexed samplers: `who` = the entry point's error prefix, `mirror` null = every code 0
+int sample_points_rows_impl(t2l_ctx* ctx, const char* who, const float* xyz, const float* rgb, const int64_t* point_offsets_dev,
+                            int n_objects, const int32_t* ids, const uint32_t* salts, const uint8_t* mirror, int n_rows, uint32_t seed,
+                            int flags, float rotate_deg, float* out_pos, float* out_rgb, hipStream_t s);
 // the row lists of the row-indexed entry points: checked, then staged through the context's pinned buffer (ids | salts | mirror)
 int check_rows(t2l_ctx* ctx, const char* who, const int32_t* ids, const uint8_t* mirror, int n_rows, int n_objects);
 int stage_rows(t2l_ctx* ctx, const char* who, const int32_t* ids, const uint32_t* salts, const uint8_t* mirror, int n_rows, hipStream_t s,

@@ -15,6 +15,8 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
+from .packing import POINT_TRANSFORMS
+
 EMBED_DIM = 256
 OBJECT_SIZE = 28
 # what the eval-mode cell encoder is compiled for (include/t2l.h: t2l_load_weights_shaped); the search, the text entry points and the
@@ -296,17 +298,42 @@ class Engine:
         -> (pos f32[n_objects,256,3], rgb f32[n_objects,256,3]). ``transform`` (packing.POINT_TRANSFORMS): "fixed" =
         FixedPoints(256) only (`--no_pc_augment`, the published commands), "normalize" = + NormalizeScale, "rotate_normalize" =
         + RandomRotate(rotate_deg, axis=2) before it (training without the flag)."""
-        from .packing import POINT_TRANSFORMS
-
-        if transform not in POINT_TRANSFORMS:
-            raise T2LError(f"sample_object_points: transform must be one of {sorted(POINT_TRANSFORMS)}, got {transform!r}")
+        flags = self._transform_flags("sample_object_points", transform)
         n = int(point_offsets.numel()) - 1
         pos = torch.empty((max(n, 0), 256, 3), dtype=torch.float32, device=xyz.device)
         col = torch.empty_like(pos)
         self._check(self.lib.t2l_sample_object_points(self._h, self._ptr(xyz, torch.float32, "xyz"), self._ptr(rgb, torch.float32, "rgb"),
                                                       self._ptr(point_offsets, torch.int64, "point_offsets"), n, int(seed) & 0xFFFFFFFF,
-                                                      POINT_TRANSFORMS[transform], float(rotate_deg), pos.data_ptr(), col.data_ptr(),
-                                                      _stream_ptr(self.device)))
+                                                      flags, float(rotate_deg), pos.data_ptr(), col.data_ptr(), _stream_ptr(self.device)))
+        return pos, col
+
+    @staticmethod
+    def _transform_flags(who: str, transform: str) -> int:
+        """The T2L_SAMPLE_* flags of a ``packing.POINT_TRANSFORMS`` name; any other name raises in ``who``'s name."""
+        if transform not in POINT_TRANSFORMS:
+            raise T2LError(f"{who}: transform must be one of {sorted(POINT_TRANSFORMS)}, got {transform!r}")
+        return POINT_TRANSFORMS[transform]
+
+    def _sample_rows(self, who: str, entry, mirrored: bool, xyz, rgb, point_offsets, object_ids, salts, mirror, seed, transform, rotate_deg):
+        """Both row samplers: ``entry`` is the library's entry point, which takes a ``mirror`` argument when ``mirrored``; ``who``
+        names the public method in this side's own messages."""
+        flags = self._transform_flags(who, transform)
+        ids = np.ascontiguousarray(object_ids, dtype=np.int32).reshape(-1)
+        sl = None if salts is None else np.ascontiguousarray(salts, dtype=np.uint32).reshape(-1)
+        mi = None if mirror is None else np.ascontiguousarray(mirror, dtype=np.uint8).reshape(-1)
+        if sl is not None and sl.size != ids.size:
+            raise T2LError(f"{who}: {ids.size} object ids but {sl.size} salts")
+        if mi is not None and mi.size != ids.size:
+            raise T2LError(f"{who}: {ids.size} object ids but {mi.size} mirror codes")
+        host = (ids.ctypes.data, None if sl is None else sl.ctypes.data)
+        if mirrored:
+            host += (None if mi is None else mi.ctypes.data,)
+        n = int(point_offsets.numel()) - 1
+        pos = torch.empty((ids.size, 256, 3), dtype=torch.float32, device=xyz.device)
+        col = torch.empty_like(pos)
+        self._check(entry(self._h, self._ptr(xyz, torch.float32, "xyz"), self._ptr(rgb, torch.float32, "rgb"),
+                          self._ptr(point_offsets, torch.int64, "point_offsets"), n, *host, int(ids.size), int(seed) & 0xFFFFFFFF, flags,
+                          float(rotate_deg), pos.data_ptr(), col.data_ptr(), _stream_ptr(self.device)))
         return pos, col
 
     def sample_object_points_indexed(self, xyz: torch.Tensor, rgb: torch.Tensor, point_offsets: torch.Tensor, object_ids, salts=None,
@@ -315,22 +342,8 @@ class Engine:
         and ``salts`` u32[n_rows] | None are HOST arrays; row r = object ``object_ids[r]`` drawn under ``seed ^ salts[r]``, equal bit
         for bit to that row of a whole-set call with that seed. -> (pos f32[n_rows,256,3], rgb f32[n_rows,256,3]). An id outside
         [0, n_objects) raises before anything is launched; the outputs are then never written."""
-        from .packing import POINT_TRANSFORMS
-
-        if transform not in POINT_TRANSFORMS:
-            raise T2LError(f"sample_object_points_indexed: transform must be one of {sorted(POINT_TRANSFORMS)}, got {transform!r}")
-        ids = np.ascontiguousarray(object_ids, dtype=np.int32).reshape(-1)
-        sl = None if salts is None else np.ascontiguousarray(salts, dtype=np.uint32).reshape(-1)
-        if sl is not None and sl.size != ids.size:
-            raise T2LError(f"sample_object_points_indexed: {ids.size} object ids but {sl.size} salts")
-        n = int(point_offsets.numel()) - 1
-        pos = torch.empty((ids.size, 256, 3), dtype=torch.float32, device=xyz.device)
-        col = torch.empty_like(pos)
-        self._check(self.lib.t2l_sample_object_points_indexed(
-            self._h, self._ptr(xyz, torch.float32, "xyz"), self._ptr(rgb, torch.float32, "rgb"),
-            self._ptr(point_offsets, torch.int64, "point_offsets"), n, ids.ctypes.data, None if sl is None else sl.ctypes.data, int(ids.size),
-            int(seed) & 0xFFFFFFFF, POINT_TRANSFORMS[transform], float(rotate_deg), pos.data_ptr(), col.data_ptr(), _stream_ptr(self.device)))
-        return pos, col
+        return self._sample_rows("sample_object_points_indexed", self.lib.t2l_sample_object_points_indexed, False, xyz, rgb, point_offsets,
+                                 object_ids, salts, None, seed, transform, rotate_deg)
 
     def sample_object_points_mirrored(self, xyz: torch.Tensor, rgb: torch.Tensor, point_offsets: torch.Tensor, object_ids, salts=None,
                                       mirror=None, seed: int = 0, transform: str = "fixed", rotate_deg: float = 120.0):
@@ -338,26 +351,8 @@ class Engine:
         is a HOST array of codes 0..3 — bit 0: the gathered x becomes ``1 - x``, bit 1: the gathered y becomes ``1 - y``, one float32
         subtraction each, before the transform. The code is not part of a row's key: the same indices, the same angle, the same colours
         as the un-mirrored row. An id out of range or a code above 3 raises before anything is launched."""
-        from .packing import POINT_TRANSFORMS
-
-        if transform not in POINT_TRANSFORMS:
-            raise T2LError(f"sample_object_points_mirrored: transform must be one of {sorted(POINT_TRANSFORMS)}, got {transform!r}")
-        ids = np.ascontiguousarray(object_ids, dtype=np.int32).reshape(-1)
-        sl = None if salts is None else np.ascontiguousarray(salts, dtype=np.uint32).reshape(-1)
-        mi = None if mirror is None else np.ascontiguousarray(mirror, dtype=np.uint8).reshape(-1)
-        if sl is not None and sl.size != ids.size:
-            raise T2LError(f"sample_object_points_mirrored: {ids.size} object ids but {sl.size} salts")
-        if mi is not None and mi.size != ids.size:
-            raise T2LError(f"sample_object_points_mirrored: {ids.size} object ids but {mi.size} mirror codes")
-        n = int(point_offsets.numel()) - 1
-        pos = torch.empty((ids.size, 256, 3), dtype=torch.float32, device=xyz.device)
-        col = torch.empty_like(pos)
-        self._check(self.lib.t2l_sample_object_points_mirrored(
-            self._h, self._ptr(xyz, torch.float32, "xyz"), self._ptr(rgb, torch.float32, "rgb"),
-            self._ptr(point_offsets, torch.int64, "point_offsets"), n, ids.ctypes.data, None if sl is None else sl.ctypes.data,
-            None if mi is None else mi.ctypes.data, int(ids.size), int(seed) & 0xFFFFFFFF, POINT_TRANSFORMS[transform], float(rotate_deg),
-            pos.data_ptr(), col.data_ptr(), _stream_ptr(self.device)))
-        return pos, col
+        return self._sample_rows("sample_object_points_mirrored", self.lib.t2l_sample_object_points_mirrored, True, xyz, rgb, point_offsets,
+                                 object_ids, salts, mirror, seed, transform, rotate_deg)
 
     def gather_object_rows(self, table: Dict[str, torch.Tensor], object_ids, mirror=None) -> Dict[str, torch.Tensor]:
         """Rows of resident per-object tables (t2l_gather_object_rows). ``table``: class_idx / color_idx i32[n], rgb / center f32[n,3],

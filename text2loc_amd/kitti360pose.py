@@ -25,9 +25,12 @@ without the flag (dataloading/kitti360pose/utils.py:91-147, evaluation/pipeline.
 The fine stage's counterpart (dataloading/kitti360pose/poses.py:36-172, 368-590) is ``Kitti360FineDataset``: one item per pose,
 what ``load_pose_and_cell`` returns, for ``fine_training.train_epoch``. Its third point mode, ``object_points="ids"``, leaves the
 points on the GPU: an item names 16 rows of the dataset's ``packing.PackedCellSet`` and ``fine_batches`` samples a whole batch of
-them in one launch (t2l_sample_object_points_indexed) in the process that owns the engine.
+them in one launch in the process that owns the engine.
 ``Kitti360PoseDataset(object_points="ids")`` with ``coarse_batches`` is the coarse stage's form of it: an item names its cell's rows
-and a flip code instead of carrying a mirrored copy of the cell (t2l_sample_object_points_mirrored, t2l_gather_object_rows).
+and a flip code instead of carrying a mirrored copy of the cell (t2l_gather_object_rows gathers its packed features by them).
+What the two datasets share (loading, the point properties, ``packed()``, ``collate_fn``) is ``_PoseDataset``; their batches come out
+of one loop, ``_batches``, and one launch per batch (``PackedCellSet.sample_rows``: t2l_sample_object_points_mirrored, the fine
+stage's rows without a code) — each dataset adds only its own GPU step, ``_device_batch``.
 """
 from __future__ import annotations
 
@@ -156,6 +159,20 @@ def _swap_words(text: str, a: str, b: str) -> str:
     return text.replace(a, a + "-flipped").replace(b, a).replace(a + "-flipped", b)
 
 
+def _flipped_pose(pose, code: int):
+    """The pose half of a flip about x = 0.5 (bit 0 of ``code``) and / or y = 0.5 (bit 1): ONE copy (a pose is a few hundred bytes, its
+    deep copy tens of microseconds) whose pose-in-cell and whose descriptions' ``closest_point`` are mirrored."""
+    import copy
+
+    pose = copy.deepcopy(pose)
+    for ax in (0, 1):
+        if code >> ax & 1:
+            pose.pose[ax] = 1.0 - pose.pose[ax]
+            for d in pose.descriptions:
+                d.closest_point[ax] = 1.0 - d.closest_point[ax]
+    return pose
+
+
 def flip_pose_in_cell(pose, cell, text: str, direction: int):
     """dataloading/kitti360pose/utils.py:15-88 (the three-value form the coarse dataset uses): mirror the cell about x = 0.5
     (``direction`` +1, "horizontally": east <-> west in the text) or y = 0.5 (-1, "vertically": north <-> south). Pose and
@@ -165,15 +182,12 @@ def flip_pose_in_cell(pose, cell, text: str, direction: int):
 
     if direction not in (-1, 1):
         raise ValueError("direction must be +1 (horizontal) or -1 (vertical)")
-    pose, cell = copy.deepcopy(pose), copy.deepcopy(cell)
     ax = 0 if direction == 1 else 1
-    pose.pose[ax] = 1.0 - pose.pose[ax]
+    pose, cell = _flipped_pose(pose, 1 << ax), copy.deepcopy(cell)
     for obj in cell.objects:
         obj.xyz[:, ax] = 1 - obj.xyz[:, ax]
         if hasattr(obj, "_t2l_feat"):
             del obj._t2l_feat  # cached reductions of the un-mirrored points
-    for d in pose.descriptions:
-        d.closest_point[ax] = 1.0 - d.closest_point[ax]
     text = _swap_words(text, "east", "west") if direction == 1 else _swap_words(text, "north", "south")
     return pose, cell, text
 
@@ -228,7 +242,74 @@ class CellOnlyDataset:
         return {"cells": cell, "cell_ids": cell.id, "objects": cell.objects, "object_points": self._object_points(cell, idx)}
 
 
-class Kitti360PoseDataset:
+class _PoseDataset:
+    """What ``Kitti360PoseDataset`` and ``Kitti360FineDataset`` share: one item per pose over the scenes of a KITTI360Pose directory or
+    of a dict ``{scene: (cells, poses)}`` of records already in memory, a point mode, and the cells flattened once."""
+
+    def __init__(self, base_path, scene_names: Sequence[str], object_points: Optional[str], transform: str, seed, points: bool = True):
+        if object_points not in (None, "sample", "ids"):
+            raise ValueError("object_points must be None, 'sample' or 'ids'")
+        if transform not in packing.POINT_TRANSFORMS:
+            raise ValueError(f"transform must be one of {sorted(packing.POINT_TRANSFORMS)}")
+        self.scene_names = list(scene_names)
+        self._points, self._transform, self._seed, self._epoch = object_points, transform, seed, 0
+        self.all_cells: List[CellRecord] = []
+        self.all_poses: List[PoseRecord] = []
+        self.hint_descriptions: List[List[str]] = []
+        self._packed_holder: dict = {}
+        self._ids_points = bool(points)
+        self._scenes = []  # (scene, cells, poses) as loaded: each dataset builds its own tables (scene names, cell rows) from them
+        for s in self.scene_names:
+            cells, poses = base_path[s] if isinstance(base_path, dict) else load_scene(base_path, s)
+            self._scenes.append((s, cells, poses))
+            self.all_cells.extend(cells)
+            self.all_poses.extend(poses)
+            self.hint_descriptions.extend(hint_sentences(p) for p in poses)
+
+    @classmethod
+    def from_records(cls, cells: Sequence[CellRecord], poses: Sequence[PoseRecord], *args, scene_name: str = "in_memory", **kw):
+        """The same dataset over records that are already in memory (one scene): what ``load_scene`` would have returned."""
+        return cls({scene_name: (list(cells), list(poses))}, [scene_name], *args, **kw)
+
+    def __len__(self):
+        return len(self.all_poses)
+
+    @property
+    def point_mode(self) -> Optional[str]:
+        return self._points
+
+    @property
+    def point_transform(self) -> str:
+        return self._transform
+
+    @property
+    def point_seed(self) -> int:
+        return int(self._seed)
+
+    @property
+    def wants_points(self) -> bool:
+        """Whether a batch carries point rows: "sample" always; "ids" unless built with ``points=False``."""
+        return self._points == "sample" or (self._points == "ids" and self._ids_points)
+
+    def set_epoch(self, epoch: int):
+        """Call once per epoch (as DistributedSampler.set_epoch): part of the key of the point draws that are redrawn per fetch — the
+        coarse set's under transform="rotate_normalize" (DataLoader workers restart from a copy of this object every epoch), all of
+        the fine set's, and ``draw_salts`` of both "ids" modes."""
+        self._epoch = int(epoch)
+
+    def packed(self) -> packing.PackedCellSet:
+        """Every cell of the dataset flattened once; ``object_rows`` index its objects, its ``pad_row`` stands for a fine-stage pad."""
+        ps = self._packed_holder.get("set")
+        if ps is None:
+            ps = self._packed_holder["set"] = packing.PackedCellSet(self.all_cells)
+        return ps
+
+    @staticmethod
+    def collate_fn(data):
+        return {key: [d[key] for d in data] for key in data[0].keys()}
+
+
+class Kitti360PoseDataset(_PoseDataset):
     """One item per pose over several scenes (cells.py:36-185 ``Kitti360CoarseDataset`` / ``...Multi``).
 
     ``transform``: the point transform of ``object_points="sample"`` — "fixed" (FixedPoints(256) only: `--no_pc_augment`,
@@ -249,40 +330,16 @@ class Kitti360PoseDataset:
 
     def __init__(self, base_path: str, scene_names: Sequence[str], object_points: Optional[str] = None, seed: int = 0,
                  transform: str = "fixed", shuffle_hints: bool = False, flip_poses: bool = False, aug_rng=None, points: bool = True):
-        if object_points not in (None, "sample", "ids"):
-            raise ValueError("object_points must be None, 'sample' or 'ids'")
-        if transform not in packing.POINT_TRANSFORMS:
-            raise ValueError(f"transform must be one of {sorted(packing.POINT_TRANSFORMS)}")
-        self.scene_names = list(scene_names)
-        self._points, self._seed, self._transform = object_points, seed, transform
-        self._ids_points = bool(points)
+        super().__init__(base_path, scene_names, object_points, transform, seed, points)
         self.shuffle_hints, self.flip_poses = bool(shuffle_hints), bool(flip_poses)
         self._aug = aug_rng if aug_rng is not None else np.random
         self._epoch_draw = 0
-        self._epoch = 0
-        self.all_cells: List[CellRecord] = []
-        self.all_poses: List[PoseRecord] = []
-        self._pose_scene: List[str] = []
-        self._packed_holder: dict = {}
-        for s in self.scene_names:
-            cells, poses = base_path[s] if isinstance(base_path, dict) else load_scene(base_path, s)
-            self.all_cells.extend(cells)
-            self.all_poses.extend(poses)
-            self._pose_scene.extend([s] * len(poses))
+        self._pose_scene: List[str] = [s for s, _, poses in self._scenes for _ in poses]
         ids = [c.id for c in self.all_cells]
         if len(set(ids)) != len(ids):
             raise ValueError("cell ids repeat across scenes")  # cells.py:137-138
         self.cells_dict: Dict[str, CellRecord] = {c.id: c for c in self.all_cells}
         self._cell_row = {c.id: i for i, c in enumerate(self.all_cells)}
-        self.hint_descriptions = [hint_sentences(p) for p in self.all_poses]
-
-    @classmethod
-    def from_records(cls, cells: Sequence[CellRecord], poses: Sequence[PoseRecord], scene_name: str = "in_memory", **kw):
-        """The same dataset over records that are already in memory (one scene): what ``load_scene`` would have returned."""
-        return cls({scene_name: (list(cells), list(poses))}, [scene_name], **kw)
-
-    def __len__(self):
-        return len(self.all_poses)
 
     def eval_texts(self) -> Optional[List[str]]:
         """Every item's ``texts`` in item order WITHOUT building the items — None when items are augmented (then the texts are a
@@ -293,74 +350,40 @@ class Kitti360PoseDataset:
             return None
         return [" ".join(h) for h in self.hint_descriptions]
 
-    @property
-    def point_mode(self) -> Optional[str]:
-        return self._points
-
-    @property
-    def wants_points(self) -> bool:
-        """Whether a batch carries point rows: "sample" always; "ids" unless built with ``points=False``."""
-        return self._points == "sample" or (self._points == "ids" and self._ids_points)
-
-    @property
-    def point_transform(self) -> str:
-        return self._transform
-
-    @property
-    def point_seed(self) -> int:
-        return int(self._seed)
-
-    def packed(self) -> packing.PackedCellSet:
-        """Every cell of the dataset flattened once (shared with ``get_cell_dataset()``); ``object_rows`` index its objects."""
-        ps = self._packed_holder.get("set")
-        if ps is None:
-            ps = self._packed_holder["set"] = packing.PackedCellSet(self.all_cells)
-        return ps
-
-    def _ids_item(self, idx):
-        """The "ids" item: the draws of ``__getitem__`` in its order; the flips become a code, a flipped POSE copy and the swapped text."""
-        import copy
-
-        pose = self.all_poses[idx]
-        cell = self.cells_dict[pose.cell_id]
+    def _draw(self, idx):
+        """The augmentation draws of item ``idx`` in the reference's order — one ``choice`` over the hints (cells.py:80-81), then the
+        two ``choice((True, False))`` (cells.py:86-90) — as (hints, their text with the flips' word swaps, flip code: bit 0 horizontal,
+        bit 1 vertical). No draw depends on a flip, so flipping afterwards consumes ``aug_rng`` as flipping in between did."""
         hints = self.hint_descriptions[idx]
-        if self.shuffle_hints:  # cells.py:80-81
+        if self.shuffle_hints:
             hints = self._aug.choice(hints, size=len(hints), replace=False)
-        text = " ".join(hints)
-        mirror = 0
-        if self.flip_poses:     # cells.py:86-90
-            for bit, ax, a, b in ((1, 0, "east", "west"), (2, 1, "north", "south")):
+        text, code = " ".join(hints), 0
+        if self.flip_poses:
+            for bit, a, b in ((1, "east", "west"), (2, "north", "south")):
                 if self._aug.choice((True, False)):
-                    if not mirror:
-                        pose = copy.deepcopy(pose)  # as flip_pose_in_cell does; a pose is a few hundred bytes
-                    mirror |= bit
-                    pose.pose[ax] = 1.0 - pose.pose[ax]
-                    for d in pose.descriptions:
-                        d.closest_point[ax] = 1.0 - d.closest_point[ax]
+                    code |= bit
                     text = _swap_words(text, a, b)
-        ps, row = self.packed(), self._cell_row[cell.id]
-        lo, hi = int(ps.offsets[row]), int(ps.offsets[row + 1])
-        return {"poses": pose, "cells": cell, "objects": cell.objects, "object_points": None, "texts": text,
-                "cell_ids": pose.cell_id, "scene_names": self._pose_scene[idx], "debug_hint_descriptions": hints,
-                "cell_row": row, "mirror": mirror, "object_rows": np.arange(lo, hi, dtype=np.int32),
-                "draw_salts": draw_salts(self._epoch, idx, hi - lo)}
+        return hints, text, code
 
     def __getitem__(self, idx):
-        if self._points == "ids":
-            return self._ids_item(int(idx))
+        idx = int(idx)
         pose = self.all_poses[idx]
         cell = self.cells_dict[pose.cell_id]
-        hints = self.hint_descriptions[idx]
-        if self.shuffle_hints:  # cells.py:80-81
-            hints = self._aug.choice(hints, size=len(hints), replace=False)
-        text = " ".join(hints)
-        if self.flip_poses:     # cells.py:86-90
-            if self._aug.choice((True, False)):
-                pose, cell, text = flip_pose_in_cell(pose, cell, text, 1)
-            if self._aug.choice((True, False)):
-                pose, cell, text = flip_pose_in_cell(pose, cell, text, -1)
+        hints, text, code = self._draw(idx)
+        if self._points == "ids":  # the flips are the code and a flipped POSE copy; the resident cell is not copied, no point touched
+            if code:
+                pose = _flipped_pose(pose, code)
+            ps, row = self.packed(), self._cell_row[cell.id]
+            lo, hi = int(ps.offsets[row]), int(ps.offsets[row + 1])
+            return {"poses": pose, "cells": cell, "objects": cell.objects, "object_points": None, "texts": text,
+                    "cell_ids": pose.cell_id, "scene_names": self._pose_scene[idx], "debug_hint_descriptions": hints,
+                    "cell_row": row, "mirror": code, "object_rows": np.arange(lo, hi, dtype=np.int32),
+                    "draw_salts": draw_salts(self._epoch, idx, hi - lo)}
+        for bit, direction in ((1, 1), (2, -1)):
+            if code & bit:
+                pose, cell, _ = flip_pose_in_cell(pose, cell, "", direction)  # ``text`` carries its swaps already
         pts = None
-        if self._points is not None:
+        if self._points == "sample":
             if self._transform == "rotate_normalize":  # a fresh rotation / draw every time an item is fetched
                 # keyed on (seed, cell, epoch, DataLoader worker, per-process counter): a worker process starts from a COPY of the
                 # parent's counter every epoch, so the counter alone repeated the draws across epochs and collided across workers
@@ -373,21 +396,24 @@ class Kitti360PoseDataset:
         return {"poses": pose, "cells": cell, "objects": cell.objects, "object_points": pts, "texts": text,
                 "cell_ids": pose.cell_id, "scene_names": self._pose_scene[idx], "debug_hint_descriptions": hints}
 
-    def set_epoch(self, epoch: int):
-        """Call once per epoch (as DistributedSampler.set_epoch): part of the key of the augmentation draws under
-        transform="rotate_normalize" (DataLoader workers restart from a copy of this object every epoch)."""
-        self._epoch = int(epoch)
-
     def get_known_classes(self):
         return list(packing.KNOWN_CLASS)
 
     def get_cell_dataset(self) -> CellOnlyDataset:
         points = self._points if self._points != "ids" else ("sample" if self._ids_points else None)  # the eval path is not row-indexed
-        return CellOnlyDataset(self.all_cells, points, self._seed, self._transform, self._packed_holder)
+        return CellOnlyDataset(self.all_cells, points, self._seed, self._transform, self._packed_holder)  # one packed set for both
 
-    @staticmethod
-    def collate_fn(data):
-        return {key: [d[key] for d in data] for key in data[0].keys()}
+    def _device_batch(self, batch, engine, device):
+        """``_batches``' GPU step: ``batch["objects"]`` names the cells' rows and flip codes; when the dataset wants points, all objects
+        of the batch in one launch, each under its cell's code, cut into one view pair per cell."""
+        ps, rows = self.packed(), batch["object_rows"]
+        mirror = np.array(batch["mirror"], dtype=np.uint8)
+        batch["objects"] = CoarseBatchObjects(batch["objects"], ps, rows, mirror)
+        if self._ids_points:
+            counts = [len(r) for r in rows]
+            pos, col = ps.sample_rows(engine, device, np.concatenate(rows), np.concatenate(batch["draw_salts"]), seed=self.point_seed,
+                                      transform=self.point_transform, mirror=np.repeat(mirror, counts))
+            batch["object_points"] = _row_views(pos, col, counts)
 
 
 # ---- the fine stage's dataset ---------------------------------------------------------------------------------------------------------
@@ -424,7 +450,7 @@ def draw_salts(epoch: int, item: int, n_slots: int = 16) -> np.ndarray:
     return _mix32(h ^ np.arange(n_slots, dtype=np.uint64)).astype(np.uint32)
 
 
-class Kitti360FineDataset:
+class Kitti360FineDataset(_PoseDataset):
     """One item per pose over several scenes: ``Kitti360FineDatasetMulti`` over ``Kitti360FineDataset`` (poses.py:368-590), an item
     being what ``load_pose_and_cell`` (poses.py:36-172) returns.
 
@@ -443,10 +469,7 @@ class Kitti360FineDataset:
 
     def __init__(self, base_path, scene_names: Sequence[str], args, object_points: Optional[str] = None, transform: str = "fixed",
                  seed: int = 0, flip_pose: bool = False, pmc_prob: float = 0.0, pmc_threshold: float = 0.4, count_threshold: int = 1):
-        if object_points not in (None, "sample", "ids"):
-            raise ValueError("object_points must be None, 'sample' or 'ids'")
-        if transform not in packing.POINT_TRANSFORMS:
-            raise ValueError(f"transform must be one of {sorted(packing.POINT_TRANSFORMS)}")
+        super().__init__(base_path, scene_names, object_points, transform, int(seed))
         if pmc_prob > 0.0:
             raise NotImplementedError(_MAP_CLONING_REFUSAL)
         cell, learn = getattr(args, "regressor_cell", None), getattr(args, "regressor_learn", None)
@@ -455,56 +478,18 @@ class Kitti360FineDataset:
         from .cross_matcher import PadObject
 
         self.args, self.pad_size = args, int(args.pad_size)
-        self.scene_names = list(scene_names)
         self.flip_pose = bool(flip_pose)
-        self._points, self._transform, self._seed, self._epoch = object_points, transform, int(seed), 0
         self._pad = PadObject()  # ONE pad object per dataset: its reductions are cached on it like any other object's
-        self.all_cells: List[CellRecord] = []
-        self.all_poses: List[PoseRecord] = []
-        self.hint_descriptions: List[List[str]] = []
         self._pose_cell_row: List[int] = []
-        for s in self.scene_names:
-            cells, poses = base_path[s] if isinstance(base_path, dict) else load_scene(base_path, s)
+        first = 0
+        for s, cells, poses in self._scenes:
             ids = [c.id for c in cells]
             if len(set(ids)) != len(ids):
                 raise ValueError(f"{s}: cell ids repeat")  # base.py:45-46
-            row = {c.id: len(self.all_cells) + i for i, c in enumerate(cells)}  # per scene, as the reference's per-scene cells_dict
-            self.all_cells.extend(cells)
-            self.all_poses.extend(poses)
+            row = {c.id: first + i for i, c in enumerate(cells)}  # per scene, as the reference's per-scene cells_dict
             self._pose_cell_row.extend(row[p.cell_id] for p in poses)
-            self.hint_descriptions.extend(hint_sentences(p) for p in poses)
-        self._packed = None
+            first += len(cells)
         self._positions: Dict[int, Dict[object, int]] = {}
-
-    @classmethod
-    def from_records(cls, cells: Sequence[CellRecord], poses: Sequence[PoseRecord], args, scene_name: str = "in_memory", **kw):
-        """The same dataset over records that are already in memory (one scene): what ``load_scene`` would have returned."""
-        return cls({scene_name: (list(cells), list(poses))}, [scene_name], args, **kw)
-
-    def __len__(self):
-        return len(self.all_poses)
-
-    @property
-    def point_mode(self) -> Optional[str]:
-        return self._points
-
-    @property
-    def point_transform(self) -> str:
-        return self._transform
-
-    @property
-    def point_seed(self) -> int:
-        return self._seed
-
-    def set_epoch(self, epoch: int):
-        """Part of the key of every point draw ("sample": the host generator; "ids": ``draw_salts``)."""
-        self._epoch = int(epoch)
-
-    def packed(self) -> packing.PackedCellSet:
-        """Every cell of the dataset flattened once; ``object_rows`` index its objects, its ``pad_row`` stands for a pad."""
-        if self._packed is None:
-            self._packed = packing.PackedCellSet(self.all_cells)
-        return self._packed
 
     def get_known_classes(self) -> List[str]:
         """poses.py:583-587 over base.py:70-71: the sorted names of the class index ('pad' included)."""
@@ -557,9 +542,11 @@ class Kitti360FineDataset:
             item["draw_salts"] = draw_salts(self._epoch, idx, self.pad_size)
         return item
 
-    @staticmethod
-    def collate_fn(data):
-        return {key: [d[key] for d in data] for key in data[0].keys()}
+    def _device_batch(self, batch, engine, device):
+        """``_batches``' GPU step: the batch's pad_size * B rows in one launch, cut into one view pair per pose."""
+        pos, col = self.packed().sample_rows(engine, device, np.concatenate(batch["object_rows"]), np.concatenate(batch["draw_salts"]),
+                                             seed=self.point_seed, transform=self.point_transform)
+        batch["object_points"] = _row_views(pos, col, [self.pad_size] * len(batch["object_rows"]))
 
 
 def fine_datasets_from_args(args, object_points: Optional[str] = "sample", seed: int = 0, scenes=None):
@@ -575,6 +562,43 @@ def fine_datasets_from_args(args, object_points: Optional[str] = "sample", seed:
             Kitti360FineDataset(args.base_path, te, args, object_points, val_t, seed))
 
 
+def _checked_batch_size(who: str, batch_size) -> int:
+    """What ``who`` (fine_batches / coarse_batches) refuses before anything else: a DataLoader worker, a batch size below 1."""
+    if torch.utils.data.get_worker_info() is not None:
+        raise RuntimeError(f"{who} works on the GPU and must run in the process that owns the engine, not in a DataLoader worker: let "
+                           f"workers build host items (object_points='sample') or iterate {who} in the main process")
+    if int(batch_size) <= 0:
+        raise ValueError("batch_size must be positive")
+    return int(batch_size)
+
+
+def _row_views(pos, col, counts):
+    """(pos, rgb) f32[n_rows,256,3] of ``sample_rows`` cut into per-item ``{"pos", "x"}`` views [counts[i] * 256, 3] of consecutive rows."""
+    ends = np.cumsum(counts).tolist()
+    return [{"pos": pos[e - c:e].reshape(-1, 3), "x": col[e - c:e].reshape(-1, 3)} for c, e in zip(counts, ends)]
+
+
+def _batches(dataset: _PoseDataset, who: str, batch_size, device, shuffle, seed, epoch, drop_last, engine):
+    """The one batch loop behind ``fine_batches`` and ``coarse_batches`` (``who``): the items of ``dataset`` in the order of
+    ``default_rng([seed, epoch])`` (``shuffle``) or as they lie, collated ``batch_size`` at a time; an ``object_points="ids"`` dataset
+    then finishes each batch on ``device`` (``_device_batch``). ``engine`` None: the weightless engine the dataset keeps per device."""
+    batch_size = _checked_batch_size(who, batch_size)
+    order = np.random.default_rng([int(seed), int(epoch)]).permutation(len(dataset)) if shuffle else np.arange(len(dataset))
+    if dataset.point_mode == "ids" and dataset.wants_points and engine is None:
+        from .plumbing import engine_for
+
+        engine, _ = engine_for(getattr(dataset, "_sampler_engine", None), torch.device(device), who)
+        dataset._sampler_engine = engine
+    for lo in range(0, len(order), batch_size):
+        chunk = order[lo:lo + batch_size]
+        if drop_last and len(chunk) < batch_size:
+            return
+        batch = dataset.collate_fn([dataset[int(i)] for i in chunk])
+        if dataset.point_mode == "ids":
+            dataset._device_batch(batch, engine, device)
+        yield batch
+
+
 def fine_batches(dataset: Kitti360FineDataset, batch_size: int, device, shuffle: bool = False, seed: int = 0, epoch: int = 0,
                  drop_last: bool = False, engine=None):
     """One epoch of ``Kitti360FineDataset.collate_fn`` batches for ``fine_training.train_epoch`` / ``eval_epoch``. With an
@@ -585,33 +609,9 @@ def fine_batches(dataset: Kitti360FineDataset, batch_size: int, device, shuffle:
     epoch) always gives the same batches.
     GPU work belongs to the process that owns the engine: a DataLoader worker may build host items, it may not run this generator.
     ``engine``: the ``Engine`` to sample with (e.g. ``model.engine()``); without one the dataset keeps a weightless one per device."""
-    if torch.utils.data.get_worker_info() is not None:
-        raise RuntimeError("fine_batches samples on the GPU and must run in the process that owns the engine, not in a DataLoader "
-                           "worker: let workers build host items (object_points='sample') or iterate fine_batches in the main process")
-    batch_size = int(batch_size)
-    if batch_size <= 0:
-        raise ValueError("batch_size must be positive")
+    batch_size = _checked_batch_size("fine_batches", batch_size)  # a refused call leaves the dataset's epoch alone
     dataset.set_epoch(epoch)
-    order = np.random.default_rng([int(seed), int(epoch)]).permutation(len(dataset)) if shuffle else np.arange(len(dataset))
-    on_gpu = dataset.point_mode == "ids"
-    if on_gpu and engine is None:
-        from .plumbing import engine_for
-
-        dev = torch.device(device)
-        engine, _ = engine_for(getattr(dataset, "_sampler_engine", None), dev, "fine_batches")
-        dataset._sampler_engine = engine
-    for lo in range(0, len(order), batch_size):
-        chunk = order[lo:lo + batch_size]
-        if drop_last and len(chunk) < batch_size:
-            return
-        batch = Kitti360FineDataset.collate_fn([dataset[int(i)] for i in chunk])
-        if on_gpu:
-            pos, col = dataset.packed().sample_rows(engine, device, np.concatenate(batch["object_rows"]), np.concatenate(batch["draw_salts"]),
-                                                    seed=dataset.point_seed, transform=dataset.point_transform)
-            n = dataset.pad_size
-            batch["object_points"] = [{"pos": pos[i * n:(i + 1) * n].reshape(-1, 3), "x": col[i * n:(i + 1) * n].reshape(-1, 3)}
-                                      for i in range(len(chunk))]
-        yield batch
+    yield from _batches(dataset, "fine_batches", batch_size, device, shuffle, seed, epoch, drop_last, engine)
 
 
 # ---- coarse training batches from the resident cell set -------------------------------------------------------------------------------
@@ -637,39 +637,9 @@ class CoarseBatches:
         return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
 
     def __iter__(self):
-        if torch.utils.data.get_worker_info() is not None:
-            raise RuntimeError(_COARSE_WORKER_REFUSAL)
-        ds = self.dataset
-        epoch = int(getattr(ds, "_epoch", 0))  # train_epoch has advanced it; the items' salts read the same value
-        order = np.random.default_rng([self.seed, epoch]).permutation(len(ds)) if self.shuffle else np.arange(len(ds))
-        on_gpu = ds.point_mode == "ids"
-        engine = self.engine
-        if on_gpu and ds.wants_points and engine is None:
-            from .plumbing import engine_for
-
-            engine, _ = engine_for(getattr(ds, "_sampler_engine", None), torch.device(self.device), "coarse_batches")
-            ds._sampler_engine = engine
-        for lo in range(0, len(order), self.batch_size):
-            chunk = order[lo:lo + self.batch_size]
-            if self.drop_last and len(chunk) < self.batch_size:
-                return
-            batch = Kitti360PoseDataset.collate_fn([ds[int(i)] for i in chunk])
-            if on_gpu:
-                ps, rows = ds.packed(), batch["object_rows"]
-                mirror = np.array(batch["mirror"], dtype=np.uint8)
-                batch["objects"] = CoarseBatchObjects(batch["objects"], ps, rows, mirror)
-                if ds.wants_points:
-                    counts = [len(r) for r in rows]
-                    pos, col = ps.sample_rows(engine, self.device, np.concatenate(rows), np.concatenate(batch["draw_salts"]),
-                                              seed=ds.point_seed, transform=ds.point_transform, mirror=np.repeat(mirror, counts))
-                    ends = np.cumsum(counts)
-                    batch["object_points"] = [{"pos": pos[e - c:e].reshape(-1, 3), "x": col[e - c:e].reshape(-1, 3)}
-                                              for c, e in zip(counts, ends.tolist())]
-            yield batch
-
-
-_COARSE_WORKER_REFUSAL = ("coarse_batches works on the GPU and must run in the process that owns the engine, not in a DataLoader worker: let "
-                          "workers build host items (object_points='sample') or iterate coarse_batches in the main process")
+        # train_epoch has advanced the dataset's epoch; the items' salts read the same value
+        return _batches(self.dataset, "coarse_batches", self.batch_size, self.device, self.shuffle, self.seed, self.dataset._epoch,
+                        self.drop_last, self.engine)
 
 
 def coarse_batches(dataset: Kitti360PoseDataset, batch_size: int, device, shuffle: bool = False, seed: int = 0, drop_last: bool = False,
@@ -685,9 +655,5 @@ def coarse_batches(dataset: Kitti360PoseDataset, batch_size: int, device, shuffl
     The other point modes are collated as they are. The same (dataset seed, seed, epoch) always gives the same batches.
     GPU work belongs to the process that owns the engine: iterating inside a DataLoader worker raises.
     ``engine``: the ``Engine`` to sample with (e.g. ``model.engine()``); without one the dataset keeps a weightless one per device."""
-    if torch.utils.data.get_worker_info() is not None:
-        raise RuntimeError(_COARSE_WORKER_REFUSAL)
-    batch_size = int(batch_size)
-    if batch_size <= 0:
-        raise ValueError("batch_size must be positive")
+    batch_size = _checked_batch_size("coarse_batches", batch_size)
     return CoarseBatches(dataset, batch_size, device, bool(shuffle), int(seed), bool(drop_last), engine)

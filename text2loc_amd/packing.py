@@ -202,13 +202,11 @@ class PackedCellSet:
 
     def sample_rows(self, engine, device, rows, salts=None, seed: int = 0, transform: str = "fixed", mirror=None):
         """FixedPoints(256) (+ the transform) for a list of object rows of this set, ``pad_row`` included, in ONE launch
-        (t2l_sample_object_points_indexed) from the resident points: -> (pos f32[n_rows,256,3], rgb f32[n_rows,256,3]) on ``device``.
+        (t2l_sample_object_points_mirrored) from the resident points: -> (pos f32[n_rows,256,3], rgb f32[n_rows,256,3]) on ``device``.
         Row r is drawn under ``seed ^ salts[r]``; chunking, order and repetition of rows do not change a draw.
-        ``mirror`` u8[n_rows] (t2l_sample_object_points_mirrored): the rows of flipped cells — bit 0: x -> 1 - x, bit 1: y -> 1 - y on
-        the gathered points, before the transform, with the draws of the un-mirrored row."""
+        ``mirror`` u8[n_rows] | None (= every code 0): the rows of flipped cells — bit 0: x -> 1 - x, bit 1: y -> 1 - y on the gathered
+        points, before the transform, with the draws of the un-mirrored row."""
         d = self.on_device(device)
-        if mirror is None:
-            return engine.sample_object_points_indexed(d["xyz"], d["rgb"], d["point_offsets_pad"], rows, salts, seed=seed, transform=transform)
         return engine.sample_object_points_mirrored(d["xyz"], d["rgb"], d["point_offsets_pad"], rows, salts, mirror, seed=seed,
                                                     transform=transform)
 

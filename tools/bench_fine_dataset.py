@@ -7,7 +7,7 @@ on: both draw 256 indices per object whatever its size), at B = 32 and B = 256:
   host_upload_ms   what the step then does with those batches first: concatenate and copy them over (``plumbing.point_batch_tensors``);
   ids_host_ms      ``object_points="ids"`` + ``fine_batches``: items + collate + the ONE launch, host time per batch (the launch is
                    asynchronous; ``ids_wall_ms`` is the same loop with the device drained at the end of the 20 batches);
-  sample_rows_ms   device time of that launch (t2l_sample_object_points_indexed over 16 * B rows), by events;
+  sample_rows_ms   device time of that launch (the row sampler over 16 * B rows, no mirror codes), by events;
   pack_first_ms /  ``plumbing.pack_objects`` on a batch's objects, the first time that batch is packed and again. An item's colour indices
   pack_again_ms    already put every object's reductions into the host cache (``packing.object_features``), so neither goes through
                    t2l_reduce_objects here: both are the host packing of cached values plus their copy;
