@@ -354,6 +354,13 @@ __device__ __forceinline__ void f_attention_regs(const float* __restrict__ x, Ti
   }
 }
 
+// In-layer tap of the decoder passes below: called with the x tile after the first (0) and the second (1) residual + LayerNorm. Empty
+// in the product (no instruction is emitted for it); the dev-only block library (fine_blocks.hip) passes one that copies the tile out.
+struct FNoTap {
+  template <typename TILE>
+  __device__ __forceinline__ void operator()(int, const TILE&) const {}
+};
+
 // x += A @ W^T + b for a 128 -> 128 Linear (out_proj): one 32-column tile per wave
 __device__ __forceinline__ void f_proj_add(const float* __restrict__ A, const FPacked L, float* __restrict__ x) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, col = lane & 31, half = lane >> 5;
@@ -371,8 +378,9 @@ __device__ __forceinline__ void f_proj_add(const float* __restrict__ A, const FP
 // mem2 != nullptr: the memory is TWO tiles (the hint tile of four pairs attends the pairs' two object tiles).
 // This f32 tile form (f32 MFMA on f32 token tiles) stands beside the plane form below because it is the fallback: the workgroups
 // the run-time guard turns away, weights that do not bound the activations, and option encoder_f32.
+template <typename TAP = FNoTap>
 __device__ void f_decoder(float* x, TileGroups gx, const float* mem, TileGroups gm, const FDecoder D, float* buf,
-                          const float* mem2 = nullptr, TileGroups gm2 = TileGroups{0, 0, 0, 0}) {
+                          const float* mem2 = nullptr, TileGroups gm2 = TileGroups{0, 0, 0, 0}, TAP tap = TAP{}) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, col = lane & 31, half = lane >> 5;
   f_attention_regs(x, gx, x, gx, D.sa_in, buf);
   __syncthreads();
@@ -380,6 +388,7 @@ __device__ void f_decoder(float* x, TileGroups gx, const float* mem, TileGroups 
   __syncthreads();
   f_ln_rows(x, kFS, gx.rows, D.g1, D.b1);
   __syncthreads();
+  tap(0, x);
   f_attention_regs(x, gx, mem, gm, D.ca_in, buf);
   if (mem2) f_attention_regs<true>(x, gx, mem2, gm2, D.ca_in, buf);  // (same wave, same obuf columns: ordered without a barrier)
   __syncthreads();
@@ -387,6 +396,7 @@ __device__ void f_decoder(float* x, TileGroups gx, const float* mem, TileGroups 
   __syncthreads();
   f_ln_rows(x, kFS, gx.rows, D.g2, D.b2);
   __syncthreads();
+  tap(1, x);
   {  // feed-forward 128 -> 512 -> 128: the hidden layer passes through buf in four quarters of 128 units — the units that
      // k-steps [16 q, 16 q + 16) of the half-split packing of W2 (K = 512) cover — W2's product accumulates in registers
     f32x16 acc;
@@ -600,9 +610,9 @@ __device__ __forceinline__ void fp_attention(const FP x, TileGroups gx, const FP
     if (!SHARED || any) plane_put4(obuf.hi, obuf.lo, off, o4);
   }
 }
-template <int H>
+template <int H, typename TAP = FNoTap>
 __device__ void fp_decoder(const FP x, TileGroups gx, const FP mem, TileGroups gm, const FDecoder D, const FP buf, float* red,
-                           const FP* mem2 = nullptr, TileGroups gm2 = TileGroups{0, 0, 0, 0}) {
+                           const FP* mem2 = nullptr, TileGroups gm2 = TileGroups{0, 0, 0, 0}, TAP tap = TAP{}) {
   constexpr bool SG = H == 2;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, col = lane & 31, half = lane >> 5;
   const int aoff = col * kLdF + half * (kFD / 2);
@@ -617,6 +627,7 @@ __device__ void fp_decoder(const FP x, TileGroups gx, const FP mem, TileGroups g
   __syncthreads();
   proj_add_ln(D.sa_out, D.g1, D.b1);
   __syncthreads();
+  tap(0, x);
   if (!mem2) {
     fp_attention<H, false>(x, gx, mem, gm, false, D.ca_in, buf);
   } else {  // (every query row has its keys in exactly one of the two tiles)
@@ -626,6 +637,7 @@ __device__ void fp_decoder(const FP x, TileGroups gx, const FP mem, TileGroups g
   __syncthreads();
   proj_add_ln(D.ca_out, D.g2, D.b2);
   __syncthreads();
+  tap(1, x);
   {  // feed-forward 128 -> 512 -> 128, the hidden layer through buf in four quarters (see f_decoder)
     f32x16 acc;
 #pragma unroll
