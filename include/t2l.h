@@ -461,6 +461,48 @@ int t2l_pointnet_features_train(t2l_ctx* ctx, const float* pos, const float* rgb
  * dev f32[n_objects,256]. Parameter gradients are ADDED to the bound buffers. */
 int t2l_pointnet_backward(t2l_ctx* ctx, const float* grad_features2, void* stream);
 
+/* ---- pretraining the backbone as an object classifier (what produces the reference's --pointnet_path file) ------------------- */
+/* The reference loads a pretrained backbone unconditionally (models/object_encoder.py:50); that checkpoint comes from training
+ * PointNet2 as a classifier: class_pred = class_classifier(features2), color_pred = color_classifier(features2)
+ * (models/pointcloud/pointnet2.py:64-65, 91-92), two Linear(256, C) heads. The snapshot has no script for the step, so it is defined
+ * by those heads, the key layout, the transforms of training/coarse.py:182-193 and the plain softmax cross-entropy.
+ * PARITY UNPINNED like the rest of the backbone. */
+#define T2L_CLS_MAX_CLASSES 32 /* classes per head: 2 <= C <= 32, read off the bound bias tensors (22 and 8 today) */
+
+/* Binds every object_encoder.pointnet.{sa1,sa2,sa3,ga,lin1,lin2} tensor as t2l_train_bind does for the backbone — all WITH gradient
+ * buffers, or all WITHOUT (frozen: only the heads train; the forward still runs in training mode) — and the four head tensors
+ * object_encoder.pointnet.{class,color}_classifier.{weight [C,256], bias [C]} WITH gradient buffers. Anything else is T2L_EINVAL
+ * and the previous binding stays intact. The state is this call's own: t2l_train_bind / t2l_fine_train_bind are not touched.
+ * Pointers must stay valid until the next bind. Synchronous. */
+int t2l_pointnet_cls_bind(t2l_ctx* ctx, const t2l_train_tensor* tensors, int32_t n);
+
+/* PointNet2.forward up to features2 under model.train() (pointnet2.py:67-90) over ONE batch of objects — one segment: every
+ * BatchNorm1d uses the statistics of all n_objects and updates its running statistics once, as a single PyG batch does.
+ * pos, rgb: dev f32[n_objects,256,3]; out_features2: dev f32[n_objects,256]. Activations stay in the context until the next call. */
+int t2l_pointnet_cls_forward(t2l_ctx* ctx, const float* pos, const float* rgb, int32_t n_objects, float* out_features2, void* stream);
+
+/* The two heads of the bound tensors (pointnet2.py:91-92) and their softmax cross-entropy over any features2 the caller supplies,
+ * forward and backward in ONE launch. features2: dev f32[n,256]; class_labels, color_labels: HOST i32[n], range-checked before
+ * anything is launched — a label outside [0, C) is T2L_EINVAL naming the row, and no output byte is written (no ignore index, no
+ * class weights). out_logits: dev f32[n, C1 + C2] (class columns first) or NULL; out_loss: dev f32[2], the mean cross-entropy of
+ * each head over the n rows (float64 accumulation); out_correct: dev i32[2], rows whose FIRST arg-max equals the label.
+ * grad_features2: dev f32[n,256] receiving d (w_class loss[0] + w_color loss[1]) / d features2, and the four head gradients are
+ * ADDED to the bound buffers (float atomics across workgroups: beyond 32 rows their last bits vary between runs; everything
+ * else is the same bits every run) — or NULL: forward only, no gradient buffer is touched (eval mode: t2l_pointnet_features,
+ * then this). Alignment: 4 bytes for every device array. */
+int t2l_pointnet_cls_heads(t2l_ctx* ctx, const float* features2, int32_t n, const int32_t* class_labels, const int32_t* color_labels,
+                           float w_class, float w_color, float* out_logits, float* out_loss, int32_t* out_correct, float* grad_features2,
+                           void* stream);
+
+/* Backward of t2l_pointnet_cls_forward: grad_features2 as the heads call wrote it, dev f32[n_objects,256]. Backbone gradients are
+ * ADDED to the bound buffers. T2L_ESTATE on a frozen binding (bound without gradient buffers) or without a forward. */
+int t2l_pointnet_cls_backward(t2l_ctx* ctx, const float* grad_features2, void* stream);
+
+/* Eval-mode weights of the backbone ALONE (what t2l_pointnet_features reads), for a state dict that holds no object branch — a
+ * --pointnet_path file (pointnet2.py:91-92 heads included, which this call ignores): keys object_encoder.pointnet.*. T2L_EINVAL when
+ * the list holds none of them or an incomplete set; a failed load changes nothing. */
+int t2l_pointnet_load_weights(t2l_ctx* ctx, const t2l_weight_desc* w, int32_t n);
+
 /* optimizer.zero_grad() and torch.optim.Adam(lr, betas, eps).step() (no weight decay, no amsgrad — what
  * training/coarse.py:258 constructs) over every bound tensor that has a gradient buffer. torch.optim.Adam skips parameters
  * whose .grad is None and counts steps per parameter; here the bound tensors form two groups with a step counter each — the

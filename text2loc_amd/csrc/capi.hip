@@ -134,6 +134,7 @@ void t2l_destroy(t2l_ctx* ctx) {
   free_sample_stage(ctx);
   free_fine(ctx);
   free_fine_train(ctx);
+  free_cls_train(ctx);
   free_text_head(ctx);
   for (void* p : {(void*)ctx->db, (void*)ctx->db_split, (void*)ctx->db_half, (void*)ctx->db_norm_max, (void*)ctx->cand_score, (void*)ctx->seg_idx,
                   (void*)ctx->seg_score, (void*)ctx->flags, (void*)(ctx->fb_count < ctx->fb_prev ? ctx->fb_count : ctx->fb_prev), ctx->fast_ws, (void*)ctx->fast_zero, ctx->reduce_ws, ctx->loss_ws, (void*)ctx->small_ticket, ctx->small_part, (void*)ctx->scan_span})
@@ -625,6 +626,43 @@ int t2l_pointnet_backward(t2l_ctx* ctx, const float* grad_features2, void* strea
   if (!ctx) return T2L_EINVAL;
   T2L_HIP(ctx, hipSetDevice(ctx->device));
   return pn_train_backward_impl(ctx, grad_features2, (hipStream_t)stream);
+}
+
+int t2l_pointnet_load_weights(t2l_ctx* ctx, const t2l_weight_desc* w, int32_t n) {
+  if (!ctx) return T2L_EINVAL;
+  if (!w || n <= 0) return fail(ctx, T2L_EINVAL, "t2l_pointnet_load_weights: null/empty arguments");
+  T2L_HIP(ctx, hipSetDevice(ctx->device));
+  PointNetStaged* pn = nullptr;
+  if (int rc = pointnet_stage(ctx, "t2l_pointnet_load_weights", w, n, &pn)) return rc;
+  if (!pn) return fail(ctx, T2L_EINVAL, "t2l_pointnet_load_weights: the list holds no object_encoder.pointnet.* tensor");
+  return pointnet_commit(ctx, "t2l_pointnet_load_weights", pn);
+}
+
+int t2l_pointnet_cls_bind(t2l_ctx* ctx, const t2l_train_tensor* tensors, int32_t n) {
+  if (!ctx) return T2L_EINVAL;
+  T2L_HIP(ctx, hipSetDevice(ctx->device));
+  return cls_bind_impl(ctx, tensors, n);
+}
+
+int t2l_pointnet_cls_forward(t2l_ctx* ctx, const float* pos, const float* rgb, int32_t n_objects, float* out_features2, void* stream) {
+  if (!ctx) return T2L_EINVAL;
+  T2L_HIP(ctx, hipSetDevice(ctx->device));
+  return cls_forward_impl(ctx, pos, rgb, n_objects, out_features2, (hipStream_t)stream);
+}
+
+int t2l_pointnet_cls_heads(t2l_ctx* ctx, const float* features2, int32_t n, const int32_t* class_labels, const int32_t* color_labels,
+                           float w_class, float w_color, float* out_logits, float* out_loss, int32_t* out_correct, float* grad_features2,
+                           void* stream) {
+  if (!ctx) return T2L_EINVAL;
+  T2L_HIP(ctx, hipSetDevice(ctx->device));
+  return cls_heads_impl(ctx, features2, n, class_labels, color_labels, w_class, w_color, out_logits, out_loss, out_correct, grad_features2,
+                        (hipStream_t)stream);
+}
+
+int t2l_pointnet_cls_backward(t2l_ctx* ctx, const float* grad_features2, void* stream) {
+  if (!ctx) return T2L_EINVAL;
+  T2L_HIP(ctx, hipSetDevice(ctx->device));
+  return cls_backward_impl(ctx, grad_features2, (hipStream_t)stream);
 }
 
 int t2l_zero_grad(t2l_ctx* ctx, void* stream) {

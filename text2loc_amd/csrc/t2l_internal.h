@@ -120,6 +120,7 @@ struct t2l_ctx {
   void* fine_train = nullptr;    // t2l::ft::FineTrain (fine_train.hip): the fine stage's training state
   void* text_head = nullptr;     // t2l::th::Weights (text_head.hip)
   void* text_train = nullptr;    // t2l::TextTrain (train.hip): the text head's training state
+  void* cls_train = nullptr;     // t2l::cls::ClsTrain (pointnet_cls.hip): the backbone's pretraining as a classifier
   // cross-rank BatchNorm statistics (t2l_train_sync_bn): the accumulator slots live in the caller's buffer and the callback sums a
   // range of it over the ranks, ordered on the stream it is handed
   int (*sync_fn)(void* user, double* buf, int64_t n, void* stream) = nullptr;
@@ -294,6 +295,13 @@ int fine_train_forward_points_impl(t2l_ctx* ctx, const t2l_packed_cells* in, con
                                    int n_pairs, int n_hints, float p, uint32_t seed, float* out, hipStream_t s);
 int fine_train_backward_impl(t2l_ctx* ctx, const float* grad_offsets, float* grad_hint, float* grad_pn, hipStream_t s);
 void free_fine_train(t2l_ctx* ctx);
+// pointnet_cls.hip
+int cls_bind_impl(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n);
+int cls_forward_impl(t2l_ctx* ctx, const float* pos, const float* rgb, int n_objects, float* out_f2, hipStream_t s);
+int cls_heads_impl(t2l_ctx* ctx, const float* f2, int n, const int32_t* class_labels, const int32_t* color_labels, float w_class,
+                   float w_color, float* out_logits, float* out_loss, int32_t* out_correct, float* grad_f2, hipStream_t s);
+int cls_backward_impl(t2l_ctx* ctx, const float* grad_f2, hipStream_t s);
+void free_cls_train(t2l_ctx* ctx);
 // text_head.hip
 int text_head_load_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const char* prefix, int inter_num_heads);
 int text_head_impl(t2l_ctx* ctx, const float* hidden, int n_sentences, int n_tokens, float* out, int32_t* overflow, hipStream_t s);

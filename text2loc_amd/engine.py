@@ -138,6 +138,12 @@ EXPORTS = {
     "t2l_text_head_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "t2l_pointnet_features_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "t2l_pointnet_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "t2l_pointnet_cls_bind": (C.c_int, [C.c_void_p, C.POINTER(_TrainTensor), C.c_int32]),
+    "t2l_pointnet_cls_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "t2l_pointnet_cls_heads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "t2l_pointnet_cls_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "t2l_pointnet_load_weights": (C.c_int, [C.c_void_p, C.POINTER(_WeightDesc), C.c_int32]),
     "t2l_text_adam_step": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "t2l_text_zero_grad": (C.c_int, [C.c_void_p, C.c_void_p]),
     "t2l_text_adam_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
@@ -656,6 +662,67 @@ class Engine:
     def pointnet_backward(self, grad_features2: torch.Tensor):
         self._check(self.lib.t2l_pointnet_backward(self._h, self._ptr(grad_features2, torch.float32, "grad_features2"),
                                                    _stream_ptr(self.device)))
+
+    # ------------------------------------------------------------------ pretraining the backbone as a classifier (t2l_pointnet_cls_*)
+    def pointnet_load_weights(self, state_dict: Dict[str, object]):
+        """Eval-mode weights of the backbone alone (``pointnet_features``) from the ``object_encoder.pointnet.*`` keys of a state
+        dict that holds no object branch (a ``pointnet_path`` file under that prefix); the classifier heads are not read."""
+        heads = ("object_encoder.pointnet.class_classifier.", "object_encoder.pointnet.color_classifier.")
+        arr, _keep = _weight_descs(state_dict, lambda name: name.startswith("object_encoder.pointnet.") and not name.startswith(heads))
+        self._check(self.lib.t2l_pointnet_load_weights(self._h, arr, len(arr)))
+
+    def pointnet_cls_bind(self, tensors: Dict[str, Tuple[torch.Tensor, Optional[torch.Tensor]]]):
+        """tensors: ``object_encoder.pointnet.*`` key -> (live fp32 CUDA tensor, its gradient buffer | None): the whole backbone with
+        gradient buffers or without (frozen), the four classifier-head tensors with. POINTERS are kept: keep the tensors alive.
+        A refused bind leaves the previous one serving."""
+        descs, keep = [], []
+        for name, (data, grad) in tensors.items():
+            keep.append((data, grad))
+            descs.append(_TrainTensor(name.encode(), self._ptr(data, torch.float32, name),
+                                      self._ptr(grad, torch.float32, name + ".grad"), data.numel()))
+        arr = (_TrainTensor * len(descs))(*descs)
+        self._check(self.lib.t2l_pointnet_cls_bind(self._h, arr, len(descs)))
+        self._cls_keepalive = keep
+        self._cls_classes = tuple(int(tensors[f"object_encoder.pointnet.{h}_classifier.bias"][0].numel()) for h in ("class", "color"))
+
+    def pointnet_cls_forward(self, pos: torch.Tensor, rgb: torch.Tensor) -> torch.Tensor:
+        """pos, rgb f32[n,256,3] -> features2 f32[n,256] under model.train(), the batch as ONE BatchNorm segment."""
+        n = int(pos.shape[0])
+        if tuple(pos.shape) != (n, 256, 3) or tuple(rgb.shape) != (n, 256, 3):
+            raise T2LError(f"pointnet_cls_forward: expected [n,256,3] points, got {tuple(pos.shape)}, {tuple(rgb.shape)}")
+        out = torch.empty((n, EMBED_DIM), dtype=torch.float32, device=pos.device)
+        self._check(self.lib.t2l_pointnet_cls_forward(self._h, self._ptr(pos, torch.float32, "pos"), self._ptr(rgb, torch.float32, "rgb"),
+                                                      n, out.data_ptr(), _stream_ptr(self.device)))
+        self._cls_inputs = (pos, rgb)
+        return out
+
+    def pointnet_cls_heads(self, features2: torch.Tensor, class_labels, color_labels, w_class: float = 1.0, w_color: float = 1.0,
+                           need_grad: bool = True, need_logits: bool = True):
+        """features2 f32[n,256]; ``class_labels`` / ``color_labels`` i32[n] are HOST arrays (a label out of range raises before anything
+        is launched; no output is written). -> (logits f32[n,C1+C2] | None, loss f32[2], correct i32[2], d features2 f32[n,256] | None).
+        With ``need_grad`` the four head gradients are ADDED to the bound buffers."""
+        n = int(features2.shape[0])
+        if tuple(features2.shape) != (n, EMBED_DIM):
+            raise T2LError(f"pointnet_cls_heads: features2 must be [n,{EMBED_DIM}], got {tuple(features2.shape)}")
+        lc = np.ascontiguousarray(class_labels, dtype=np.int32).reshape(-1)
+        lk = np.ascontiguousarray(color_labels, dtype=np.int32).reshape(-1)
+        if lc.size != n or lk.size != n:
+            raise T2LError(f"pointnet_cls_heads: {n} rows but {lc.size} class labels and {lk.size} colour labels")
+        c1, c2 = getattr(self, "_cls_classes", None) or (0, 0)  # (unbound: the library raises below)
+        dev = features2.device
+        logits = torch.empty((n, c1 + c2), dtype=torch.float32, device=dev) if need_logits else None
+        loss = torch.empty((2,), dtype=torch.float32, device=dev)
+        correct = torch.empty((2,), dtype=torch.int32, device=dev)
+        grad = torch.empty_like(features2) if need_grad else None
+        self._check(self.lib.t2l_pointnet_cls_heads(self._h, self._ptr(features2, torch.float32, "features2"), n, lc.ctypes.data,
+                                                    lk.ctypes.data, float(w_class), float(w_color), self._ptr(logits, torch.float32, "logits"),
+                                                    loss.data_ptr(), correct.data_ptr(), self._ptr(grad, torch.float32, "grad_features2"),
+                                                    _stream_ptr(self.device)))
+        return logits, loss, correct, grad
+
+    def pointnet_cls_backward(self, grad_features2: torch.Tensor):
+        self._check(self.lib.t2l_pointnet_cls_backward(self._h, self._ptr(grad_features2, torch.float32, "grad_features2"),
+                                                       _stream_ptr(self.device)))
 
     def train_sync_bn(self, group=None, enable: bool = True):
         """Cross-rank BatchNorm statistics for data-parallel training (t2l.h: t2l_train_sync_bn): every BatchNorm of the object branch

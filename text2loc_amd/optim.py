@@ -58,7 +58,7 @@ class Adam(torch.optim.Optimizer):
                 text.append(p)  # the text head's trained parameters: t2l_text_adam_step (one launch, moments inside the library)
                 continue
             if n.startswith(("object_encoder.pointnet.class_classifier.", "object_encoder.pointnet.color_classifier.")):
-                rest.append(p)  # not on the path (features2 is consumed): .grad stays None, torch skips them as in the reference
+                rest.append(p)  # not on the coarse path (features2 is consumed; they train in pointnet_pretrain): .grad stays None, torch skips them as in the reference
             elif n.startswith(("object_encoder.", "obj_inter_module.")):
                 obj.append(p)   # incl. the PointNet++ backbone unless --pointnet_freeze
             else:

@@ -88,7 +88,7 @@ def make_object_branch_weights(seed: int = 0, embed_dim: int = 256, num_layers: 
 def make_pointnet_weights(seed: int = 0, n_classes: int = 22, n_colors: int = 8) -> dict:
     """state_dict (numpy) of ``object_encoder.pointnet.*`` with the reference's key layout
     (models/pointcloud/pointnet2.py:52-64): three SetAbstraction get_mlp's, the global get_mlp, lin1, lin2 and the
-    two (unused on this path) classifier heads."""
+    two classifier heads (read by the backbone's pretraining step only: ``pointnet_pretrain``, t2l_pointnet_cls_heads)."""
     rng = np.random.default_rng([seed, 0x9A27])
     sd: dict = {}
     p = "object_encoder.pointnet."
