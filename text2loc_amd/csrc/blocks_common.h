@@ -1,4 +1,4 @@
-// What the translation units of the dev-only block library (libt2l_blocks.so: train_blocks.hip, pointnet_blocks.hip, fine_blocks.hip, fine_train_blocks.hip) share: one
+// What the translation units of the dev-only block library (libt2l_blocks.so: train_blocks.hip, pointnet_blocks.hip, fine_blocks.hip, fine_train_blocks.hip, text_head_blocks.hip) share: one
 // thread-local error text behind t2l_blk_last_error. Defined in train_blocks.hip.
 #pragma once
 #include <string>

@@ -233,7 +233,11 @@ __global__ __launch_bounds__(512, 1) void th_gemm_kernel(const GemmArgs p) {
   issue();
   issue();
   issue();
-  // (total >= 64: every wait below has its three younger groups except at the very end)
+  // The four issue() calls above put min(total, 4) groups in flight, and vmcnt(3 * PPW) certifies group 0 only when FOUR were issued
+  // (with fewer, at most 3 * PPW pieces are outstanding and the wait passes at once): the kernel needs total = n_my * KT >= 4 for every
+  // workgroup that has a job, i.e. K >= 64 for a lone tile. The product never goes below: the head's K is 1024 / 4096, fast_gemm pads
+  // the contraction to a multiple of 64 and its k-split keeps KT >= 8. From there on every wait has its three younger groups except at
+  // the very end (`ahead`).
   wait_vmcnt<3 * PPW>();
   asm volatile("s_barrier" ::: "memory");
   Frags fa, fb;
@@ -702,6 +706,7 @@ struct Weights {
   size_t ws_cap = 0;
   int* flag = nullptr;        // device overflow flag
   int* flag_host = nullptr;   // pinned copy target
+  int last_n_sent = 0, last_L = 0, last_rows = 0;  // the shape of the last t2l_text_head call (th_layout's arguments)
 };
 
 static void pack_t16(const float* W, int rows, int rows_pad, int K, std::vector<uint16_t>& hi, std::vector<uint16_t>& lo) {
@@ -721,6 +726,8 @@ static void pack_t16(const float* W, int rows, int rows_pad, int K, std::vector<
 }  // namespace th
 
 using th::Weights;
+
+static hipError_t th_kernel_attributes(int device);
 
 void free_text_head(t2l_ctx* ctx) {
   Weights* W = (Weights*)ctx->text_head;
@@ -820,17 +827,7 @@ int text_head_load_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const cha
       W->inter_heads = inter_num_heads;
     }
   }
-  static PerDeviceOnce attr_done;
-  if (attr_done.need(ctx->device)) {
-    const int lds = kSlots * kSlotBytes;
-#define T2L_TH_ATTR(E, S) T2L_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&th_gemm_kernel<E, S>), hipFuncAttributeMaxDynamicSharedMemorySize, lds))
-    T2L_TH_ATTR(kEpiT32, false); T2L_TH_ATTR(kEpiT32, true); T2L_TH_ATTR(kEpiResidT32, false); T2L_TH_ATTR(kEpiResidT32, true);
-    T2L_TH_ATTR(kEpiReluT16, false); T2L_TH_ATTR(kEpiReluT16, true); T2L_TH_ATTR(kEpiRowMajor, false); T2L_TH_ATTR(kEpiRowMajor, true);
-#undef T2L_TH_ATTR
-    T2L_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&th_ln_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 32 * 1028 * 4));
-    T2L_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&th_ln_kernel<true, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, 32 * 260 * 4));
-    attr_done.mark(ctx->device);
-  }
+  T2L_HIP(ctx, th_kernel_attributes(ctx->device));
   // everything is validated and staged: the overflow flag pair, one allocation and one copy of the weights, then the old set goes and
   // the new one is published
   hipError_t e = hipMalloc(&W->flag, sizeof(int));
@@ -848,8 +845,29 @@ int text_head_load_impl(t2l_ctx* ctx, const t2l_weight_desc* w, int n, const cha
   return T2L_OK;
 }
 
-template <int EPI>
-static void th_launch_gemm(bool single, const th::GemmArgs& a, hipStream_t s) {
+// The dynamic-LDS attributes of every th_gemm_kernel instance (the four-slot ring: 128 KiB) and of the pooling LayerNorm, once per device.
+static hipError_t th_kernel_attributes(int device) {
+  using namespace th;
+  static PerDeviceOnce attr_done;
+  if (!attr_done.need(device)) return hipSuccess;
+  const int lds = kSlots * kSlotBytes;
+  hipError_t e = hipSuccess;
+#define T2L_TH_ATTR(...) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&th_gemm_kernel<__VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)
+  T2L_TH_ATTR(kEpiT32, false); T2L_TH_ATTR(kEpiT32, true); T2L_TH_ATTR(kEpiResidT32, false); T2L_TH_ATTR(kEpiResidT32, true);
+  T2L_TH_ATTR(kEpiReluT16, false); T2L_TH_ATTR(kEpiReluT16, true); T2L_TH_ATTR(kEpiRowMajor, false); T2L_TH_ATTR(kEpiRowMajor, true);
+  T2L_TH_ATTR(kEpiRowMajor, false, true); T2L_TH_ATTR(kEpiRowMajor, true, true);  // the bf16 instances of fast_gemm
+#undef T2L_TH_ATTR
+  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&th_ln_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 32 * 1028 * 4);
+  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&th_ln_kernel<true, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, 32 * 260 * 4);
+  if (e == hipSuccess) attr_done.mark(device);
+  return e;
+}
+
+// Launch geometry of th_gemm_kernel: ONE CU count and ONE grid rule for every launch of it (the head's GEMMs and fast_gemm). The kernel
+// is persistent and written for any grid that is a multiple of 8 (vb % 8 = blockIdx % 8 picks the m tile within a group of eight).
+static int th_cu_override = 0;  // dev only: the block library sets it (text_head_blocks.hip: t2l_blk_th_set_cus); the product never does
+static int th_cu_count() {
+  if (th_cu_override) return th_cu_override;
   static int n_cu = 0;
   if (!n_cu) {
     int dev = 0;
@@ -857,11 +875,45 @@ static void th_launch_gemm(bool single, const th::GemmArgs& a, hipStream_t s) {
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
     if (n_cu < 8) n_cu = 256;
   }
-  const int n_vb = (a.m_tiles + 7) / 8 * 8 * a.n_tiles;
-  const int grid = min(n_cu / 8 * 8, n_vb);  // persistent: one workgroup per CU, a multiple of the 8 XCDs
+  return n_cu;
+}
+static int th_gemm_grid(int m_tiles, int n_tiles, int ks) {  // one workgroup per CU, a multiple of the 8 XCDs, at most one per job slot
+  const int n_vb = (m_tiles + 7) / 8 * 8 * n_tiles * ks;
+  return min(th_cu_count() / 8 * 8, n_vb);
+}
+
+template <int EPI>
+static void th_launch_gemm(bool single, const th::GemmArgs& a, hipStream_t s) {
+  const int grid = th_gemm_grid(a.m_tiles, a.n_tiles, 1);
   const int lds = th::kSlots * th::kSlotBytes;
   if (single) hipLaunchKernelGGL((th::th_gemm_kernel<EPI, true>), dim3(grid), dim3(512), lds, s, a);
   else hipLaunchKernelGGL((th::th_gemm_kernel<EPI, false>), dim3(grid), dim3(512), lds, s, a);
+}
+
+// The workspace of one t2l_text_head call: X planes, QKV (T32), O planes, Y (T32), X1 planes, H planes of one pass (m_cap rows); pooled
+// f32 + its planes of all sentences (sp_cap rows). Byte offsets, each a multiple of 256.
+struct ThLayout {
+  int spc, m_cap, n_chunks, sp_cap;  // sentences per pass, padded token rows of a pass, passes, padded pooled rows
+  size_t o_xh, o_xl, o_qkv, o_oh, o_ol, o_y, o_1h, o_1l, o_hh, o_hl, o_pool, o_ph, o_pl, bytes;
+};
+static ThLayout th_layout(int n_sent, int L, int text_head_rows) {
+  using namespace th;
+  ThLayout y;
+  // sentences per pass: ~16 k token rows keep every intermediate of a pass inside the 256 MB Infinity Cache and make every
+  // GEMM grid a multiple of the 256 CUs (64 m tiles x 12 / 4 / 16 / 4 n tiles)
+  const int rows_target = text_head_rows > 0 ? text_head_rows : 16384;
+  y.spc = max(1, min(n_sent, rows_target / L));
+  y.m_cap = (y.spc * L + kTile - 1) / kTile * kTile;
+  y.n_chunks = (n_sent + y.spc - 1) / y.spc;
+  y.sp_cap = (n_sent + kTile - 1) / kTile * kTile;
+  const size_t plane = (size_t)y.m_cap * kDM * 2;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+  y.o_xh = take(plane), y.o_xl = take(plane), y.o_qkv = take((size_t)y.m_cap * 3 * kDM * 4), y.o_oh = take(plane), y.o_ol = take(plane),
+  y.o_y = take((size_t)y.m_cap * kDM * 4), y.o_1h = take(plane), y.o_1l = take(plane), y.o_hh = take(plane * 4), y.o_hl = take(plane * 4),
+  y.o_pool = take((size_t)y.sp_cap * kDM * 4), y.o_ph = take((size_t)y.sp_cap * kDM * 2), y.o_pl = take((size_t)y.sp_cap * kDM * 2);
+  y.bytes = off;
+  return y;
 }
 
 int text_head_impl(t2l_ctx* ctx, const float* hidden, int n_sent, int L, float* out, int32_t* overflow, hipStream_t s) {
@@ -872,20 +924,11 @@ int text_head_impl(t2l_ctx* ctx, const float* hidden, int n_sent, int L, float* 
   if (n_sent <= 0) return n_sent == 0 ? T2L_OK : fail(ctx, T2L_EINVAL, "t2l_text_head: n_sentences < 0");
   if (L < 1 || L > kMaxL) return fail(ctx, T2L_EINVAL, "t2l_text_head: need 1 <= n_tokens <= 32");
   const bool single = ctx->encoder_f16 != 0;
-  // sentences per pass: ~16 k token rows keep every intermediate of a pass inside the 256 MB Infinity Cache and make every
-  // GEMM grid a multiple of the 256 CUs (64 m tiles x 12 / 4 / 16 / 4 n tiles)
-  const int rows_target = ctx->text_head_rows > 0 ? ctx->text_head_rows : 16384;
-  const int spc = max(1, min(n_sent, rows_target / L));
-  const int m_cap = (spc * L + kTile - 1) / kTile * kTile;
-  const int n_chunks = (n_sent + spc - 1) / spc;
-  const int sp_cap = (n_sent + kTile - 1) / kTile * kTile;  // pooled rows (all sentences), padded
-  // workspace: X planes, QKV (T32), O planes, Y (T32), X1 planes, H planes; pooled f32 + its planes
-  const size_t plane = (size_t)m_cap * kDM * 2;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-  const size_t o_xh = take(plane), o_xl = take(plane), o_qkv = take((size_t)m_cap * 3 * kDM * 4), o_oh = take(plane), o_ol = take(plane),
-               o_y = take((size_t)m_cap * kDM * 4), o_1h = take(plane), o_1l = take(plane), o_hh = take(plane * 4), o_hl = take(plane * 4),
-               o_pool = take((size_t)sp_cap * kDM * 4), o_ph = take((size_t)sp_cap * kDM * 2), o_pl = take((size_t)sp_cap * kDM * 2);
+  const ThLayout y = th_layout(n_sent, L, ctx->text_head_rows);
+  const int spc = y.spc, n_chunks = y.n_chunks, sp_cap = y.sp_cap;
+  const size_t off = y.bytes, o_xh = y.o_xh, o_xl = y.o_xl, o_qkv = y.o_qkv, o_oh = y.o_oh, o_ol = y.o_ol, o_y = y.o_y, o_1h = y.o_1h, o_1l = y.o_1l,
+               o_hh = y.o_hh, o_hl = y.o_hl, o_pool = y.o_pool, o_ph = y.o_ph, o_pl = y.o_pl;
+  W->last_n_sent = n_sent, W->last_L = L, W->last_rows = ctx->text_head_rows;
   if (W->ws_cap < off) {
     if (W->ws) T2L_HIP(ctx, hipFree(W->ws));
     W->ws = nullptr;
@@ -982,6 +1025,12 @@ int text_inter_impl(t2l_ctx* ctx, const float* sent, int n_desc, int S, float* o
 // b_trans, accumulate). single: one bf16 product per operand pair (text_train_bf16 = 1); else split-bf16 (three). No must be a
 // multiple of 256, the contraction is zero-padded to a multiple of 32. Workspace: the operand planes, grown on demand.
 // ---------------------------------------------------------------------------------------------------------------
+static int fast_ksplit(int m_tiles, int n_tiles, int kt) {  // k-parts per output tile: every part keeps an even number >= 8 of k-steps
+  int ks = 1;
+  while (ks < 8 && m_tiles * n_tiles * ks < 192 && kt % (ks * 4) == 0 && kt / (ks * 2) >= 8) ks *= 2;
+  return ks;
+}
+
 int fast_gemm(t2l_ctx* ctx, const float* A, bool a_trans, const float* B, bool b_trans, const float* bias, float* out, int Mo, int No, int Kc,
               int relu, int accumulate, bool single, hipStream_t s, float* a_colsum) {
   using namespace th;
@@ -992,8 +1041,7 @@ int fast_gemm(t2l_ctx* ctx, const float* A, bool a_trans, const float* B, bool b
   // contraction is cut into ks jobs per tile, every job stores its partial tile into its own slab (plain stores — float atomics
   // into the output were measured 2x SLOWER than no split at all) and one pass adds the slabs up (+ bias, ReLU, accumulate)
   const int m_tiles = m_pad / kTile, n_tiles = No / kTile, kt = k_pad >> 4;
-  int ks = 1;
-  while (ks < 8 && m_tiles * n_tiles * ks < 192 && kt % (ks * 4) == 0 && kt / (ks * 2) >= 8) ks *= 2;
+  const int ks = fast_ksplit(m_tiles, n_tiles, kt);
   const size_t part_bytes = ks > 1 ? sizeof(float) * (size_t)ks * Mo * No : 0;
   const size_t need = 2 * pa + 2 * pb + part_bytes + 256;
   if (ctx->fast_ws_cap < need) {  // (the context's own scratch: calls of one context are serialised by its caller)
@@ -1013,13 +1061,7 @@ int fast_gemm(t2l_ctx* ctx, const float* A, bool a_trans, const float* B, bool b
   if (No > 16384) return fail(ctx, T2L_EINVAL, "fast_gemm: more than 16384 output columns");
   char *ah = (char*)ctx->fast_ws, *al = ah + pa, *bh = al + pa, *bl = bh + pb;
   float* parts = reinterpret_cast<float*>(bl + pb);
-  static PerDeviceOnce once;
-  if (once.need(ctx->device)) {
-    const int lds = kSlots * kSlotBytes;
-    T2L_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&th_gemm_kernel<kEpiRowMajor, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    T2L_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&th_gemm_kernel<kEpiRowMajor, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    once.mark(ctx->device);
-  }
+  T2L_HIP(ctx, th_kernel_attributes(ctx->device));
   const dim3 ga(m_pad / 32, (k_pad + 255) / 256), gb(No / 32, (k_pad + 255) / 256), gat(m_pad / 128, k_pad / 64), gbt(No / 128, k_pad / 64);
   if (a_trans) hipLaunchKernelGGL(th_split_bf16_kernel<true>, gat, dim3(256), 0, s, A, Kc, Mo, k_pad, (__bf16*)ah, (__bf16*)al, a_colsum);
   else hipLaunchKernelGGL(th_split_bf16_kernel<false>, ga, dim3(256), 0, s, A, Mo, Kc, k_pad, (__bf16*)ah, (__bf16*)al, (float*)nullptr);
@@ -1029,14 +1071,7 @@ int fast_gemm(t2l_ctx* ctx, const float* A, bool a_trans, const float* B, bool b
   g.wh = bh; g.wl = bl; g.xh = ah; g.xl = al; g.bias = bias ? bias : ctx->fast_zero; g.out0 = ks > 1 ? (void*)parts : (void*)out;
   g.m_tiles = m_tiles; g.n_tiles = n_tiles; g.K = k_pad; g.N = No; g.M = Mo; g.n_real = No;
   g.relu = ks > 1 ? 0 : relu; g.accumulate = ks > 1 ? 3 : accumulate; g.ksplit = ks;
-  static int n_cu = 0;
-  if (!n_cu) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess) n_cu = prop.multiProcessorCount;
-    if (n_cu < 8) n_cu = 256;
-  }
-  const int n_vb = (g.m_tiles + 7) / 8 * 8 * g.n_tiles * ks;
-  const int grid = min(n_cu / 8 * 8, n_vb);
+  const int grid = th_gemm_grid(g.m_tiles, g.n_tiles, ks);
   const int lds = kSlots * kSlotBytes;
   if (single) hipLaunchKernelGGL((th_gemm_kernel<kEpiRowMajor, true, true>), dim3(grid), dim3(512), lds, s, g);
   else hipLaunchKernelGGL((th_gemm_kernel<kEpiRowMajor, false, true>), dim3(grid), dim3(512), lds, s, g);
