@@ -513,8 +513,9 @@ int t2l_zero_grad(t2l_ctx* ctx, void* stream);
 /* ---- training step of the fine stage (f-1 under model.train()) -------------------------------------- */
 /* Replaces, for everything downstream of the text branch, the body of the reference's fine train_epoch (training/fine.py:38-91):
  * CrossMatch.forward under model.train() (models/cross_matcher.py:86-135), loss.backward() through it. The text branch
- * (LanguageEncoder(is_fine=True): T5 + its head) stays on PyTorch autograd; the two meet at the hint encodings. torch.optim.Adam
- * steps the parameters (the library has no optimizer state for this stage).
+ * (LanguageEncoder(is_fine=True): T5 + its head) stays on PyTorch autograd or on t2l_text_head_train's fine layout; the two meet at
+ * the hint encodings. The parameters are stepped by t2l_fine_adam_step below (or by torch.optim.Adam: the gradients are the caller's
+ * tensors either way).
  *
  * t2l_fine_train_bind: t2l_train_tensor entries (live data / grad pointers, the a9 convention) named as in the fine checkpoint:
  * object_encoder.* at fine_embed_dim 128 for the configured features — class_embedding.weight (class_embed) or mlp_pointnet.0.*
@@ -568,6 +569,25 @@ int t2l_fine_train_forward_points(t2l_ctx* ctx, const t2l_packed_cells* in, cons
  * features2 by the caller, or features2 feeding mlp_pointnet's statistics only leave the backbone's buffers untouched. */
 int t2l_fine_train_backward(t2l_ctx* ctx, const float* grad_offsets, float* grad_hint_desc, float* grad_pn_feat, void* stream);
 
+/* The fine stage's optimizer: optimizer.zero_grad() / optim.Adam(model.parameters(), lr).step() of training/fine.py:57,72,229
+ * (torch.optim.Adam defaults: no weight decay, no amsgrad) over every tensor that t2l_fine_train_bind received WITH a gradient buffer
+ * — the decoders, mlp_offsets, the object-encoder branches and, when it trains, the PointNet++ backbone — in bind order, with the
+ * object_encoder.pointnet.* group moved behind the rest. A frozen tensor (grad = NULL) and the running buffers are in neither call.
+ * exp_avg / exp_avg_sq live inside the library and belong to this binding alone: the coarse step's state (t2l_train_bind /
+ * t2l_adam_step) and the text head's (t2l_text_adam_step, which steps the hint encoder in its fine layout) are not touched, nor the
+ * reverse. A bind starts from zero moments and step 0; a re-bind of an unchanged list (same names and element counts in the same order,
+ * new pointers: model.to(), a re-assigned .grad) keeps moments and steps IF option "train_keep_adam_state" is 1 at that time. A refused
+ * bind leaves the previous binding, its moments and its steps as they were.
+ * t2l_fine_zero_grad zeroes the bound gradient buffers in place: one launch. t2l_fine_adam_step is one launch too. As in t2l_adam_step
+ * the backbone is a group of its own with its own step count: it steps only when a t2l_fine_train_backward went through it since the
+ * last t2l_fine_zero_grad (torch.optim.Adam skips a .grad of None: a batch fed precomputed features2 leaves the backbone's weights AND
+ * moments untouched); once the two counts differ the backbone's tensors take a second launch with their own bias correction.
+ * t2l_fine_adam_state: as t2l_adam_state (m, v: dev f32[numel] in the order above; *step = step | backbone step << 32; m == v == NULL
+ * queries numel and, set == 0, step). */
+int t2l_fine_adam_step(t2l_ctx* ctx, float lr, float beta1, float beta2, float eps, void* stream);
+int t2l_fine_zero_grad(t2l_ctx* ctx, void* stream);
+int t2l_fine_adam_state(t2l_ctx* ctx, int32_t set, float* m, float* v, int64_t* step, int64_t* numel, void* stream);
+
 /* ---- the text head in TRAINING mode (f-4 / the text half of a9) ---------------------------------- */
 /* Replaces: LanguageEncoder.forward downstream of T5's last_hidden_state under model.train() + its autograd backward
  * (models/language_encoder.py:127-147 as run by training/coarse.py:44,55-56; the published command trains this head —
@@ -620,13 +640,27 @@ int t2l_text_adam_state(t2l_ctx* ctx, int32_t set, float* m, float* v, int64_t* 
  * and the apply launch of every BatchNorm — torch.nn.SyncBatchNorm's exchange. The library has no collectives of its own
  * (RCCL stays with the host: sharded.py / torch.distributed), so the caller supplies both the memory and the sum:
  *   buf   dev f64[t2l_train_sync_bn_doubles()] — replaces the library's own accumulator slots from the next forward on;
- *   fn    called from inside t2l_encode_cells_train / _backward / t2l_text_head_train / _backward, on the calling thread, once per
- *         BatchNorm stage (3 or 4 per direction of an object-branch step, 1 per direction of a text-head step): must replace buf[0..n) at `range` by its sum over
+ *   fn    called from inside t2l_encode_cells_train / _backward / t2l_text_head_train / _backward / t2l_fine_train_forward[_points] /
+ *         _backward, on the calling thread, once per BatchNorm stage (3 or 4 per direction of an object-branch step, 1 per direction of a
+ *         text-head step, up to 3 per direction of a fine step — below): must replace buf[0..n) at `range` by its sum over
  *         all ranks, ordered on `stream` after what is already enqueued there and before what follows (torch.distributed.all_reduce
  *         on the current stream does exactly that). Returns 0, or non-zero to fail the enclosing call with T2L_ESTATE.
  * fn == NULL returns to per-rank statistics (and the library's own slots). Running statistics are updated with the global values on
  * every rank; the parameter gradients of the BatchNorm layers stay per rank (the gradient all_reduce adds them up). PointNet++'s
- * BatchNorms are per cell (pointnet_train.h) and never cross ranks. */
+ * BatchNorms are per cell (pointnet_train.h) and never cross ranks.
+ * The fine step (t2l_fine_train_forward / _forward_points / _backward) takes part while fn is set: every BatchNorm1d of its
+ * ObjectEncoder then normalises over the 16 * n_pairs objects of ALL ranks (W ranks x B / W pairs take the reference's one-process step
+ * on B pairs, training/fine.py:38-91), in a statistics launch, the exchange and an apply launch per layer; with fn == NULL it launches
+ * exactly the one-launch kernels it always did. The branches' MLPs are independent, so their layers share an exchange: one for layer 0
+ * of every MLP branch (color_encoder, pos_encoder, num_encoder, mlp_pointnet — also when mlp_pointnet only moves its statistics), one
+ * for layer 1 of the two-layer ones, one for mlp_merge (more than one feature) — per direction the number of those three that the
+ * configuration has: 3 with all four features (class_embed or not), 1 when every feature is an embedding lookup, 0 for one embedded
+ * feature alone (the backward has no exchange for a statistics-only mlp_pointnet). The fine step's slots lie behind the coarse step's
+ * and the text head's, whose offsets did not move; t2l_train_sync_bn_doubles() counts them. Its backbone (forward_points) keeps
+ * per-cell statistics: a cell lives on one rank. A backward uses the mode of its forward; turning fn off in between is T2L_ESTATE, and
+ * so is a failing callback: the step ends at that exchange (nothing more is launched, fn is not called again, a failed forward
+ * cannot be differentiated). The fine loss is a mean over the local rows, so the ranks' gradients are AVERAGED (the coarse step's
+ * gathered loss wants their sum). */
 typedef int (*t2l_allreduce_fn)(void* user, double* range, int64_t n, void* stream);
 int64_t t2l_train_sync_bn_doubles(void);
 int t2l_train_sync_bn(t2l_ctx* ctx, double* buf, int64_t n_doubles, t2l_allreduce_fn fn, void* user);

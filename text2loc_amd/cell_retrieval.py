@@ -331,7 +331,11 @@ class LanguageEncoder(nn.Module):
         """[(name, parameter)] of the head parameters the engine's training path binds — what ``optim.Adam`` hands to
         ``engine_adam_step`` instead of a torch optimizer — or [] when this head stays on the PyTorch modules in training, and for a
         fine head: the engine trains it, but ``torch.optim.Adam(model.parameters())`` steps it with the rest of CrossMatch."""
-        if self.is_fine or self._train_structure_gate() is None:
+        return [] if self.is_fine else self.engine_head_params()
+
+    def engine_head_params(self):
+        """``engine_optimizer_params`` without the fine head's exception: ``optim.Adam(CrossMatch)`` steps a fine head on the engine too."""
+        if self._train_structure_gate() is None:
             return []
         return [(n, p) for n, p in self.named_parameters()
                 if n.startswith(("intra_module.0.", "inter_mlp.0.", "inter_module.0.")) and p.requires_grad]

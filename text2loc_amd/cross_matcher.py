@@ -19,7 +19,9 @@ Under ``model.train()``, ``forward`` is one training step's forward in the engin
 batch's objects, the decoder layers' dropout, and a backward that adds every parameter gradient straight into the live
 ``.grad`` tensors and hands d loss / d hint encodings (and d features2) back to autograd, so ``loss.backward()`` continues into
 the text branch — the engine's text-head backward, which adds the head's gradients into its ``.grad`` tensors the same way — and
-``torch.optim.Adam(model.parameters())`` steps everything (training/fine.py:38-91). ``encode_cells`` /
+``torch.optim.Adam(model.parameters())`` steps everything (training/fine.py:38-91) — or ``text2loc_amd.optim.Adam(model)``, which
+zeroes and steps the engine-side parameters with one launch each (t2l_fine_zero_grad / t2l_fine_adam_step, the moments inside the
+library), the hint encoder's head through t2l_text_adam_step, and leaves only what remains to a torch optimizer. ``encode_cells`` /
 ``match`` stay eval-only.
 
 With class_embed off (the published fine command) ``object_points`` holds per cell EITHER features2 [16,256] as tensors OR the
@@ -41,10 +43,10 @@ import torch
 import torch.nn as nn
 
 from . import packing
-from .cell_retrieval import LanguageEncoder, ObjectEncoderParams
+from .cell_retrieval import LanguageEncoder, ObjectEncoderParams, _apply_sync_bn
 from .engine import Engine, T2LError
-from .plumbing import (adopt_grad, bind_key, bump_batches_tracked, check_token, engine_for, hook_leaf, new_token, pack_objects,
-                       read_object_points, tensors_version)
+from .plumbing import (adopt_grad, bump_batches_tracked, check_token, engine_for, hook_leaf, new_token, pack_objects, read_object_points,
+                       rebind, tensors_version)
 
 FINE_DIM, PAD_SIZE = 128, 16
 BACKBONE = "object_encoder.pointnet."
@@ -115,7 +117,10 @@ class CrossMatch(nn.Module):
         self._weights_version = None
         self._train_generation = 0  # bumped by every training-mode forward (running statistics move outside torch's _version)
         self._fine_train_bound = None
-        self._fine_train_grads = {}
+        self._fine_train_grads = {}  # name -> persistent gradient buffer (kept when .grad is set to None): views of _fine_train_flat
+        self._fine_train_flat = None
+        self._fine_train_flat_layout = None
+        self._sync_bn_cfg = None
         self._fine_train_token = None
         self._fine_train_hook = None
         self._fine_train_pn_live = []  # (backbone parameter, its bound gradient buffer) of the last bind that trains the backbone
@@ -221,15 +226,27 @@ class CrossMatch(nn.Module):
         run, with_grad = self._fine_train_modules()
         out = {}
         self._fine_train_pn_live = []
-        for n, t in self.named_parameters():
-            if not n.startswith(run) or n.startswith(_HEADS):
-                continue
-            if not t.requires_grad or not n.startswith(with_grad):
+        live = [(n, t) for n, t in self.named_parameters() if n.startswith(run) and not n.startswith(_HEADS)]
+        # The gradient buffers are views into ONE flat tensor (64-float aligned), as CellRetrievalNetwork._train_tensors makes them:
+        # data-parallel training all-reduces it as a single collective (optim.Adam(group=...)), and zero_grad(set_to_none=True) /
+        # model.to() only drop or move references, never the buffers the engine is bound to.
+        steps = lambda n, t: bool(t.requires_grad) and n.startswith(with_grad)  # (engine_steps with the module lists at hand)
+        want = [(n, t) for n, t in live if steps(n, t)]
+        layout = tuple((n, int(t.numel())) for n, t in want)
+        dev = want[0][1].device if want else None
+        if want and (self._fine_train_flat is None or self._fine_train_flat_layout != layout or self._fine_train_flat.device != dev):
+            offs, total = [], 0
+            for _, t in want:
+                offs.append(total)
+                total += (int(t.numel()) + 63) // 64 * 64
+            self._fine_train_flat = torch.zeros(total, dtype=torch.float32, device=dev)
+            self._fine_train_flat_layout = layout
+            self._fine_train_grads = {n: self._fine_train_flat[o:o + t.numel()].view(t.shape) for (n, t), o in zip(want, offs)}
+        for n, t in live:
+            if not steps(n, t):
                 out[n] = (t.data, None)  # frozen: no gradient
                 continue
-            g = self._fine_train_grads.get(n)
-            if g is None or g.shape != t.shape or g.device != t.device:
-                g = self._fine_train_grads[n] = torch.zeros_like(t.data)
+            g = self._fine_train_grads[n]
             if n.startswith(BACKBONE):
                 self._fine_train_pn_live.append((t, g))
             else:
@@ -239,6 +256,21 @@ class CrossMatch(nn.Module):
             if n.startswith(run) and n.endswith(("running_mean", "running_var")):
                 out[n] = (b, None)
         return out
+
+    def engine_steps(self, name: str, param) -> bool:
+        """Does the engine step differentiate (and ``optim.Adam`` step on the engine) this parameter? The modules of
+        ``_fine_train_modules`` that receive a gradient, minus the backbone's classifier heads and whatever is frozen."""
+        _, with_grad = self._fine_train_modules()
+        return bool(param.requires_grad) and name.startswith(with_grad) and not name.startswith(_HEADS)
+
+    def engine_adam_order(self):
+        """[(name, parameter)] in the order of t2l_fine_adam_state's moments: bind order, the backbone's group behind the rest."""
+        own = [(n, p) for n, p in self.named_parameters() if self.engine_steps(n, p)]
+        return [x for x in own if not x[0].startswith(BACKBONE)] + [x for x in own if x[0].startswith(BACKBONE)]
+
+    def train_flat_grad(self) -> Optional[torch.Tensor]:
+        """The flat buffer every engine-stepped parameter's ``.grad`` is a view of (None before the first bind)."""
+        return self._fine_train_flat
 
     def _fine_train_dropout(self) -> float:
         """The one dropout probability the engine applies at all six sites of every decoder layer; layers (or sites) that
@@ -254,16 +286,26 @@ class CrossMatch(nn.Module):
 
     def _fine_train_engine(self) -> Engine:
         """The engine with t2l_fine_train_bind pointing at the CURRENT parameter / gradient / buffer storage (no re-packing:
-        the step reads the live tensors)."""
-        eng = self._device_engine()
-        tensors = self._fine_train_tensors()
-        key = bind_key(tensors)
-        if key != self._fine_train_bound:
-            a = self.args
-            eng.fine_train_bind(tensors, class_embed=bool(getattr(a, "class_embed", False)), color_embed=bool(getattr(a, "color_embed", False)),
-                                use_features=tuple(a.use_features), num_layers=a.fine_num_decoder_layers, num_heads=a.fine_num_decoder_heads)
-            self._fine_train_bound = key
+        the step reads the live tensors). Every call walks the module's parameters as they are now: a replaced Parameter re-binds."""
+        eng, a = self._device_engine(), self.args
+        # (rebind: the same model on moved storage — model.to(), a re-assigned .grad — keeps the engine-side Adam moments)
+        self._fine_train_bound = rebind(eng, self._fine_train_tensors(), self._fine_train_bound, lambda tensors: eng.fine_train_bind(
+            tensors, class_embed=bool(getattr(a, "class_embed", False)), color_embed=bool(getattr(a, "color_embed", False)),
+            use_features=tuple(a.use_features), num_layers=a.fine_num_decoder_layers, num_heads=a.fine_num_decoder_heads))
+        _apply_sync_bn(eng, self._sync_bn_cfg)
         return eng
+
+    def sync_batchnorm(self, group=None, enable: bool = True):
+        """Data-parallel training with the reference's batch statistics: every BatchNorm1d of the ObjectEncoder's branches and
+        mlp_merge (object_encoder.py:41-52,121-149) and the hint encoder's inter_mlp (language_encoder.py:99) normalises over the
+        objects / hints of ALL ranks' pairs — W ranks x B/W pairs then take the step the reference takes on its one batch of B
+        (training/fine.py:38-91). The PointNet++ backbone is not part of this: its BatchNorms use per-cell statistics and a cell lives
+        on one rank. Needs an initialised process group; ``optim.Adam(model, data_parallel=True, grad_reduce="mean")`` completes the
+        step (the fine loss is a mean over the local rows)."""
+        cfg = (group,) if enable else None
+        self._sync_bn_cfg = cfg
+        if hasattr(self.language_encoder, "_bind_text_train"):
+            self.language_encoder._sync_bn_cfg = cfg
 
     def _forward_train(self, objects, hints, object_points):
         if any(len(o) != PAD_SIZE for o in objects):

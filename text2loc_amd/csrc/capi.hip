@@ -524,6 +524,26 @@ int t2l_fine_train_backward(t2l_ctx* ctx, const float* grad_offsets, float* grad
   return fine_train_backward_impl(ctx, grad_offsets, grad_hint_desc, grad_pn_feat, (hipStream_t)stream);
 }
 
+int t2l_fine_adam_step(t2l_ctx* ctx, float lr, float beta1, float beta2, float eps, void* stream) {
+  if (!ctx) return T2L_EINVAL;
+  if (!(lr >= 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f))
+    return fail(ctx, T2L_EINVAL, "t2l_fine_adam_step: need lr >= 0, 0 <= beta < 1, eps >= 0");
+  T2L_HIP(ctx, hipSetDevice(ctx->device));
+  return fine_adam_step_impl(ctx, lr, beta1, beta2, eps, (hipStream_t)stream);
+}
+
+int t2l_fine_zero_grad(t2l_ctx* ctx, void* stream) {
+  if (!ctx) return T2L_EINVAL;
+  T2L_HIP(ctx, hipSetDevice(ctx->device));
+  return fine_zero_grad_impl(ctx, (hipStream_t)stream);
+}
+
+int t2l_fine_adam_state(t2l_ctx* ctx, int32_t set, float* m, float* v, int64_t* step, int64_t* numel, void* stream) {
+  if (!ctx) return T2L_EINVAL;
+  T2L_HIP(ctx, hipSetDevice(ctx->device));
+  return fine_adam_state_impl(ctx, set, m, v, step, numel, (hipStream_t)stream);
+}
+
 int t2l_text_head_train(t2l_ctx* ctx, const float* hidden, int32_t n_sentences, int32_t n_tokens, int32_t n_descriptions, float dropout_p,
                         uint32_t seed, float* out, void* stream) {
   if (!ctx) return T2L_EINVAL;

@@ -10,6 +10,10 @@
 //                             state of this context's own)
 //   t2l_fine_train_backward : d offsets -> parameter gradients ADDED into the bound .grad buffers, d hint encodings, d features2,
 //                             and on through the backbone after a points forward when it is bound with gradients
+//   t2l_fine_zero_grad / t2l_fine_adam_step / t2l_fine_adam_state : optimizer.zero_grad() / Adam over the tensors bound with a gradient
+//                             buffer (train.hip's AdamSet through train_common.h), one launch each
+// With t2l_train_sync_bn set, the ObjectEncoder's BatchNorms take their statistics over every rank's rows: k_bn_stats_* / k_bn_apply_*
+// around the caller's sum, the branches' layers side by side (one exchange per layer index, one for mlp_merge).
 // Everything is f32 on the vector ALU. Residual + dropout + LayerNorm, F.normalize, the feed-forward dropout with its ReLU backward
 // and the max over the hints are the coarse step's row kernels (train_kernels.h) at width 128, reached through train.hip's launchers
 // (train_common.h). The kernels below are the ones the coarse step has no counterpart for:
@@ -202,6 +206,88 @@ __global__ __launch_bounds__(256) void k_bn_bwd(const float* dout, const float* 
   }
 }
 
+// ---- the same two in PHASES, for BatchNorm statistics over the rows of ALL ranks (t2l_train_sync_bn): a statistics launch leaves this
+// rank's float64 column sums and its row count in an accumulator slot (train_common.h; plain stores — a column has one owner, so a slot
+// needs no clearing and carries nothing from one launch to the next), the host sums the slot over the ranks, and an apply launch
+// normalises by the global sums and the global row count at kBnCount. The scheme and the parameter-gradient rule are the coarse step's
+// (train_kernels.h: bn_stats_body / bn_apply_*): dgamma / dbeta are this rank's OWN sums, taken in the statistics launch — the gradient
+// all_reduce adds the ranks' up. The variance is E[y²] - mean² in float64 (the operands are float32, their squares exact in float64:
+// the cancellation costs M 2^-52 (mean² + var), nothing beside the float32 rounding of mean and rstd), clamped at 0.
+using train::kBnCount;
+using train::kBnStride;
+
+__global__ __launch_bounds__(256) void k_bn_stats_fwd(const float* Y, int M, int N, double* acc) {
+  __shared__ double red[256];
+  const int n = blockIdx.x;
+  double s = 0.0, q = 0.0;
+  for (int m = threadIdx.x; m < M; m += 256) {
+    const double y = Y[(int64_t)m * N + n];
+    s += y;
+    q += y * y;
+  }
+  const double st = block_sum_d(s, red), qt = block_sum_d(q, red);
+  if (threadIdx.x == 0) {
+    acc[n] = st;
+    acc[N + n] = qt;
+    if (n == 0) acc[kBnCount] = (double)M;
+  }
+}
+
+// Y: pre-BN in, x̂ out (in place), as k_bn_fwd; acc: the summed slot
+__global__ __launch_bounds__(256) void k_bn_apply_fwd(float* Y, int M, int N, const float* g, const float* b, float* rm, float* rv,
+                                                      float* rstd_out, float* out, const double* acc) {
+  const int n = blockIdx.x;
+  const double Mg = acc[kBnCount];
+  const double mean = acc[n] / Mg;
+  const double var = fmax(acc[N + n] / Mg - mean * mean, 0.0);
+  const float rstd = 1.f / sqrtf((float)var + kBnEps);
+  const float mf = (float)mean, gn = g[n], bn = b[n];
+  for (int m = threadIdx.x; m < M; m += 256) {
+    const int64_t i = (int64_t)m * N + n;
+    const float xh = (Y[i] - mf) * rstd;
+    Y[i] = xh;
+    out[i] = fmaxf(fmaf(xh, gn, bn), 0.f);
+  }
+  if (threadIdx.x == 0) {
+    rstd_out[n] = rstd;
+    if (rm) rm[n] = (1.f - kBnMom) * rm[n] + kBnMom * mf;
+    if (rv) rv[n] = (1.f - kBnMom) * rv[n] + kBnMom * (float)(var * Mg / (Mg > 1.0 ? Mg - 1.0 : 1.0));
+  }
+}
+
+__global__ __launch_bounds__(256) void k_bn_stats_bwd(const float* dout, const float* out, const float* xhat, int M, int N, float* dg,
+                                                      float* db, double* acc) {
+  __shared__ double red[256];
+  const int n = blockIdx.x;
+  double s = 0.0, sx = 0.0;
+  for (int m = threadIdx.x; m < M; m += 256) {
+    const int64_t i = (int64_t)m * N + n;
+    const float dz = out[i] > 0.f ? dout[i] : 0.f;
+    s += dz;
+    sx += (double)dz * xhat[i];
+  }
+  const double sd = block_sum_d(s, red), sdx = block_sum_d(sx, red);
+  if (threadIdx.x == 0) {
+    acc[n] = sd;
+    acc[N + n] = sdx;
+    if (n == 0) acc[kBnCount] = (double)M;
+    if (dg) dg[n] += (float)sdx;
+    if (db) db[n] += (float)sd;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_bn_apply_bwd(const float* dout, const float* out, const float* xhat, const float* rstd,
+                                                      const float* g, int M, int N, const double* acc, float* dy) {
+  const int n = blockIdx.x;
+  const float Mg = (float)acc[kBnCount];
+  const float k = g[n] * rstd[n] / Mg, sdf = (float)acc[n], sdxf = (float)acc[N + n];
+  for (int m = threadIdx.x; m < M; m += 256) {
+    const int64_t i = (int64_t)m * N + n;
+    const float dz = out[i] > 0.f ? dout[i] : 0.f;
+    dy[i] = k * (Mg * dz - sdf - xhat[i] * sdxf);
+  }
+}
+
 // nn.Embedding lookup and its backward (padding_idx = 0 gets no gradient; out-of-range rows read zero and get nothing)
 __global__ void k_gather(const float* table, int rows, const int32_t* idx, int M, float* out) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -345,6 +431,9 @@ struct Branch {
   Ten table;  // nn.Embedding [rows,128]
   std::vector<BnLayer> mlp;
   float *raw = nullptr, *nrm = nullptr, *in = nullptr;  // embedding rows / F.normalize norms / num-encoder input
+  // cross-rank statistics only: the backward runs the branches' layers side by side (one exchange per layer index), so each MLP branch
+  // keeps its own d output [M0,128], d pre-BN of the last layer [M0,128], and for a two-layer branch d hidden / d pre-BN [M0,64]
+  float *s_draw = nullptr, *s_dy = nullptr, *s_d0 = nullptr, *s_dy0 = nullptr;
 };
 struct DecLayer {
   Ten in_w, in_b, out_w, out_b, cin_w, cin_b, cout_w, cout_b, l1_w, l1_b, l2_w, l2_b, n1_w, n1_b, n2_w, n2_b, n3_w, n3_b;
@@ -363,8 +452,16 @@ struct FineTrain {
   std::vector<DecLayer> dec;  // cascade order: cross_objects.0, cross_hints.0, cross_objects.1, ... (or cross_hints alone)
   Ten o0w, o0b, o2w, o2b;
   PnTrain* pn = nullptr;  // the PointNet++ backbone's training state (object_encoder.pointnet.* bound), or null
+  // the optimizer (t2l_fine_adam_step): every tensor bound with a gradient buffer, in bind order with the backbone's group behind the
+  // rest — tensors [0, n_own) step on every call, [n_own, n_adam) only when the backward went through the backbone since the last
+  // t2l_fine_zero_grad (torch.optim.Adam skips a .grad of None and counts steps per parameter: the coarse step's rule, train.hip)
+  AdamSet* adam = nullptr;  // null: nothing is trained
+  size_t n_own = 0, n_adam = 0;
+  int64_t step = 0, step_pn = 0;
+  bool pn_touched = false;
   // the last forward
   bool have_fwd = false;
+  bool sync = false;      // ... exchanged its BatchNorm statistics across the ranks (ctx->sync_fn was set): the backward does too
   bool pn_fwd = false;    // ... took features2 from the backbone (t2l_fine_train_forward_points)
   int P = 0, H = 0;
   float p = 0.f;
@@ -384,6 +481,7 @@ static void free_ft(FineTrain* st) {
   if (!st) return;
   if (st->ws.base) (void)hipFree(st->ws.base);
   pn_train_release(st->pn);
+  adam_set_free(st->adam);
   delete st;
 }
 
@@ -422,7 +520,7 @@ static void lin_dw(hipStream_t s, const float* dY, int64_t ldd, const float* X, 
 }
 
 // every pointer of the step inside one arena (count pass with base == null, then the real pass)
-static void plan(FineTrain* st, Arena& a, int P, int H, float p) {
+static void plan(FineTrain* st, Arena& a, int P, int H, float p, bool sync) {
   const int M0 = P * kObj, M1 = P * H, Mx = M0 > M1 ? M0 : M1;
   for (auto& b : st->br) {
     if (!b.used) continue;
@@ -434,6 +532,14 @@ static void plan(FineTrain* st, Arena& a, int P, int H, float p) {
     }
     b.nrm = a.take<float>(M0);
     b.in = a.take<float>(M0);
+    if (sync && !b.embed) {
+      b.s_draw = a.take<float>((int64_t)M0 * kW);
+      b.s_dy = a.take<float>((int64_t)M0 * kW);
+      if (b.mlp.size() > 1) {
+        b.s_d0 = a.take<float>((int64_t)M0 * 64);
+        b.s_dy0 = a.take<float>((int64_t)M0 * 64);
+      }
+    }
   }
   st->E = a.take<float>((int64_t)M0 * kW * st->n_feat);
   if (st->n_feat > 1) {
@@ -556,6 +662,78 @@ static bool dec_bwd(FineTrain* st, DecLayer& L, float p, uint32_t seed, const fl
   lin_dw(s, dq, 3 * kW, L.x, kW, M, 3 * kW, kW, L.in_w.g, kW, L.in_b.g);
   lin_dx(s, dq, 3 * kW, M, 3 * kW, L.in_w.d, kW, kW, dx, kW, 1);
   return ok;
+}
+
+// ---- launchers of the phased BatchNorm (the dev library's wrapper goes through them too)
+static void bn_stats_fwd_launch(const float* Y, int M, int N, double* acc, hipStream_t s) {
+  hipLaunchKernelGGL(k_bn_stats_fwd, dim3(N), dim3(256), 0, s, Y, M, N, acc);
+}
+static void bn_apply_fwd_launch(float* Y, int M, int N, const float* g, const float* b, float* rm, float* rv, float* rstd, float* out,
+                                const double* acc, hipStream_t s) {
+  hipLaunchKernelGGL(k_bn_apply_fwd, dim3(N), dim3(256), 0, s, Y, M, N, g, b, rm, rv, rstd, out, acc);
+}
+static void bn_stats_bwd_launch(const float* dout, const float* out, const float* xhat, int M, int N, float* dg, float* db, double* acc,
+                                hipStream_t s) {
+  hipLaunchKernelGGL(k_bn_stats_bwd, dim3(N), dim3(256), 0, s, dout, out, xhat, M, N, dg, db, acc);
+}
+static void bn_apply_bwd_launch(const float* dout, const float* out, const float* xhat, const float* rstd, const float* g, int M, int N,
+                                const double* acc, float* dy, hipStream_t s) {
+  hipLaunchKernelGGL(k_bn_apply_bwd, dim3(N), dim3(256), 0, s, dout, out, xhat, rstd, g, M, N, acc, dy);
+}
+
+// One exchange of the cross-rank statistics: up to kFineBnSlots independent layers of the same row count, slot i for layer i — every
+// statistics launch, ONE call of the caller's sum over the slots in use, every apply launch.
+struct BnJob {
+  BnLayer* l;
+  const float* x;     // forward: the layer's input
+  const float* dout;  // backward: d of the layer's output
+  float *dy, *dx;     // backward: d pre-BN (scratch [M,N]); d input [M,K] or null
+};
+static double* sync_slot(t2l_ctx* ctx, size_t i) { return ctx->sync_buf + (size_t)(train::kFineBnSlot0 + i) * kBnStride; }
+static void sync_sum(t2l_ctx* ctx, size_t slots, hipStream_t s) {
+  if (ctx->sync_failed) return;  // (no further collective from a rank whose last one failed)
+  if (ctx->sync_fn(ctx->sync_user, sync_slot(ctx, 0), (int64_t)slots * kBnStride, (void*)s) != 0) ctx->sync_failed = true;
+}
+// false (here and in bn_stage_bwd): more layers than slots, or the callback failed — nothing more of the step should run
+static bool bn_stage_fwd(t2l_ctx* ctx, const std::vector<BnJob>& jobs, int M, hipStream_t s) {
+  if (jobs.empty()) return true;
+  if (jobs.size() > (size_t)train::kFineBnSlots) return false;  // (at most class, color, position, num side by side)
+  for (size_t i = 0; i < jobs.size(); ++i) {
+    BnLayer& l = *jobs[i].l;
+    l.x = jobs[i].x;
+    lin_fwd(s, l.x, l.K, M, l.K, l.w.d, l.K, l.b.d, l.N, l.xhat, l.N);
+    bn_stats_fwd_launch(l.xhat, M, l.N, sync_slot(ctx, i), s);
+  }
+  sync_sum(ctx, jobs.size(), s);
+  if (ctx->sync_failed) return false;
+  for (size_t i = 0; i < jobs.size(); ++i) {
+    BnLayer& l = *jobs[i].l;
+    bn_apply_fwd_launch(l.xhat, M, l.N, l.bw.d, l.bb.d, l.rm.d, l.rv.d, l.rstd, l.out, sync_slot(ctx, i), s);
+  }
+  return true;
+}
+static bool bn_stage_bwd(t2l_ctx* ctx, const std::vector<BnJob>& jobs, int M, hipStream_t s) {
+  if (jobs.empty()) return true;
+  if (jobs.size() > (size_t)train::kFineBnSlots) return false;
+  for (size_t i = 0; i < jobs.size(); ++i) {
+    BnLayer& l = *jobs[i].l;
+    bn_stats_bwd_launch(jobs[i].dout, l.out, l.xhat, M, l.N, l.bw.g, l.bb.g, sync_slot(ctx, i), s);
+  }
+  sync_sum(ctx, jobs.size(), s);
+  if (ctx->sync_failed) return false;
+  for (size_t i = 0; i < jobs.size(); ++i) {
+    BnLayer& l = *jobs[i].l;
+    bn_apply_bwd_launch(jobs[i].dout, l.out, l.xhat, l.rstd, l.bw.d, M, l.N, sync_slot(ctx, i), jobs[i].dy, s);
+    lin_dw(s, jobs[i].dy, l.N, l.x, l.K, M, l.N, l.K, l.w.g, l.K, l.b.g);
+    if (jobs[i].dx) lin_dx(s, jobs[i].dy, l.N, M, l.N, l.w.d, l.K, l.K, jobs[i].dx, l.K, 0);
+  }
+  return true;
+}
+// what a step answers when a stage returned false
+static int stage_failed(t2l_ctx* ctx, const char* who) {
+  (void)hipGetLastError();
+  if (ctx->sync_failed) return fail(ctx, T2L_ESTATE, std::string(who) + ": the cross-rank sum callback (t2l_train_sync_bn) failed");
+  return fail(ctx, T2L_ESTATE, std::string(who) + ": more BatchNorm layers in one exchange than the fine step has slots");
 }
 
 static void bn_layer_fwd(BnLayer& l, const float* x, int M, hipStream_t s) {
@@ -704,7 +882,30 @@ int fine_train_bind_impl(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n, c
     return fail(ctx, T2L_EINVAL, "fine_train_bind: object_encoder.pointnet.* is bound only with class_embed == 0 (class_embed looks the "
                                  "classes up instead of running the backbone)");
   }
+  // Adam over what arrived with a gradient buffer (a name given twice counts once: the entry the step reads)
+  std::vector<AdamBound> trained, backbone;
+  for (int i = 0; i < n; ++i) {
+    const t2l_train_tensor& x = tensors[i];
+    if (!x.grad || x.numel <= 0 || by[x.name] != &x) continue;
+    (strncmp(x.name, "object_encoder.pointnet.", 24) ? trained : backbone).push_back(AdamBound{x.name, x.data, x.grad, x.numel});
+  }
+  st->n_own = trained.size();
+  trained.insert(trained.end(), backbone.begin(), backbone.end());
+  st->n_adam = trained.size();
   T2L_HIP(ctx, hipDeviceSynchronize());  // the previous state's arena may still be in use
+  // from here on the bind is accepted: the previous binding's moments move over (an unchanged list under "train_keep_adam_state") or go
+  auto* prev = (FineTrain*)ctx->fine_train;
+  if (st->n_adam) {
+    bool kept = false;
+    if (int rc = adam_set_make(ctx, trained, prev ? prev->adam : nullptr, &kept, &st->adam)) {
+      free_ft(st);
+      return rc;
+    }
+    if (kept) {
+      st->step = prev->step;
+      st->step_pn = prev->step_pn;
+    }
+  }
   free_fine_train(ctx);
   ctx->fine_train = st;
   return T2L_OK;
@@ -744,8 +945,10 @@ int fine_train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, const floa
     L.Tq = L.obj ? kObj : n_hints;
     L.Tk = L.obj ? n_hints : kObj;
   }
+  const bool sync = ctx->sync_fn != nullptr;  // BatchNorm statistics over every rank's rows (t2l_train_sync_bn)
+  ctx->sync_failed = false;
   Arena count;  // (no base: the count pass)
-  plan(st, count, n_pairs, n_hints, p);
+  plan(st, count, n_pairs, n_hints, p, sync);
   if (count.off > st->ws.cap) {
     T2L_HIP(ctx, hipStreamSynchronize(s));  // the old arena may still be read by queued work of this stream
     if (st->ws.base) (void)hipFree(st->ws.base);
@@ -754,7 +957,7 @@ int fine_train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, const floa
     st->ws.cap = count.off;
   }
   st->ws.off = 0;
-  plan(st, st->ws, n_pairs, n_hints, p);
+  plan(st, st->ws, n_pairs, n_hints, p, sync);
   st->class_idx = in->class_idx;
   st->color_idx = in->color_idx;
   st->rgb = in->rgb;
@@ -766,12 +969,30 @@ int fine_train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, const floa
   const int ldE = st->n_feat * kW;
   bool ok = true;  // every row kernel has its instance of width 128
   // ---- ObjectEncoder (object_encoder.py:102-149) + F.normalize (cross_matcher.py:103-104)
+  if (sync) {
+    // the branches' MLPs side by side, one exchange per layer index: layer 0 of every MLP branch (and mlp_pointnet's statistics-only
+    // run), then layer 1 of the two-layer ones
+    if (st->br[3].used) hipLaunchKernelGGL(k_num_in, dim3(nblk(M0, 256)), dim3(256), 0, s, in->n_pts, M0, st->br[3].in);
+    for (size_t li = 0; li < 2; ++li) {
+      std::vector<BnJob> jobs;
+      for (int f = 0; f < 4; ++f) {
+        Branch& br = st->br[f];
+        if (!br.used || br.embed || br.mlp.size() <= li) continue;
+        const float* x = li > 0 ? br.mlp[li - 1].out : f == 0 ? pn_feat : f == 1 ? in->rgb : f == 2 ? in->center : br.in;
+        jobs.push_back(BnJob{&br.mlp[li], x, nullptr, nullptr, nullptr});
+      }
+      if (li == 0 && st->pn_stats) jobs.push_back(BnJob{&st->pn_only, pn_feat, nullptr, nullptr, nullptr});
+      if (!bn_stage_fwd(ctx, jobs, M0, s)) return stage_failed(ctx, "fine_train_forward");
+    }
+  }
   int col = 0;
   for (int f = 0; f < 4; ++f) {
     Branch& br = st->br[f];
     if (!br.used) continue;
     const float* last;
-    if (br.embed) {
+    if (sync && !br.embed) {
+      last = br.mlp.back().out;
+    } else if (br.embed) {
       const int32_t* idx = f == 0 ? in->class_idx : in->color_idx;
       hipLaunchKernelGGL(k_gather, dim3(nblk((int64_t)M0 * kW, 256)), dim3(256), 0, s, br.table.d, (int)(br.table.n / kW), idx, M0, br.raw);
       last = br.raw;
@@ -787,10 +1008,13 @@ int fine_train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, const floa
     ok = rownorm_rows(true, kW, last, nullptr, st->E + col * kW, br.nrm, M0, ldE, s) && ok;
     ++col;
   }
-  if (st->pn_stats) bn_layer_fwd(st->pn_only, pn_feat, M0, s);  // running statistics only
+  if (st->pn_stats && !sync) bn_layer_fwd(st->pn_only, pn_feat, M0, s);  // running statistics only
   const float* feat = st->E;
   if (st->n_feat > 1) {
-    bn_layer_fwd(st->merge, st->E, M0, s);
+    if (!sync)
+      bn_layer_fwd(st->merge, st->E, M0, s);
+    else if (!bn_stage_fwd(ctx, {BnJob{&st->merge, st->E, nullptr, nullptr, nullptr}}, M0, s))
+      return stage_failed(ctx, "fine_train_forward");
     feat = st->merge.out;
   }
   ok = rownorm_rows(true, kW, feat, nullptr, st->D0, st->nrm0, M0, kW, s) && ok;
@@ -808,6 +1032,8 @@ int fine_train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, const floa
   lin_fwd(s, st->a1, 64, P, 64, st->o2w.d, 64, st->o2b.d, 2, out, 2);
   T2L_HIP(ctx, hipGetLastError());
   if (!ok) return fail(ctx, T2L_ESTATE, "fine_train_forward: the row kernels have no instance of width 128");
+  if (ctx->sync_failed) return fail(ctx, T2L_ESTATE, "fine_train_forward: the cross-rank sum callback (t2l_train_sync_bn) failed");
+  st->sync = sync;
   st->have_fwd = true;
   st->p = p;
   st->seed = seed;
@@ -839,6 +1065,11 @@ int fine_train_backward_impl(t2l_ctx* ctx, const float* grad_offsets, float* gra
   auto* st = (FineTrain*)ctx->fine_train;
   if (!st || !st->have_fwd) return fail(ctx, T2L_ESTATE, "fine_train_backward: no training-mode forward to differentiate");
   if (!grad_offsets) return fail(ctx, T2L_EINVAL, "fine_train_backward: null grad_offsets");
+  if (st->sync && !ctx->sync_fn)
+    return fail(ctx, T2L_ESTATE, "fine_train_backward: the forward summed its BatchNorm statistics over the ranks; t2l_train_sync_bn was "
+                                 "turned off before its backward");
+  const bool sync = st->sync;
+  ctx->sync_failed = false;
   const float p = st->p;
   const uint32_t seed = st->seed;
   const int P = st->P, H = st->H, M0 = P * kObj, M1 = P * H;
@@ -873,18 +1104,23 @@ int fine_train_backward_impl(t2l_ctx* ctx, const float* grad_offsets, float* gra
   const int ldE = st->n_feat * kW;
   float* dfeat = st->n_feat > 1 ? st->ta : st->dE;
   ok = rownorm_rows(false, kW, g0, st->D0, dfeat, st->nrm0, M0, kW, s) && ok;
-  if (st->n_feat > 1) bn_layer_bwd(st->merge, st->ta, M0, st->tb, st->dE, s);
+  if (st->n_feat > 1) {
+    if (!sync)
+      bn_layer_bwd(st->merge, st->ta, M0, st->tb, st->dE, s);
+    else if (!bn_stage_bwd(ctx, {BnJob{&st->merge, nullptr, st->ta, st->tb, st->dE}}, M0, s))
+      return stage_failed(ctx, "fine_train_backward");
+  }
   int col = 0;
   for (int f = 0; f < 4; ++f) {
     Branch& br = st->br[f];
     if (!br.used) continue;
-    float* draw = br.embed ? st->ta : st->gA0;  // d of the branch output before its F.normalize
+    float* draw = br.embed ? st->ta : sync ? br.s_draw : st->gA0;  // d of the branch output before its F.normalize
     ok = rownorm_rows(false, kW, st->dE + col * kW, st->E + col * kW, draw, br.nrm, M0, ldE, s) && ok;
     if (br.embed) {
       if (br.table.g)
         hipLaunchKernelGGL(k_scatter_add, dim3(nblk((int64_t)M0 * kW, 256)), dim3(256), 0, s, st->ta, (int)(br.table.n / kW),
                            f == 0 ? st->class_idx : st->color_idx, M0, br.table.g);
-    } else {
+    } else if (!sync) {
       // layers in reverse: dout in gA0 / gB0 alternately, dy in ta, dx of the first layer only for features2
       float *dout = st->gA0, *dnext = st->gB0;
       for (int li = (int)br.mlp.size() - 1; li >= 0; --li) {
@@ -895,10 +1131,76 @@ int fine_train_backward_impl(t2l_ctx* ctx, const float* grad_offsets, float* gra
     }
     ++col;
   }
+  if (sync) {
+    // the MLP branches side by side, in reverse: layer 1 of the two-layer ones (d hidden into s_d0), then every layer 0 (d features2
+    // of mlp_pointnet into dpn)
+    for (int li = 1; li >= 0; --li) {
+      std::vector<BnJob> jobs;
+      for (int f = 0; f < 4; ++f) {
+        Branch& br = st->br[f];
+        if (!br.used || br.embed || (int)br.mlp.size() <= li) continue;
+        const bool last = li + 1 == (int)br.mlp.size();
+        jobs.push_back(BnJob{&br.mlp[li], nullptr, last ? br.s_draw : br.s_d0, last ? br.s_dy : br.s_dy0,
+                             li > 0 ? br.s_d0 : (f == 0 ? dpn : nullptr)});
+      }
+      if (!bn_stage_bwd(ctx, jobs, M0, s)) return stage_failed(ctx, "fine_train_backward");
+    }
+  }
   T2L_HIP(ctx, hipGetLastError());
   if (!ok) return fail(ctx, T2L_ESTATE, "fine_train_backward: the row kernels have no instance of width 128");
-  if (pn_bwd) return pn_train_backward_on(ctx, st->pn, "fine_train_backward", dpn, s);
+  if (ctx->sync_failed) return fail(ctx, T2L_ESTATE, "fine_train_backward: the cross-rank sum callback (t2l_train_sync_bn) failed");
+  if (pn_bwd) {
+    st->pn_touched = true;  // the backbone's gradients carry this batch: its tensors take part in the next t2l_fine_adam_step
+    return pn_train_backward_on(ctx, st->pn, "fine_train_backward", dpn, s);
+  }
   return T2L_OK;
+}
+
+// ---- the optimizer (training/fine.py:57 optimizer.zero_grad(), :72 optimizer.step(), :229 optim.Adam(model.parameters(), lr)): train.hip's
+// adam_kernel / zero_kernel over this binding's tensors
+int fine_adam_step_impl(t2l_ctx* ctx, float lr, float b1, float b2, float eps, hipStream_t s) {
+  auto* st = (FineTrain*)ctx->fine_train;
+  if (!st) return fail(ctx, T2L_ESTATE, "t2l_fine_adam_step: call t2l_fine_train_bind first");
+  st->step += 1;
+  const bool pn = st->n_own < st->n_adam && st->pn_touched;
+  if (pn) st->step_pn += 1;
+  if (!st->adam) return T2L_OK;
+  event_begin(ctx, "fine_adam_step", s);
+  if (pn && st->step_pn == st->step) {  // one launch: both groups at the same bias correction (every step went through the backbone)
+    adam_set_step(st->adam, 0, st->n_adam, st->step, lr, b1, b2, eps, s);
+  } else {
+    adam_set_step(st->adam, 0, st->n_own, st->step, lr, b1, b2, eps, s);
+    if (pn) adam_set_step(st->adam, st->n_own, st->n_adam, st->step_pn, lr, b1, b2, eps, s);
+  }
+  event_end(ctx, "fine_adam_step", s);
+  T2L_HIP(ctx, hipGetLastError());
+  return T2L_OK;
+}
+
+int fine_zero_grad_impl(t2l_ctx* ctx, hipStream_t s) {
+  auto* st = (FineTrain*)ctx->fine_train;
+  if (!st) return fail(ctx, T2L_ESTATE, "t2l_fine_zero_grad: call t2l_fine_train_bind first");
+  if (st->adam) adam_set_zero(st->adam, s);
+  st->pn_touched = false;
+  T2L_HIP(ctx, hipGetLastError());
+  return T2L_OK;
+}
+
+int fine_adam_state_impl(t2l_ctx* ctx, int set, float* m, float* v, int64_t* step, int64_t* numel, hipStream_t s) {
+  auto* st = (FineTrain*)ctx->fine_train;
+  if (!st) return fail(ctx, T2L_ESTATE, "t2l_fine_adam_state: call t2l_fine_train_bind first");
+  const int64_t packed = st->step | (st->step_pn << 32);
+  if (!st->adam) {  // nothing is trained: no moments to move
+    if (numel) *numel = 0;
+    if (step && !set) *step = packed;
+    return T2L_OK;
+  }
+  const int rc = adam_set_state(ctx, st->adam, "t2l_fine_adam_state", set, m, v, step, numel, packed, s);
+  if (rc == T2L_OK && set && m) {
+    st->step = *step & 0xFFFFFFFFll;
+    st->step_pn = st->n_own < st->n_adam ? (*step >> 32) : 0;
+  }
+  return rc;
 }
 
 }  // namespace t2l

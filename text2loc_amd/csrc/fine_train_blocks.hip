@@ -4,6 +4,8 @@
 // every launch goes through the product's own static launchers (lin_fwd / lin_dx / lin_dw, so the split over the rows is the
 // product's policy) or is the product's own hipLaunchKernelGGL line with the caller's pointers.
 //
+// t2l_blk_ft_bn_sync_fwd / _bwd run the phased BatchNorm of the cross-rank statistics with the ranks emulated as parts of the rows.
+//
 // Two doors into a bound context (t2l_fine_train_bind through this library) after the product's own t2l_fine_train_forward:
 //   t2l_blk_ft_saved    copies one saved activation of the last forward out of the context's arena
 //   t2l_blk_ft_dec_bwd  one call of the product's dec_bwd on one layer of the bound state
@@ -152,6 +154,68 @@ int t2l_blk_ft_bn_bwd(const float* dout, const float* out, const float* xhat, co
   if (M < 1 || N < 1) return blk_refuse(who + ": need M, N >= 1");
   hipLaunchKernelGGL(k_bn_bwd, dim3(N), dim3(256), 0, nullptr, dout, out, xhat, rstd, g, M, N, dg, db, dy);
   return blk_finish("t2l_blk_ft_bn_bwd");
+}
+
+// ---- the phased BatchNorm (cross-rank statistics) with the ranks emulated in one process: the M rows are `parts` consecutive parts of
+// rows[p] rows (a host array). Each part's statistics launch goes into the part's own accumulator slot, the slots are added up on the
+// device in the callback's place (every slot then holds the total, as after an all_reduce), each part's apply launch reads its slot.
+// The slots start out as NaN: a launch must store whatever it later reads. Through the product's launchers (bn_stats_* / bn_apply_*).
+__global__ void k_blk_slot_sum(double* slots, int parts) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= kBnStride) return;
+  double t = 0.0;
+  for (int p = 0; p < parts; ++p) t += slots[(size_t)p * kBnStride + i];
+  for (int p = 0; p < parts; ++p) slots[(size_t)p * kBnStride + i] = t;
+}
+static int blk_sync_parts(const std::string& who, const int32_t* rows, int parts, int N, double** slots) {
+  if (!rows || parts < 1 || parts > 16) return blk_refuse(who + ": need 1..16 parts");
+  if (N < 1 || N > 1024) return blk_refuse(who + ": need 1 <= N <= 1024 (a slot holds 2 x 1024 column sums)");
+  for (int p = 0; p < parts; ++p)
+    if (rows[p] < 1) return blk_refuse(who + ": every part needs at least one row");
+  const size_t bytes = sizeof(double) * (size_t)parts * kBnStride;
+  if (hipMalloc(slots, bytes) != hipSuccess || hipMemset(*slots, 0xFF, bytes) != hipSuccess) return blk_refuse(who + ": no memory for the slots");
+  return 0;
+}
+static void blk_slot_sum(double* slots, int parts) {
+  hipLaunchKernelGGL(k_blk_slot_sum, dim3((kBnStride + 255) / 256), dim3(256), 0, nullptr, slots, parts);
+}
+
+// forward: Y [M,N] pre-BN in, x̂ out in place; out, rstd written; rm / rv (nullable) updated once (a rank's own copy: the first part's)
+int t2l_blk_ft_bn_sync_fwd(float* Y, const int32_t* rows, int parts, int N, const float* g, const float* b, float* rm, float* rv,
+                           float* rstd, float* out) {
+  const std::string who = "t2l_blk_ft_bn_sync_fwd";
+  if (!Y || !g || !b || !rstd || !out) return blk_refuse(who + ": null pointer");
+  double* slots = nullptr;
+  if (int rc = blk_sync_parts(who, rows, parts, N, &slots)) return rc;
+  int64_t r0 = 0;
+  for (int p = 0; p < parts; r0 += rows[p++]) bn_stats_fwd_launch(Y + r0 * N, rows[p], N, slots + (size_t)p * kBnStride, nullptr);
+  blk_slot_sum(slots, parts);
+  r0 = 0;
+  for (int p = 0; p < parts; r0 += rows[p++])
+    bn_apply_fwd_launch(Y + r0 * N, rows[p], N, g, b, p ? nullptr : rm, p ? nullptr : rv, rstd, out + r0 * N, slots + (size_t)p * kBnStride,
+                        nullptr);
+  const int rc = blk_finish("t2l_blk_ft_bn_sync_fwd");
+  (void)hipFree(slots);
+  return rc;
+}
+
+// backward: dy written; dg / db (nullable) get every part's own sums added (what the gradient all_reduce makes of the ranks')
+int t2l_blk_ft_bn_sync_bwd(const float* dout, const float* out, const float* xhat, const float* rstd, const float* g, const int32_t* rows,
+                           int parts, int N, float* dg, float* db, float* dy) {
+  const std::string who = "t2l_blk_ft_bn_sync_bwd";
+  if (!dout || !out || !xhat || !rstd || !g || !dy) return blk_refuse(who + ": null pointer");
+  double* slots = nullptr;
+  if (int rc = blk_sync_parts(who, rows, parts, N, &slots)) return rc;
+  int64_t r0 = 0;
+  for (int p = 0; p < parts; r0 += rows[p++])
+    bn_stats_bwd_launch(dout + r0 * N, out + r0 * N, xhat + r0 * N, rows[p], N, dg, db, slots + (size_t)p * kBnStride, nullptr);
+  blk_slot_sum(slots, parts);
+  r0 = 0;
+  for (int p = 0; p < parts; r0 += rows[p++])
+    bn_apply_bwd_launch(dout + r0 * N, out + r0 * N, xhat + r0 * N, rstd, g, rows[p], N, slots + (size_t)p * kBnStride, dy + r0 * N, nullptr);
+  const int rc = blk_finish("t2l_blk_ft_bn_sync_bwd");
+  (void)hipFree(slots);
+  return rc;
 }
 
 static int blk_attn_shape(const std::string& who, int Tq, int Tk, int pairs, float p) {

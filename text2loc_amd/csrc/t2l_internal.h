@@ -294,6 +294,9 @@ int fine_train_forward_impl(t2l_ctx* ctx, const t2l_packed_cells* in, const floa
 int fine_train_forward_points_impl(t2l_ctx* ctx, const t2l_packed_cells* in, const float* pos, const float* rgb, const float* hint_desc,
                                    int n_pairs, int n_hints, float p, uint32_t seed, float* out, hipStream_t s);
 int fine_train_backward_impl(t2l_ctx* ctx, const float* grad_offsets, float* grad_hint, float* grad_pn, hipStream_t s);
+int fine_adam_step_impl(t2l_ctx* ctx, float lr, float b1, float b2, float eps, hipStream_t s);
+int fine_zero_grad_impl(t2l_ctx* ctx, hipStream_t s);
+int fine_adam_state_impl(t2l_ctx* ctx, int set, float* m, float* v, int64_t* step, int64_t* numel, hipStream_t s);
 void free_fine_train(t2l_ctx* ctx);
 // pointnet_cls.hip
 int cls_bind_impl(t2l_ctx* ctx, const t2l_train_tensor* tensors, int n);

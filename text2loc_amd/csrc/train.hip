@@ -105,6 +105,48 @@ struct AdamSet {
   }
 };
 
+// the same set for an owner outside this file (train_common.h): the fine stage's optimizer
+int adam_set_make(t2l_ctx* ctx, const std::vector<AdamBound>& trained, AdamSet* prev, bool* kept, AdamSet** out) {
+  AdamSet* a = new AdamSet();
+  TensorMap t;
+  std::vector<int64_t> numel;
+  for (auto& b : trained) {
+    a->names.push_back(b.name);
+    numel.push_back(b.numel);
+    t[b.name] = TTensor{b.data, b.grad, b.numel};
+  }
+  // prev's moments leave it only when they are adopted; if the build then fails they go back, so the caller's previous binding — pointer
+  // tables included — is as it was. Moments that are not adopted stay with prev until the caller frees it.
+  AdamSet::Old old;
+  const bool adopt = prev && adam_keep(ctx->train_keep_adam != 0, prev->mv != nullptr, prev->names, prev->numel, a->names, numel);
+  if (adopt) prev->detach(old);
+  if (int rc = a->build(ctx, t, old, kept)) {
+    if (adopt) {  // (build swapped them into a before anything could fail)
+      prev->mv = a->mv ? a->mv : old.mv;
+      a->mv = old.mv = nullptr;
+    }
+    adam_set_free(a);
+    return rc;
+  }
+  *out = a;
+  return T2L_OK;
+}
+void adam_set_free(AdamSet* a) {
+  if (!a) return;
+  a->release();
+  delete a;
+}
+void adam_set_step(const AdamSet* a, size_t t0, size_t t1, int64_t step, float lr, float b1, float b2, float eps, hipStream_t s) {
+  a->launch(a->plan.first_chunk(t0), a->plan.first_chunk(t1), step, lr, b1, b2, eps, s);
+}
+void adam_set_zero(const AdamSet* a, hipStream_t s) {
+  if (a->plan.n_chunks() > 0) a->zero(s);
+}
+int adam_set_state(t2l_ctx* ctx, AdamSet* a, const char* api, int set, float* m, float* v, int64_t* step, int64_t* numel, int64_t packed,
+                   hipStream_t s) {
+  return a->state(ctx, api, set, m, v, step, numel, packed, s);
+}
+
 // One [Linear, BatchNorm1d, ReLU] block of get_mlp (models/language_encoder.py:16-41) with its saved activations.
 struct MlpLayer {
   std::string prefix;  // e.g. "object_encoder.pos_encoder.1"
@@ -168,8 +210,9 @@ static int pn_train_bind(t2l_ctx* ctx, TrainState* st, std::vector<std::string>&
 static TrainState* state(t2l_ctx* ctx) { return reinterpret_cast<TrainState*>(ctx->train); }
 
 // ---- cross-rank BatchNorm statistics (t2l_train_sync_bn): slots [0, 2 kBnSlots) are the object branch's (forward | backward), the two
-// behind them the text head's inter_mlp (forward, backward)
-int64_t train_sync_bn_doubles() { return (int64_t)(2 * kBnSlots + 2) * kBnStride; }
+// behind them the text head's inter_mlp (forward, backward), then the fine step's (fine_train.hip; train_common.h)
+static_assert(kFineBnSlot0 == 2 * kBnSlots + 2, "the fine step's slots start behind the text head's");
+int64_t train_sync_bn_doubles() { return (int64_t)(kFineBnSlot0 + kFineBnSlots) * kBnStride; }
 void train_sync_changed(t2l_ctx* ctx) {
   if (TrainState* st = state(ctx)) st->fwd_acc_clean = st->bwd_acc_clean = false;
 }

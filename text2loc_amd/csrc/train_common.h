@@ -8,6 +8,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <string>
+#include <vector>
+
+struct t2l_ctx;
+
 namespace t2l {
 namespace train {
 
@@ -36,6 +41,14 @@ static inline Drop make_drop(uint32_t seed, int site, float p) {
   d.scale = d.thr ? 1.0f / (1.0f - p) : 1.0f;
   return d;
 }
+
+// One accumulator slot of a BatchNorm stage: [2 * 1024] channel sums + the ROW COUNT at kBnCount (cross-rank BatchNorm only, `sync`: the
+// slot is summed over the ranks between the statistics and the apply launch — t2l_train_sync_bn — and the apply side then divides by
+// the global count). The caller's buffer of t2l_train_sync_bn holds, in slots: [0, 16) the coarse object branch (forward | backward),
+// 16 / 17 the text head's inter_mlp (forward, backward), [kFineBnSlot0, + kFineBnSlots) the fine step's current stage.
+constexpr int kBnCount = 2048;
+constexpr int kBnStride = 2056;
+constexpr int kFineBnSlot0 = 18, kFineBnSlots = 4;
 
 // Bump arena over one device allocation: take() only advances (256-byte granules), the owner compares off with cap after laying a
 // pass out and rewinds off itself. Without a base (a pass that only counts) every pointer is null.
@@ -67,5 +80,23 @@ void seq_max_bwd_launch(const float* g, const int32_t* arg, int B, int S, int D,
 // hd = dropout(h) over n elements; d = dropout'(d) where h > 0, else 0, in place (Drop{}: the plain ReLU backward)
 void drop_fwd_launch(const float* h, size_t n, const train::Drop& dr, float* hd, hipStream_t s);
 void relu_drop_bwd_launch(float* d, const float* h, size_t n, const train::Drop& dr, hipStream_t s);
+
+// train.hip: its optimizer state (AdamSet: the moments, the chunk tables of adam_kernel / zero_kernel, the keep rule of adam_plan.h)
+// for an owner in another translation unit — the fine stage. adam_set_make builds the set over `trained` in list order; `prev` (may be
+// null) is the set of the binding this one replaces: its moments are adopted (*kept; prev then has none) when adam_keep says so and
+// stay with it otherwise; prev stays the caller's to adam_set_free, and after a failed call it is as it was. A step takes the tensors
+// [t0, t1) of the list (one launch; none for an empty range), the zeroing all of them.
+struct AdamSet;
+struct AdamBound {
+  std::string name;
+  float *data, *grad;
+  int64_t numel;
+};
+int adam_set_make(t2l_ctx* ctx, const std::vector<AdamBound>& trained, AdamSet* prev, bool* kept, AdamSet** out);
+void adam_set_free(AdamSet* a);
+void adam_set_step(const AdamSet* a, size_t t0, size_t t1, int64_t step, float lr, float b1, float b2, float eps, hipStream_t s);
+void adam_set_zero(const AdamSet* a, hipStream_t s);
+int adam_set_state(t2l_ctx* ctx, AdamSet* a, const char* api, int set, float* m, float* v, int64_t* step, int64_t* numel, int64_t packed,
+                   hipStream_t s);
 
 }  // namespace t2l

@@ -155,10 +155,7 @@ __global__ __launch_bounds__(256) void smallk_bwd_kernel(SmallkMulti m) {
 // unbiased variance (momentum 0.1), as torch does.
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int kBnRows = 64;
-// One accumulator slot: [2 * 1024] channel sums + the ROW COUNT at kBnCount (cross-rank BatchNorm only, `sync`: the slot is summed over
-// the ranks between the statistics and the apply launch — t2l_train_sync_bn — and the apply side then divides by the global count).
-constexpr int kBnCount = 2048;
-constexpr int kBnStride = 2056;
+// (the accumulator slot's layout, kBnCount / kBnStride: train_common.h)
 // MODE 0: acc[c] += sum y, acc[C+c] += sum y^2.  MODE 1: dv = out>0 ? d : 0; acc[c] += sum dv, acc[C+c] += sum dv*xhat
 template <int MODE>
 __device__ __forceinline__ void bn_stats_body(const float* __restrict__ y, const float* __restrict__ d, const float* __restrict__ out, int M,

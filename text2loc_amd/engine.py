@@ -133,6 +133,10 @@ EXPORTS = {
     "t2l_fine_train_forward_points": (C.c_int, [C.c_void_p, C.POINTER(_PackedCells), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                                 C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]),
     "t2l_fine_train_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "t2l_fine_adam_step": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "t2l_fine_zero_grad": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "t2l_fine_adam_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                      C.c_void_p]),
     "t2l_text_train_bind": (C.c_int, [C.c_void_p, C.POINTER(_TrainTensor), C.c_int32, C.c_char_p]),
     "t2l_text_head_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]),
     "t2l_text_head_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -550,6 +554,36 @@ class Engine:
         self._check(self.lib.t2l_fine_train_backward(self._h, self._ptr(grad_offsets, torch.float32, "grad_offsets"),
                                                      self._ptr(grad_hint_desc, torch.float32, "grad_hint_desc"),
                                                      self._ptr(grad_pn_feat, torch.float32, "grad_pn_feat"), _stream_ptr(self.device)))
+
+    # ---- the fine stage's optimizer (t2l_fine_adam_step: the tensors of fine_train_bind that carry a gradient buffer, bind order with
+    # the backbone's group last)
+    def fine_zero_grad(self):
+        self._check(self.lib.t2l_fine_zero_grad(self._h, _stream_ptr(self.device)))
+
+    def fine_adam_step(self, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8):
+        self._check(self.lib.t2l_fine_adam_step(self._h, float(lr), float(beta1), float(beta2), float(eps), _stream_ptr(self.device)))
+
+    def fine_adam_state(self):
+        """(exp_avg f32[n], exp_avg_sq f32[n], step | backbone step << 32) of the fine stage's engine-stepped tensors (GPU tensors)."""
+        n, step = C.c_int64(0), C.c_int64(0)
+        self._check(self.lib.t2l_fine_adam_state(self._h, 0, None, None, C.byref(step), C.byref(n), _stream_ptr(self.device)))
+        dev = torch.device("cuda", self.device)
+        m = torch.empty((int(n.value),), dtype=torch.float32, device=dev)
+        v = torch.empty_like(m)
+        if int(n.value):
+            self._check(self.lib.t2l_fine_adam_state(self._h, 0, m.data_ptr(), v.data_ptr(), C.byref(step), C.byref(n), _stream_ptr(self.device)))
+        return m, v, int(step.value)
+
+    def set_fine_adam_state(self, m: torch.Tensor, v: torch.Tensor, step: int):
+        n, st = C.c_int64(0), C.c_int64(int(step))
+        self._check(self.lib.t2l_fine_adam_state(self._h, 0, None, None, C.byref(C.c_int64(0)), C.byref(n), _stream_ptr(self.device)))
+        if int(m.numel()) != int(n.value) or int(v.numel()) != int(n.value):
+            raise T2LError(f"fine-stage adam state of {int(m.numel())} elements does not match the bound tensors ({int(n.value)})")
+        dev = torch.device("cuda", self.device)
+        m = m.to(dev, torch.float32).contiguous()
+        v = v.to(dev, torch.float32).contiguous()
+        self._check(self.lib.t2l_fine_adam_state(self._h, 1, m.data_ptr(), v.data_ptr(), C.byref(st), C.byref(n), _stream_ptr(self.device)))
+        torch.cuda.current_stream(self.device).synchronize()  # m, v may be temporaries
 
     # ------------------------------------------------------------------ training step (a9)
     def _packed_struct(self, packed: Dict[str, torch.Tensor]) -> "_PackedCells":

@@ -572,17 +572,27 @@ def _checked_batch_size(who: str, batch_size) -> int:
     return int(batch_size)
 
 
+def _checked_split(who: str, batch_size, rank, world):
+    """``_checked_batch_size`` plus the data-parallel split: -> (batch_size, rank, world) as ints, or ValueError."""
+    batch_size, rank, world = _checked_batch_size(who, batch_size), int(rank), int(world)
+    if world < 1 or not 0 <= rank < world or batch_size % world:
+        raise ValueError(f"{who}: need 0 <= rank < world and batch_size a multiple of world (every rank takes an equal slice of each "
+                         f"batch), got rank={rank}, world={world}, batch_size={batch_size}")
+    return batch_size, rank, world
+
+
 def _row_views(pos, col, counts):
     """(pos, rgb) f32[n_rows,256,3] of ``sample_rows`` cut into per-item ``{"pos", "x"}`` views [counts[i] * 256, 3] of consecutive rows."""
     ends = np.cumsum(counts).tolist()
     return [{"pos": pos[e - c:e].reshape(-1, 3), "x": col[e - c:e].reshape(-1, 3)} for c, e in zip(counts, ends)]
 
 
-def _batches(dataset: _PoseDataset, who: str, batch_size, device, shuffle, seed, epoch, drop_last, engine):
+def _batches(dataset: _PoseDataset, who: str, batch_size, device, shuffle, seed, epoch, drop_last, engine, rank=0, world=1):
     """The one batch loop behind ``fine_batches`` and ``coarse_batches`` (``who``): the items of ``dataset`` in the order of
     ``default_rng([seed, epoch])`` (``shuffle``) or as they lie, collated ``batch_size`` at a time; an ``object_points="ids"`` dataset
-    then finishes each batch on ``device`` (``_device_batch``). ``engine`` None: the weightless engine the dataset keeps per device."""
-    batch_size = _checked_batch_size(who, batch_size)
+    then finishes each batch on ``device`` (``_device_batch``). ``engine`` None: the weightless engine the dataset keeps per device.
+    ``rank`` of ``world``: the same global batches, of which this rank collates its contiguous slice."""
+    batch_size, rank, world = _checked_split(who, batch_size, rank, world)
     order = np.random.default_rng([int(seed), int(epoch)]).permutation(len(dataset)) if shuffle else np.arange(len(dataset))
     if dataset.point_mode == "ids" and dataset.wants_points and engine is None:
         from .plumbing import engine_for
@@ -593,6 +603,10 @@ def _batches(dataset: _PoseDataset, who: str, batch_size, device, shuffle, seed,
         chunk = order[lo:lo + batch_size]
         if drop_last and len(chunk) < batch_size:
             return
+        if world > 1:
+            if len(chunk) < world:  # a tail that cannot give every rank an item: all ranks leave it, so they take the same number of steps
+                return
+            chunk = chunk[rank * len(chunk) // world:(rank + 1) * len(chunk) // world]
         batch = dataset.collate_fn([dataset[int(i)] for i in chunk])
         if dataset.point_mode == "ids":
             dataset._device_batch(batch, engine, device)
@@ -600,7 +614,7 @@ def _batches(dataset: _PoseDataset, who: str, batch_size, device, shuffle, seed,
 
 
 def fine_batches(dataset: Kitti360FineDataset, batch_size: int, device, shuffle: bool = False, seed: int = 0, epoch: int = 0,
-                 drop_last: bool = False, engine=None):
+                 drop_last: bool = False, engine=None, rank: int = 0, world: int = 1):
     """One epoch of ``Kitti360FineDataset.collate_fn`` batches for ``fine_training.train_epoch`` / ``eval_epoch``. With an
     ``object_points="ids"`` dataset the batch's 16 * B point rows are sampled on ``device`` in ONE launch
     (``PackedCellSet.sample_rows``: slot s of item i under ``dataset.point_seed ^ draw_salts(epoch, i)[s]``) and
@@ -608,10 +622,14 @@ def fine_batches(dataset: Kitti360FineDataset, batch_size: int, device, shuffle:
     modes are collated as they are. ``shuffle``: the permutation of ``default_rng([seed, epoch])``. The same (dataset seed, seed,
     epoch) always gives the same batches.
     GPU work belongs to the process that owns the engine: a DataLoader worker may build host items, it may not run this generator.
-    ``engine``: the ``Engine`` to sample with (e.g. ``model.engine()``); without one the dataset keeps a weightless one per device."""
-    batch_size = _checked_batch_size("fine_batches", batch_size)  # a refused call leaves the dataset's epoch alone
+    ``engine``: the ``Engine`` to sample with (e.g. ``model.engine()``); without one the dataset keeps a weightless one per device.
+    Data parallel (``rank`` of ``world``): ``batch_size`` is the GLOBAL one and must be a multiple of ``world``; every global batch is
+    the one-process batch, of which rank r yields its contiguous slice — the same items, draw salts and flips, so the ranks' slices
+    concatenate to the batch one process would have collated. A short last batch is split as evenly as it goes (and left out by all
+    ranks when it has fewer items than ranks); ``drop_last`` keeps the shards equal, which the mean of the ranks' gradients assumes."""
+    batch_size, rank, world = _checked_split("fine_batches", batch_size, rank, world)  # a refused call leaves the dataset's epoch alone
     dataset.set_epoch(epoch)
-    yield from _batches(dataset, "fine_batches", batch_size, device, shuffle, seed, epoch, drop_last, engine)
+    yield from _batches(dataset, "fine_batches", batch_size, device, shuffle, seed, epoch, drop_last, engine, rank, world)
 
 
 # ---- coarse training batches from the resident cell set -------------------------------------------------------------------------------

@@ -9,7 +9,15 @@ the gradients at the top of ``step()``. The engine-stepped parameters' ``.grad``
 (``CellRetrievalNetwork.train_flat_grad``), so they travel as a single RCCL all_reduce (16.5 M floats = 66 MB with the
 backbone: per-link bound on xGMI, one large collective instead of ~150 small ones); the language head's gradients are
 flattened into a second one. ``grad_reduce="sum"`` pairs with ``ContrastiveLoss(group=pg)`` (every rank differentiates the
-GLOBAL loss w.r.t. its own rows: the sum over ranks is the exact gradient); ``"mean"`` is the usual average for per-rank losses.
+GLOBAL loss w.r.t. its own rows: the sum over ranks is the exact gradient; the default here); ``"mean"`` is the usual average for
+per-rank losses.
+
+``Adam(model)`` with a ``text2loc_amd.CrossMatch`` is the fine stage's optimizer (training/fine.py:57,72,229) and returns a ``FineAdam``:
+the decoders, mlp_offsets, the object-encoder branches and the jointly trained backbone on t2l_fine_zero_grad / t2l_fine_adam_step,
+the hint encoder's head on t2l_text_adam_step. The fine loss is a MEAN over the local rows (``offset_lambda * MSE``), so its
+data-parallel step takes ``grad_reduce="mean"`` (a ``FineAdam``'s default): with equal shards the mean of the ranks' gradients is the gradient of the
+one-process batch (the coarse step's ``"sum"`` belongs to its gathered, global loss). Only several processes on one GPU were run; no
+scaling curve was measured.
 """
 from __future__ import annotations
 
@@ -33,13 +41,33 @@ def all_reduce_flat(buf: torch.Tensor, group=None, mean: bool = False) -> torch.
 
 
 class Adam(torch.optim.Optimizer):
-    def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, group=None, grad_reduce: str = "sum",
+    DEFAULT_GRAD_REDUCE = "sum"  # (the coarse step differentiates a gathered, global loss)
+
+    def __new__(cls, model=None, *args, **kwargs):
+        # Adam(model) with a CrossMatch is a FineAdam: the one __init__ below runs for both, through the three hooks FineAdam overrides
+        # (which parameters the engine steps, which head parameters, the default reduction)
+        return super().__new__(FineAdam if cls is Adam and hasattr(model, "_fine_train_engine") else cls)
+
+    @staticmethod
+    def _engine_steps(model, n, p) -> bool:
+        """Does the engine's Adam kernel step parameter ``n``? The object branch incl. the PointNet++ backbone unless --pointnet_freeze;
+        not the backbone's classifier heads (not on the coarse path — features2 is consumed, they train in pointnet_pretrain: .grad
+        stays None and torch skips them as in the reference)."""
+        return n.startswith(("object_encoder.", "obj_inter_module.")) and not n.startswith(
+            ("object_encoder.pointnet.class_classifier.", "object_encoder.pointnet.color_classifier."))
+
+    @staticmethod
+    def _head_params(le):
+        return le.engine_optimizer_params() if hasattr(le, "engine_optimizer_params") else []
+
+    def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, group=None, grad_reduce: str = None,
                  data_parallel: bool = False, sync_bn: bool = False, text_engine: bool = True):
         """``group``: a torch.distributed process group, or ``data_parallel=True`` for the default one — turns the gradient
         all-reduce of ``step()`` on. ``sync_bn``: also ``model.sync_batchnorm(group)`` — BatchNorm statistics over all ranks' batches,
         i.e. the reference's one-process step on the global batch. ``text_engine``: the language head's trained parameters (when the
         engine's training head serves this model: ``LanguageEncoder.engine_optimizer_params``) are stepped by ``t2l_text_adam_step`` — one
         launch, moments inside the library — instead of a torch.optim.Adam beside the engine."""
+        grad_reduce = self.DEFAULT_GRAD_REDUCE if grad_reduce is None else grad_reduce
         if grad_reduce not in ("sum", "mean"):
             raise ValueError("grad_reduce must be 'sum' or 'mean'")
         if not getattr(model, "published_shape", True):
@@ -50,19 +78,13 @@ class Adam(torch.optim.Optimizer):
         obj, rest, text = [], [], []
         le = getattr(model, "language_encoder", None)
         on_gpu = any(p.is_cuda for p in model.parameters())
-        text_ids = {id(p) for _, p in le.engine_optimizer_params()} if (text_engine and on_gpu and hasattr(le, "engine_optimizer_params")) else set()
+        head = self._head_params(le) if (text_engine and on_gpu) else []
+        text_ids = {id(p) for _, p in head}
         for n, p in model.named_parameters():
             if not p.requires_grad:
                 continue
-            if id(p) in text_ids:
-                text.append(p)  # the text head's trained parameters: t2l_text_adam_step (one launch, moments inside the library)
-                continue
-            if n.startswith(("object_encoder.pointnet.class_classifier.", "object_encoder.pointnet.color_classifier.")):
-                rest.append(p)  # not on the coarse path (features2 is consumed; they train in pointnet_pretrain): .grad stays None, torch skips them as in the reference
-            elif n.startswith(("object_encoder.", "obj_inter_module.")):
-                obj.append(p)   # incl. the PointNet++ backbone unless --pointnet_freeze
-            else:
-                rest.append(p)
+            # the text head's trained parameters: t2l_text_adam_step (one launch, moments inside the library)
+            (text if id(p) in text_ids else obj if self._engine_steps(model, n, p) else rest).append(p)
         # names in named_parameters order of everything the object-branch kernel does NOT step, and which optimizer steps each here:
         # a checkpoint written under the other ``text_engine`` setting (or before the head moved into the engine) holds the same
         # moments under the other layout — load_state_dict migrates by these names
@@ -78,6 +100,8 @@ class Adam(torch.optim.Optimizer):
         super().__init__(groups, dict(lr=lr, betas=tuple(betas), eps=eps))
         self._model = model
         self._text = bool(text)
+        self._head = [("language_encoder." + n, p) for n, p in head]
+        self._rest = rest
         if sync_bn:
             model.sync_batchnorm(group)
         self._torch = torch.optim.Adam(rest, lr=lr, betas=tuple(betas), eps=eps) if rest else None
@@ -90,6 +114,9 @@ class Adam(torch.optim.Optimizer):
                 self._model.language_encoder.engine_zero_grad()  # in place: the engine accumulates into the bound buffers
         if self._torch is not None:
             self._torch.zero_grad(set_to_none=set_to_none)
+
+    def _bound_engine(self):
+        return self._model.train_engine()
 
     # ---- data parallel ------------------------------------------------------------------------------------------------
     def _world(self) -> int:
@@ -105,7 +132,7 @@ class Adam(torch.optim.Optimizer):
         world = self._world()
         if world == 1:
             return
-        self._model.train_engine()  # binds (and so allocates) the flat buffer if nothing has yet
+        self._bound_engine()  # binds (and so allocates) the flat buffer if nothing has yet
         bufs = []
         flat = self._model.train_flat_grad()
         if flat is not None:
@@ -254,3 +281,148 @@ class Adam(torch.optim.Optimizer):
                 m = torch.cat([saved[n][0].detach().to(dev, torch.float32).reshape(-1) for n, _ in text])
                 v = torch.cat([saved[n][1].detach().to(dev, torch.float32).reshape(-1) for n, _ in text])
                 le._th_train_engine.set_text_adam_state(m, v, steps.pop())
+
+
+class FineAdam(Adam):
+    """``Adam(model)`` for a ``CrossMatch`` (constructed through ``Adam``; same keywords and the same ``__init__``, except that
+    ``grad_reduce`` defaults to ``"mean"``). Three parameter groups at most: the
+    engine's (``CrossMatch.engine_steps``: one zeroing launch, one Adam launch, moments inside the library, ``.grad`` views of
+    ``CrossMatch.train_flat_grad()``), whatever is left (``torch.optim.Adam``: a text branch on its PyTorch modules, parameters the
+    configuration never differentiates — their ``.grad`` stays None and torch skips them), and the hint encoder's engine head
+    (``LanguageEncoder.engine_head_params``: t2l_text_adam_step in its fine layout). Data parallel: ``all_reduce_grads`` sends the flat
+    buffer as one collective and every other gradient, the hint encoder's included, as a second.
+
+    ``state_dict()`` is ``torch.optim.Adam(model.parameters())``'s own: one group over every parameter in ``model.parameters()``
+    order, exp_avg / exp_avg_sq / step per stepped parameter — a checkpoint written by either optimizer loads into the other."""
+
+    DEFAULT_GRAD_REDUCE = "mean"  # the fine loss is a mean over the local rows: the ranks' gradients are averaged
+
+    @staticmethod
+    def _engine_steps(model, n, p) -> bool:
+        return model.engine_steps(n, p)
+
+    @staticmethod
+    def _head_params(le):
+        return le.engine_head_params() if hasattr(le, "engine_head_params") else []
+
+    def _bound_engine(self):
+        return self._model._fine_train_engine()
+
+    def zero_grad(self, set_to_none: bool = False):
+        """The engine's gradients are zeroed IN PLACE by one kernel (it accumulates into fixed buffers); the backbone then sits out the
+        next step unless a backward goes through it again, as a ``.grad`` of None would make it under torch."""
+        if self._model.device.type == "cuda":
+            self._bound_engine().fine_zero_grad()
+            if self._text:
+                self._model.language_encoder.engine_zero_grad()
+        if self._torch is not None:
+            self._torch.zero_grad(set_to_none=set_to_none)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self.all_reduce_grads()
+        g = self.param_groups[0]
+        self._bound_engine().fine_adam_step(g["lr"], g["betas"][0], g["betas"][1], g["eps"])
+        self._model._train_generation += 1  # parameters changed behind torch's back: the eval path must re-load its weights
+        if self._torch is not None:
+            for src, dst in zip([g_ for g_ in self.param_groups[1:] if g_["t2l_engine"] is False], self._torch.param_groups):
+                dst["lr"], dst["betas"], dst["eps"] = src["lr"], src["betas"], src["eps"]
+            self._torch.step()
+        if self._text:
+            gt = self.param_groups[-1]
+            self._model.language_encoder.engine_adam_step(gt["lr"], gt["betas"], gt["eps"])
+        return loss
+
+    # ---- checkpoint / resume in torch.optim.Adam(model.parameters())'s layout -----------------------------------------------
+    def _torch_group(self, n_params: int):
+        g = self.param_groups[0]
+        ref = torch.optim.Adam([torch.zeros(1)], lr=g["lr"], betas=tuple(g["betas"]), eps=g["eps"]).state_dict()["param_groups"][0]
+        return dict(ref, params=list(range(n_params)))
+
+    @staticmethod
+    def _flat_entries(order, m, v, steps):
+        """{id(parameter): state entry} of the tensors of ``order`` = [(name, parameter, which step)] whose step is > 0."""
+        out, off = {}, 0
+        for _, p, k in order:
+            n = p.numel()
+            if steps[k] > 0:
+                out[id(p)] = {"step": torch.tensor(float(steps[k])), "exp_avg": m[off:off + n].view_as(p).clone(),
+                              "exp_avg_sq": v[off:off + n].view_as(p).clone()}
+            off += n
+        return out
+
+    def _engine_order(self):
+        from .cross_matcher import BACKBONE
+
+        return [(n, p, 1 if n.startswith(BACKBONE) else 0) for n, p in self._model.engine_adam_order()]
+
+    def state_dict(self):
+        model = self._model
+        params = list(model.parameters())
+        entries = {}
+        if model.device.type == "cuda":
+            m, v, step = self._bound_engine().fine_adam_state()
+            entries.update(self._flat_entries(self._engine_order(), m, v, (step & 0xFFFFFFFF, step >> 32)))
+            if self._text:
+                le = model.language_encoder
+                le._bind_text_train(model.device)
+                m, v, step = le._th_train_engine.text_adam_state()
+                entries.update(self._flat_entries([(n, p, 0) for n, p in self._head], m, v, (int(step),)))
+        if self._torch is not None:
+            ts = self._torch.state_dict()["state"]
+            for i, p in enumerate(self._rest):
+                if i in ts:
+                    entries[id(p)] = ts[i]
+        return {"state": {i: entries[id(p)] for i, p in enumerate(params) if id(p) in entries},
+                "param_groups": [self._torch_group(len(params))]}
+
+    def _flat_from(self, order, saved, what):
+        """(m, v, steps) for the engine from the checkpoint's entries: zeros for a tensor it holds nothing for (never stepped), one step
+        count per group — the engine keeps one."""
+        dev = self._model.device
+        ms, vs, steps = [], [], {}
+        for n, p, k in order:
+            e = saved.get(id(p))
+            if e is None:
+                ms.append(torch.zeros(p.numel(), dtype=torch.float32, device=dev))
+                vs.append(torch.zeros(p.numel(), dtype=torch.float32, device=dev))
+                continue
+            if tuple(e["exp_avg"].shape) != tuple(p.shape):
+                raise ValueError(f"optimizer checkpoint: moments of {n} are {tuple(e['exp_avg'].shape)}, the parameter is {tuple(p.shape)}")
+            ms.append(e["exp_avg"].detach().to(dev, torch.float32).reshape(-1))
+            vs.append(e["exp_avg_sq"].detach().to(dev, torch.float32).reshape(-1))
+            steps.setdefault(k, set()).add(int(e["step"]))
+        for k, st in steps.items():
+            if len(st) != 1:
+                raise ValueError(f"{what} tensors of the checkpoint disagree on the Adam step ({sorted(st)}): the engine keeps one per group")
+        return torch.cat(ms), torch.cat(vs), {k: st.pop() for k, st in steps.items()}
+
+    def load_state_dict(self, sd):
+        model = self._model
+        params = list(model.parameters())
+        ids = [i for g in sd["param_groups"] for i in g["params"]]
+        if len(ids) != len(params):
+            raise ValueError(f"optimizer checkpoint holds {len(ids)} parameters; this model has {len(params)}: not a checkpoint of "
+                             f"torch.optim.Adam(model.parameters()) for this model")
+        src = sd["param_groups"][0]
+        for g in self.param_groups:
+            g.update({k: src[k] for k in ("lr", "betas", "eps") if k in src})
+            g["betas"] = tuple(g["betas"])
+        saved = {id(p): sd["state"][i] for i, p in zip(ids, params) if i in sd["state"]}
+        if self._torch is not None:
+            state = {i: {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in saved[id(p)].items()}
+                     for i, p in enumerate(self._rest) if id(p) in saved}
+            self._torch.load_state_dict({"state": state, "param_groups": [self._torch_group(len(self._rest))]})
+        order = self._engine_order()
+        if order:
+            m, v, steps = self._flat_from(order, saved, "engine-stepped")
+            self._bound_engine().set_fine_adam_state(m, v, steps.get(0, 0) | (steps.get(1, 0) << 32))
+        if self._text:
+            le = model.language_encoder
+            le._bind_text_train(model.device)
+            m, v, steps = self._flat_from([(n, p, 0) for n, p in self._head], saved, "text-head")
+            le._th_train_engine.set_text_adam_state(m, v, steps.get(0, 0))

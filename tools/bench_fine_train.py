@@ -16,7 +16,14 @@ _backward) and off (the head on its PyTorch modules: exactly the step before the
 the packing of the objects, the engine's decoder step, the optimizer — is the same code in both. Every row gives the five
 repetitions' medians' median and their spread (max - min). ``--text-only on|off`` runs one of the two (a kernel trace of its own).
 
+`--optimizer engine|torch|both`: the step through ``CrossMatch.forward`` under ``train()`` (embedding mode, `--points`: point batches
+with the backbone trained jointly, `--text`: with the real hint encoder; the two combine) with ``text2loc_amd.optim.Adam(model)`` — t2l_fine_zero_grad /
+t2l_fine_adam_step, the hint encoder's head on t2l_text_adam_step — or ``torch.optim.Adam(model.parameters())``, which is the step as it
+was before the engine had the fine stage's optimizer. ``both`` puts the two rows of a size side by side in one run, with the gain and
+whether it exceeds the larger of the two spreads.
+
     python tools/bench_fine_train.py [--batches 32,256] [--iters 20] [--warmup 10] [--reps 5] [--points | --text [--tokens 12]]
+                                     [--optimizer engine|torch|both]
 """
 from __future__ import annotations
 
@@ -192,9 +199,54 @@ def _stub_tokenizer(sentences, return_tensors="pt", padding="longest"):
     return {"input_ids": ids, "attention_mask": torch.ones_like(ids)}
 
 
-def bench_text(B, L, engine_head, iters, warmup, reps, H=6):
-    from text2loc_amd.cell_retrieval import LanguageEncoder
+def _objects(B):
     from text2loc_amd.cross_matcher import pad_objects
+
+    cells = synth.make_cells(B, seed=1, min_obj=16, max_obj=16)
+    objects = [[] for _ in range(B)]
+    for b, o, label, xyz, rgb in synth.make_object_points(cells, 1):
+        objects[b].append(_Obj(label, xyz, rgb))
+    return cells, [pad_objects(o) for o in objects]
+
+
+def bench_optimizer(mode, B, kind, L, iters, warmup, reps, H=6):
+    """One row: the model-level step in ``mode`` (embed / points / text / points+text) stepped by ``kind`` (engine: optim.Adam(model);
+    torch)."""
+    from text2loc_amd import optim
+
+    target = torch.from_numpy(np.random.default_rng(2).random((B, 2)).astype(np.float32)).cuda()
+    points = None
+    if mode in ("text", "points+text"):
+        model, objects, hints, cells = _text_problem(B, L, True, H, points=mode == "points+text")
+    else:
+        args = make_args(mode == "embed")
+        args.pointnet_freeze = mode != "points"
+        model = CrossMatch(synth.KNOWN_CLASS, synth.COLOR_NAMES, args, language_encoder=torch.nn.Identity())
+        sd = dict(synth.make_fine_weights(0))
+        if mode == "points":
+            sd.update(synth.make_pointnet_weights(0))
+        model.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=False)
+        model = model.cuda().train()
+        cells, objects = _objects(B)
+        hints = torch.from_numpy(np.random.default_rng(2).standard_normal((B, H, 128)).astype(np.float32)).cuda()
+    if mode in ("points", "points+text"):
+        pos, rgb = (torch.from_numpy(a).cuda() for a in synth.make_sampled_points(cells, 3))
+        points = [{"pos": pos[16 * b:16 * b + 16].reshape(-1, 3), "x": rgb[16 * b:16 * b + 16].reshape(-1, 3)} for b in range(B)]
+    opt = optim.Adam(model, lr=1e-4) if kind == "engine" else torch.optim.Adam(model.parameters(), lr=1e-4)
+
+    def step():
+        opt.zero_grad(set_to_none=False)
+        loss = LAMBDA * F.mse_loss(model(objects, hints, points), target)
+        loss.backward()
+        opt.step()
+
+    ms = time_steps(step, iters, warmup, reps, all_reps=True)
+    return {"mode": mode, "B": B, "optimizer": kind, "ms_step": round(float(np.median(ms)), 4), "spread_ms": round(max(ms) - min(ms), 4),
+            "reps_ms": [round(x, 4) for x in ms]}
+
+
+def _text_problem(B, L, engine_head, H=6, points=False):
+    from text2loc_amd.cell_retrieval import LanguageEncoder
 
     hidden = torch.from_numpy(synth.make_t5_hidden(B * H, L, seed=3)).cuda()
     enc = LanguageEncoder(128, fixed_embedding=True, intra_module_num_layers=1, is_fine=True, llm_model=_StubT5(hidden),
@@ -203,15 +255,23 @@ def bench_text(B, L, engine_head, iters, warmup, reps, H=6):
             if ".inter_module." not in k}
     enc.load_state_dict(head, strict=False)
     enc.use_engine_train_head = bool(engine_head)
-    model = CrossMatch(synth.KNOWN_CLASS, synth.COLOR_NAMES, make_args(True), language_encoder=enc)
-    model.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in synth.make_fine_weights(0).items()}, strict=False)
+    args = make_args(not points)
+    args.pointnet_freeze = not points  # point batches: the published command, the backbone trains with everything else
+    model = CrossMatch(synth.KNOWN_CLASS, synth.COLOR_NAMES, args, language_encoder=enc)
+    sd = dict(synth.make_fine_weights(0))
+    if points:
+        sd.update(synth.make_pointnet_weights(0))
+    model.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=False)
     model = model.cuda().train()
-    cells = synth.make_cells(B, seed=1, min_obj=16, max_obj=16)
-    objects = [[] for _ in range(B)]
-    for b, o, label, xyz, rgb in synth.make_object_points(cells, 1):
-        objects[b].append(_Obj(label, xyz, rgb))
-    objects = [pad_objects(o) for o in objects]
+    cells, objects = _objects(B)
     texts = [" ".join(["The pose is north of a gray pole."] * H)] * B
+    return model, objects, texts, cells
+
+
+def bench_text(B, L, engine_head, iters, warmup, reps, H=6):
+    from text2loc_amd.cell_retrieval import LanguageEncoder
+
+    model, objects, texts, _ = _text_problem(B, L, engine_head, H)
     target = torch.from_numpy(np.random.default_rng(2).random((B, 2)).astype(np.float32)).cuda()
     opt = torch.optim.Adam(model.parameters(), lr=1e-4)
     n0 = LanguageEncoder.train_engine_calls
@@ -239,8 +299,23 @@ def main():
     ap.add_argument("--text", action="store_true", help="the whole step with a real LanguageEncoder(is_fine) behind fixed hidden states")
     ap.add_argument("--tokens", type=int, default=12, help="--text: tokens per hint sentence")
     ap.add_argument("--text-only", choices=["on", "off"], default=None, help="--text: only the row with the engine head on / off")
+    ap.add_argument("--optimizer", choices=["engine", "torch", "both"], default=None,
+                    help="the model-level step with optim.Adam(model) (engine), torch.optim.Adam(model.parameters()) (torch), or both rows")
     a = ap.parse_args()
     torch.manual_seed(0)
+    if a.optimizer is not None:
+        mode = "points+text" if (a.text and a.points) else "text" if a.text else "points" if a.points else "embed"
+        kinds = ["engine", "torch"] if a.optimizer == "both" else [a.optimizer]
+        rows = [bench_optimizer(mode, int(B), k, a.tokens, a.iters, a.warmup, a.reps) for B in a.batches.split(",") for k in kinds]
+        by = {(r["B"], r["optimizer"]): r for r in rows}
+        for B in {r["B"] for r in rows}:
+            if (B, "engine") in by and (B, "torch") in by:
+                e, t = by[(B, "engine")], by[(B, "torch")]
+                e["gain_ms"] = round(t["ms_step"] - e["ms_step"], 4)
+                e["beats_torch_adam_by_more_than_the_spread"] = bool(e["gain_ms"] > max(e["spread_ms"], t["spread_ms"]))
+        print(json.dumps({"metric": "fine-stage training step through CrossMatch.forward under train() (fwd + offset_lambda*MSE + bwd + "
+                                    "zero_grad + Adam), 2 decoder layers, 6 hints, dropout 0.1, by optimizer", "unit": "ms/step", "rows": rows}))
+        return
     if a.text:
         heads = [True, False] if a.text_only is None else [a.text_only == "on"]
         rows = [bench_text(int(B), a.tokens, h, a.iters, a.warmup, a.reps) for B in a.batches.split(",") for h in heads]
