@@ -128,16 +128,22 @@ def visible(gx, gm, mut=None):
     return own & ok[None, :] & (j < gm[2])[None, :]
 
 
-def heads_core(q, k, v, vis=None):
-    """(o [Tq, 128], any [Tq], p [4, Tq, Tk], z [4, Tq, Tk]): softmax(q k^T / sqrt(32)) v per head over the visible keys"""
+def head_scale(hd):
+    """the kernels' literal of 1 / sqrt(head_dim) (fine.hip; encode.hip: planes_layer)"""
+    return {32: SCALE, 64: 0.125}[hd]
+
+
+def heads_core(q, k, v, vis=None, hd=HD):
+    """(o [Tq, W], any [Tq], p [heads, Tq, Tk], z [heads, Tq, Tk]): softmax(q k^T / sqrt(hd)) v per head of ``hd`` features over the
+    visible keys; W = q's width (128 and four heads of 32 in the fine match; tests/encode_blocks.py: 128 or 256, heads of 32 or 64)"""
     Tq, Tk = q.shape[0], k.shape[0]
     vis = np.ones((Tq, Tk), bool) if vis is None else vis
     anyk = vis.any(axis=1)
-    o = np.zeros((Tq, D))
+    o = np.zeros((Tq, q.shape[1]))
     ps, zs = [], []
-    for h in range(HEADS):
-        c = slice(h * HD, (h + 1) * HD)
-        s = mm(q[:, c], k[:, c].T) * SCALE
+    for h in range(q.shape[1] // hd):
+        c = slice(h * hd, (h + 1) * hd)
+        s = mm(q[:, c], k[:, c].T) * head_scale(hd)
         s = np.where(vis, s, -np.inf)
         m = np.where(anyk, s.max(axis=1, initial=-np.inf), 0.0)
         z = s - m[:, None]
@@ -152,16 +158,21 @@ def heads_core(q, k, v, vis=None):
     return o, anyk, np.stack(ps), np.stack(zs)
 
 
-def mha_core(xq, xk, W, b, vis=None, mut=None):
+def mha_core(xq, xk, W, b, vis=None, mut=None, hd=HD):
     W, b = np.asarray(W, np.float64), np.asarray(b, np.float64)
-    # the lo plane dropped from the activation operand of ONE product: the value projection's (drop_lo), the query projection's (drop_lo_q)
+    width = W.shape[1]  # (the module's D unless tests/encode_blocks.py calls)
+    # the lo plane dropped from the activation operand of ONE product: the value projection's (drop_lo), the query projection's
+    # (drop_lo_q), the key projection's (drop_lo_k)
     xq_q = split(xq)[0].astype(np.float64) if mut == "drop_lo_q" else xq
+    xk_k = split(xk)[0].astype(np.float64) if mut == "drop_lo_k" else xk
     xk_v = split(xk)[0].astype(np.float64) if mut == "drop_lo" else xk
-    q, k, v = linear(xq_q, W[:D], b[:D]), linear(xk, W[D:2 * D], b[D:2 * D]), linear(xk_v, W[2 * D:], b[2 * D:])
-    o, anyk, p, z = heads_core(q, k, v, vis)
-    if mut == "head_cols":
+    q, k, v = (linear(xq_q, W[:width], b[:width]), linear(xk_k, W[width:2 * width], b[width:2 * width]),
+               linear(xk_v, W[2 * width:], b[2 * width:]))
+    o, anyk, p, z = heads_core(q, k, v, vis, hd)
+    if mut == "head_cols":  # heads 1 and 2 change places
+        assert width >= 3 * hd, "the mutant swaps the second and the third head"
         o = o.copy()
-        o[:, 32:64], o[:, 64:96] = o[:, 64:96].copy(), o[:, 32:64].copy()
+        o[:, hd:2 * hd], o[:, 2 * hd:3 * hd] = o[:, 2 * hd:3 * hd].copy(), o[:, hd:2 * hd].copy()
     return o, anyk, (q, k, v, p, z)
 
 
@@ -224,25 +235,28 @@ def lin_b(a, ea, W, b, arm):
     return linear(a, W, b), ey
 
 
-def attention_b(x, ex, mem, em, gx, gm, W, b, arm, mut=None):
-    """One attention block on tiles -> (o, eo, any): o, eo [32, 128] BEFORE the store, any [32] = the query sees a key in mem"""
+def attention_b(x, ex, mem, em, gx, gm, W, b, arm, mut=None, vis=None, hd=HD):
+    """One attention block on tiles -> (o, eo, any): o, eo [32, W] BEFORE the store, any [32] = the query sees a key in mem.
+    vis: the visibility matrix itself instead of the one the tile groups give (tests/encode_blocks.py; gx, gm are then unused);
+    hd: the head size (the width is W's)."""
     W, b = np.asarray(W, np.float64), np.asarray(b, np.float64)
+    width, heads, scale = W.shape[1], W.shape[1] // hd, head_scale(hd)
     core = "f32" if arm == "f32" else "split"
     Pc, relc, floorc = ARMS[core]
-    vis = visible(gx, gm, mut)
-    o, anyk, (q, k, v, p, z) = mha_core(x, mem, W, b, vis, mut)
-    _, eq = lin_b(x, ex, W[:D], b[:D], arm)
-    _, ek = lin_b(mem, em, W[D:2 * D], b[D:2 * D], arm)
-    _, ev = lin_b(mem, em, W[2 * D:], b[2 * D:], arm)
-    eo = np.zeros((32, D))
+    vis = visible(gx, gm, mut) if vis is None else vis
+    o, anyk, (q, k, v, p, z) = mha_core(x, mem, W, b, vis, mut, hd)
+    _, eq = lin_b(x, ex, W[:width], b[:width], arm)
+    _, ek = lin_b(mem, em, W[width:2 * width], b[width:2 * width], arm)
+    _, ev = lin_b(mem, em, W[2 * width:], b[2 * width:], arm)
+    eo = np.zeros((32, width))
     seen = vis.any(axis=0)
-    for h in range(HEADS):
-        c = slice(h * HD, (h + 1) * HD)
+    for h in range(heads):
+        c = slice(h * hd, (h + 1) * hd)
         aq, ak, av = np.abs(q[:, c]), np.abs(k[:, c]), np.where(seen[:, None], np.abs(v[:, c]), 0.0)
         evh = np.where(seen[:, None], ev[:, c], 0.0)
-        s_abs = SCALE * (aq @ ak.T)
-        es = SCALE * (eq[:, c] @ ak.T + aq @ ek[:, c].T + eq[:, c] @ ek[:, c].T)
-        es = es + C * ((Pc * (HD + 8) * U + relc) * s_abs + floorc * SCALE * (aq.sum(axis=1)[:, None] + ak.sum(axis=1)[None, :]))
+        s_abs = scale * (aq @ ak.T)
+        es = scale * (eq[:, c] @ ak.T + aq @ ek[:, c].T + eq[:, c] @ ek[:, c].T)
+        es = es + C * ((Pc * (hd + 8) * U + relc) * s_abs + floorc * scale * (aq.sum(axis=1)[:, None] + ak.sum(axis=1)[None, :]))
         zh = np.where(vis, z[h], 0.0)
         es = es + C * U * (s_abs + np.abs(zh))  # the scale, the subtraction of the maximum
         delta = np.where(vis, es, 0.0).max(axis=1)
@@ -250,7 +264,7 @@ def attention_b(x, ex, mem, em, gx, gm, W, b, arm, mut=None):
         ep = np.minimum(p[h] * rho[:, None] + np.where(vis & (zh < -LOGIT_RANGE), EXP_TAIL * (1 + ETA), 0.0), 1.0)  # (a probability)
         pv = p[h] @ av
         eo[:, c] = ep @ av + p[h] @ evh + ep @ evh
-        eo[:, c] += C * ((Pc * (HD + 8) * U + relc) * pv + floorc * (p[h].sum(axis=1)[:, None] + (vis.astype(np.float64) @ av)))
+        eo[:, c] += C * ((Pc * (hd + 8) * U + relc) * pv + floorc * (p[h].sum(axis=1)[:, None] + (vis.astype(np.float64) @ av)))
     eo[~anyk] = 0.0
     return o, eo, anyk
 
@@ -276,14 +290,15 @@ def attention_tiles_b(x, ex, mems, gx, gms, W, b, arm, shared, init=None, mut=No
 
 def layer_norm_b(y, ey, g, b, mut=None):
     g, b = np.asarray(g, np.float64), np.asarray(b, np.float64)
+    width = y.shape[-1]
     out = layer_norm(y, g, b, mut)
     mu = y.mean(axis=-1, keepdims=True)
     sig = np.sqrt(((y - mu) ** 2).mean(axis=-1, keepdims=True) + LN_EPS)
     e_in = ey + LN_DEPTH * U * np.abs(y).mean(axis=-1, keepdims=True) + U * np.abs(y - mu)
     nrm = np.sqrt((e_in * e_in).sum(axis=-1, keepdims=True))
-    sig_eff = sig - nrm / np.sqrt(D)
+    sig_eff = sig - nrm / np.sqrt(width)
     ref = layer_norm(y, g, b)
-    cap = 2 * np.sqrt(D - 1.0) * np.abs(g)  # |out - b| <= sqrt(D - 1) |g| whatever the row holds
+    cap = 2 * np.sqrt(width - 1.0) * np.abs(g)  # |out - b| <= sqrt(D - 1) |g| whatever the row holds
     with np.errstate(divide="ignore", invalid="ignore"):
         e = np.where(sig_eff > 0, np.abs(g).max() * nrm / sig_eff, np.inf)
     e = np.minimum(e, cap) + C * ((LN_DEPTH / 2 + 4) * U + EPS_RSQRT) * np.abs(ref - b) + C * U * np.abs(ref)

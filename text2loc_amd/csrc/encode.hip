@@ -202,8 +202,15 @@ __device__ __forceinline__ _Float16* pl_bl(_Float16* base, int t) { return base 
 //   * pass c of the feed-forward covers k-steps [c D/16, (c + 1) D/16) of linear2's half-split packing at K = FFP D (mfma_h3.h:
 //     lane half kh of step s holds k = kh K/2 + 8 s ..), i.e. hidden units [c D/2, (c + 1) D/2) in columns [0, D/2) of the B planes and
 //     units K/2 + [c D/2, (c + 1) D/2) in columns [D/2, D): waves below D / 64 compute the former's tiles, the others the latter's.
-template <bool SG, int D, int HD, int FFP, bool WATCH, typename Mask>
-__device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& W, Mask mask, bool& bad, bool last_to_f32, float* lnred) {
+// tap(where, c): an empty functor in the product; the dev block library (encode_blocks.hip) copies the planes out behind the layer's own
+// barriers — where = 0 the B planes behind the attention, 1 the X planes behind the first residual + LayerNorm, 2 the B planes of
+// feed-forward pass c.
+struct PlNoTap {
+  __device__ __forceinline__ void operator()(int, int) const {}
+};
+template <bool SG, int D, int HD, int FFP, bool WATCH, typename Mask, typename TAP = PlNoTap>
+__device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& W, Mask mask, bool& bad, bool last_to_f32, float* lnred,
+                                             const TAP& tap = TAP()) {
   static_assert(D == 128 || D == 256, "one wave per 32-wide feature tile, four or eight waves");
   static_assert(HD == 32 || HD == 64, "a head is one or two 32-row tiles of q^T / k^T / v");
   constexpr int LDP = PlaneGeo<D>::kLd, LDX = PlaneGeo<D>::kLdF, NW = PlaneGeo<D>::kWaves;
@@ -400,6 +407,7 @@ __device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& 
     }
   }
   __syncthreads();
+  tap(0, 0);
   // operand fragments of the row-wise products: token fragment of tile t at k-step s (this lane's row `col`, k half `half`)
   const int frow = col * LDP + half * KH;
   // x = LayerNorm(x + acc^T + bias) * g + be for both tiles — the residual epilogue and the LayerNorm behind it in one go (round 5; proven
@@ -479,6 +487,7 @@ __device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& 
     resid_ln(acc, W.out_b, W.ln1_w, W.ln1_b, false);
   }
   __syncthreads();
+  tap(1, 0);
   {  // ---- feed-forward, FFP passes of D hidden units; wave w: one hidden tile per pass and one output tile, both token tiles
     f32x16 acc[2];
 #pragma unroll
@@ -514,6 +523,7 @@ __device__ __forceinline__ void planes_layer(_Float16* base, const InterFusedW& 
           plane_put4(pl_bh<D>(base, t), pl_bl<D>(base, t), col * LDP + cbase + u0, v);
         }
       __syncthreads();
+      tap(2, c);
       const uint4* w2 = W.ff2_hp + (((size_t)wave * FS + HS * c) * 64 + lane) * 2;
       stream_weights<SG, HS, kRingDepth>(w2, [&](int s, const HFrag& wf) {
 #pragma unroll

@@ -151,12 +151,7 @@ __global__ __launch_bounds__(256) void blk_fine_decoder_kernel(FDecoder D, BlkTi
 
 // the three forms whose float32 error the bounds of tests/fine_blocks.py cannot derive from the code: as fine.hip spells them
 __global__ void blk_fine_probe_kernel(const float* __restrict__ in, float* __restrict__ e, float* __restrict__ rs, float* __restrict__ rc, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float v = in[i];
-  e[i] = __expf(v);
-  rs[i] = 1.0f / sqrtf(v);
-  rc[i] = 1.f / v;
+  blk_probe_body(in, e, rs, rc, n);
 }
 
 static bool blk_groups(const int32_t* g, TileGroups* out, int* kind) {  // kind: 0 / 1 object tile A / B, 2 the hint tile

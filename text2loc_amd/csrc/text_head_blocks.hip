@@ -29,6 +29,17 @@ int th_blk_device(const std::string& who) {
 }
 
 }  // namespace
+
+// for encode_blocks.hip: the inter layer as text_inter_impl hands it to text_inter_fused_launch
+bool blk_text_inter_weights(t2l_ctx* ctx, InterFusedW* W, int* D, int* heads) {
+  const th::Weights* T = ctx ? (const th::Weights*)ctx->text_head : nullptr;
+  if (!T || !T->has_inter) return false;
+  *W = T->fused;
+  *D = T->inter_dim;
+  *heads = T->inter_heads;
+  return true;
+}
+
 }  // namespace t2l
 
 using namespace t2l;
